@@ -312,6 +312,9 @@ def main():
     ap.add_argument("--preprocessed-cache", action="store_true",
                     help="NOT the headline number: keep the committed preprocessed tree between proofs (SURVEY 8f-4); the "
                          "default recomputes tree 0 in every proof like the reference does")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the words of the last timed proof (rank 0) to DIR/proof_words.npy as float64, "
+                         "so that two builds can be compared output for output (the input is the same in every run)")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -395,6 +398,8 @@ def main():
                         p = be.prove_device(dev)
                         if i == n - 1:
                             last = p.stats()
+                            if args.dump_outputs:
+                                last["proof_words"] = p.words()
                         p.free()
                     self.done.put(last)
                 except Exception as e:  # noqa: BLE001
@@ -440,6 +445,13 @@ def main():
         dist.barrier()
     kprof = kprof_report() if not args.no_kprof else {}
     be.L.cm_kprof_enable(C.c_int32(0))
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        words = st.pop("proof_words").astype(np.float64)   # u32 words: exact in float64
+        if words.nbytes > 64 << 20:
+            sys.exit(f"bench.py: --dump-outputs: the proof is {words.nbytes} bytes as float64, more than 64 MB")
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "proof_words.npy"), words)
     pipelined = None
     if world == 1 and args.pipelined > 1:
         # SURVEY §8f-4 segment pipeline: continuation segments are independent proofs, so several can be in

@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -22,8 +23,16 @@ def _bench(*args):
     return json.loads(lines[0])
 
 
-def test_single_gpu_line():
-    d = _bench("--steps", "2", "--warmup", "1", "--fib-n", "3000", "--cpu-sample-n", "3000", "--pipelined", "2", "--big-fib-n", "6000")
+def test_single_gpu_line(oracle, tmp_path):
+    d = _bench("--steps", "2", "--warmup", "1", "--fib-n", "3000", "--cpu-sample-n", "3000", "--pipelined", "2", "--big-fib-n", "6000",
+               "--dump-outputs", str(tmp_path))
+    # --dump-outputs: the last timed proof's words, as float64, equal to the oracle's proof of the same input
+    from cairo_m_amd.lib import synth_fibonacci
+    got = np.load(tmp_path / "proof_words.npy")
+    inp = synth_fibonacci(3000)
+    want, _ = oracle.prove(inp.view)
+    inp.free()
+    assert got.dtype == np.float64 and got.size == want.size and np.array_equal(got, want.astype(np.float64))
     base = json.load(open(os.path.join(ROOT, "BASELINE.json")))
     assert d["metric"] == base["metric"] and d["unit"] == "M31 trace cells/s" and d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1
     assert d["higher_is_better"] is True and d["scaling"] == "weak" and d["vs_baseline"] is None and d["dtype"] == "u32" and d["data"] == "synthetic"

@@ -1,5 +1,7 @@
 """GPU parity (through the C ABI) for the commit path: circle IFFT / LDE, eval_at_point,
 Blake2s Merkle layers, grind — bit-exact against the CPU oracle on seeded inputs."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -139,15 +141,19 @@ def test_merkle_commit_parity(backend, oracle, logs):
 def test_merkle_commit_layer_parity(backend, oracle, n_cols, with_prev):
     """MerkleOps::commit_on_layer through the C ABI (cm_merkle_commit_layer) at 2^19 nodes = k_merkle_layer: every hash of
     the layer equals the oracle's, with and without a previous layer, for column counts below / at / above one 16-word
-    Blake2s chunk and for the 42-column shape of the metric config's largest component."""
-    if n_cols == 0 and not with_prev:
-        pytest.skip("a layer needs children or columns")
+    Blake2s chunk and for the 42-column shape of the metric config's largest component.  A layer with neither children nor
+    columns is 2^19 hashes of an empty node: the root of the oracle's commit of no columns."""
     L = 19
     rng = np.random.default_rng(1000 + n_cols + (100 if with_prev else 0))
     upper = [rng.integers(0, P, size=2 << L, dtype=np.uint32) for _ in range(3)] if with_prev else []
     here = [rng.integers(0, P, size=1 << L, dtype=np.uint32) for _ in range(n_cols)]
-    _, layers = oracle.merkle_commit(upper + here)
-    layers = layers.reshape(-1, 8)
+    if upper or here:
+        _, layers = oracle.merkle_commit(upper + here)
+        layers = layers.reshape(-1, 8)
+    else:
+        empty = (C.c_uint8 * 32)()
+        oracle.L.orc_merkle_commit(None, None, C.c_size_t(0), empty, None)
+        layers = np.tile(np.frombuffer(bytes(empty), dtype=np.uint32), (1 << L, 1))
     prev = 0
     hs = []
     if with_prev:

@@ -22,10 +22,21 @@ def _free_port():
         return s.getsockname()[1]
 
 
+# At most this many rank processes share the one GPU (with the test process and the launcher: six processes hold it).  Larger worlds
+# run as threads of ONE child process over the blocking loop-back communicator of tests/test_gpu_sharded_threads.py: the same
+# host-blocking form of cm_comm that the gloo ranks use, with device copies in place of torch.distributed.
+MAX_RANK_PROCESSES = 4
+
+
 def _run_sharded(world, fib_n, out, mixed_iters=0, comm="torch", extra_env=None, cfg=None):
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), "-m", "cairo_m_amd.sharded", "--fib-n", str(fib_n), "--dist-backend", "gloo",
-           "--force-device", "0", "--steps", "0", "--out", out, "--mixed-iters", str(mixed_iters), "--comm", comm]
+    if world > MAX_RANK_PROCESSES:
+        assert comm == "torch", comm
+        cmd = [sys.executable, "-m", "tests.test_gpu_sharded_threads", "--world", str(world), "--fib-n", str(fib_n), "--out", out,
+               "--mixed-iters", str(mixed_iters)]
+    else:
+        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
+               "--master-port", str(_free_port()), "-m", "cairo_m_amd.sharded", "--fib-n", str(fib_n), "--dist-backend", "gloo",
+               "--force-device", "0", "--steps", "0", "--out", out, "--mixed-iters", str(mixed_iters), "--comm", comm]
     if cfg:
         cmd += ["--cfg", ",".join(str(x) for x in cfg)]
     env = dict(os.environ, PYTHONPATH=ROOT, HSA_ENABLE_IPC_MODE_LEGACY="0")
@@ -211,7 +222,7 @@ def _gpus():
 
 @pytest.mark.parametrize("world,fib_n,comm", [(2, 50, "rccl"), (2, 419_000, "rccl"), (2, 419_000, "torch"), (4, 30_000, "rccl"),
                                                (8, 419_000, "rccl")])
-def test_multi_gpu_rccl_proof_equals_single_gpu_proof(backend, oracle, tmp_path, world, fib_n, comm):
+def test_multi_gpu_rccl_proof_equals_single_gpu_proof(request, tmp_path, world, fib_n, comm):
     """Switches itself on where the box has `world` GPUs (the round's test boxes have one: skipped there).  One process per GPU
     (LOCAL_RANK = device), backend nccl = RCCL over xGMI: the library's own stream-ordered communicator (cm_rccl_comm_create —
     ncclAllGather and the grouped ncclSend / ncclRecv row exchange of comm_rccl.hip get real peers here for the first time) or the
@@ -220,6 +231,7 @@ def test_multi_gpu_rccl_proof_equals_single_gpu_proof(backend, oracle, tmp_path,
     multi-GPU node, before `bench.py --gpus N`."""
     if _gpus() < world:
         pytest.skip(f"needs {world} GPUs, this box has {_gpus()}")
+    backend, oracle = request.getfixturevalue("backend"), request.getfixturevalue("oracle")
     inp = synth_fibonacci(fib_n)
     p = backend.prove(inp)
     want = p.words().copy()

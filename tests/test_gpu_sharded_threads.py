@@ -7,9 +7,16 @@ would be exercised with one rank only.  Here the ranks are THREADS of this proce
 buffers, and the communicator is a loop-back: a collective is device-to-device copies from every rank's send buffer into the
 caller's receive buffer, enqueued on the caller's current stream behind an event the owner recorded on ITS stream, plus a
 second round of events so that nobody overwrites a send buffer a peer is still reading.  The host threads only meet at two
-barriers per collective (to exchange the events): nothing waits for the GPU.  Every rank's proof equals the single-GPU proof."""
+barriers per collective (to exchange the events): nothing waits for the GPU.  Every rank's proof equals the single-GPU proof.
+
+The loop-back also has the BLOCKING form of cm_comm (flags 0, the form the gloo runs use: the prover drains its stream before a
+collective, the data has landed when the callback returns).  `python -m tests.test_gpu_sharded_threads --world 8 ...` runs it in a
+child process for tests/test_gpu_sharded.py, whose cases with more ranks than processes may share the GPU run there."""
+import argparse
 import ctypes as C
+import os
 import threading
+import time
 
 import numpy as np
 import pytest
@@ -18,9 +25,10 @@ from cairo_m_amd.lib import Proof, synth_fibonacci
 from cairo_m_amd.sharded import CmComm, _A2A, _AG, _SETSTREAM, _ABORT, shard_plan
 
 pytestmark = pytest.mark.gpu
-HIP = None   # libamdhip64, loaded by the first Loopback (not at collection: a box without a GPU only deselects this file)
+HIP = None   # the HIP runtime of the library, bound by the first Loopback (not at collection: a box without a GPU only deselects this file)
 hipMemcpyDeviceToDevice = 3
 hipEventDisableTiming = 2
+hipStreamNonBlocking = 1
 
 
 def _ck(rc, what):
@@ -30,11 +38,13 @@ def _ck(rc, what):
 class Loopback:
     """shared state of `world` loop-back ranks"""
 
-    def __init__(self, backend, world, words):
+    def __init__(self, backend, world, words, blocking=False):
         global HIP
         if HIP is None:
-            HIP = C.CDLL("libamdhip64.so")
-        self.world, self.words = world, words
+            # dlsym through the library's handle searches its dependencies: the runtime it is linked against.  A bare
+            # CDLL("libamdhip64.so") can bind torch's bundled copy instead (a second runtime that knows no device of the library's).
+            HIP = backend.L
+        self.world, self.words, self.blocking = world, words, blocking
         self.send = [backend.col_alloc(words) for _ in range(world)]
         self.recv = [backend.col_alloc(words) for _ in range(world)]
         self.stream = [C.c_void_p(0)] * world
@@ -47,6 +57,11 @@ class Loopback:
         self.lock = threading.Lock()
         self.calls = 0
         self.backend = backend
+        self.copy_stream = []           # blocking form: the stream each rank copies on before its callback returns
+        for _ in range(world if blocking else 0):
+            st = C.c_void_p()
+            _ck(HIP.hipStreamCreateWithFlags(C.byref(st), C.c_uint(hipStreamNonBlocking)), "hipStreamCreateWithFlags")
+            self.copy_stream.append(st)
 
     def event(self):
         e = C.c_void_p()
@@ -58,6 +73,8 @@ class Loopback:
     def free(self):
         for e in self.events:
             HIP.hipEventDestroy(e)
+        for st in self.copy_stream:
+            HIP.hipStreamDestroy(st)
         for h in self.send + self.recv:
             self.backend.col_free(h)
 
@@ -69,7 +86,7 @@ class LoopbackRank:
         self._ss, self._ab = _SETSTREAM(self._set_stream), _ABORT(self._abort)
         self.set_stream_calls = 0
         self.c = CmComm(rank, shared.world, None, int(shared.send[rank]), int(shared.recv[rank]), shared.words, self._a2a, self._ag,
-                        1, self._ss, self._ab)   # flags = CM_COMM_STREAM_ORDERED
+                        *((0, _SETSTREAM()) if shared.blocking else (1, self._ss)), self._ab)   # flags 1 = CM_COMM_STREAM_ORDERED
 
     def _set_stream(self, _ctx, stream):
         self.s.stream[self.rank] = C.c_void_p(stream)
@@ -83,6 +100,8 @@ class LoopbackRank:
     def _exchange(self, arg, copies_for):
         """copies_for(args of all ranks) -> [(source rank, source word offset, destination word offset, words)] of THIS rank"""
         s, r = self.s, self.rank
+        if s.blocking:
+            return self._exchange_blocking(arg, copies_for)
         st = s.stream[r]
         try:
             s.arg[r] = arg
@@ -102,6 +121,27 @@ class LoopbackRank:
                 if peer != r:
                     _ck(HIP.hipStreamWaitEvent(st, s.done[peer], C.c_uint(0)), "hipStreamWaitEvent")
             s.barrier.wait()                                    # (nobody re-publishes ready / arg while a peer still reads them)
+            if r == 0:
+                s.calls += 1
+            return 0
+        except Exception as e:  # noqa: BLE001 — a Python exception must not unwind through the C frame
+            print(f"[loop-back rank {r}] collective failed: {e!r}")
+            return 1
+
+    def _exchange_blocking(self, arg, copies_for):
+        """the blocking form: every prover drained its stream before calling, and this rank's data has landed on return"""
+        s, r = self.s, self.rank
+        st = s.copy_stream[r]
+        try:
+            s.arg[r] = arg
+            s.barrier.wait()                                    # every rank's send buffer is complete and its argument published
+            for src, so, do, n in copies_for(list(s.arg)):
+                if n == 0:
+                    continue
+                _ck(HIP.hipMemcpyAsync(C.c_void_p(int(s.recv[r]) + 4 * do), C.c_void_p(int(s.send[src]) + 4 * so), C.c_size_t(4 * n),
+                                       C.c_int(hipMemcpyDeviceToDevice), st), "hipMemcpyAsync")
+            _ck(HIP.hipStreamSynchronize(st), "hipStreamSynchronize")
+            s.barrier.wait()                                    # every rank has read every send buffer: they may be overwritten
             if r == 0:
                 s.calls += 1
             return 0
@@ -129,9 +169,9 @@ class LoopbackRank:
         return self._exchange(sw, copies)
 
 
-def _prove_threads(backend, inp, world, cfg=None):
+def _prove_threads(backend, inp, world, cfg=None, blocking=False):
     _, words = shard_plan(inp, world, backend.L, cfg)
-    shared = Loopback(backend, world, words)
+    shared = Loopback(backend, world, words, blocking)
     ranks = [LoopbackRank(shared, r) for r in range(world)]
     dev = backend.upload_input(inp)
     out, err = [None] * world, [None] * world
@@ -153,6 +193,12 @@ def _prove_threads(backend, inp, world, cfg=None):
         t.start()
     for t in ts:
         t.join()
+    # join() returns when the Python thread state is gone; the library's per-thread teardown (C++ thread_local destructors:
+    # the thread's streams, its cached pool blocks) runs after that, while the OS thread exits.  Wait for it, so that a process
+    # that ends next does not tear the HIP runtime down under it.
+    deadline = time.monotonic() + 120
+    while any(os.path.exists(f"/proc/self/task/{t.native_id}") for t in ts) and time.monotonic() < deadline:
+        time.sleep(0.01)
     backend.free_input(dev)
     calls, set_streams = shared.calls, [x.set_stream_calls for x in ranks]
     shared.free()
@@ -217,3 +263,33 @@ def test_stream_ordered_ranks_all_opcode_segment(backend):
     for r in range(4):
         assert got[r].size == want.size and np.array_equal(got[r], want), f"rank {r}"
     inp.free()
+
+
+def main():
+    """child process of tests/test_gpu_sharded.py: `world` ranks as threads over the BLOCKING loop-back; rank r writes its proof
+    words to <out>.<r>.npy like cairo_m_amd.sharded does.  The CM_SHARD_* switches are read from the environment."""
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--world", type=int, required=True)
+    ap.add_argument("--fib-n", type=int, default=0)
+    ap.add_argument("--mixed-iters", type=int, default=0)
+    ap.add_argument("--cfg", default="")
+    ap.add_argument("--out", required=True)
+    a = ap.parse_args()
+    from cairo_m_amd import Backend
+    from cairo_m_amd.lib import vm_run
+    from cairo_m_amd.workloads import all_opcodes_program
+    be = Backend(0)
+    if a.mixed_iters:
+        inp = vm_run(all_opcodes_program(a.mixed_iters)[0], entry_pc=0, args=(), n_returns=0)
+    else:
+        inp = synth_fibonacci(a.fib_n)
+    cfg = tuple(int(x) for x in a.cfg.split(",")) if a.cfg else None
+    got, calls, _ = _prove_threads(be, inp, a.world, cfg, blocking=True)
+    for r, w in enumerate(got):
+        np.save(f"{a.out}.{r}.npy", w)
+    print({"world": a.world, "collectives": calls, "words": int(got[0].size)})
+    inp.free()
+
+
+if __name__ == "__main__":
+    main()

@@ -1,6 +1,6 @@
 #!/bin/bash
 # development tool: lone / four-in-flight ms per proof under GPU_MAX_HW_QUEUES = 4 (default), 8, 6, alternating processes in one session
-cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
+export TMPDIR=/tmp && cd "$(dirname "$0")/.."
 for i in 1 2 3; do
   for q in 4 8 6; do
     echo -n "GPU_MAX_HW_QUEUES=$q "

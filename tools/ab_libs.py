@@ -7,7 +7,7 @@ ap.add_argument("libs", nargs="+")
 ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--pipelined", type=int, default=4)
 a = ap.parse_args()
-root = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 res = {l: {"lone": [], "pipe": [], "phases": []} for l in a.libs}
 for r in range(a.rounds):
     for l in (a.libs if r % 2 == 0 else a.libs[::-1]):

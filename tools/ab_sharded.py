@@ -4,7 +4,7 @@
 #       [--reps 8] [--block 6] shard_tree_stream shard_fri_stop_log=18,16
 # (key alone: 1 against 0; key=a,b: value a against value b; no key: only the single-GPU / sharded pair)
 import argparse, os, statistics, sys, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import ctypes as C
 import torch
 import torch.distributed as dist

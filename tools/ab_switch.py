@@ -4,7 +4,7 @@
 # (key alone: 1 against 0; key=a,b: value a against value b)
 # prints, per key, the median ms per proof with the switch on and off (all other switches at their defaults) and the paired difference.
 import argparse, os, statistics, sys, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import ctypes as C
 import torch
 from cairo_m_amd.lib import Backend, synth_fibonacci

@@ -1,6 +1,6 @@
 #!/bin/bash
 # kernel split of the device adapter (run on the GPU box): tools/adapter_prof.sh [out.csv]
-cd /tmp && export TMPDIR=/tmp && cd ${GRAFT_REPO_ROOT:-/root/repo}
+export TMPDIR=/tmp && cd "$(dirname "$0")/.."
 out=${1:-gpurun_out/adapter_kernel_stats.csv}
 timeout 200 python tools/adapter_prof.py 2>&1 | tail -1
 timeout 300 rocprofv3 --kernel-trace --stats -d gpurun_out/adprof -o ad -- python tools/adapter_prof.py --reps 5 > /dev/null 2>&1

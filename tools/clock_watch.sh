@@ -2,12 +2,12 @@
 # Sustained shader clock / power while proofs run back to back (is the chip power-limited under this load?):
 #   tools/clock_watch.sh <tag> [inflight]  -> gpurun_out/<tag>_clocks.txt  (rocm-smi samples next to a 12-second proving loop)
 tag=${1:-x}; inflight=${2:-1}
-cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
+export TMPDIR=/tmp && cd "$(dirname "$0")/.."
 out=gpurun_out/${tag}_clocks.txt
 rocm-smi --showclocks --showpower --showuse 2>/dev/null | grep -E "sclk|mclk|Power|busy" > $out
 python - "$inflight" >> $out 2>&1 <<'P' &
 import sys, time, os
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.getcwd())
 import torch
 from cairo_m_amd.lib import Backend, synth_fibonacci
 inflight = int(sys.argv[1])

@@ -6,7 +6,7 @@
 # 3. two PMC passes (FETCH_SIZE, WRITE_SIZE; separate runs)   -> gpurun_out/<tag>_pmc_traffic.json
 # 4. one PMC pass of SQ issue / stall counters                 -> gpurun_out/<tag>_pmc_sq.json
 tag=${1:-rXX}
-cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
+export TMPDIR=/tmp && cd "$(dirname "$0")/.."
 python bench.py > gpurun_out/${tag}_bench_n1.json 2> gpurun_out/${tag}_bench_n1.err
 # the same line with the 2^26-row leg (BASELINE configs[4] on one GPU: ~116 GiB, about two more minutes): the larger-sizes model
 python bench.py --no-cpu-baseline --no-end-to-end --alt-fib-n 0 --pipelined 0 --cached-setup-steps 0 --sharded-one-rank-blocks 0 --big-mixed-iters 1545000 > gpurun_out/${tag}_bench_big_legs.json 2> gpurun_out/${tag}_bench_big_legs.err

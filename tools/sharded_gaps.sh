@@ -1,7 +1,7 @@
 #!/bin/bash
 # GPU idle time inside one SHARDED proof on one rank (in-library RCCL): tools/sharded_gaps.sh <tag> [--list] -> gpurun_out/<tag>_sharded_gaps.txt
 tag=$1; shift
-cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
+export TMPDIR=/tmp && cd "$(dirname "$0")/.."
 rm -rf gpurun_out/${tag}_stl
 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d gpurun_out/${tag}_stl -- \
   python -m torch.distributed.run --nnodes=1 --nproc-per-node=1 --master-addr 127.0.0.1 --master-port 29517 -m cairo_m_amd.sharded \

@@ -3,7 +3,7 @@
 # GPUs): the time per proof is the SUM of all ranks' work on one device + every exchange as device copies — what sharding ADDS in
 # total GPU work and host time, not a scaling figure.   python tools/sharded_threads.py [--fib-n 419000] [--worlds 1,2,4,8] [--reps 8]
 import argparse, ctypes as C, os, statistics, sys, threading, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from cairo_m_amd.lib import Backend, Proof, synth_fibonacci
 from cairo_m_amd.sharded import shard_plan
