@@ -347,6 +347,107 @@ struct DomainEval : air::LogupStream<DomainEval, M31, QM31> {
   }
 };
 
+// PCS-free AIR check (debug_tools/assert_constraints.rs): the constraints of one TRACE-domain row, each tested for zero.  No random
+// coefficients, no accumulator, no vanishing inverse; the LogUp batches use the [-1, 0] mask through prev_row = shifted_row(r, n, n, -1).
+// first_bad = the lowest failing constraint index (base constraints 0..n_base-1, then the LogUp constraints), -1 = none.
+struct RowCheckEval : air::LogupStream<RowCheckEval, M31, QM31> {
+  const uint32_t* const* tr;   // tree-1 trace-domain columns
+  const uint32_t* const* it;   // tree-2 trace-domain columns
+  const uint32_t* const* pp;   // preprocessed trace-domain columns by PreprocId
+  const DevRelations* rels;
+  uint32_t row, prev_row;
+  int n_base;
+  QM31 cumsum_shift;
+  int ci = 0, ii = 0, kb = 0, kl = 0;
+  int first_bad = -1;
+  QM31 prev_col;
+  const uint32_t* trv = nullptr;  // trace cells of this row already in registers
+  __device__ M31 next() { return trv ? M31(trv[ci++]) : M31(CM_GCOL(tr[ci++])[row]); }
+  __device__ M31 preproc(int id) { return M31(CM_GCOL(pp[id])[row]); }
+  __device__ M31 c(uint32_t v) { return M31(v); }
+  // constraints are visited in index order within each class, so "first seen" = lowest index of its class
+  __device__ void constraint(M31 x) {
+    const int k = kb++;
+    if (!x.is_zero() && (first_bad < 0 || k < first_bad)) first_bad = k;
+  }
+  __device__ void constraint_q(QM31 x) {
+    const int k = n_base + kl++;
+    if (!(x.a.a.is_zero() && x.a.b.is_zero() && x.b.a.is_zero() && x.b.b.is_zero()) && first_bad < 0) first_bad = k;
+  }
+  __device__ QM31 combine(int r, const M31* v, int n) { return dev_combine(rels, r, v, n); }
+  __device__ QM31 ef_from(M31 m) { return QM31(m); }
+  __device__ void on_entry(int, M31, const M31*, int) {}
+  __device__ QM31 mask(uint32_t r) { return QM31(M31(CM_GCOL(it[ii])[r]), M31(CM_GCOL(it[ii + 1])[r]), M31(CM_GCOL(it[ii + 2])[r]), M31(CM_GCOL(it[ii + 3])[r])); }
+  __device__ void emit_batch(bool last, QM31 num, QM31 den) {
+    const QM31 cur = mask(row);
+    if (!last) {
+      constraint_q((cur - prev_col) * den - num);
+      prev_col = cur;
+    } else {
+      constraint_q((cur - mask(prev_row) - prev_col + cumsum_shift) * den - num);
+    }
+    ii += 4;
+  }
+};
+
+// Relation tracker: sum over the row's entries of relation r of mult / combine_r(values), for every r at once.  Each relation keeps
+// its sum as ONE fraction n/d (n/d + m/e = (n e + m d) / (d e): three QM31 products per entry, no inverse); the row ends with one
+// M31 inversion for all relations together (Montgomery's trick over the norms, as LogupEval::flush).  The relation index of every
+// entry is a compile-time constant after inlining, so the per-relation state stays in registers for the relations a component uses.
+struct RelSumEval : air::LogupStream<RelSumEval, M31, QM31> {
+  const uint32_t* const* tr;
+  const uint32_t* const* pp;
+  const DevRelations* rels;
+  uint32_t row;
+  int ci = 0;
+  QM31 num[air::N_RELATIONS], den[air::N_RELATIONS];
+  bool used[air::N_RELATIONS] = {};
+  __device__ M31 next() { return M31(CM_GCOL(tr[ci++])[row]); }
+  __device__ M31 preproc(int id) { return M31(CM_GCOL(pp[id])[row]); }
+  __device__ M31 c(uint32_t v) { return M31(v); }
+  __device__ void constraint(M31) {}
+  __device__ QM31 combine(int r, const M31* v, int n) { return dev_combine(rels, r, v, n); }
+  __device__ QM31 ef_from(M31 m) { return QM31(m); }
+  __device__ void on_entry(int, M31, const M31*, int) {}
+  __device__ void emit_batch(bool, QM31, QM31) {}
+  __device__ __forceinline__ void rel_arr(int r, M31 mult, const M31* vals, int n) {
+    const QM31 d = dev_combine(rels, r, vals, n);
+    if (!used[r]) { num[r] = QM31(mult); den[r] = d; used[r] = true; }
+    else { num[r] = num[r] * d + den[r] * mult; den[r] = den[r] * d; }
+  }
+  __device__ __forceinline__ void finalize_pairs() {}
+  __device__ __forceinline__ void finalize_single() {}
+  // out[r] = num[r] / den[r] (0 for an unused relation)
+  __device__ __forceinline__ void finish(QM31 out[air::N_RELATIONS]) {
+    CM31 t[air::N_RELATIONS];
+    M31 nr[air::N_RELATIONS], pre[air::N_RELATIONS];
+    M31 all(1);
+#pragma unroll
+    for (int r = 0; r < air::N_RELATIONS; r++) {
+      if (used[r]) {
+        t[r] = den[r].a * den[r].a - mul_R(den[r].b * den[r].b);   // norm over CM31
+        nr[r] = t[r].a * t[r].a + t[r].b * t[r].b;                  // norm over M31
+      } else {
+        nr[r] = M31(1);
+      }
+      pre[r] = all;            // product of the norms before r
+      all = all * nr[r];
+    }
+    M31 run = inv(all);
+#pragma unroll
+    for (int r = air::N_RELATIONS - 1; r >= 0; r--) {
+      const M31 ni = run * pre[r];   // 1 / nr[r]
+      run = run * nr[r];
+      if (used[r]) {
+        const CM31 ti(t[r].a * ni, -(t[r].b * ni));                 // 1 / norm_u(den)
+        out[r] = num[r] * QM31(den[r].a * ti, -(den[r].b * ti));   // num * conj_u(den) / norm_u(den)
+      } else {
+        out[r] = QM31();
+      }
+    }
+  }
+};
+
 // (shifted_row: device_common.hpp)
 
 }  // namespace cm

@@ -10,6 +10,7 @@
 #include "point_eval.hpp"
 #include "host_adapter.hpp"
 #include "shard_kernels.hpp"
+#include "segment_input.hpp"
 #include "tail_plan.hpp"
 #include <atomic>
 #include <chrono>
@@ -25,18 +26,7 @@
 
 namespace cm {
 
-static inline uint32_t log_size_for(uint64_t n) {  // max(LOG_N_LANES, ceil_log2(n))
-  uint32_t l = 4;
-  while ((1ull << l) < n) l++;
-  return l;
-}
-
-// ---- device-resident prover input ------------------------------------------------------------------------
-struct DeviceInput {
-  cm_prover_input meta;  // scalar fields + counts; pointers are replaced by device pointers below
-  DevBuf bundles[CM_N_OPCODE_COMPONENTS], data_accesses, init_mem, fin_mem, clock_updates, init_tree, fin_tree;
-  PublicData public_data;
-};
+// (log_size_for, DeviceInput: segment_input.hpp)
 
 static PublicData make_public_data(const cm_prover_input& in) {  // PublicData::new (public_data.rs:244-272)
   PublicData d;
@@ -219,17 +209,7 @@ static F coset_vanishing_canonic(uint32_t log, CPoint<F> p) {
   return x;
 }
 
-// log2 rows of every component, known from the input lengths (Claim::log_sizes)
-static void component_logs(const cm_prover_input& in, uint32_t* clog) {
-  uint64_t nrows[air::N_COMPONENTS] = {0};
-  for (int c = 0; c < air::N_OPCODE_COMPONENTS; c++) nrows[c] = in.n_bundles[c];
-  nrows[air::C_MEMORY] = in.n_initial_memory + in.n_final_memory;
-  nrows[air::C_MERKLE] = in.n_initial_tree + in.n_final_tree;
-  nrows[air::C_CLOCK_UPDATE] = in.n_clock_updates;
-  nrows[air::C_POSEIDON2] = in.n_initial_tree + in.n_final_tree;
-  for (int c = 0; c <= air::C_POSEIDON2; c++) clog[c] = log_size_for(nrows[c]);
-  clog[air::C_RC8] = 8; clog[air::C_RC16] = 16; clog[air::C_RC20] = 20; clog[air::C_BITWISE] = 18;
-}
+// (component_logs: segment_input.hpp)
 // ---- transcript steps shared by the single-GPU and the sharded prover ------------------------------------------------------
 // PcsConfig::mix_into + PublicData::mix_into (prover.rs:33-36, 62-66)
 static void mix_config_and_public_data(Channel& ch, const cm_pcs_config& cfg, const PublicData& d) {
@@ -248,18 +228,7 @@ static void mix_config_and_public_data(Channel& ch, const cm_pcs_config& cfg, co
     ch.mix_u32s(words.data(), words.size());
   }
 }
-// Relations::draw (prover.rs:94): (z, alpha) per relation, alpha powers for the device
-static void draw_relations(Channel& ch, HostRelations& hrel, DevRelations& drel_h) {
-  for (int r = 0; r < air::N_RELATIONS; r++) {
-    QM31 z, alpha;
-    ch.draw_two_felts(z, alpha);
-    hrel.z[r] = z;
-    QM31 cur(M31(1));
-    for (int i = 0; i < air::MAX_REL_SIZE; i++) { hrel.alpha_pow[r][i] = cur; cur = cur * alpha; }
-    z.to_u32(drel_h.z[r]);
-    for (int i = 0; i < air::MAX_REL_SIZE; i++) hrel.alpha_pow[r][i].to_u32(drel_h.alpha_pow[r][i]);
-  }
-}
+// (draw_relations: segment_input.hpp)
 // random coefficient of the composition polynomial: powers[g] = rho^(total - 1 - g), uploaded as words
 static void draw_constraint_powers(Channel& ch, std::vector<QM31>& powers, DevBuf& d_powers, hipStream_t st) {
   QM31 random_coeff = ch.draw_felt();
@@ -1576,7 +1545,6 @@ struct cm_proof {   // owns its ProofData: every failure path (parse error, exce
   cm::ProofData* d = nullptr; std::string json, transcript_json; std::vector<uint32_t> words;
   ~cm_proof() { delete d; }
 };
-struct cm_device_input { cm::DeviceInput* d = nullptr; ~cm_device_input() { delete d; } };
 extern "C" int32_t cm_set_last_error(const char* msg);
 
 template <class F>

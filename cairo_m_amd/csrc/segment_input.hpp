@@ -1,0 +1,54 @@
+// Device-resident prover input and the input-level steps every whole-segment driver shares: the single-GPU and sharded provers
+// (prover.hip) and the PCS-free AIR check (check.hip).
+#pragma once
+#include "../../include/cairom_hip.h"
+#include "prover_common.hpp"
+#include "gpu_air.hpp"
+#include "point_eval.hpp"
+
+namespace cm {
+
+inline uint32_t log_size_for(uint64_t n) {  // max(LOG_N_LANES, ceil_log2(n))
+  uint32_t l = 4;
+  while ((1ull << l) < n) l++;
+  return l;
+}
+
+// ---- device-resident prover input ------------------------------------------------------------------------
+struct DeviceInput {
+  cm_prover_input meta;  // scalar fields + counts; pointers are replaced by device pointers below
+  DevBuf bundles[CM_N_OPCODE_COMPONENTS], data_accesses, init_mem, fin_mem, clock_updates, init_tree, fin_tree;
+  PublicData public_data;
+};
+
+// log2 rows of every component, known from the input lengths (Claim::log_sizes)
+inline void component_logs(const cm_prover_input& in, uint32_t* clog) {
+  uint64_t nrows[air::N_COMPONENTS] = {0};
+  for (int c = 0; c < air::N_OPCODE_COMPONENTS; c++) nrows[c] = in.n_bundles[c];
+  nrows[air::C_MEMORY] = in.n_initial_memory + in.n_final_memory;
+  nrows[air::C_MERKLE] = in.n_initial_tree + in.n_final_tree;
+  nrows[air::C_CLOCK_UPDATE] = in.n_clock_updates;
+  nrows[air::C_POSEIDON2] = in.n_initial_tree + in.n_final_tree;
+  for (int c = 0; c <= air::C_POSEIDON2; c++) clog[c] = log_size_for(nrows[c]);
+  clog[air::C_RC8] = 8; clog[air::C_RC16] = 16; clog[air::C_RC20] = 20; clog[air::C_BITWISE] = 18;
+}
+// Relations::draw (prover.rs:94): (z, alpha) per relation, alpha powers for the device
+inline void draw_relations(hostch::Channel& ch, HostRelations& hrel, DevRelations& drel_h) {
+  for (int r = 0; r < air::N_RELATIONS; r++) {
+    QM31 z, alpha;
+    ch.draw_two_felts(z, alpha);
+    hrel.z[r] = z;
+    QM31 cur(M31(1));
+    for (int i = 0; i < air::MAX_REL_SIZE; i++) { hrel.alpha_pow[r][i] = cur; cur = cur * alpha; }
+    z.to_u32(drel_h.z[r]);
+    for (int i = 0; i < air::MAX_REL_SIZE; i++) hrel.alpha_pow[r][i].to_u32(drel_h.alpha_pow[r][i]);
+  }
+}
+
+// public_data.rs:291-394: the LogUp contribution of the public data (the verifier's initial_logup_sum); per_relation (optional)
+// receives its part per relation (registers, merkle, memory; zero for the others).  verifier.hip
+QM31 public_logup_sum(const PublicData& d, const HostRelations& rel, QM31* per_relation = nullptr);
+
+}  // namespace cm
+
+struct cm_device_input { cm::DeviceInput* d = nullptr; ~cm_device_input() { delete d; } };

@@ -186,27 +186,35 @@ QM31 combine(const HostRelations& rel, int r, std::initializer_list<M31> vals) {
   for (M31 v : vals) a += rel.alpha_pow[r][i++] * v;
   return a - rel.z[r];
 }
-QM31 initial_logup_sum(const PublicData& d, const HostRelations& rel) {
+// per_relation (optional): the same sum split by relation (registers, merkle, memory; the other relations stay zero) — the AIR
+// check (check.hip) reports it next to the components' relation sums
+QM31 initial_logup_sum(const PublicData& d, const HostRelations& rel, QM31* per_relation = nullptr) {
   const M31 one(1), zero;
-  std::vector<QM31> dens;
-  dens.push_back(combine(rel, air::REL_REGISTERS, {M31(d.initial_pc), M31(d.initial_fp), one}));
-  dens.push_back(-combine(rel, air::REL_REGISTERS, {M31(d.final_pc), M31(d.final_fp), M31(d.clock) + one}));
-  dens.push_back(combine(rel, air::REL_MERKLE, {zero, zero, M31(d.initial_root), M31(d.initial_root)}));
-  dens.push_back(combine(rel, air::REL_MERKLE, {zero, zero, M31(d.final_root), M31(d.final_root)}));
+  std::vector<std::pair<int, QM31>> dens;   // (relation, denominator of a +1 entry)
+  dens.push_back({air::REL_REGISTERS, combine(rel, air::REL_REGISTERS, {M31(d.initial_pc), M31(d.initial_fp), one})});
+  dens.push_back({air::REL_REGISTERS, -combine(rel, air::REL_REGISTERS, {M31(d.final_pc), M31(d.final_fp), M31(d.clock) + one})});
+  dens.push_back({air::REL_MERKLE, combine(rel, air::REL_MERKLE, {zero, zero, M31(d.initial_root), M31(d.initial_root)})});
+  dens.push_back({air::REL_MERKLE, combine(rel, air::REL_MERKLE, {zero, zero, M31(d.final_root), M31(d.final_root)})});
   auto add = [&](const std::vector<PublicEntry>& es, bool emit) {
     const M31 root(emit ? d.initial_root : d.final_root), height(air::TREE_HEIGHT), four(4);
     for (auto& e : es) {
       if (!e.present) continue;
       QM31 mem = combine(rel, air::REL_MEMORY, {M31(e.addr), M31(e.clock), M31(e.value[0]), M31(e.value[1]), M31(e.value[2]), M31(e.value[3])});
-      dens.push_back(emit ? mem : -mem);
-      for (uint32_t k = 0; k < 4; k++) dens.push_back(-combine(rel, air::REL_MERKLE, {four * M31(e.addr) + M31(k), height, M31(e.value[k]), root}));
+      dens.push_back({air::REL_MEMORY, emit ? mem : -mem});
+      for (uint32_t k = 0; k < 4; k++) dens.push_back({air::REL_MERKLE, -combine(rel, air::REL_MERKLE, {four * M31(e.addr) + M31(k), height, M31(e.value[k]), root})});
     }
   };
   add(d.program, true);
   add(d.input, true);
   add(d.output, false);
   QM31 s;
-  for (auto& x : dens) s += inv(x);
+  if (per_relation)
+    for (int r = 0; r < air::N_RELATIONS; r++) per_relation[r] = QM31();
+  for (auto& x : dens) {
+    const QM31 f = inv(x.second);
+    s += f;
+    if (per_relation) per_relation[x.first] += f;
+  }
   return s;
 }
 
@@ -281,6 +289,9 @@ bool rebuild_evals(const std::vector<uint32_t>& queries, const std::vector<QM31>
 }
 
 }  // namespace
+
+// the public data's LogUp sum, split by relation, for the AIR check (check.hip; declared in segment_input.hpp)
+QM31 public_logup_sum(const PublicData& d, const HostRelations& rel, QM31* per_relation) { return initial_logup_sum(d, rel, per_relation); }
 
 // "" = the proof verifies; otherwise the name of the failed check
 // `expected` is the verifier's OWN PcsConfig (verify_cairo_m takes it from the caller, defaulting to REGULAR_96_BITS,

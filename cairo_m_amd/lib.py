@@ -724,3 +724,105 @@ def _b_col_zero(self, h, n):
 Backend.accumulate = _b_accumulate
 Backend.secure_powers = _b_secure_powers
 Backend.col_zero = _b_col_zero
+
+
+# ---- PCS-free AIR check (include/cairom_hip.h: cm_check_report; reference: debug_tools::assert_constraints) ----------------
+N_RELATIONS = 8
+RELATION_NAMES = ("registers", "memory", "merkle", "poseidon2", "range_check_8", "range_check_16", "range_check_20", "bitwise")
+P_M31 = (1 << 31) - 1
+
+
+class _CheckReportC(C.Structure):
+    _fields_ = [("status", C.c_int32), ("component", C.c_int32), ("constraint", C.c_int32), ("reserved", C.c_int32),
+                ("row", C.c_uint64),
+                ("failing_rows", C.c_uint64 * N_COMPONENTS),
+                ("first_constraint", C.c_int32 * N_COMPONENTS),
+                ("first_row", C.c_uint64 * N_COMPONENTS),
+                ("claimed_sum", (C.c_uint32 * 4) * N_COMPONENTS),
+                ("relation_sum", ((C.c_uint32 * 4) * N_RELATIONS) * N_COMPONENTS),
+                ("public_sum", (C.c_uint32 * 4) * N_RELATIONS),
+                ("total", C.c_uint32 * 4),
+                ("relations", C.c_uint32 * RELATION_WORDS),
+                ("message", C.c_char * 256)]
+
+
+class CheckReport(_CheckReportC):
+    """Verdict of cm_check_constraints (the fields of cm_check_report): status 0 ok, 1 lookup value out of range, 2 a constraint
+    fails, 3 the LogUp sums do not cancel.  QM31 values are 4 words (to_m31_array order)."""
+
+    @property
+    def message(self):
+        return _CheckReportC.message.__get__(self).decode(errors="replace")
+
+    @property
+    def claimed_sums(self):
+        return np.ctypeslib.as_array(self.claimed_sum).copy()
+
+    @property
+    def relation_sums(self):
+        return np.ctypeslib.as_array(self.relation_sum).copy()
+
+    @property
+    def public_sums(self):
+        return np.ctypeslib.as_array(self.public_sum).copy()
+
+    @property
+    def relation_words(self):
+        return np.ctypeslib.as_array(self.relations).copy()
+
+    def relation_balance(self):
+        """[8, 4]: sum over the components of relation_sum[c][r] + public_sum[r], per relation (all zero when it balances)"""
+        s = self.relation_sums.astype(np.int64).sum(axis=0) + self.public_sums.astype(np.int64)
+        return (s % P_M31).astype(np.uint32)
+
+    def unbalanced_relations(self):
+        return [RELATION_NAMES[r] for r, w in enumerate(self.relation_balance()) if w.any()]
+
+    def __repr__(self):
+        return f"CheckReport(status={self.status}, message={self.message!r})"
+
+
+def _b_check(self, dev_or_host_input, relations=None):
+    """debug_tools::assert_constraints on the GPU.  dev_or_host_input: a device input (upload_input / adapt_segment) or a host
+    input with a `.view` (uploaded for the call).  relations: cm_relations words, None = drawn from a default channel."""
+    rep = CheckReport()
+    r = None
+    if relations is not None:
+        r = np.ascontiguousarray(relations, dtype=np.uint32)
+        assert r.size == RELATION_WORDS
+    dev, own = dev_or_host_input, False
+    if hasattr(dev_or_host_input, "view"):
+        dev, own = self.upload_input(dev_or_host_input), True
+    try:
+        self._ck(self.L.cm_check_constraints(dev, _p(r) if r is not None else None, C.byref(rep)))
+    finally:
+        if own:
+            self.free_input(dev)
+    return rep
+
+
+def _b_constraints_check(self, cid, trace_cols, interaction_cols, preprocessed, log_size, rel_words, claimed_sum, row_status=0):
+    """one component on its trace domain: (failing_rows, first_constraint, first_row); row_status = an optional column handle"""
+    r = np.ascontiguousarray(rel_words, dtype=np.uint32)
+    assert r.size == RELATION_WORDS
+    cs = np.ascontiguousarray(claimed_sum, dtype=np.uint32)
+    n, k, row = C.c_uint64(0), C.c_int32(0), C.c_uint64(0)
+    self._ck(self.L.cm_constraints_check(C.c_int32(cid), self._harr(trace_cols), self._harr(interaction_cols), self._harr(preprocessed),
+                                         C.c_uint32(log_size), _p(r), _p(cs), C.c_uint64(row_status), C.byref(n), C.byref(k),
+                                         C.byref(row), C.c_uint64(0)))
+    return n.value, k.value, row.value
+
+
+def _b_relation_sums(self, cid, trace_cols, preprocessed, log_size, rel_words):
+    """[8, 4] words: per relation, sum over rows and entries of mult / combine(values)"""
+    r = np.ascontiguousarray(rel_words, dtype=np.uint32)
+    assert r.size == RELATION_WORDS
+    out = np.zeros((N_RELATIONS, 4), dtype=np.uint32)
+    self._ck(self.L.cm_relation_sums(C.c_int32(cid), self._harr(trace_cols), self._harr(preprocessed), C.c_uint32(log_size), _p(r),
+                                     _p(out), C.c_uint64(0)))
+    return out
+
+
+Backend.check = _b_check
+Backend.constraints_check = _b_constraints_check
+Backend.relation_sums = _b_relation_sums

@@ -27,8 +27,8 @@
 /* Revision of this header.  4: cm_comm.struct_size at offset 0 (breaking for cm_comm users).  5: cm_shard_plan* take the PCS
  * config and column-array capacities; cm_set_device_tail, cm_tail_list.  6: cm_runner_segment grows by initial_heap /
  * n_initial_heap at its END (a revision-5 caller must be recompiled: the library reads the two fields);
- * cm_host_segment_set_initial_heap. */
-#define CM_ABI_REVISION 6
+ * cm_host_segment_set_initial_heap.  7: cm_check_report, cm_check_constraints, cm_constraints_check, cm_relation_sums. */
+#define CM_ABI_REVISION 7
 
 #ifdef __cplusplus
 extern "C" {
@@ -519,6 +519,47 @@ int32_t cm_constraints_accumulate(int32_t component, const cm_handle* trace_lde,
                                   const cm_handle* preprocessed_lde, uint32_t log_size, const cm_relations* relations,
                                   const uint32_t* coeff_powers, const uint32_t claimed_sum[4], const cm_handle acc[4],
                                   cm_stream_t s);
+/* ---- PCS-free AIR check (reference: debug_tools::assert_constraints, relation_tracker) ------------------------------------
+ * Builds the three traces of a segment on their trace domains only (no twiddles, LDE, Merkle trees or FRI), draws the relations
+ * (from a default channel unless the caller passes them), and checks that every constraint of every component vanishes on every
+ * row and that the LogUp sums cancel.  Verdict, in the order of precedence:
+ *   status 1  a range-check / bitwise lookup value is out of range: message "lookup value out of range for <rc8|rc16|rc20|bitwise>: ..."
+ *   status 2  the lowest component id with a failing row: "<ComponentName>: constraint <k> fails on row <r>" (r = lowest failing
+ *             row in column storage order, k = lowest failing constraint on that row: base constraints first, then LogUp)
+ *   status 3  the LogUp sums do not cancel: "LogUp sums do not cancel: <names of the relations whose sum is not zero>"
+ *   status 0  none of the above
+ * Relation ids (relation_sum / public_sum): 0 registers, 1 memory, 2 merkle, 3 poseidon2, 4 range_check_8, 5 range_check_16,
+ * 6 range_check_20, 7 bitwise.  For every component c, sum_r relation_sum[c][r] = claimed_sum[c]; the segment balances when
+ * sum_c relation_sum[c][r] + public_sum[r] = 0 for every r, and total = sum_c claimed_sum[c] + sum_r public_sum[r]. */
+typedef struct {
+  int32_t status;                      /* 0 ok, 1 lookup out of range, 2 constraint fails, 3 LogUp sums do not cancel */
+  int32_t component, constraint;       /* status 1: component (constraint = table: 0 rc8, 1 rc16, 2 rc20, 3 bitwise); 2: as named; else -1 */
+  int32_t reserved;                    /* keeps `row` 8-byte aligned without implicit padding */
+  uint64_t row;                        /* status 1 / 2: the row named in the message */
+  uint64_t failing_rows[CM_N_COMPONENTS];
+  int32_t first_constraint[CM_N_COMPONENTS];   /* -1 = none */
+  uint64_t first_row[CM_N_COMPONENTS];
+  uint32_t claimed_sum[CM_N_COMPONENTS][4];
+  uint32_t relation_sum[CM_N_COMPONENTS][CM_N_RELATIONS][4];
+  uint32_t public_sum[CM_N_RELATIONS][4];
+  uint32_t total[4];
+  cm_relations relations;              /* the relations the check used */
+  char message[256];
+} cm_check_report;
+/* relations NULL = drawn from a default channel (debug_tools/assert_constraints.rs:42).  Returns 0 when the check ran (the verdict
+ * is in the report), non-zero when it could not run (cm_last_error).  Threading as cm_prove_device: the calling thread's stream
+ * and device pool. */
+int32_t cm_check_constraints(const cm_device_input* input, const cm_relations* relations, cm_check_report* out);
+/* op level, beside cm_constraints_accumulate: the trace-domain columns of one component (preprocessed = all CM_N_PREPROCESSED
+ * columns on their trace domains), claimed_sum = its InteractionClaim.  row_status (0 = none): a column of 2^log_size words that
+ * receives the lowest failing constraint of every row, 0xFFFFFFFF = none.  first_constraint = -1 when no row fails. */
+int32_t cm_constraints_check(int32_t component, const cm_handle* trace_cols, const cm_handle* interaction_cols,
+                             const cm_handle* preprocessed, uint32_t log_size, const cm_relations* relations,
+                             const uint32_t claimed_sum[4], cm_handle row_status, uint64_t* failing_rows, int32_t* first_constraint,
+                             uint64_t* first_row, cm_stream_t s);
+/* sums[r] = sum over the component's rows and its entries of relation r of multiplicity / (sum_i alpha_r^i v_i - z_r) */
+int32_t cm_relation_sums(int32_t component, const cm_handle* trace_cols, const cm_handle* preprocessed, uint32_t log_size,
+                         const cm_relations* relations, uint32_t sums[CM_N_RELATIONS][4], cm_stream_t s);
 /* AccumulationOps::accumulate: dst[k][i] += src[k][i] (4 coordinate columns of n words); generate_secure_powers:
  * out[i] = felt^i for i < n (host array of 4 * n words).  Column::zeros = cm_col_alloc + cm_col_zero. */
 int32_t cm_accumulate(const cm_handle dst[4], const cm_handle src[4], uint64_t n, cm_stream_t s);

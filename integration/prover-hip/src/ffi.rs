@@ -125,6 +125,26 @@ pub struct cm_relations {
     pub z: [[u32; 4]; CM_N_RELATIONS],
     pub alpha_pow: [[[u32; 4]; CM_MAX_RELATION_SIZE]; CM_N_RELATIONS],
 }
+/// Verdict of `cm_check_constraints` (the PCS-free AIR check, `debug_tools::assert_constraints`): status 0 ok, 1 a lookup value
+/// out of range, 2 a constraint fails, 3 the LogUp sums do not cancel.  Plain words only (no implicit padding).
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct cm_check_report {
+    pub status: i32,
+    pub component: i32,
+    pub constraint: i32,
+    pub reserved: i32,
+    pub row: u64,
+    pub failing_rows: [u64; CM_N_COMPONENTS],
+    pub first_constraint: [i32; CM_N_COMPONENTS],
+    pub first_row: [u64; CM_N_COMPONENTS],
+    pub claimed_sum: [[u32; 4]; CM_N_COMPONENTS],
+    pub relation_sum: [[[u32; 4]; CM_N_RELATIONS]; CM_N_COMPONENTS],
+    pub public_sum: [[u32; 4]; CM_N_RELATIONS],
+    pub total: [u32; 4],
+    pub relations: cm_relations,
+    pub message: [c_char; 256],
+}
 /// One runner segment (crates/common/src/execution.rs:10-15) as plain arrays
 #[repr(C)]
 pub struct cm_runner_segment {
@@ -255,6 +275,9 @@ unsafe extern "C" {
     pub fn cm_preprocessed_column(id: i32, col: cm_handle, s: cm_stream_t) -> i32;
     pub fn cm_interaction_write(component: i32, trace_cols: *const cm_handle, preprocessed: *const cm_handle, log_size: u32, relations: *const cm_relations, out: *const cm_handle, claimed_sum: *mut u32, s: cm_stream_t) -> i32;
     pub fn cm_constraints_accumulate(component: i32, trace_lde: *const cm_handle, interaction_lde: *const cm_handle, preprocessed_lde: *const cm_handle, log_size: u32, relations: *const cm_relations, coeff_powers: *const u32, claimed_sum: *const u32, acc: *const cm_handle, s: cm_stream_t) -> i32;
+    pub fn cm_check_constraints(input: *const cm_device_input, relations: *const cm_relations, out: *mut cm_check_report) -> i32;
+    pub fn cm_constraints_check(component: i32, trace_cols: *const cm_handle, interaction_cols: *const cm_handle, preprocessed: *const cm_handle, log_size: u32, relations: *const cm_relations, claimed_sum: *const u32, row_status: cm_handle, failing_rows: *mut u64, first_constraint: *mut i32, first_row: *mut u64, s: cm_stream_t) -> i32;
+    pub fn cm_relation_sums(component: i32, trace_cols: *const cm_handle, preprocessed: *const cm_handle, log_size: u32, relations: *const cm_relations, sums: *mut [u32; 4], s: cm_stream_t) -> i32;
     pub fn cm_accumulate(dst: *const cm_handle, src: *const cm_handle, n: u64, s: cm_stream_t) -> i32;
     pub fn cm_generate_secure_powers(felt: *const u32, n: u64, out: *mut u32) -> i32;
     pub fn cm_col_zero(h: cm_handle, n_u32: u64, s: cm_stream_t) -> i32;

@@ -176,3 +176,60 @@ pub fn verify_words_hip(proof: &ProofHandleRef, pcs_config: Option<PcsConfig>) -
 }
 /// Borrowed library proof object (e.g. kept by a caller that proves many segments and verifies them later).
 pub struct ProofHandleRef(pub *const cm_proof);
+
+/// Why `assert_constraints` rejected an input: the library's whole report (per-component failing rows, lowest failing
+/// (row, constraint), claimed sums, per-relation sums, the relations used) and its one-line verdict.
+#[derive(Clone)]
+pub struct ConstraintFailure {
+    pub report: Box<cm_check_report>,
+    pub message: String,
+}
+impl std::fmt::Debug for ConstraintFailure {
+    fn fmt(&self, f: &mut std::fmt::Formatter<'_>) -> std::fmt::Result {
+        write!(f, "ConstraintFailure(status {}: {})", self.report.status, self.message)
+    }
+}
+impl ConstraintFailure {
+    /// names of the relations whose sums over all components and the public data do not cancel (status 3 names them too)
+    pub fn unbalanced_relations(&self) -> Vec<&'static str> {
+        const NAMES: [&str; CM_N_RELATIONS] =
+            ["registers", "memory", "merkle", "poseidon2", "range_check_8", "range_check_16", "range_check_20", "bitwise"];
+        const P: u64 = (1 << 31) - 1;
+        let mut out = Vec::new();
+        for r in 0..CM_N_RELATIONS {
+            let mut s = [0u64; 4];
+            for k in 0..4 {
+                s[k] = self.report.public_sum[r][k] as u64;
+                for c in 0..CM_N_COMPONENTS {
+                    s[k] += self.report.relation_sum[c][r][k] as u64;
+                }
+            }
+            if s.iter().any(|w| w % P != 0) {
+                out.push(NAMES[r]);
+            }
+        }
+        out
+    }
+}
+
+/// Twin of `debug_tools::assert_constraints` (crates/prover/src/debug_tools/assert_constraints.rs:24-60) on the GPU: the three
+/// traces on their trace domains, relations drawn from a default channel, every constraint of every row tested and the LogUp
+/// sums checked.  The reference panics on the first failure; this returns it.  `input` is consumed in place as by
+/// `prove_cairo_m_hip`.  A library error (no GPU, out of memory) panics.
+pub fn assert_constraints(input: &mut ProverInput) -> Result<(), ConstraintFailure> {
+    ensure_init();
+    let flat = Flat::new(input, MemoryOrder::AscendingAddress);
+    let view = flat.view();
+    let mut dev: *mut cm_device_input = std::ptr::null_mut();
+    let rc = unsafe { cm_input_upload(&view, &mut dev) };
+    assert!(rc == 0, "cm_input_upload: {}", last_error());
+    let mut report: Box<cm_check_report> = Box::new(unsafe { std::mem::zeroed() });
+    let rc = unsafe { cm_check_constraints(dev, std::ptr::null(), &mut *report) };
+    unsafe { cm_input_free(dev) };
+    assert!(rc == 0, "cm_check_constraints: {}", last_error());
+    if report.status == 0 {
+        return Ok(());
+    }
+    let message = unsafe { CStr::from_ptr(report.message.as_ptr()).to_string_lossy().into_owned() };
+    Err(ConstraintFailure { report, message })
+}
