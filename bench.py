@@ -8,7 +8,12 @@ the barrier and the max-over-ranks reduction); every rank proves an independent 
 segments are independent proofs — SURVEY §8e-1), so scaling is weak and there is no data-path collective.
 
 Prints ONE JSON line (rank 0) with `roofline` (dominant kernel, HIP-event timed inside the library on
-its launch stream) and `cpu_baseline` (the CPU oracle on a bounded sample, rank 0 / N=1 only).
+its launch stream).  A plain run does only what that line needs: set-up, warm-up (with the one fully instrumented proof that picks
+the kernel class the timed steps keep their events on), the timed steps, --dump-outputs.  Everything
+else it can measure or check runs only with --full: the proof verification, `cpu_baseline` (the CPU oracle on a bounded sample,
+with the parity check against the HIP proof), the other modes and sizes (`pipelined`, `with_cached_setup`, `alt_reading`,
+`roofline.whole_path_model_larger_sizes`, `sharded_one_rank`, `end_to_end`; N > 1: `sharded`).  Their objects are null in a
+plain run.
 """
 import argparse
 import ctypes as C
@@ -275,6 +280,9 @@ def run_sharded_child(args, world, comm="torch", timeout=None):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other leg: proof verification, CPU baseline and parity, the other modes, "
+                         "sizes and configurations (the options below that select or size a leg act only with --full)")
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--fib-n", type=int, default=FIB_N)
@@ -453,7 +461,7 @@ def main():
         os.makedirs(args.dump_outputs, exist_ok=True)
         np.save(os.path.join(args.dump_outputs, "proof_words.npy"), words)
     pipelined = None
-    if world == 1 and args.pipelined > 1:
+    if world == 1 and args.full and args.pipelined > 1:
         # SURVEY §8f-4 segment pipeline: continuation segments are independent proofs, so several can be in
         # flight on one GPU (one host thread each); their launch gaps and host round trips overlap.
         n_pipe = 8 * args.pipelined   # like the streamed legs below: enough proofs that the fill and the drain of the pipeline
@@ -472,7 +480,7 @@ def main():
                      "note": "throughput with several independent segment proofs in flight on the GPU (not the headline value)"}
 
     cached_setup = None
-    if world == 1 and rank == 0 and not args.preprocessed_cache and args.cached_setup_steps > 0:
+    if world == 1 and rank == 0 and args.full and not args.preprocessed_cache and args.cached_setup_steps > 0:
         # What a service that proves many segments of ONE AIR would run with: the preprocessed tree (tree 0: it depends on the AIR only)
         # and the twiddle tables kept between proofs (cm_set_preprocessed_cache, cm_set_twiddle_cache; proof bytes unchanged:
         # test_preprocessed_cache_keeps_proof_bytes).  NOT the headline: the reference rebuilds both inside prove_cairo_m, and so does
@@ -497,7 +505,7 @@ def main():
                                 "not the headline value: the timed region rebuilds both in every proof like the reference does"}
 
     alt = None
-    if world == 1 and rank == 0 and args.alt_fib_n > 0:
+    if world == 1 and rank == 0 and args.full and args.alt_fib_n > 0:
         # the other reading of "2^22 rows" — the LARGEST COLUMN has 2^22 rows (n = 838 000, store_fp_imm 3.35 M rows)
         a_inp = synth_fibonacci(args.alt_fib_n)
         a_dev = be.upload_input(a_inp)
@@ -519,7 +527,7 @@ def main():
         be.pool_trim()
 
     big_legs = []
-    if world == 1 and rank == 0:
+    if world == 1 and rank == 0 and args.full:
         # whole-path model at the larger sizes north_star names (same 52 B / cell model): the share of protocol-serial latency
         # (17 tree tops, 12 FRI layers, transcript steps) shrinks with the size, so the fraction of the HBM roofline rises
         def leg(name, make_input, reps, upload=None):
@@ -558,7 +566,7 @@ def main():
                 lambda: vm_segment(all_opcodes_program(args.big_mixed_iters)[0], entry_pc=0, args=(), n_returns=0), 1, upload=be.adapt_segment)
 
     sharded = None
-    if world > 1 and not args.no_sharded:
+    if world > 1 and args.full and not args.no_sharded:
         # Second mode (BASELINE configs[3]): the `world` ranks prove ONE segment together — components split across
         # the ranks, rows split for Merkle hashing and DEEP quotients, collectives over RCCL (cairo_m_amd/sharded.py).  This is
         # single-proof LATENCY scaling (strong scaling); the headline `value` above stays the replica throughput.
@@ -577,7 +585,7 @@ def main():
     verified = None
     hip_words = None
     end_to_end = None
-    if rank == 0:
+    if rank == 0 and args.full:
         # one more (untimed) proof of the same input: the product verifier must accept it, and its words are what the
         # cpu_baseline leg compares the oracle's proof with
         p = be.prove_device(dev)
@@ -588,7 +596,7 @@ def main():
         if not verified:
             sys.exit(f"bench.py: the HIP proof of the bench workload does not verify: {verr}")
     sharded_one = None
-    if rank == 0 and world == 1 and args.sharded_one_rank_blocks > 0:
+    if rank == 0 and world == 1 and args.full and args.sharded_one_rank_blocks > 0:
         # SURVEY 8e-2 on the one GPU there is: the SAME segment through cm_prove_sharded with ONE rank (the in-library stream-ordered
         # RCCL communicator, world = 1) in blocks alternating with the single-GPU prover inside this process — what the sharded
         # path costs by itself (collective plumbing, sub-root gathers, host-planned decommitment), before any rank is added.
@@ -632,7 +640,7 @@ def main():
                                    "object of a --gpus N run)"}
         except Exception as e:   # noqa: BLE001 — the bench line must survive
             sharded_one = {"error": repr(e)[:300]}
-    if rank == 0 and world == 1 and not args.no_end_to_end:
+    if rank == 0 and world == 1 and args.full and not args.no_end_to_end:
         # PCIe-inclusive figures (never `value`): (a) cm_prove_segment from a host ProverInput = upload + prove;
         # (b) runner segment (trace + memory log in host memory) -> device adapter -> prove
         from cairo_m_amd.lib import synth_fibonacci_segment
@@ -742,7 +750,7 @@ def main():
         out = {"metric": "M31 trace cells/sec proved, fibonacci_loop 2^22 rows; end-to-end proof ms",
                "value": value, "unit": "M31 trace cells/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-               "dtype": "u32", "data": "synthetic",
+               "dtype": "u32", "data": "synthetic", "full": args.full,
                "config": {"workload": f"fibonacci_loop n={args.fib_n} ({inp.steps} VM steps, one segment, "
                                       f"{cells} committed trace cells), REGULAR_96_BITS PCS config, "
                                       "ProverInput resident in HBM (upload excluded: see `end_to_end`), twiddle tables "
@@ -758,7 +766,7 @@ def main():
                "alt_reading": alt,
                "phase_ms": phases, "roofline": roofline, "pipelined": pipelined, "with_cached_setup": cached_setup, "sharded": sharded, "sharded_one_rank": sharded_one, "end_to_end": end_to_end,
                "proof_verified": verified}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             same = args.cpu_sample_n == args.fib_n
             parity, out["cpu_baseline"] = cpu_baseline(args.cpu_sample_n, args.cpu_single_n, args.cpu_threads, hip_words if same else None)
             # bit-exactness AT the metric config: the oracle proves the very ProverInput the GPU was timed on

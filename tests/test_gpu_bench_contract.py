@@ -1,7 +1,8 @@
 """bench.py's output contract on a small workload (the driver runs the default workload itself): one JSON line with
-BASELINE.json's metric / unit, the whole-job `value`, `roofline` (dominant kernel, HIP-event timed, HBM bound, traffic from
-the committed PMC profile), `cpu_baseline` (the oracle on the host cores, kind "port") and the parity flag; `--gpus 2`
-without a launcher spawns its own ranks (here: two ranks sharing the GPU over gloo) and reports the sharded mode too."""
+BASELINE.json's metric / unit, the whole-job `value` and `roofline` (dominant kernel, HIP-event timed, HBM bound, traffic from
+the committed PMC profile).  A plain run stops there; with --full the line also carries `cpu_baseline` (the oracle on the host
+cores, kind "port"), the parity flag and the other legs, and `--gpus 2` without a launcher spawns its own ranks (here: two ranks
+sharing the GPU over gloo) and reports the sharded mode too."""
 import json
 import os
 import subprocess
@@ -23,19 +24,41 @@ def _bench(*args):
     return json.loads(lines[0])
 
 
-def test_single_gpu_line(oracle, tmp_path):
-    d = _bench("--steps", "2", "--warmup", "1", "--fib-n", "3000", "--cpu-sample-n", "3000", "--pipelined", "2", "--big-fib-n", "6000",
-               "--dump-outputs", str(tmp_path))
-    # --dump-outputs: the last timed proof's words, as float64, equal to the oracle's proof of the same input
+def _oracle_words(oracle, fib_n):
     from cairo_m_amd.lib import synth_fibonacci
-    got = np.load(tmp_path / "proof_words.npy")
-    inp = synth_fibonacci(3000)
+    inp = synth_fibonacci(fib_n)
     want, _ = oracle.prove(inp.view)
     inp.free()
-    assert got.dtype == np.float64 and got.size == want.size and np.array_equal(got, want.astype(np.float64))
+    return want.astype(np.float64)
+
+
+FULL_ONLY = ("alt_reading", "pipelined", "with_cached_setup", "sharded", "sharded_one_rank", "end_to_end", "proof_verified",
+             "cpu_baseline", "parity_at_metric_config")
+
+
+def test_plain_line_has_only_the_headline_legs(oracle, tmp_path):
+    # no --full: the headline fields, the roofline of the timed steps and the dumped words; every other leg is null
+    d = _bench("--steps", "2", "--warmup", "1", "--fib-n", "3000", "--dump-outputs", str(tmp_path))
+    got, want = np.load(tmp_path / "proof_words.npy"), _oracle_words(oracle, 3000)
+    assert got.dtype == np.float64 and got.size == want.size and np.array_equal(got, want)
     base = json.load(open(os.path.join(ROOT, "BASELINE.json")))
     assert d["metric"] == base["metric"] and d["unit"] == "M31 trace cells/s" and d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1
-    assert d["higher_is_better"] is True and d["scaling"] == "weak" and d["vs_baseline"] is None and d["dtype"] == "u32" and d["data"] == "synthetic"
+    assert d["higher_is_better"] is True and d["dtype"] == "u32" and d["ms_per_step"] > 0 and d["full"] is False
+    assert abs(d["value"] - d["config"]["cells_per_proof"] / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    r = d["roofline"]
+    assert r["launches"] > 0 and r["stages"] and r["whole_path_model_larger_sizes"] is None
+    assert all(d[k] is None for k in FULL_ONLY), {k: d[k] for k in FULL_ONLY if d[k] is not None}
+
+
+def test_single_gpu_line(oracle, tmp_path):
+    d = _bench("--full", "--steps", "2", "--warmup", "1", "--fib-n", "3000", "--cpu-sample-n", "3000", "--pipelined", "2", "--big-fib-n", "6000",
+               "--dump-outputs", str(tmp_path))
+    # --dump-outputs: the last timed proof's words, as float64, equal to the oracle's proof of the same input
+    got, want = np.load(tmp_path / "proof_words.npy"), _oracle_words(oracle, 3000)
+    assert got.dtype == np.float64 and got.size == want.size and np.array_equal(got, want)
+    base = json.load(open(os.path.join(ROOT, "BASELINE.json")))
+    assert d["metric"] == base["metric"] and d["unit"] == "M31 trace cells/s" and d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1
+    assert d["full"] is True and d["higher_is_better"] is True and d["scaling"] == "weak" and d["vs_baseline"] is None and d["dtype"] == "u32" and d["data"] == "synthetic"
     assert "workload" in d["config"] and "model" not in d["config"]
     assert abs(d["value"] - d["config"]["cells_per_proof"] / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
     r = d["roofline"]
@@ -67,7 +90,7 @@ def test_single_gpu_line(oracle, tmp_path):
 
 
 def test_gpus_2_self_spawns_and_reports_both_modes():
-    d = _bench("--gpus", "2", "--dist-backend", "gloo", "--force-device", "0", "--steps", "2", "--warmup", "1", "--fib-n", "3000",
+    d = _bench("--full", "--gpus", "2", "--dist-backend", "gloo", "--force-device", "0", "--steps", "2", "--warmup", "1", "--fib-n", "3000",
                "--no-cpu-baseline", "--pipelined", "0")
     assert d["n_gpus"] == 2 and d["cpu_baseline"] is None
     assert abs(d["value"] - 2 * d["config"]["cells_per_proof"] / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]     # whole-job aggregate
@@ -78,7 +101,7 @@ def test_gpus_2_self_spawns_and_reports_both_modes():
 
 def test_a_stuck_sharded_child_costs_only_the_sharded_object():
     # a 1-second limit is shorter than the child's start-up: the child job is killed, the replica line must still be complete
-    d = _bench("--gpus", "2", "--dist-backend", "gloo", "--force-device", "0", "--steps", "1", "--warmup", "1", "--fib-n", "3000",
+    d = _bench("--full", "--gpus", "2", "--dist-backend", "gloo", "--force-device", "0", "--steps", "1", "--warmup", "1", "--fib-n", "3000",
                "--no-cpu-baseline", "--pipelined", "0", "--sharded-timeout", "1")
     assert d["n_gpus"] == 2 and d["value"] > 0 and d["proof_verified"] is True
     assert "error" in d["sharded"] and "killed" in d["sharded"]["error"]

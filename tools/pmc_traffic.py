@@ -4,8 +4,8 @@ TCC has 4 slots, FETCH_SIZE takes 3 and WRITE_SIZE 2 — /opt/skills/guides/MI35
 
 usage: pmc_traffic.py <fetch_results.db> <write_results.db> --proofs N [--json out.json]
 
-  rocprofv3 --kernel-trace --pmc FETCH_SIZE -d gpurun_out/pmc_fetch -o f -- python bench.py --steps 1 --warmup 1 ...
-  rocprofv3 --kernel-trace --pmc WRITE_SIZE -d gpurun_out/pmc_write -o w -- python bench.py --steps 1 --warmup 1 ...
+  rocprofv3 --kernel-trace --pmc FETCH_SIZE -d pmc_fetch -o f -- python bench.py --full --steps 1 --warmup 1 ...
+  rocprofv3 --kernel-trace --pmc WRITE_SIZE -d pmc_write -o w -- python bench.py --full --steps 1 --warmup 1 ...
 
 Both counters are in KiB.  gfx950 correction (same guide, §HBM): FETCH_SIZE reports half of the bytes of a
 coalesced streaming read, so  hbm_bytes = (2 * FETCH_SIZE + WRITE_SIZE) * 1024.  The factor is calibrated in

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """GPU-idle gaps of the LAST proof in a rocprofv3 kernel + memory-copy trace (csv output):
-   rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d DIR -- python bench.py --steps 3 --warmup 2 --pipelined 0 --no-kprof
+   rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d DIR -- python bench.py --full --steps 3 --warmup 2 --pipelined 0 --no-kprof
    tools/timeline_gaps.py DIR/<host>/<pid>_kernel_trace.csv DIR/<host>/<pid>_memory_copy_trace.csv [--list]
 Prints span / busy / idle and the largest gaps with the events around them (development tool)."""
 import csv, re, sys
@@ -17,8 +17,8 @@ ev.sort()
 gi = [i for i, e in enumerate(ev) if 'k_tail_gather' in e[2]]   # device-side tail (round 5): the last kernel of a proof
 if not gi:
     gi = [i for i, e in enumerate(ev) if 'k_grind' in e[2]]
-# a proof has ONE k_grind launch (the final PoW; the interaction PoW is part of k_step_pow_relations).  bench.py's LAST proof is
-# the verification proof made on the main host thread (cold device pool: hipMallocs), so the proof analysed is the one before
+# a proof has ONE k_grind launch (the final PoW; the interaction PoW is part of k_step_pow_relations).  bench.py --full's LAST proof
+# is the verification proof made on the main host thread (cold device pool: hipMallocs), so the proof analysed is the one before
 # it: the last TIMED proof.
 def proof_start(after_grind):
     i = after_grind + 1
