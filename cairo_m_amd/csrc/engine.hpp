@@ -262,12 +262,14 @@ struct DevBuf {
 // synchronised and until the next call on this thread.
 const void* stage_download_async(const void* src, size_t bytes, hipStream_t st);
 void* stage_landing(size_t bytes, hipStream_t st);   // the buffer alone (>= bytes): the caller enqueues its own copies into it
-// 1024 pinned words per host thread; fixed slots (words): 0 range-check flag, 2-3 grind nonce, 8-15 Merkle root,
-// 16-23 root of tree 0, 32-167 claimed sums, 172-175 random coefficient + 176-183 root of tree 2 (one copy), 208-219 the OODS felt + root 3 of the device-side step, 256-351 FRI challenges, 384-575 FRI roots, 640-1023 last FRI layer
+// PIN_WORDS pinned words per host thread; fixed slots (words): 0 range-check flag, 2-3 grind nonce, 8-15 Merkle root,
+// 16-23 root of tree 0, 32-167 claimed sums, 172-175 random coefficient + 176-183 root of tree 2 (one copy), 208-219 the OODS felt + root 3 of the device-side step, 256-351 FRI challenges, 384-575 FRI roots, 640-1023 last FRI layer;
+// (the last layer's slot ends at PIN_LAST_LAYER_END: a longer one goes through the batched gather, fri_phase.hip);
+// the sharded prover's own, behind it: 1024-2127 every rank's claimed sums, 2176-8191 the row-sharded FRI layers' challenges, roots and sub-roots
 uint32_t* pinned_words();
 constexpr uint32_t INTERACTION_POW_BITS = 2;   // relations::INTERACTION_POW_BITS (prover.rs:90, verifier.rs:55-58)
 enum PinnedSlot : uint32_t { PIN_FLAG = 0, PIN_NONCE = 2, PIN_ROOT = 8, PIN_ROOT0 = 16, PIN_SUMS = 32, PIN_COEFF = 172, PIN_ROOT2 = 176, PIN_STEP1 = 192, PIN_STEP3 = 208, PIN_ALPHAS = 256, PIN_ROOTS = 384,
-                            PIN_LAST_LAYER = 640, PIN_WORDS = 1024 };
+                            PIN_LAST_LAYER = 640, PIN_LAST_LAYER_END = 1024, PIN_SHARD_SUMS = 1024, PIN_SHARD_FRI = 2176, PIN_WORDS = 8192 };
 // Small host->device uploads (pointer arrays, coefficients, positions) go through a pinned staging ring
 // and hipMemcpyAsync on the launch stream: no host sync, no pageable-copy stall.
 template <class T>

@@ -251,8 +251,8 @@ void FriPhase::commit_finish(Prover& P, const cm_pcs_config& cfg, ProofData& pf,
     const uint32_t* h_alphas = pinned_words() + PIN_ALPHAS;
     const uint32_t* h_roots = h_alphas + (size_t)(n_inner + 1) * 4;
     if (!from_pinned) CM_HIP(hipMemcpyAsync((void*)h_alphas, d_ar.p, (size_t)(n_inner + 1) * 48, hipMemcpyDeviceToHost, st));
-    if (from_pinned || 4 * n <= PIN_WORDS - PIN_LAST_LAYER) {
-      CM_CHECK(4 * n <= PIN_WORDS - PIN_LAST_LAYER, "fri: last layer does not fit the pinned slot");
+    if (from_pinned || 4 * n <= PIN_LAST_LAYER_END - PIN_LAST_LAYER) {
+      CM_CHECK(4 * n <= PIN_LAST_LAYER_END - PIN_LAST_LAYER, "fri: last layer does not fit the pinned slot");
       uint32_t* ll = pinned_words() + PIN_LAST_LAYER;
       if (!from_pinned) {
         if (c4[1] == c4[0] + n && c4[2] == c4[0] + 2 * n && c4[3] == c4[0] + 3 * n) CM_HIP(hipMemcpyAsync(ll, c4[0], n * 16, hipMemcpyDeviceToHost, st));   // one arena

@@ -290,12 +290,12 @@ void* tail_pinned(int which, size_t bytes) {
 void* tail_pinned_desc(size_t bytes) { return tail_pinned(0, bytes); }
 void* tail_pinned_out(size_t bytes) { return tail_pinned(1, bytes); }
 
-// 1024 pinned words per host thread for the small fixed-slot results of a proof (flag, nonce, roots, claimed sums,
+// PIN_WORDS pinned words per host thread for the small fixed-slot results of a proof (flag, nonce, roots, claimed sums,
 // FRI challenges): copies into pageable memory block the caller and cost 15-25 us each
 uint32_t* pinned_words() {
   static thread_local uint32_t* p = nullptr;
   if (!p) {
-    CM_HIP(hipHostMalloc((void**)&p, 4096, hipHostMallocDefault));
+    CM_HIP(hipHostMalloc((void**)&p, PIN_WORDS * 4, hipHostMallocDefault));
     uint32_t* own = p;
     at_thread_exit([own] { (void)hipHostFree(own); });
   }

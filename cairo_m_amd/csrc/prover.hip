@@ -5,6 +5,7 @@
 // quotients, FRI folds, PoW search, decommit gathers) is a kernel.  No CPU fallback exists.
 #include "../../include/cairom_hip.h"
 #include "prover_common.hpp"
+#include "quotient_plan.hpp"
 #include "air_kernels.hpp"
 #include "gpu_air.hpp"
 #include "point_eval.hpp"
@@ -300,15 +301,23 @@ static int fork_width(int dflt) {
 // CM_HOST_TRACE=1: host-side time between marks on stderr (where the GPU sits idle waiting for the host)
 // (the split of the sampled values, per mille in the chunk evaluated and hashed first: tuning key "oods_split", 780)
 struct HostTrace {
-  bool on = getenv("CM_HOST_TRACE") != nullptr || getenv("CM_HOST_MARKS") != nullptr;   // MARKS: no synchronising ticks
+  const char* prefix; int width; bool on;
   std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+  HostTrace(const char* prefix_, int width_, const char* env, const char* env2 = nullptr)   // env2 = CM_HOST_MARKS: no synchronising ticks
+      : prefix(prefix_), width(width_), on(getenv(env) != nullptr || (env2 && getenv(env2) != nullptr)) {}
   void mark(const char* what) {
     if (!on) return;
     auto n = std::chrono::steady_clock::now();
-    fprintf(stderr, "[host] %-40s %8.1f us\n", what, std::chrono::duration<double, std::micro>(n - t).count());
+    fprintf(stderr, "%s %-*s %8.1f us\n", prefix, width, what, std::chrono::duration<double, std::micro>(n - t).count());
     t = n;
   }
 };
+// the PcsConfig ranges both provers accept (max_log: the largest trace column)
+static void check_pcs_config(const cm_pcs_config& cfg, uint32_t max_log) {
+  CM_CHECK(cfg.n_queries >= 1 && cfg.n_queries <= 4096, "PcsConfig: n_queries must be in 1..4096");
+  CM_CHECK(cfg.pow_bits <= 64, "PcsConfig: pow_bits must be at most 64");
+  CM_CHECK(cfg.log_last_layer_degree_bound <= max_log, "PcsConfig: log_last_layer_degree_bound exceeds the largest trace column");
+}
 // One segment proof on one GPU: the phases of prove_cairo_m (prover.rs:23-147) in transcript order.  Each phase enqueues its
 // kernels and returns at the next point where the transcript needs a device result; what crosses a phase boundary is a member.
 struct SegmentProver {
@@ -317,7 +326,7 @@ struct SegmentProver {
   const cm_pcs_config cfg;
   std::unique_ptr<ProofData> out;
   ProofData& pf;
-  HostTrace ht;
+  HostTrace ht{"[host]", 40, "CM_HOST_TRACE", "CM_HOST_MARKS"};
   struct DtorMark { HostTrace* ht; const char* what; ~DtorMark() { ht->mark(what); } };   // (CM_HOST_MARKS: where the teardown goes)
   DtorMark dm_p{&ht, "~ everything else (P: trees, events)"};
   Prover P;
@@ -355,12 +364,7 @@ struct SegmentProver {
   bool oods_poll = false;                    // the host watches the landing words of the sampled values instead of waiting for an event
   static void cpu_relax() { __builtin_ia32_pause(); }
   size_t n_oods_out0 = 0, n_flat0 = 0;       // sampled values / flat samples of chunk 0 (the part hashed while chunk 1 is evaluated)
-  struct QRef { int t; uint32_t c; };
-  struct QEntry { uint32_t col; uint32_t sidx; };   // column of the group, index of its sampled value in d_oods_out
-  struct QBatch { CPoint<QM31> pt; std::vector<QEntry> entries; };
-  struct QGroup { uint32_t log = 0; std::vector<const uint32_t*> cols; std::vector<QBatch> batches; ColumnSet out;
-                  size_t o_cols = 0, o_out = 0, o_ci = 0, o_cc = 0, o_qb = 0, o_sidx = 0, o_ep = 0; };
-  std::vector<QGroup> qg;                    // DEEP-quotient size groups
+  std::vector<QuotientGroup> qg;             // DEEP-quotient size groups (quotient_plan.hpp)
   AffinityScope cpu_scope;   // the calling thread sits next to the GPU for this proof only (pool.hip)
   SegmentProver(const DeviceInput& din_, const cm_pcs_config& cfg_)
       : din(din_), in(din_.meta), cfg(cfg_), out(new ProofData()), pf(*out), st(nullptr), ch(P.ch) {
@@ -413,7 +417,7 @@ struct SegmentProver {
     ht.mark("finish: done");
     return out.release();
   }
-  struct Parked { FriPhase fri; std::vector<QGroup> qg; std::vector<OJob> ojobs; std::vector<ColumnSet> quotients; };
+  struct Parked { FriPhase fri; std::vector<QuotientGroup> qg; std::vector<OJob> ojobs; std::vector<ColumnSet> quotients; };
   static std::unique_ptr<Parked>& parked() {
     static thread_local std::unique_ptr<Parked> g;
     static thread_local bool hooked = false;
@@ -438,9 +442,7 @@ struct SegmentProver {
     std::stable_sort(by_size.begin(), by_size.end(), bigger);
     std::stable_sort(by_size_all.begin(), by_size_all.end(), bigger);
     comp_log = max_log + 1;
-    CM_CHECK(cfg.n_queries >= 1 && cfg.n_queries <= 4096, "PcsConfig: n_queries must be in 1..4096");
-    CM_CHECK(cfg.pow_bits <= 64, "PcsConfig: pow_bits must be at most 64");
-    CM_CHECK(cfg.log_last_layer_degree_bound <= max_log, "PcsConfig: log_last_layer_degree_bound exceeds the largest trace column");
+    check_pcs_config(cfg, max_log);
     if (tw_cache_enabled()) P.tw = cached_twiddles(comp_log + cfg.log_blowup_factor, st);
     else {
       tw_fork.reset(new Fork(st));
@@ -736,8 +738,7 @@ struct SegmentProver {
       // the host only waits for THIS copy (an event), after the tree-2 transforms and hashes have been enqueued behind it:
       // no GPU idle time while the host reads and mixes the 34 sums
       static thread_local hipEvent_t ev_sums = nullptr;
-      if (!ev_sums) { CM_HIP(hipEventCreateWithFlags(&ev_sums, hipEventDisableTiming)); thread_event_owned(ev_sums); }
-      CM_HIP(hipEventRecord(ev_sums, sf));
+      CM_HIP(hipEventRecord(thread_event(ev_sums), sf));
       sums_ready = ev_sums;
       late.ready = ev_sums;
     }
@@ -1101,8 +1102,7 @@ struct SegmentProver {
       chan_mix_root_draw(d_chan, P.trees[3].merkle.layers[0].u32(), d_step3.u32(), d_step3.u32() + 4, st);
       // root 3 and the felt come back HERE in stream order — in front of the evaluation kernels enqueued next
       CM_HIP(hipMemcpyAsync(pinned_words() + PIN_STEP3, d_step3.p, 48, hipMemcpyDeviceToHost, st));   // {felt[4], root 3 [8]}: one copy
-      if (!ev_root3) { CM_HIP(hipEventCreateWithFlags(&ev_root3, hipEventDisableTiming)); thread_event_owned(ev_root3); }
-      CM_HIP(hipEventRecord(ev_root3, st));
+      CM_HIP(hipEventRecord(thread_event(ev_root3), st));
       std::vector<EapJob> ej[2];
       for (auto& j : ojobs) {
         EapJob e{j.log, (uint32_t)j.refs.size(), d_oods_table.as<const uint32_t*>() + j.off, QM31(), QM31(), d_oods_out.u32() + 4 * j.out_off};
@@ -1128,8 +1128,7 @@ struct SegmentProver {
       if (n_oods_out0 && !host_write) CM_HIP(hipMemcpyAsync(land, d_oods_out.p, n_oods_out0 * 16, hipMemcpyDeviceToHost, st));
       if (!ej[1].empty()) {
         if (!oods_poll) {
-          if (!ev_chunk0) { CM_HIP(hipEventCreateWithFlags(&ev_chunk0, hipEventDisableTiming)); thread_event_owned(ev_chunk0); }
-          CM_HIP(hipEventRecord(ev_chunk0, st));
+          CM_HIP(hipEventRecord(thread_event(ev_chunk0), st));
         }
         chunk0_event = true;
         eval_at_point_multi(ej[1], st, d_step3.u32());
@@ -1158,16 +1157,6 @@ struct SegmentProver {
     ch.mix_root(P.trees[3].root);
     ht.mark("composition: host replay of the coefficient step");
     if (!dev_oods) P.tick("composition_commit");
-
-    // host side of compute_fri_quotients for every size group, packed into ONE upload:
-    // [column pointers | out pointers | col_index | coef_c | batches] per group, 16-byte aligned
-    std::vector<uint8_t> qblob;
-    auto qput = [&](const void* ptr, size_t bytes) {
-      size_t o = (qblob.size() + 15) & ~(size_t)15;
-      qblob.resize(o + bytes);
-      if (bytes && ptr) memcpy(qblob.data() + o, ptr, bytes);
-      return o;
-    };
 
     ht.mark("(composition commit done)");
     // ---- OODS sampling ----
@@ -1205,66 +1194,18 @@ struct SegmentProver {
         for (auto& r : j.refs) pf.sampled_values[r.t][r.c].push_back(QM31());   // mask order [-1, 0]: sized now, filled below
       size_t n_samples = 0;
       for (auto& t : pf.sampled_values) for (auto& c : t) n_samples += c.size();
-      std::map<uint32_t, std::vector<QRef>, std::greater<uint32_t>> qgroups;  // LDE log -> columns (tree-major order)
-      for (int t = 0; t < 4; t++)
-        for (uint32_t c = 0; c < P.trees[t].lde.size(); c++) qgroups[P.trees[t].lde.logs[c]].push_back({t, c});
-      for (auto& kv : qgroups) {
-        QGroup g;
-        g.log = kv.first;
-        for (uint32_t i = 0; i < kv.second.size(); i++) {
-          const QRef& r = kv.second[i];
-          g.cols.push_back(P.trees[r.t].lde.ptrs[r.c]);
-          const size_t ns = pf.sampled_values[r.t][r.c].size();
-          for (size_t k = 0; k < ns; k++) {
-            // sample points: [oods] or [prev, oods]
-            CPoint<QM31> pt = (ns == 2 && k == 0) ? prev_points[P.trees[r.t].coeffs.logs[r.c]] : oods;
-            size_t bi = 0;
-            for (; bi < g.batches.size(); bi++) if (g.batches[bi].pt.x == pt.x && g.batches[bi].pt.y == pt.y) break;
-            if (bi == g.batches.size()) g.batches.push_back(QBatch{pt, {}});
-            g.batches[bi].entries.push_back(QEntry{i, (ns == 2 && k == 0) ? sidx_prev[r.t][r.c] : sidx_cur[r.t][r.c]});
-          }
-        }
-        if (framing().sample_batch_sorted)   // ColumnSampleBatch::new_vec as a BTreeMap keyed by point (framing.hpp)
-          std::stable_sort(g.batches.begin(), g.batches.end(), [](const QBatch& a, const QBatch& b) { return secure_point_less(a.pt, b.pt); });
-        size_t n_entries = 0;
-        for (auto& bt : g.batches) n_entries += bt.entries.size();
-        g.out.alloc(std::vector<uint32_t>(4, g.log), st, false);
-        g.o_cols = qput(g.cols.data(), g.cols.size() * sizeof(void*));
-        g.o_out = qput(g.out.ptrs.data(), 4 * sizeof(void*));
-        {
-          std::vector<uint32_t> ci, si;
-          std::vector<const uint32_t*> ep;   // per entry: the column pointer itself
-          std::vector<QuotientBatch> qb(g.batches.size());
-          for (size_t bi = 0; bi < g.batches.size(); bi++) {
-            memset(&qb[bi], 0, sizeof(QuotientBatch));
-            qb[bi].begin = (uint32_t)ci.size();
-            for (auto& en : g.batches[bi].entries) { ci.push_back(en.col); si.push_back(en.sidx); ep.push_back(g.cols[en.col]); }
-            qb[bi].end = (uint32_t)ci.size();
-            g.batches[bi].pt.x.to_u32(qb[bi].point);   // words = (Pr.x, Pi.x): QM31 = (a.a, a.b, b.a, b.b)
-            g.batches[bi].pt.y.to_u32(qb[bi].point + 4);
-          }
-          g.o_ci = qput(ci.data(), ci.size() * 4);
-          g.o_ep = qput(ep.data(), ep.size() * sizeof(void*));
-          g.o_sidx = qput(si.data(), si.size() * 4);
-          g.o_cc = qput(nullptr, n_entries * 16);            // filled by k_quotient_coeffs
-          g.o_qb = qput(qb.data(), qb.size() * sizeof(QuotientBatch));   // sums / batch coefficient filled on the device
-        }
-        n_qjobs += g.batches.size();
-        qg.push_back(std::move(g));
-      }
-      {  // the whole plan goes to the device now, behind the OODS kernels; only the random coefficient is still missing
-        o_qjobs = qput(nullptr, n_qjobs * sizeof(QuotientCoefJob));
-        d_qblob.alloc(qblob.size());
-        uint8_t* base = d_qblob.as<uint8_t>();
-        QuotientCoefJob* qj = (QuotientCoefJob*)(qblob.data() + o_qjobs);
-        size_t k = 0;
-        for (auto& g : qg)
-          for (size_t bi = 0; bi < g.batches.size(); bi++, k++) {
-            qj[k].qb = (QuotientBatch*)(base + g.o_qb) + bi;
-            qj[k].coef_c = (uint32_t*)(base + g.o_cc);
-            qj[k].sample_idx = (const uint32_t*)(base + g.o_sidx);
-          }
-        stage_upload(d_qblob.p, qblob.data(), qblob.size(), st);
+      // compute_fri_quotients' host side (quotient_plan.hpp): to the device now, behind the OODS kernels; only the random coefficient is missing
+      {
+        std::vector<QuotientCol> qcols;
+        for (int t = 0; t < 4; t++)
+          for (uint32_t c = 0; c < P.trees[t].lde.size(); c++) qcols.push_back({t, c, P.trees[t].lde.logs[c], P.trees[t].lde.ptrs[c]});
+        QuotientPlan plan;
+        plan.build(qcols, pf.sampled_values, sidx_cur, sidx_prev, oods, prev_points, cfg.log_blowup_factor, QuotientWindow(), st);
+        d_qblob.alloc(plan.blob.size());
+        plan.bind(d_qblob.as<uint8_t>());
+        stage_upload(d_qblob.p, plan.blob.data(), plan.blob.size(), st);
+        o_qjobs = plan.o_jobs; n_qjobs = plan.n_jobs;
+        qg = std::move(plan.groups);
       }
       ht.mark("oods: overlapped quotient planning");
       // channel.mix_felts(flattened sampled values): chunk 0 is hashed as soon as it has landed, while chunk 1 is evaluated
@@ -1336,26 +1277,12 @@ struct SegmentProver {
       KProfRegion kregq("k_quotients", st);   // concurrent launches: timed as one interval
       Fork fkq(st);
       int qk = 0;
-      std::vector<std::pair<QuotientArgs, double>> qargs;
-      for (auto& g : qg) {
-        QuotientArgs a;
-        a.tw = view(*P.tw); a.log_size = g.log;
-        a.cols = (const uint32_t* const*)(base + g.o_cols);
-        a.out = (uint32_t* const*)(base + g.o_out);
-        a.col_index = (const uint32_t*)(base + g.o_ci);
-        a.entry_cols = (const uint32_t* const*)(base + g.o_ep);
-        a.coef_c = (const uint32_t*)(base + g.o_cc);
-        a.batches = (const QuotientBatch*)(base + g.o_qb);
-        a.n_batches = (uint32_t)g.batches.size();
-        qargs.push_back({a, (double)g.cols.size()});
-        q_logs.push_back(g.log);
-        quotients.push_back(std::move(g.out));
-      }
+      std::vector<std::pair<QuotientArgs, double>> qargs = quotient_args(qg, base, *P.tw);
+      for (auto& g : qg) { q_logs.push_back(g.log); quotients.push_back(std::move(g.out)); }
       // (round 6) The FRI first-layer tree's leaf layer — 2^log hashes of four words each, 8.4 M compressions at the metric config,
       // 0.21 ms as a launch of its own with the GPU otherwise idle — is written by the quotient kernel of the LARGEST size group:
       // that kernel waits on HBM (4 B per LDE cell in, 4.1 TB/s) and its VALU ports are half idle.  "quot_leaf" = 0: separate launch.
-      if (tune(T_QUOT_LEAF) != 0 && !qargs.empty() && (qargs.size() == 1 || qargs[1].first.log_size < qargs[0].first.log_size) &&
-          quotient_leaf_serves(qargs[0].first)) {
+      if (quotient_leaf_wanted(qargs)) {
         fri.first_tree.leaf_prealloc.alloc((size_t)32 << qargs[0].first.log_size);
         qargs[0].first.leaf_hashes = fri.first_tree.leaf_prealloc.u32();
         fri.first_leaf_done = true;

@@ -76,6 +76,10 @@ constexpr uint32_t FFT_CHUNK_MB_DEFAULT = 0;   // Infinity-Cache blocking of the
 inline std::atomic<int> g_transcript_log{0};     // cm_set_transcript_log: proofs record every Fiat-Shamir step (ProofData::transcript)
 inline std::atomic<int> g_proofs_in_flight{0};   // proofs being made by cm_prove_many runners right now (0 outside of it)
 inline void thread_event_owned(hipEvent_t e) { at_thread_exit([e] { (void)hipEventDestroy(e); }); }   // destroyed when the creating thread ends
+inline hipEvent_t thread_event(hipEvent_t& ev) {   // a (thread_local) event of the calling thread, made on first use
+  if (!ev) { CM_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); thread_event_owned(ev); }
+  return ev;
+}
 struct Prover {
   FramingUse framing_use;   // the process-wide framing cannot change while this proof is being made (framing.hpp)
   hipStream_t st = 0;

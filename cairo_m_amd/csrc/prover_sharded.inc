@@ -1,6 +1,6 @@
 // Intra-proof sharding: `world` ranks (one process per GPU) prove ONE segment (SURVEY §8e-2, BASELINE configs[3]).
-// Included by prover.hip (same translation unit: it reuses ColumnSet / CommittedTree / Prover and the FRI code shape of
-// prove()).  Reference units being sharded: the components of `Components::provers()` (components/mod.rs:420-431) for
+// Included by prover.hip (same translation unit: it reuses ColumnSet / CommittedTree / Prover); the driver is `ShardedProver` at the
+// end of this file, phase by phase like prover.hip's SegmentProver.  Reference units being sharded: the components of `Components::provers()` (components/mod.rs:420-431) for
 // everything that is per-component in prove_cairo_m (write_trace, write_interaction_trace, interpolate / evaluate,
 // evaluate_constraint_quotients_on_domain, eval_at_point), and ROW RANGES of the evaluation domain for what needs every
 // column of a row (Merkle leaf hashing, accumulate_quotients).
@@ -258,8 +258,7 @@ static void enqueue_sliced(const ShardComm& cm, SlicedTree& out) {
 // the gathered sub-roots -> pinned words behind an event (complete_sliced(cm, out, later) waits for it)
 static void sliced_land_later(const ShardComm& cm, SlicedLater& later) {
   static thread_local hipEvent_t ev = nullptr;
-  if (!ev) { CM_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); thread_event_owned(ev); }
-  later.ev = ev;
+  later.ev = thread_event(ev);
   later.land = pinned_words() + PIN_LAST_LAYER + 128;   // (8 N <= 64 words; the FRI phase, much later, owns the slot again)
   CM_HIP(hipMemcpyAsync(later.land, cm.c->recv_buf, 8 * cm.N * 4, hipMemcpyDeviceToHost, cm.st));   // behind the collective
   CM_HIP(hipEventRecord(ev, cm.st));
@@ -486,259 +485,176 @@ struct ShardedFriLayer { uint32_t log = 0; ColumnSet slice; SlicedTree tree; };
 // 99 = the replicated FRI of rounds 2-3)
 static uint32_t shard_fri_stop_log() { return (uint32_t)tune(T_SHARD_FRI_STOP_LOG); }   // (tuning key "shard_fri_stop_log", default 16)
 
-// host-side marks of one sharded proof (CM_SHARD_MARKS=1: microseconds of host time between the marks, to stderr; development aid)
-struct ShardMarks {
-  const bool on = getenv("CM_SHARD_MARKS") != nullptr;
-  std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-  void mark(const char* name) {
-    if (!on) return;
-    const auto n = std::chrono::steady_clock::now();
-    fprintf(stderr, "[shard] %-44s %8.1f us\n", name, std::chrono::duration<double, std::micro>(n - t).count());
-    t = n;
-  }
-};
-
-ProofData* prove_sharded(const DeviceInput& din, const cm_pcs_config& cfg, const cm_comm& comm_c) {
-  ShardMarks hm;
-  const cm_prover_input& in = din.meta;
-  std::unique_ptr<ProofData> out(new ProofData());
-  ProofData& pf = *out;
-  pf.config = cfg;
-  bind_thread_to_library_device();
-  release_thread_parked();   // a single-GPU proof of this thread may have parked its FRI phase and quotient columns (prover.hip)
+// One proof sharded over the ranks: the eight phases of prover.hip's SegmentProver, in transcript order.  Each phase enqueues its
+// kernels and collectives and returns at the next point where the transcript needs a device result.  What crosses a phase boundary
+// is a member, declared in the order in which it is made: members die in reverse order, and that order is behaviour (every Fork
+// dies before `P`; see the guards).  The private methods named like the old lambdas (commit_own, sums_arrive, check_halo,
+// fri_replay, check_flags) are where a later phase finishes an earlier phase's wait.
+struct ShardedProver {
+  HostTrace hm{"[shard]", 44, "CM_SHARD_MARKS"};   // host time between the marks of one sharded proof (development aid)
+  const DeviceInput& din; const cm_prover_input& in;
+  const cm_pcs_config cfg; const cm_comm& comm_c;
+  std::unique_ptr<ProofData> out; ProofData& pf;
   AffinityScope cpu_scope;   // restored when the proof returns (pool.hip)
   Prover P;
-  if (g_transcript_log.load()) P.ch.log.p = &pf.transcript;
-  P.cfg = cfg;
-  P.st = thread_main_stream();
-  hipStream_t st = P.st;
-  P.start();
-  Channel& ch = P.ch;
-  ShardComm cm{&comm_c, st, comm_c.world, comm_c.rank, 0};
-  cm.bind();   // a stream-ordered comm enqueues its collectives on this proof's stream
-  CM_CHECK(cm.N >= 1 && cm.N <= 8 && (cm.N & (cm.N - 1)) == 0 && cm.r < cm.N, "cm_prove_sharded: world must be 1, 2, 4 or 8");
-  while ((1u << cm.logN) < cm.N) cm.logN++;
-  const uint32_t N = cm.N, R = cm.r, logN = cm.logN;
-  // log_blowup_factor B: the commitment domain of a column of 2^log rows is CanonicCoset(log + B); the constraints are evaluated
-  // on CanonicCoset(log + 1).  With B = 1 (REGULAR_96_BITS) that IS the committed LDE; with B > 1 every owner evaluates its
-  // polynomials on the (log + 1) domain separately, as Stwo and the single-GPU prover do — and components stay whole (the
-  // row-range constraints of a split component read the committed LDE slices the exchange leaves on every rank).
-  const uint32_t B = cfg.log_blowup_factor;
-  CM_CHECK(B >= 1 && B <= 4, "PcsConfig: log_blowup_factor must be in 1..4");
-  CM_CHECK(cfg.n_queries >= 1 && cfg.n_queries <= 4096 && cfg.pow_bits <= 64, "PcsConfig out of range");
-
-  uint32_t clog[air::N_COMPONENTS];
-  component_logs(in, clog);
-  uint32_t max_log = 0;
-  for (int c = 0; c < air::N_COMPONENTS; c++) { max_log = std::max(max_log, clog[c]); CM_CHECK(clog[c] <= 26, "component too large"); }
-  CM_CHECK(cfg.log_last_layer_degree_bound <= max_log, "PcsConfig: log_last_layer_degree_bound exceeds the largest trace column");
-  const uint32_t comp_log = max_log + 1;
-  const ShardPlan plan = make_shard_plan(clog, N, /*allow_split=*/B == 1);
+  hipStream_t st; Channel& ch; ShardComm cm;
+  const uint32_t N, R, B;                    // ranks, this rank, log_blowup_factor
+  uint32_t logN = 0, clog[air::N_COMPONENTS], max_log = 0, comp_log = 0;
+  ShardPlan plan;
+  const std::vector<int>&tr_owner, &it_owner;   // plan.tr_owner / plan.it_owner
   std::vector<int> by_size;   // launch order of the fork regions: components by descending size (stable), as in the single-GPU prover
-  for (int c = 0; c < air::N_COMPONENTS; c++) by_size.push_back(c);
-  std::stable_sort(by_size.begin(), by_size.end(), [&](int x, int y) { return clog[x] > clog[y]; });
-  const int* owner = plan.owner;                                    // -1: the component is split over all ranks (ShardPlan)
-  auto mine = [&](int c) { return owner[c] == (int)R; };           // whole components of this rank
-  auto split = [&](int c) { return plan.split(c); };
-  // (round 6) "shard_tree_stream": the commitment trees' transcript steps stay ON THE STREAM like the sharded FRI layers' — behind a
-  // tree's sub-root all-gather k_shard_top hashes the top log2 N levels on the device and the single-GPU prover's transcript kernels
-  // take the root from there: k_step_pow_relations behind tree 1 (mix_root, interaction proof of work, Relations::draw -> the LogUp
-  // kernels start), k_chan_init_mix_root_draw + k_coeff_powers behind tree 2 (-> the constraint kernels start), k_chan_mix_root_draw
-  // behind tree 3 (-> the OODS evaluations start from the felt in device memory).  The host rebuilds the top levels from the copied-
-  // back sub-roots and replays every step at the two synchronisation points that are left before FRI (the claimed sums; the sampled
-  // values), refusing the proof on any mismatch.  0 = the host-driven form: a round trip per root, the PoW and the halo check.
-  const bool tree_stream = tune(T_SHARD_TREE_STREAM) != 0 && !framing().hash_node_rfc;
+  bool tree_stream = false;   // "shard_tree_stream", see setup()
+  // the device words of the tree_stream transcript steps (d_ts) ...
   enum : uint32_t { TS_CHAN = 0, TS_COEFF = 16, TS_ROOT2_LOG = 20, TS_ROOT1 = 32, TS_SUB1 = 40, TS_STEP1 = 104, TS_ROOT2 = 120, TS_SUB2 = 128,
                     TS_ROOT3 = 192, TS_SUB3 = 200, TS_STEP3 = 264, TS_WORDS = 280 };
-  DevBuf d_ts;
-  if (tree_stream) d_ts.alloc(TS_WORDS * 4);
-  uint32_t* const ts = d_ts.u32();
-  // pinned landing words of the sub-roots of trees 1 / 2 / 3 (tree 0's sit at + 128; the FRI phase, much later, owns the slot again)
-  uint32_t* const pin_sub1 = pinned_words() + PIN_LAST_LAYER + 192;
-  uint32_t* const pin_sub2 = pinned_words() + PIN_LAST_LAYER + 256;
-  uint32_t* const pin_sub3 = pinned_words() + PIN_LAST_LAYER + 320;
-  static_assert(PIN_LAST_LAYER + 320 + 64 <= PIN_WORDS, "pinned slot layout");
-  uint32_t* const pin_halo_err = pinned_words() + PIN_FLAG + 1;
+  DevBuf d_ts; uint32_t* ts = nullptr;
+  // ... and the pinned words their results land in: the sub-roots of trees 1 / 2 / 3 (tree 0's sit at + 128; the FRI phase, much
+  // later, owns the slot again), the halo exchange's error word, and — dedicated, no other download of the thread lands there —
+  // every rank's claimed sums (PIN_SHARD_SUMS, read by sums_arrive) and the sharded FRI layers' words (PIN_SHARD_FRI, fri_replay)
+  enum : uint32_t { PIN_SUB1 = PIN_LAST_LAYER + 192, PIN_SUB2 = PIN_LAST_LAYER + 256, PIN_SUB3 = PIN_LAST_LAYER + 320, PIN_HALO_ERR = PIN_FLAG + 1,
+                    SW = air::N_COMPONENTS * 4 + 2 /* a rank's words in the sums' exchange: sums, lookup flag, FRI plan */ };
+  static_assert(PIN_SUB3 + 64 <= PIN_LAST_LAYER_END && PIN_LAST_LAYER_END <= PIN_SHARD_SUMS && PIN_SHARD_SUMS + SW * 8 <= PIN_SHARD_FRI && PIN_SHARD_FRI < PIN_WORDS, "pinned slot layout");
+  uint32_t *pin_sub1 = nullptr, *pin_sub2 = nullptr, *pin_sub3 = nullptr, *pin_halo_err = nullptr;
   ProofTwiddles own_tw;
-  // (round 5) twiddles, constant columns and the transforms of tree 0 on a side stream, like the single-GPU prover: nothing of trace
-  // generation reads them, and both are chains of short launches.  Joined — and tree 0 hashed by row range on the main stream,
-  // where the collectives live — behind the trace kernels.
-  Fork tw_fork(st);
-  hipStream_t s0 = tw_fork.stream(Fork::N - 1);
-  struct DrainOnExit { hipStream_t s = nullptr; bool joined = false; ~DrainOnExit() { if (s && !joined) (void)hipStreamSynchronize(s); } } s0_guard{s0};
-  std::unique_ptr<Fork> pp_fork;   // tree_stream: tree 0's chain (IFFT, LDE, Merkle subtree) forks behind the trace kernels
-  DrainOnExit pp_guard;
-  own_tw.build(comp_log + cfg.log_blowup_factor, s0);
-  P.tw = &own_tw.t;
-
-  // ---- transcript setup (prover.rs:33-36, 62-66) ----
-  pf.public_data = din.public_data;
-  mix_config_and_public_data(ch, cfg, pf.public_data);
-  P.tick("setup");
-  // ---- tree 0 (columns replicated, Merkle hashing row-sharded) ----
-  SlicedTree sl0, sl1, sl2, sl3;
-  SlicedLater sl0_later;
-  ColumnSet pp_evals;
-  {
-    std::vector<uint32_t> logs(air::PREPROC_LOG, air::PREPROC_LOG + air::N_PREPROC);
-    pp_evals.alloc(logs, st);
-    for (int i = 0; i < air::N_PREPROC; i++) launch_preproc(i, logs[i], pp_evals.ptrs[i], s0);
-    // (tree 0's IFFT + LDE — on every rank, hashing by row range — are enqueued BEHIND the trace-generation launches below: issued
-    // here, the host time of that chain of ~15 short launches delayed the first trace kernel by ~0.25 ms, round-6 timeline)
-  }
-  P.tick("preprocessed");
-
-  // ---- column bookkeeping of trees 1 and 2: global order, owner of every column, local (own) column sets ----
-  std::vector<size_t> tr0(air::N_COMPONENTS), it0(air::N_COMPONENTS), ltr0(air::N_COMPONENTS, 0), lit0(air::N_COMPONENTS, 0);
+  std::unique_ptr<Fork> tw_fork; hipStream_t s0 = nullptr;   // twiddles, constant columns, tree 0's transforms (setup .. trace_commit)
+  // An exception between a fork and its join must not hand the buffers declared in FRONT of these guards (own_tw, P.trees[0]) back
+  // to the pool under the side stream's kernels: the guards are declared behind them, so they drain first.
+  struct DrainOnExit { hipStream_t s = nullptr; bool joined = false; ~DrainOnExit() { if (s && !joined) (void)hipStreamSynchronize(s); } } s0_guard;
+  std::unique_ptr<Fork> pp_fork; DrainOnExit pp_guard;   // tree_stream: tree 0's chain (IFFT, LDE, subtree) forks behind the trace kernels
+  // ---- trace_commit ----
+  SlicedTree sl0, sl1, sl2, sl3; SlicedLater sl0_later; ColumnSet pp_evals;
+  std::vector<size_t> tr0, it0, ltr0, lit0;   // first column of every component: trees 1 / 2, global and among this rank's own
   std::vector<uint32_t> tr_logs, it_logs, ltr_logs, lit_logs;
-  const std::vector<int>& tr_owner = plan.tr_owner;
-  const std::vector<int>& it_owner = plan.it_owner;
   std::vector<int> ltr_of, lit_of;      // global column -> index among this rank's own columns (-1: somebody else's)
-  for (int c = 0; c < air::N_COMPONENTS; c++) {
-    tr0[c] = tr_logs.size(); it0[c] = it_logs.size();
-    ltr0[c] = ltr_logs.size(); lit0[c] = lit_logs.size();   // (meaningful for whole components of this rank: their columns are consecutive)
-    for (int k = 0; k < air::component_info(c).n_trace; k++) {
-      const bool own = (uint32_t)tr_owner[tr_logs.size()] == R;
-      ltr_of.push_back(own ? (int)ltr_logs.size() : -1);
-      tr_logs.push_back(clog[c]);
-      if (own) ltr_logs.push_back(clog[c]);
-    }
-    for (int k = 0; k < air::component_info(c).n_interaction; k++) {
-      const bool own = (uint32_t)it_owner[it_logs.size()] == R;
-      lit_of.push_back(own ? (int)lit_logs.size() : -1);
-      it_logs.push_back(clog[c]);
-      if (own) lit_logs.push_back(clog[c]);
-    }
-  }
   // split components: this rank's ROW slice of every trace / interaction column (trace domain, plain row order: row r = bundle r)
   struct SplitComp { int c; uint32_t slog; ColumnSet tr_slice, it_slice, cum_lde, cum_prev; };
   std::vector<std::unique_ptr<SplitComp>> splits;
-  for (int c = 0; c < air::N_COMPONENTS; c++)
-    if (split(c)) { splits.emplace_back(new SplitComp()); splits.back()->c = c; splits.back()->slog = clog[c] - logN; }
-  auto lde_of = [B](std::vector<uint32_t> v) { for (auto& l : v) l += B; return v; };
+  ColumnSet tr_evals;       // own components only (at least a dummy word when this rank owns nothing); released behind tree 2
+  static constexpr size_t HW = ((size_t)1 << 8) + ((size_t)1 << 16) + ((size_t)1 << 20) + ((size_t)1 << 18);
+  DevBuf hist, hist_sum, flag;   // (kept until the proof returns, as ever: the pool then hands later phases the same blocks)
+  CommittedTree own1, own2;       // coefficients + full LDE of the OWN columns of trees 1 and 2
+  HostRelations hrel; DevBuf drel;
+  // ---- interaction ----
+  std::vector<int> my_comps; DevBuf d_sums;   // components whose cumulative-sum columns (and claimed sum) this rank computes
+  std::vector<DevBuf> tail_scratch;     // scratch of the LogUp tail when it runs on a side stream: alive until the host has seen the sums
+  Prover::DeferredCols late_cols;       // the running-sum columns of tree 2: transformed behind the tail (late_cols.ready)
+  const uint32_t* sums_land = nullptr;   // pinned: this rank's sums (compact), or every rank's gathered words (sums_gathered)
+  bool sums_gathered = false, halo_pending = false;
+  hipEvent_t ev_sums = nullptr, ev_root3 = nullptr, ev_fri_back = nullptr;
+  ColumnSet it_evals;
+  std::vector<size_t> coff;             // first constraint of every component
+  std::vector<QM31> powers; DevBuf d_powers;
+  // ---- oods_sampling / deep_quotients ----
+  CPoint<QM31> oods;
+  size_t n_cols_t[4] = {0, 0, 0, 0};
+  DevBuf d_oods_out, d_oods_table, d_oods_tmp;   // (kept until the proof returns, like hist)
+  std::vector<uint32_t> q_logs; std::vector<ColumnSet> quotients;
+  std::vector<QuotientGroup> gs;   // the quotient size groups, largest first; out = this rank's rows of the four coordinate columns
+  // ---- FRI: the row-sharded part (first-layer tree + the large inner layers), the replicated rest ----
+  SlicedTree fri_first; std::vector<std::unique_ptr<ShardedFriLayer>> sfl; FriPhase fri;
+  DevBuf d_qblob;                  // the DEEP-quotient plan on the device: released behind the quotient launches
+  size_t o_qjobs = 0, n_qjobs = 0, qi_next = 0, fri_slot_words = 0;
+  std::vector<std::pair<QuotientArgs, double>> qargs;
+  uint32_t last_log = 0, layer_log = 0; QM31 alpha_c;
+  ColumnSet cur;          // this rank's rows of the layer being built
+  bool cur_valid = false, shard_fri = false, fri_stream = false;
+  DevBuf d_fs;                              // {device channel, per tree: challenge, root, sub-roots}: alive until the proof returns
+  const uint32_t* fri_back_land = nullptr;  // pinned: the slots of d_fs, valid behind ev_fri_back
+  std::vector<SlicedTree*> fri_order; const uint32_t *rs_d_chan = nullptr, *rs_d_alpha_c = nullptr;
+  ColumnSet full_layer;   // the hand-over layer, whole, on every rank
+  ShardedProver(const DeviceInput& din_, const cm_pcs_config& cfg_, const cm_comm& comm_)
+      : din(din_), in(din_.meta), cfg(cfg_), comm_c(comm_), out(new ProofData()), pf(*out), st(nullptr), ch(P.ch),
+        cm{&comm_, nullptr, comm_.world, comm_.rank, 0}, N(comm_.world), R(comm_.rank), B(cfg_.log_blowup_factor),
+        tr_owner(plan.tr_owner), it_owner(plan.it_owner) {
+    pf.config = cfg;
+    bind_thread_to_library_device();
+    release_thread_parked();   // a single-GPU proof of this thread may have parked its FRI phase and quotient columns (prover.hip)
+    if (g_transcript_log.load()) P.ch.log.p = &pf.transcript;
+    P.cfg = cfg;
+    st = cm.st = P.st = thread_main_stream();
+    P.start();
+  }
+  ProofData* run() {
+    setup();
+    trace_commit();
+    interaction();
+    composition();
+    oods_sampling();
+    deep_quotients();
+    fri_and_pow();
+    decommit();
+    P.finish();
+    fork_join_check();
+    pf.phase_ms = P.phase_ms;
+    pf.steps = 0;
+    for (int i = 0; i < CM_N_OPCODE_COMPONENTS; i++) pf.steps += in.n_bundles[i];
+    return out.release();
+  }
 
+ private:
+  bool mine(int c) const { return plan.owner[c] == (int)R; }   // whole components of this rank
+  bool split(int c) const { return plan.split(c); }            // the component is split over all ranks (ShardPlan)
+  std::vector<uint32_t> lde_of(std::vector<uint32_t> v) const { for (auto& l : v) l += B; return v; }
+  uint32_t col_log(int t, uint32_t c) const { return t == 0 ? air::PREPROC_LOG[c] : t == 1 ? tr_logs[c] : t == 2 ? it_logs[c] : comp_log; }
+  int col_owner_of(int t, uint32_t c) const { return t == 1 ? tr_owner[c] : t == 2 ? it_owner[c] : 0; }
+  // rank geometry, config checks, the ownership plan, twiddles (side stream), transcript setup (prover.rs:33-66)
+  void setup() {
+    cm.bind();   // a stream-ordered comm enqueues its collectives on this proof's stream
+    CM_CHECK(cm.N >= 1 && cm.N <= 8 && (cm.N & (cm.N - 1)) == 0 && cm.r < cm.N, "cm_prove_sharded: world must be 1, 2, 4 or 8");
+    while ((1u << cm.logN) < cm.N) cm.logN++;
+    logN = cm.logN;
+    // log_blowup_factor B: the commitment domain of a column of 2^log rows is CanonicCoset(log + B); the constraints are evaluated
+    // on CanonicCoset(log + 1).  With B = 1 (REGULAR_96_BITS) that IS the committed LDE; with B > 1 every owner evaluates its
+    // polynomials on the (log + 1) domain separately, as Stwo and the single-GPU prover do — and components stay whole (the
+    // row-range constraints of a split component read the committed LDE slices the exchange leaves on every rank).
+    CM_CHECK(B >= 1 && B <= 4, "PcsConfig: log_blowup_factor must be in 1..4");
+    component_logs(in, clog);
+    for (int c = 0; c < air::N_COMPONENTS; c++) { max_log = std::max(max_log, clog[c]); CM_CHECK(clog[c] <= 26, "component too large"); }
+    check_pcs_config(cfg, max_log);
+    comp_log = max_log + 1;
+    plan = make_shard_plan(clog, N, /*allow_split=*/B == 1);
+    for (int c = 0; c < air::N_COMPONENTS; c++) by_size.push_back(c);
+    std::stable_sort(by_size.begin(), by_size.end(), [&](int x, int y) { return clog[x] > clog[y]; });
+    // (round 6) "shard_tree_stream": the commitment trees' transcript steps stay ON THE STREAM like the sharded FRI layers' — behind a
+    // tree's sub-root all-gather k_shard_top hashes the top log2 N levels on the device and the single-GPU prover's transcript kernels
+    // take the root from there: k_step_pow_relations behind tree 1 (mix_root, interaction proof of work, Relations::draw -> the LogUp
+    // kernels start), k_chan_init_mix_root_draw + k_coeff_powers behind tree 2 (-> the constraint kernels start), k_chan_mix_root_draw
+    // behind tree 3 (-> the OODS evaluations start from the felt in device memory).  The host rebuilds the top levels from the copied-
+    // back sub-roots and replays every step at the two synchronisation points that are left before FRI (the claimed sums; the sampled
+    // values), refusing the proof on any mismatch.  0 = the host-driven form: a round trip per root, the PoW and the halo check.
+    tree_stream = tune(T_SHARD_TREE_STREAM) != 0 && !framing().hash_node_rfc;
+    if (tree_stream) d_ts.alloc(TS_WORDS * 4);
+    ts = d_ts.u32();
+    pin_sub1 = pinned_words() + PIN_SUB1; pin_sub2 = pinned_words() + PIN_SUB2; pin_sub3 = pinned_words() + PIN_SUB3; pin_halo_err = pinned_words() + PIN_HALO_ERR;
+    // (round 5) twiddles, constant columns and the transforms of tree 0 on a side stream, like the single-GPU prover: nothing of trace
+    // generation reads them, and both are chains of short launches.  Joined — and tree 0 hashed by row range on the main stream,
+    // where the collectives live — behind the trace kernels.
+    tw_fork.reset(new Fork(st));
+    s0_guard.s = s0 = tw_fork->stream(Fork::N - 1);
+    own_tw.build(comp_log + cfg.log_blowup_factor, s0);
+    P.tw = &own_tw.t;
+
+    // ---- transcript setup (prover.rs:33-36, 62-66) ----
+    pf.public_data = din.public_data;
+    mix_config_and_public_data(ch, cfg, pf.public_data);
+    P.tick("setup");
+  }
   // every rank must agree on a failure of trace generation: the flags are gathered
   // ... and, in the same exchange, that every rank runs the same FRI plan: CM_SHARD_FRI_STOP_LOG is read per process, and ranks
   // that disagree on it would issue different collectives further down and dead-lock
-  auto check_flags = [&](const std::vector<uint32_t>& all, size_t per_rank, size_t at) {
+  void check_flags(const std::vector<uint32_t>& all, size_t per_rank, size_t at) const {
     for (uint32_t k = 0; k < N; k++) {
       CM_CHECK(all[per_rank * k + at] == 0, "trace generation: a range-check / bitwise lookup value is out of range");
       CM_CHECK(all[per_rank * k + at + 1] == shard_fri_stop_log(), "cm_prove_sharded: CM_SHARD_FRI_STOP_LOG differs between the ranks");
     }
-  };
-  // ---- tree 1: execution trace of the own components ----
-  ColumnSet tr_evals;       // own components only (at least a dummy word when this rank owns nothing)
-  tr_evals.alloc(ltr_logs, st);
-  const size_t HW = ((size_t)1 << 8) + ((size_t)1 << 16) + ((size_t)1 << 20) + ((size_t)1 << 18);
-  DevBuf hist(HW * 4), hist_sum, flag(4);
-  {
-    CM_HIP(hipMemsetAsync(flag.p, 0, 4, st));
-    CM_HIP(hipMemsetAsync(hist.p, 0, HW * 4, st));
-    HistPtrs h;
-    h.rc8 = hist.u32(); h.rc16 = h.rc8 + (1u << 8); h.rc20 = h.rc16 + (1u << 16); h.bitwise = h.rc20 + (1u << 20);
-    h.error_flag = flag.u32();
-    std::vector<SmallTraceJob> small_trace;
-    for (int c = 0; c < air::N_OPCODE_COMPONENTS; c++)
-      if (mine(c) && clog[c] <= SMALL_COMPONENT_MAX_LOG)
-        small_trace.push_back(SmallTraceJob{din.bundles[c].p, (uint32_t)in.n_bundles[c], tr_evals.dev(ltr0[c]), clog[c], c});
-    DevBuf d_small_trace = upload(small_trace, st);
-    {
-      Fork fk(st);   // (round 5) whole components: trace + histogram in one launch each, on side streams (histogram adds commute)
-      if (!small_trace.empty()) launch_trace_hist_small(d_small_trace.as<SmallTraceJob>(), (uint32_t)small_trace.size(), din.data_accesses.p, h, fk.stream(Fork::N - 2));
-      int spos = 0;
-      for (int c : by_size) {   // large components first: the largest on the main stream
-        if (c >= air::N_OPCODE_COMPONENTS || !mine(c) || clog[c] <= SMALL_COMPONENT_MAX_LOG) continue;
-        launch_opcode_trace_hist(c, din.bundles[c].p, (uint32_t)in.n_bundles[c], din.data_accesses.p, clog[c], tr_evals.dev(ltr0[c]), h,
-                                 fk.stream(spos == 0 ? Fork::main_or(0) : spos % (Fork::N - 2)));
-        spos++;
-      }
-      // the builtins' traces inside the region too (the single-GPU prover's placement): they ran one after the other on the main
-      // stream behind the join, ~70 us of launch latency in the round-6 timeline
-      if (mine(air::C_MEMORY))
-        launch_memory_trace(din.init_mem.p, (uint32_t)in.n_initial_memory, din.fin_mem.p, (uint32_t)in.n_final_memory, in.initial_root, in.final_root,
-                            clog[air::C_MEMORY], tr_evals.dev(ltr0[air::C_MEMORY]), fk.stream(air::C_MEMORY));
-      if (mine(air::C_MERKLE))
-        launch_merkle_trace(din.init_tree.p, (uint32_t)in.n_initial_tree, din.fin_tree.p, (uint32_t)in.n_final_tree, in.initial_root, in.final_root,
-                            clog[air::C_MERKLE], tr_evals.dev(ltr0[air::C_MERKLE]), fk.stream(air::C_MERKLE));
-      if (mine(air::C_CLOCK_UPDATE))
-        launch_clock_update_trace(din.clock_updates.p, (uint32_t)in.n_clock_updates, clog[air::C_CLOCK_UPDATE], tr_evals.dev(ltr0[air::C_CLOCK_UPDATE]), fk.stream(air::C_CLOCK_UPDATE));
-      if (mine(air::C_POSEIDON2))
-        launch_poseidon2_trace(din.init_tree.p, (uint32_t)in.n_initial_tree, din.fin_tree.p, (uint32_t)in.n_final_tree, clog[air::C_POSEIDON2],
-                               tr_evals.dev(ltr0[air::C_POSEIDON2]), fk.stream(air::C_POSEIDON2));
-      fk.join();
-    }
-    if (!tree_stream) P.commit_enqueue(P.trees[0], &pp_evals, false, s0, /*with_merkle=*/false);   // tree 0: IFFT + LDE, next to the trace kernels
-    // split components: every rank writes the trace rows of ITS row range (a row is a function of its bundle) and counts their
-    // lookups; the slices then travel to the column owners, which transform whole columns
-    for (auto& sc : splits) {
-      const int c = sc->c;
-      sc->tr_slice.alloc(std::vector<uint32_t>(air::component_info(c).n_trace, sc->slog), st);
-      const uint64_t row0 = (uint64_t)R << sc->slog, nb = in.n_bundles[c];
-      const uint32_t n_local = nb > row0 ? (uint32_t)std::min<uint64_t>(nb - row0, (uint64_t)1 << sc->slog) : 0u;
-      launch_opcode_trace(c, (const uint8_t*)din.bundles[c].p + row0 * sizeof(air::Bundle), n_local, din.data_accesses.p, sc->slog,
-                          sc->tr_slice.dev(), st);
-      launch_hist(c, (const uint32_t* const*)sc->tr_slice.dev(), sc->slog, h, st);
-    }
-    {
-      std::vector<ColMove> mv;
-      for (auto& sc : splits)
-        for (int k = 0; k < air::component_info(sc->c).n_trace; k++) {
-          const size_t j = tr0[sc->c] + k;
-          mv.push_back(ColMove{sc->slog, sc->tr_slice.ptrs[k], tr_owner[j], ltr_of[j] >= 0 ? tr_evals.ptrs[ltr_of[j]] : nullptr});
-        }
-      exchange_to_cols(cm, mv);
-    }
-    // tree 0: its transforms have run next to the kernels above; hashing by row range + sub-root all-gather here, the host part
-    // (top levels, root) at the synchronisation point below — nothing of trace generation needs root 0
-    tw_fork.join();
-    s0_guard.joined = true;
-    if (tree_stream) {
-      // tree 0 whole — transforms AND the Merkle subtree of this rank's rows — on a side stream forked HERE (twiddles joined, trace
-      // kernels launched), next to tree 1's transforms as in the single-GPU prover; only the 32-byte all-gather of its sub-roots
-      // goes on the main stream, behind those transforms (the collectives live there)
-      pp_fork.reset(new Fork(st));
-      hipStream_t s0b = pp_fork->stream(Fork::N - 1);
-      pp_guard.s = s0b;
-      P.commit_enqueue(P.trees[0], &pp_evals, false, s0b, /*with_merkle=*/false);
-      sl0.lde_logs = P.trees[0].lde.logs;
-      sl0.slice.resize(P.trees[0].lde.size());
-      for (size_t j = 0; j < sl0.slice.size(); j++) sl0.slice[j] = P.trees[0].lde.ptrs[j] + (uint64_t)R * ((uint64_t)1 << (sl0.lde_logs[j] - logN));
-      sliced_subtree(cm, sl0, s0b);
-    } else slice_replicated(cm, P.trees[0].lde, sl0, &sl0_later);
-    // multiplicity tables = sum of every rank's partial histogram (components/mod.rs:139-160 chains all opcode components)
-    const uint32_t* hsum = hist.u32();   // (a lone rank's histogram IS the sum)
-    if (N > 1) {
-      cm.need(HW * N);
-      hist_sum.alloc(HW * 4);
-      CM_HIP(hipMemcpyAsync(comm_c.send_buf, hist.p, HW * 4, hipMemcpyDeviceToDevice, st));
-      cm.all_gather(HW);
-      sum_copies(comm_c.recv_buf, N, HW, HW, hist_sum.u32(), false, st);
-      hsum = hist_sum.u32();
-    }
-    const size_t off[4] = {0, (size_t)1 << 8, ((size_t)1 << 8) + ((size_t)1 << 16), ((size_t)1 << 8) + ((size_t)1 << 16) + ((size_t)1 << 20)};
-    const int rc[4] = {air::C_RC8, air::C_RC16, air::C_RC20, air::C_BITWISE};
-    for (int k = 0; k < 4; k++)
-      if (mine(rc[k])) CM_HIP(hipMemcpyAsync(tr_evals.ptrs[ltr0[rc[k]]], hsum + off[k], (size_t)4 << clog[rc[k]], hipMemcpyDeviceToDevice, st));
-    CM_HIP(hipMemcpyAsync(pinned_words() + PIN_FLAG, flag.p, 4, hipMemcpyDeviceToHost, st));
-    if (!tree_stream) {
-      CM_HIP(hipStreamSynchronize(st));
-      complete_sliced(cm, sl0, sl0_later);   // transcript order (prover.rs:70-82): root 0 in front of the claim and root 1
-      P.trees[0].root = sl0.root;
-      ch.mix_root(sl0.root);
-      check_flags(cm.gather_host({pinned_words()[PIN_FLAG], shard_fri_stop_log()}), 2, 0);
-    }
-    // (tree_stream: the flag is read at the claimed sums' synchronisation point and travels with them; root 0 is waited for
-    // below, with tree 1's transforms already enqueued)
   }
-  P.tick("trace_gen");
   // IFFT + LDE of the own columns, then column owner -> row-range owner, Merkle subtree, sub-roots
-  CommittedTree own1, own2;       // coefficients + full LDE of the OWN columns of trees 1 and 2
   // (round 5) the transforms go through the single-GPU prover's commitment code without its Merkle half: fused inverse / forward
   // sweeps (k_fft_fused_rb), one launch for all small columns, tree 2 interpolated in place group by group — they used to be plain
   // interpolate + evaluate passes behind a separate in-place interpolation and two stream synchronisations
-  auto commit_own = [&](CommittedTree& t, ColumnSet* evals, bool from_coeffs, bool evals_in_place, const std::vector<uint32_t>& all_logs,
-                        const std::vector<int>& col_owner, SlicedTree& sl, const std::function<void()>& between = nullptr,
-                        const Prover::DeferredCols* defer = nullptr) {
+  void commit_own(CommittedTree& t, ColumnSet* evals, bool from_coeffs, bool evals_in_place, const std::vector<uint32_t>& all_logs,
+                  const std::vector<int>& col_owner, SlicedTree& sl, const std::function<void()>& between = nullptr,
+                  const Prover::DeferredCols* defer = nullptr) {
     P.commit_enqueue(t, evals, from_coeffs, st, /*with_merkle=*/false, evals_in_place, nullptr, defer);
     if (between) between();   // work that belongs behind the transforms just enqueued and in front of the tree's exchange
     std::vector<std::pair<uint32_t, const uint32_t*>> mine_cols;
@@ -746,57 +662,182 @@ ProofData* prove_sharded(const DeviceInput& din, const cm_pcs_config& cfg, const
     for (size_t j = 0; j < all_logs.size(); j++)
       if ((uint32_t)col_owner[j] == R) mine_cols.push_back({(uint32_t)j, t.lde.ptrs[li++]});
     exchange_to_rows(cm, lde_of(all_logs), col_owner, mine_cols, sl, /*enqueue_only=*/tree_stream);
-  };
-  HostRelations hrel;
-  DevBuf drel(sizeof(DevRelations));
-  if (tree_stream) {
-    commit_own(own1, &tr_evals, false, false, tr_logs, tr_owner, sl1, [&] {
-      pp_fork->join();
-      pp_guard.joined = true;
-      sliced_gather(cm, sl0);
-      sliced_land_later(cm, sl0_later);
-    });
-    complete_sliced(cm, sl0, sl0_later);   // root 0 arrives behind tree 1's transforms; the GPU is busy with tree 1's subtree
-    P.trees[0].root = sl0.root;
-    ch.mix_root(sl0.root);
-    for (int c = 0; c < air::N_COMPONENTS; c++) { pf.claim_log_sizes.push_back(clog[c]); ch.mix_u64(clog[c]); }
-    // root 1 -> interaction proof of work -> relation challenges, all behind the all-gather (prover.hip trace_commit)
-    static_assert(sizeof(DevRelations) == 4 * 4 * (air::N_RELATIONS + air::N_RELATIONS * air::MAX_REL_SIZE), "DevRelations layout");
-    shard_top(comm_c.recv_buf, N, ts + TS_ROOT1, ts + TS_SUB1, st);
-    uint32_t cw[9];
-    memcpy(cw, ch.digest.data(), 32);
-    cw[8] = ch.n_sent;
-    step_pow_relations(cw, ts + TS_ROOT1, INTERACTION_POW_BITS, air::N_RELATIONS, air::MAX_REL_SIZE, drel.u32(), drel.u32() + 4 * air::N_RELATIONS,
-                       ts + TS_STEP1, st);
-    CM_HIP(hipMemcpyAsync(pin_sub1, ts + TS_SUB1, 8 * N * 4, hipMemcpyDeviceToHost, st));
-    CM_HIP(hipMemcpyAsync(pinned_words() + PIN_STEP1, ts + TS_STEP1, 16 * 4, hipMemcpyDeviceToHost, st));
-    P.tick("trace_commit");
-  } else {
-    commit_own(own1, &tr_evals, false, false, tr_logs, tr_owner, sl1);
-    // transcript order (prover.rs:70-82): root 0 (mixed above), claim, root 1
-    for (int c = 0; c < air::N_COMPONENTS; c++) { pf.claim_log_sizes.push_back(clog[c]); ch.mix_u64(clog[c]); }
-    ch.mix_root(sl1.root);
-    P.tick("trace_commit");
-
-    // ---- interaction PoW + relations (prover.rs:90-94): replicated ----
-    pf.interaction_pow = grind_gpu(ch.digest.data(), INTERACTION_POW_BITS, st);
-    ch.mix_u64(pf.interaction_pow);
-    DevRelations drel_h;
-    draw_relations(ch, hrel, drel_h);
-    stage_upload(drel.p, &drel_h, sizeof(DevRelations), st);
   }
+  // tree 0 (columns replicated, hashing row-sharded), tree 1 (own components), lookup flags, interaction PoW + relations (prover.rs:70-94)
+  void trace_commit() {
+    {
+      std::vector<uint32_t> logs(air::PREPROC_LOG, air::PREPROC_LOG + air::N_PREPROC);
+      pp_evals.alloc(logs, st);
+      for (int i = 0; i < air::N_PREPROC; i++) launch_preproc(i, logs[i], pp_evals.ptrs[i], s0);
+      // (tree 0's IFFT + LDE — on every rank, hashing by row range — are enqueued BEHIND the trace-generation launches below: issued
+      // here, the host time of that chain of ~15 short launches delayed the first trace kernel by ~0.25 ms, round-6 timeline)
+    }
+    P.tick("preprocessed");
 
-  // ---- tree 2: LogUp columns of the own components ----
-  std::vector<int> my_comps;          // components whose cumulative-sum columns (and claimed sum) this rank computes
-  DevBuf d_sums;
-  std::vector<DevBuf> tail_scratch;     // scratch of the LogUp tail when it runs on a side stream: alive until the host has seen the sums
-  Prover::DeferredCols late_cols;       // the running-sum columns of tree 2: transformed behind the tail (late_cols.ready)
-  const uint32_t* sums_land = nullptr;   // pinned: this rank's sums (compact), or every rank's gathered words (sums_gathered)
-  bool sums_gathered = false;
-  hipEvent_t ev_sums = nullptr;
-  ColumnSet it_evals;
-  it_evals.alloc(lit_logs, st);
-  {
+    // ---- column bookkeeping of trees 1 and 2: global order, owner of every column, local (own) column sets ----
+    tr0.assign(air::N_COMPONENTS, 0); it0.assign(air::N_COMPONENTS, 0); ltr0.assign(air::N_COMPONENTS, 0); lit0.assign(air::N_COMPONENTS, 0);
+    for (int c = 0; c < air::N_COMPONENTS; c++) {
+      tr0[c] = tr_logs.size(); it0[c] = it_logs.size();
+      ltr0[c] = ltr_logs.size(); lit0[c] = lit_logs.size();   // (meaningful for whole components of this rank: their columns are consecutive)
+      for (int k = 0; k < air::component_info(c).n_trace; k++) {
+        const bool own = (uint32_t)tr_owner[tr_logs.size()] == R;
+        ltr_of.push_back(own ? (int)ltr_logs.size() : -1);
+        tr_logs.push_back(clog[c]);
+        if (own) ltr_logs.push_back(clog[c]);
+      }
+      for (int k = 0; k < air::component_info(c).n_interaction; k++) {
+        const bool own = (uint32_t)it_owner[it_logs.size()] == R;
+        lit_of.push_back(own ? (int)lit_logs.size() : -1);
+        it_logs.push_back(clog[c]);
+        if (own) lit_logs.push_back(clog[c]);
+      }
+    }
+    for (int c = 0; c < air::N_COMPONENTS; c++)
+      if (split(c)) { splits.emplace_back(new SplitComp()); splits.back()->c = c; splits.back()->slog = clog[c] - logN; }
+    // ---- tree 1: execution trace of the own components ----
+    tr_evals.alloc(ltr_logs, st);
+    hist.alloc(HW * 4);
+    flag.alloc(4);
+    {
+      CM_HIP(hipMemsetAsync(flag.p, 0, 4, st));
+      CM_HIP(hipMemsetAsync(hist.p, 0, HW * 4, st));
+      HistPtrs h;
+      h.rc8 = hist.u32(); h.rc16 = h.rc8 + (1u << 8); h.rc20 = h.rc16 + (1u << 16); h.bitwise = h.rc20 + (1u << 20);
+      h.error_flag = flag.u32();
+      std::vector<SmallTraceJob> small_trace;
+      for (int c = 0; c < air::N_OPCODE_COMPONENTS; c++)
+        if (mine(c) && clog[c] <= SMALL_COMPONENT_MAX_LOG)
+          small_trace.push_back(SmallTraceJob{din.bundles[c].p, (uint32_t)in.n_bundles[c], tr_evals.dev(ltr0[c]), clog[c], c});
+      DevBuf d_small_trace = upload(small_trace, st);
+      {
+        Fork fk(st);   // (round 5) whole components: trace + histogram in one launch each, on side streams (histogram adds commute)
+        if (!small_trace.empty()) launch_trace_hist_small(d_small_trace.as<SmallTraceJob>(), (uint32_t)small_trace.size(), din.data_accesses.p, h, fk.stream(Fork::N - 2));
+        int spos = 0;
+        for (int c : by_size) {   // large components first: the largest on the main stream
+          if (c >= air::N_OPCODE_COMPONENTS || !mine(c) || clog[c] <= SMALL_COMPONENT_MAX_LOG) continue;
+          launch_opcode_trace_hist(c, din.bundles[c].p, (uint32_t)in.n_bundles[c], din.data_accesses.p, clog[c], tr_evals.dev(ltr0[c]), h,
+                                   fk.stream(spos == 0 ? Fork::main_or(0) : spos % (Fork::N - 2)));
+          spos++;
+        }
+        // the builtins' traces inside the region too (the single-GPU prover's placement): they ran one after the other on the main
+        // stream behind the join, ~70 us of launch latency in the round-6 timeline
+        if (mine(air::C_MEMORY))
+          launch_memory_trace(din.init_mem.p, (uint32_t)in.n_initial_memory, din.fin_mem.p, (uint32_t)in.n_final_memory, in.initial_root, in.final_root,
+                              clog[air::C_MEMORY], tr_evals.dev(ltr0[air::C_MEMORY]), fk.stream(air::C_MEMORY));
+        if (mine(air::C_MERKLE))
+          launch_merkle_trace(din.init_tree.p, (uint32_t)in.n_initial_tree, din.fin_tree.p, (uint32_t)in.n_final_tree, in.initial_root, in.final_root,
+                              clog[air::C_MERKLE], tr_evals.dev(ltr0[air::C_MERKLE]), fk.stream(air::C_MERKLE));
+        if (mine(air::C_CLOCK_UPDATE))
+          launch_clock_update_trace(din.clock_updates.p, (uint32_t)in.n_clock_updates, clog[air::C_CLOCK_UPDATE], tr_evals.dev(ltr0[air::C_CLOCK_UPDATE]), fk.stream(air::C_CLOCK_UPDATE));
+        if (mine(air::C_POSEIDON2))
+          launch_poseidon2_trace(din.init_tree.p, (uint32_t)in.n_initial_tree, din.fin_tree.p, (uint32_t)in.n_final_tree, clog[air::C_POSEIDON2],
+                                 tr_evals.dev(ltr0[air::C_POSEIDON2]), fk.stream(air::C_POSEIDON2));
+        fk.join();
+      }
+      if (!tree_stream) P.commit_enqueue(P.trees[0], &pp_evals, false, s0, /*with_merkle=*/false);   // tree 0: IFFT + LDE, next to the trace kernels
+      // split components: every rank writes the trace rows of ITS row range (a row is a function of its bundle) and counts their
+      // lookups; the slices then travel to the column owners, which transform whole columns
+      for (auto& sc : splits) {
+        const int c = sc->c;
+        sc->tr_slice.alloc(std::vector<uint32_t>(air::component_info(c).n_trace, sc->slog), st);
+        const uint64_t row0 = (uint64_t)R << sc->slog, nb = in.n_bundles[c];
+        const uint32_t n_local = nb > row0 ? (uint32_t)std::min<uint64_t>(nb - row0, (uint64_t)1 << sc->slog) : 0u;
+        launch_opcode_trace(c, (const uint8_t*)din.bundles[c].p + row0 * sizeof(air::Bundle), n_local, din.data_accesses.p, sc->slog,
+                            sc->tr_slice.dev(), st);
+        launch_hist(c, (const uint32_t* const*)sc->tr_slice.dev(), sc->slog, h, st);
+      }
+      {
+        std::vector<ColMove> mv;
+        for (auto& sc : splits)
+          for (int k = 0; k < air::component_info(sc->c).n_trace; k++) {
+            const size_t j = tr0[sc->c] + k;
+            mv.push_back(ColMove{sc->slog, sc->tr_slice.ptrs[k], tr_owner[j], ltr_of[j] >= 0 ? tr_evals.ptrs[ltr_of[j]] : nullptr});
+          }
+        exchange_to_cols(cm, mv);
+      }
+      // tree 0: its transforms have run next to the kernels above; hashing by row range + sub-root all-gather here, the host part
+      // (top levels, root) at the synchronisation point below — nothing of trace generation needs root 0
+      tw_fork->join();
+      s0_guard.joined = true;
+      if (tree_stream) {
+        // tree 0 whole — transforms AND the Merkle subtree of this rank's rows — on a side stream forked HERE (twiddles joined, trace
+        // kernels launched), next to tree 1's transforms as in the single-GPU prover; only the 32-byte all-gather of its sub-roots
+        // goes on the main stream, behind those transforms (the collectives live there)
+        pp_fork.reset(new Fork(st));
+        hipStream_t s0b = pp_fork->stream(Fork::N - 1);
+        pp_guard.s = s0b;
+        P.commit_enqueue(P.trees[0], &pp_evals, false, s0b, /*with_merkle=*/false);
+        sl0.lde_logs = P.trees[0].lde.logs;
+        sl0.slice.resize(P.trees[0].lde.size());
+        for (size_t j = 0; j < sl0.slice.size(); j++) sl0.slice[j] = P.trees[0].lde.ptrs[j] + (uint64_t)R * ((uint64_t)1 << (sl0.lde_logs[j] - logN));
+        sliced_subtree(cm, sl0, s0b);
+      } else slice_replicated(cm, P.trees[0].lde, sl0, &sl0_later);
+      // multiplicity tables = sum of every rank's partial histogram (components/mod.rs:139-160 chains all opcode components)
+      const uint32_t* hsum = hist.u32();   // (a lone rank's histogram IS the sum)
+      if (N > 1) {
+        cm.need(HW * N);
+        hist_sum.alloc(HW * 4);
+        CM_HIP(hipMemcpyAsync(comm_c.send_buf, hist.p, HW * 4, hipMemcpyDeviceToDevice, st));
+        cm.all_gather(HW);
+        sum_copies(comm_c.recv_buf, N, HW, HW, hist_sum.u32(), false, st);
+        hsum = hist_sum.u32();
+      }
+      const size_t off[4] = {0, (size_t)1 << 8, ((size_t)1 << 8) + ((size_t)1 << 16), ((size_t)1 << 8) + ((size_t)1 << 16) + ((size_t)1 << 20)};
+      const int rc[4] = {air::C_RC8, air::C_RC16, air::C_RC20, air::C_BITWISE};
+      for (int k = 0; k < 4; k++)
+        if (mine(rc[k])) CM_HIP(hipMemcpyAsync(tr_evals.ptrs[ltr0[rc[k]]], hsum + off[k], (size_t)4 << clog[rc[k]], hipMemcpyDeviceToDevice, st));
+      CM_HIP(hipMemcpyAsync(pinned_words() + PIN_FLAG, flag.p, 4, hipMemcpyDeviceToHost, st));
+      if (!tree_stream) {
+        CM_HIP(hipStreamSynchronize(st));
+        complete_sliced(cm, sl0, sl0_later);   // transcript order (prover.rs:70-82): root 0 in front of the claim and root 1
+        P.trees[0].root = sl0.root;
+        ch.mix_root(sl0.root);
+        check_flags(cm.gather_host({pinned_words()[PIN_FLAG], shard_fri_stop_log()}), 2, 0);
+      }
+      // (tree_stream: the flag is read at the claimed sums' synchronisation point and travels with them; root 0 is waited for
+      // below, with tree 1's transforms already enqueued)
+    }
+    P.tick("trace_gen");
+    drel.alloc(sizeof(DevRelations));
+    if (tree_stream) {
+      commit_own(own1, &tr_evals, false, false, tr_logs, tr_owner, sl1, [&] {
+        pp_fork->join();
+        pp_guard.joined = true;
+        sliced_gather(cm, sl0);
+        sliced_land_later(cm, sl0_later);
+      });
+      complete_sliced(cm, sl0, sl0_later);   // root 0 arrives behind tree 1's transforms; the GPU is busy with tree 1's subtree
+      P.trees[0].root = sl0.root;
+      ch.mix_root(sl0.root);
+      for (int c = 0; c < air::N_COMPONENTS; c++) { pf.claim_log_sizes.push_back(clog[c]); ch.mix_u64(clog[c]); }
+      // root 1 -> interaction proof of work -> relation challenges, all behind the all-gather (prover.hip trace_commit)
+      static_assert(sizeof(DevRelations) == 4 * 4 * (air::N_RELATIONS + air::N_RELATIONS * air::MAX_REL_SIZE), "DevRelations layout");
+      shard_top(comm_c.recv_buf, N, ts + TS_ROOT1, ts + TS_SUB1, st);
+      uint32_t cw[9];
+      memcpy(cw, ch.digest.data(), 32);
+      cw[8] = ch.n_sent;
+      step_pow_relations(cw, ts + TS_ROOT1, INTERACTION_POW_BITS, air::N_RELATIONS, air::MAX_REL_SIZE, drel.u32(), drel.u32() + 4 * air::N_RELATIONS,
+                         ts + TS_STEP1, st);
+      CM_HIP(hipMemcpyAsync(pin_sub1, ts + TS_SUB1, 8 * N * 4, hipMemcpyDeviceToHost, st));
+      CM_HIP(hipMemcpyAsync(pinned_words() + PIN_STEP1, ts + TS_STEP1, 16 * 4, hipMemcpyDeviceToHost, st));
+      P.tick("trace_commit");
+    } else {
+      commit_own(own1, &tr_evals, false, false, tr_logs, tr_owner, sl1);
+      // transcript order (prover.rs:70-82): root 0 (mixed above), claim, root 1
+      for (int c = 0; c < air::N_COMPONENTS; c++) { pf.claim_log_sizes.push_back(clog[c]); ch.mix_u64(clog[c]); }
+      ch.mix_root(sl1.root);
+      P.tick("trace_commit");
+
+      // ---- interaction PoW + relations (prover.rs:90-94): replicated ----
+      pf.interaction_pow = grind_gpu(ch.digest.data(), INTERACTION_POW_BITS, st);
+      ch.mix_u64(pf.interaction_pow);
+      DevRelations drel_h;
+      draw_relations(ch, hrel, drel_h);
+      stage_upload(drel.p, &drel_h, sizeof(DevRelations), st);
+    }
+  }
+  // the LogUp columns of the own components: the fork region of their kernels (`jobs`: the tails that follow)
+  void logup_launches(std::vector<LogupTailJob>& jobs, DevBuf& d_small) {
     // split components first: the LogUp rows of this rank's row range, then rows -> column owners
     for (auto& sc : splits) {
       const int c = sc->c;
@@ -816,7 +857,7 @@ ProofData* prove_sharded(const DeviceInput& din, const cm_pcs_config& cfg, const
     // the LogUp tail (claimed sum + prefix sum) of a component runs where its four cumulative-sum columns live: the owner of a
     // whole component, or the rank the plan gave those columns of a split one
     for (int c = 0; c < air::N_COMPONENTS; c++) if (plan.cum_owner(c) == (int)R) my_comps.push_back(c);
-    std::vector<LogupTailJob> jobs(my_comps.size());
+    jobs.resize(my_comps.size());
     std::vector<SmallLogupJob> small_jobs;
     uint32_t small_max_log = 0;
     for (int c : my_comps)
@@ -824,7 +865,7 @@ ProofData* prove_sharded(const DeviceInput& din, const cm_pcs_config& cfg, const
         small_jobs.push_back(SmallLogupJob{(const uint32_t* const*)tr_evals.dev(ltr0[c]), it_evals.dev(lit0[c]), clog[c], c});
         small_max_log = std::max(small_max_log, clog[c]);
       }
-    DevBuf d_small = upload(small_jobs, st);
+    d_small = upload(small_jobs, st);
     {
       // (round 5) the components' kernels are independent: side streams, the batched small components first (latency-bound, hidden
       // under the large ones), like the single-GPU prover's region
@@ -851,15 +892,18 @@ ProofData* prove_sharded(const DeviceInput& din, const cm_pcs_config& cfg, const
       }
       fk.join();
     }
-    // ---- the claimed sums: every rank's own sums + {lookup flag, FRI plan} -> all ranks.  tree_stream: nothing waits here — the
-    // words travel on the stream (device all-gather with a stream-ordered comm) into pinned memory behind an event, and the host
-    // picks them up in `sums_arrive` AFTER tree 2's transforms have been enqueued (they do not depend on the sums; the device step
-    // behind tree 2 does: it starts from the channel state with the sums mixed in) ----
-    // (round 6) "logup_defer", as in the single-GPU prover's interaction(): the LogUp tail — claimed sums, the running-sum columns'
-    // prefix scans: ~0.15 ms of short memory-bound kernels — and the sums' gather run on a SIDE stream while tree 2's transforms of
-    // every other column start on the main one; the running-sum columns go last in their size group (Prover::DeferredCols).
-    const size_t SW = air::N_COMPONENTS * 4 + 2;
-    const bool defer_tail = tree_stream && tune(T_LOGUP_DEFER) != 0;
+  }
+  // ---- the claimed sums: every rank's own sums + {lookup flag, FRI plan} -> all ranks.  tree_stream: nothing waits here — the
+  // words travel on the stream (device all-gather with a stream-ordered comm) into pinned memory behind an event, and the host
+  // picks them up in `sums_arrive` AFTER tree 2's transforms have been enqueued (they do not depend on the sums; the device step
+  // behind tree 2 does: it starts from the channel state with the sums mixed in) ----
+  // (round 6) "logup_defer", as in the single-GPU prover's interaction(): the LogUp tail — claimed sums, the running-sum columns'
+  // prefix scans: ~0.15 ms of short memory-bound kernels — and the sums' gather run on a SIDE stream while tree 2's transforms of
+  // every other column start on the main one; the running-sum columns go last in their size group (Prover::DeferredCols).
+  // The tail's stream `sf` is the main stream or — defer_tail — side stream 1; the collective follows it there through set_stream,
+  // so the deferred form is taken only when the communicator can follow (a stream-ordered one without set_stream stays on `st`).
+  void claimed_sums_exchange(const std::vector<LogupTailJob>& jobs) {
+    const bool defer_tail = tree_stream && tune(T_LOGUP_DEFER) != 0 && (!cm.ordered() || comm_c.set_stream);
     hipStream_t sf = st;
     if (defer_tail) {
       sf = thread_side_stream(1);
@@ -886,22 +930,19 @@ ProofData* prove_sharded(const DeviceInput& din, const cm_pcs_config& cfg, const
       if (sf != st && comm_c.set_stream) comm_c.set_stream(comm_c.ctx, (cm_stream_t)(uintptr_t)sf);
       cm.all_gather(SW);
       if (sf != st && comm_c.set_stream) comm_c.set_stream(comm_c.ctx, (cm_stream_t)(uintptr_t)st);
-      sums_land = (const uint32_t*)stage_download_async(comm_c.recv_buf, SW * N * 4, sf);
+      // (dedicated pinned words: every other fixed slot ends at PIN_LAST_LAYER_END, and the landing buffer is elsewhere)
+      CM_HIP(hipMemcpyAsync(pinned_words() + PIN_SHARD_SUMS, comm_c.recv_buf, SW * N * 4, hipMemcpyDeviceToHost, sf));
+      sums_land = pinned_words() + PIN_SHARD_SUMS;
       sums_gathered = true;
     } else if (!jobs.empty()) {
       CM_HIP(hipMemcpyAsync(pinned_words() + PIN_SUMS, d_sums.p, jobs.size() * 16, hipMemcpyDeviceToHost, sf));
       sums_land = pinned_words() + PIN_SUMS;
     }
-    {
-      static thread_local hipEvent_t ev = nullptr;
-      if (!ev) { CM_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); thread_event_owned(ev); }
-      CM_HIP(hipEventRecord(ev, sf));
-      ev_sums = ev;
-      if (defer_tail) late_cols.ready = ev;
-    }
+    static thread_local hipEvent_t ev = nullptr;
+    CM_HIP(hipEventRecord(ev_sums = thread_event(ev), sf));
+    if (defer_tail) late_cols.ready = ev;
   }
-  auto sums_arrive = [&] {
-    const size_t SW = air::N_COMPONENTS * 4 + 2;
+  void sums_arrive() {
     CM_HIP(hipEventSynchronize(ev_sums));
     d_sums.release();
     tail_scratch.clear();
@@ -942,49 +983,21 @@ ProofData* prove_sharded(const DeviceInput& din, const cm_pcs_config& cfg, const
     if (tree_stream) check_flags(all, SW, SW - 2);
     for (int c = 0; c < air::N_COMPONENTS; c++) pf.claimed_sums.push_back(QM31::from_u32(&all[(size_t)plan.cum_owner(c) * SW + 4 * c]));
     for (auto& cs : pf.claimed_sums) ch.mix_felts(&cs, 1);
-  };
-  if (!tree_stream) sums_arrive();
-  P.tick("interaction_gen");
-  size_t total_constraints = 0;
-  std::vector<size_t> coff(air::N_COMPONENTS);
-  for (int c = 0; c < air::N_COMPONENTS; c++) { coff[c] = total_constraints; total_constraints += air::component_info(c).n_constraints; }
-  std::vector<QM31> powers(total_constraints);
-  DevBuf d_powers(16 * total_constraints);
-  {
-    own2.coeffs = std::move(it_evals);   // interpolated in place, every size group right in front of its extension
-    commit_own(own2, nullptr, true, /*evals_in_place=*/true, it_logs, it_owner, sl2, tree_stream ? std::function<void()>(sums_arrive) : nullptr,
-               late_cols.ready ? &late_cols : nullptr);
-    if (tree_stream) {
-      // root 2 -> random coefficient -> its powers, behind the all-gather (prover.hip composition): the constraint kernels start
-      // without the host having seen the root
-      shard_top(comm_c.recv_buf, N, ts + TS_ROOT2, ts + TS_SUB2, st);
-      uint32_t cw[9];
-      memcpy(cw, ch.digest.data(), 32);
-      cw[8] = ch.n_sent;
-      chan_init_mix_root_draw(cw, ts + TS_CHAN, ts + TS_ROOT2, ts + TS_COEFF, ts + TS_ROOT2_LOG, st);
-      coeff_powers(ts + TS_COEFF, d_powers.u32(), (uint32_t)total_constraints, st);
-      static_assert(PIN_COEFF + 4 == PIN_ROOT2 && TS_COEFF + 4 == TS_ROOT2_LOG, "{coefficient, root 2} come back in one copy");
-      CM_HIP(hipMemcpyAsync(pin_sub2, ts + TS_SUB2, 8 * N * 4, hipMemcpyDeviceToHost, st));
-      CM_HIP(hipMemcpyAsync(pinned_words() + PIN_COEFF, ts + TS_COEFF, 48, hipMemcpyDeviceToHost, st));
-    }
   }
-  tr_evals.buf.release();
-  for (auto& sc : splits) { sc->tr_slice.buf.release(); sc->it_slice.buf.release(); }
-  bool halo_pending = false;
-  auto check_halo = [&] {
+  void check_halo(bool synchronise = true) {   // (false: the caller has waited for an event behind the error word's copy)
     if (!halo_pending) return;
-    CM_HIP(hipStreamSynchronize(st));
+    if (synchronise) CM_HIP(hipStreamSynchronize(st));
     halo_pending = false;
     CM_CHECK(*pin_halo_err == 0, "sharded constraints: a previous-row neighbour lies outside the two ranges the halo exchange covers");
-  };
-  if (!splits.empty()) {
-    // The constraints of a split component are evaluated by row range (below), but its cumulative-sum columns are also read at
-    // the PREVIOUS row of the trace domain, which lies in some other rank's range: every rank gets those four LDE columns whole.
-    // (round 6) "shard_halo" = 1: a HALO instead — on bit-reversed storage the previous row of every EVEN local position of a range
-    // lies in the range whose bit-reversed rank number is one lower (first half of the domain: natural index i - 1) and of every
-    // ODD position in the range one higher (second half: i + 1); so every rank sends the even half of its slices to one neighbour and
-    // the odd half to the other (one all_to_all_v with two non-empty destinations: 1 / N of the all-gather's bytes per rank) and
-    // builds `cum_prev[q]` = the column at the previous row of its q-th row (k_halo_build).  0 = the round-4 all-gather.
+  }
+  // The constraints of a split component are evaluated by row range (below), but its cumulative-sum columns are also read at
+  // the PREVIOUS row of the trace domain, which lies in some other rank's range: every rank gets those four LDE columns whole.
+  // (round 6) "shard_halo" = 1: a HALO instead — on bit-reversed storage the previous row of every EVEN local position of a range
+  // lies in the range whose bit-reversed rank number is one lower (first half of the domain: natural index i - 1) and of every
+  // ODD position in the range one higher (second half: i + 1); so every rank sends the even half of its slices to one neighbour and
+  // the odd half to the other (one all_to_all_v with two non-empty destinations: 1 / N of the all-gather's bytes per rank) and
+  // builds `cum_prev[q]` = the column at the previous row of its q-th row (k_halo_build).  0 = the round-4 all-gather.
+  void cum_columns_exchange() {
     const bool halo = tune(T_SHARD_HALO) != 0 && N >= 2;
     if (halo) {
       auto brev = [&](uint32_t x) { return bit_reverse(x, logN); };
@@ -1050,16 +1063,51 @@ ProofData* prove_sharded(const DeviceInput& din, const cm_pcs_config& cfg, const
       copy_segments(segs, st);
     }
   }
-  if (!tree_stream) ch.mix_root(sl2.root);
-  P.tick("interaction_commit");
-  for (auto l : P.trees[0].coeffs.logs) pf.cells += 1ull << l;
-  for (auto l : tr_logs) pf.cells += 1ull << l;
-  for (auto l : it_logs) pf.cells += 1ull << l;
-
-  // ---- composition polynomial: constraints of the own components, partial coefficients reduced across ranks ----
-  if (!tree_stream) draw_constraint_powers(ch, powers, d_powers, st);
-  ColumnSet acc_top;
-  {
+  // tree 2: LogUp columns, claimed sums (tree_stream: waited for behind tree 2's transforms), the split components' previous rows
+  void interaction() {
+    it_evals.alloc(lit_logs, st);
+    {
+      std::vector<LogupTailJob> jobs;
+      DevBuf d_small;   // the small components' job table: goes back to the pool behind the sums' exchange, as ever
+      logup_launches(jobs, d_small);
+      claimed_sums_exchange(jobs);
+    }
+    if (!tree_stream) sums_arrive();
+    P.tick("interaction_gen");
+    size_t total_constraints = 0;
+    coff.assign(air::N_COMPONENTS, 0);
+    for (int c = 0; c < air::N_COMPONENTS; c++) { coff[c] = total_constraints; total_constraints += air::component_info(c).n_constraints; }
+    powers.resize(total_constraints);
+    d_powers.alloc(16 * total_constraints);
+    {
+      own2.coeffs = std::move(it_evals);   // interpolated in place, every size group right in front of its extension
+      commit_own(own2, nullptr, true, /*evals_in_place=*/true, it_logs, it_owner, sl2, tree_stream ? std::function<void()>([this] { sums_arrive(); }) : nullptr,
+                 late_cols.ready ? &late_cols : nullptr);
+      if (tree_stream) {
+        // root 2 -> random coefficient -> its powers, behind the all-gather (prover.hip composition): the constraint kernels start
+        // without the host having seen the root
+        shard_top(comm_c.recv_buf, N, ts + TS_ROOT2, ts + TS_SUB2, st);
+        uint32_t cw[9];
+        memcpy(cw, ch.digest.data(), 32);
+        cw[8] = ch.n_sent;
+        chan_init_mix_root_draw(cw, ts + TS_CHAN, ts + TS_ROOT2, ts + TS_COEFF, ts + TS_ROOT2_LOG, st);
+        coeff_powers(ts + TS_COEFF, d_powers.u32(), (uint32_t)total_constraints, st);
+        static_assert(PIN_COEFF + 4 == PIN_ROOT2 && TS_COEFF + 4 == TS_ROOT2_LOG, "{coefficient, root 2} come back in one copy");
+        CM_HIP(hipMemcpyAsync(pin_sub2, ts + TS_SUB2, 8 * N * 4, hipMemcpyDeviceToHost, st));
+        CM_HIP(hipMemcpyAsync(pinned_words() + PIN_COEFF, ts + TS_COEFF, 48, hipMemcpyDeviceToHost, st));
+      }
+    }
+    tr_evals.buf.release();
+    for (auto& sc : splits) { sc->tr_slice.buf.release(); sc->it_slice.buf.release(); }
+    if (!splits.empty()) cum_columns_exchange();
+    if (!tree_stream) ch.mix_root(sl2.root);
+    P.tick("interaction_commit");
+    for (auto l : P.trees[0].coeffs.logs) pf.cells += 1ull << l;
+    for (auto l : tr_logs) pf.cells += 1ull << l;
+    for (auto l : it_logs) pf.cells += 1ull << l;
+  }
+  // constraints of the own components -> acc_top: the composition polynomial's coefficients, partial sums reduced across the ranks
+  void constraint_quotients(ColumnSet& acc_top) {
     std::map<uint32_t, std::vector<int>> cgroups;   // evaluation log -> own components
     for (int c = 0; c < air::N_COMPONENTS; c++) if (mine(c) || split(c)) cgroups[clog[c] + 1].push_back(c);   // split: every rank, its rows
     std::vector<DevBuf> split_tabs;   // column tables of the split components (alive until the launches are enqueued and drained)
@@ -1229,244 +1277,130 @@ ProofData* prove_sharded(const DeviceInput& din, const cm_pcs_config& cfg, const
       CM_HIP(hipMemcpyAsync(acc_top.buf.p, comm_c.recv_buf, W * 4, hipMemcpyDeviceToDevice, st));
     }
   }
-  hipEvent_t ev_root3 = nullptr;
-  {
-    CommittedTree& t = P.trees[3];
-    t.coeffs = std::move(acc_top);
-    P.commit_enqueue(t, nullptr, true, st, /*with_merkle=*/false);   // LDE of the 4 coordinate columns on every rank (0.15 ms) ...
-    slice_replicated(cm, t.lde, sl3, nullptr, /*enqueue_only=*/tree_stream);   // ... Merkle hashing by row range
-    if (tree_stream) {
-      // root 3 -> the felt of the OODS point, on the device copy of the channel the coefficient step left (prover.hip oods_sampling)
-      shard_top(comm_c.recv_buf, N, ts + TS_ROOT3, ts + TS_SUB3, st);
-      chan_mix_root_draw(ts + TS_CHAN, ts + TS_ROOT3, ts + TS_STEP3, ts + TS_STEP3 + 4, st);
-      CM_HIP(hipMemcpyAsync(pin_sub3, ts + TS_SUB3, 8 * N * 4, hipMemcpyDeviceToHost, st));
-      CM_HIP(hipMemcpyAsync(pinned_words() + PIN_STEP3, ts + TS_STEP3, 48, hipMemcpyDeviceToHost, st));   // {felt[4], root 3 [8]}
-      static thread_local hipEvent_t ev = nullptr;   // root 3 comes back HERE, in front of the evaluation kernels enqueued next
-      if (!ev) { CM_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); thread_event_owned(ev); }
-      CM_HIP(hipEventRecord(ev, st));
-      ev_root3 = ev;
-    } else {
-      t.root = sl3.root;
-      ch.mix_root(sl3.root);
-    }
-  }
-  P.tick("composition_commit");
-
-  // ---- OODS sampling: own columns (+ trees 0 and 3 on every rank), values all-gathered ----
-  CPoint<QM31> oods;
-  if (!tree_stream) oods = draw_oods_point(ch);
-  // global sample slots: (tree, column, prev?) -> slot; owner of every slot
-  struct Slot { int t; uint32_t c; bool prev; int owner; const uint32_t* coeffs; uint32_t log; };
-  std::vector<Slot> slots;
-  std::vector<std::vector<uint32_t>> sidx_cur(4), sidx_prev(4);
-  const size_t n_cols_t[4] = {P.trees[0].coeffs.size(), tr_logs.size(), it_logs.size(), 4};
-  for (int t = 0; t < 4; t++) { sidx_cur[t].assign(n_cols_t[t], 0); sidx_prev[t].assign(n_cols_t[t], 0); }
-  // where this rank holds the coefficients of every column it samples (trees 0 / 3: every rank; trees 1 / 2: the owner)
-  std::vector<std::vector<const uint32_t*>> cptr(4);
-  for (int t = 0; t < 4; t++) {
-    cptr[t].resize(n_cols_t[t]);
-    if (t == 0 || t == 3) { for (size_t c = 0; c < n_cols_t[t]; c++) cptr[t][c] = P.trees[t].coeffs.ptrs[c]; continue; }
-    const std::vector<int>& ow = t == 1 ? tr_owner : it_owner;
-    size_t li = 0;
-    for (size_t c = 0; c < n_cols_t[t]; c++) cptr[t][c] = (uint32_t)ow[c] == R ? (t == 1 ? own1 : own2).coeffs.ptrs[li++] : nullptr;
-  }
-  auto col_log = [&](int t, uint32_t c) -> uint32_t { return t == 0 ? air::PREPROC_LOG[c] : t == 1 ? tr_logs[c] : t == 2 ? it_logs[c] : comp_log; };
-  auto col_owner_of = [&](int t, uint32_t c) -> int { return t == 1 ? tr_owner[c] : t == 2 ? it_owner[c] : 0; };
-  for (int t = 0; t < 4; t++)
-    for (uint32_t c = 0; c < n_cols_t[t]; c++) {
-      sidx_cur[t][c] = (uint32_t)slots.size();
-      slots.push_back(Slot{t, c, false, col_owner_of(t, c), cptr[t][c], col_log(t, c)});
-    }
-  for (int c = 0; c < air::N_COMPONENTS; c++) {
-    int ni = air::component_info(c).n_interaction;
-    for (int k = ni - 4; k < ni; k++) {
-      const uint32_t gc = (uint32_t)(it0[c] + k);
-      sidx_prev[2][gc] = (uint32_t)slots.size();
-      slots.push_back(Slot{2, gc, true, it_owner[gc], cptr[2][gc], clog[c]});
-    }
-  }
-  const size_t n_slots = slots.size();
-  DevBuf d_oods_out(n_slots * 16);
-  std::map<uint32_t, CPoint<QM31>> prev_points;
-  std::vector<uint32_t> samples(4 * n_slots, 0);
-  // (d_oods_out: every slot is written by the upload of the gathered samples below)
-  // jobs = (log, prev?) groups of the slots this rank evaluates (trees 0 / 3: every rank, so that nobody waits for them)
-  std::map<std::pair<uint32_t, bool>, std::vector<uint32_t>> groups;
-  for (uint32_t s = 0; s < n_slots; s++)
-    if (slots[s].coeffs) groups[{slots[s].log, slots[s].prev}].push_back(s);
-  std::vector<const uint32_t*> table;
-  struct J { uint32_t log; bool prev; size_t off, n; std::vector<uint32_t> ids; };
-  std::vector<J> js;
-  for (auto& kv : groups) {
-    J j{kv.first.first, kv.first.second, table.size(), kv.second.size(), kv.second};
-    for (auto s : kv.second) table.push_back(slots[s].coeffs);
-    js.push_back(j);
-  }
-  DevBuf d_table = upload(table, st);
-  size_t n_tmp = table.size();
-  DevBuf d_tmp(n_tmp * 16 + 16);
-  std::vector<EapJob> ej;
-  for (auto& j : js) {
-    CPoint<QM31> pt = oods;
-    EapJob e{j.log, (uint32_t)j.n, d_table.as<const uint32_t*>() + j.off, QM31(), QM31(), d_tmp.u32() + 4 * j.off};
-    if (j.prev) {
-      CPoint<M31> step = point_at_index(subgroup_gen_index(j.log));
-      if (tree_stream) { e.has_shift = true; e.shift_x = step.x.v; e.shift_y = (-step.y).v; }
-      else pt = cadd(oods, CPoint<QM31>{QM31(step.x), QM31(-step.y)});
-    }
-    e.px = pt.x; e.py = pt.y;
-    ej.push_back(e);
-  }
-  eval_at_point_multi(ej, st, tree_stream ? ts + TS_STEP3 : nullptr);
-  std::vector<uint32_t> tmp(4 * n_tmp);
-  const void* tmp_land = n_tmp ? stage_download_async(d_tmp.p, tmp.size() * 4, st) : nullptr;   // pinned: read after the synchronisation below
-  if (tree_stream) {
-    // host replay of the steps behind trees 2 and 3, in transcript order, as soon as root 3 is back — the evaluation kernels are
-    // still running (the one round trip since the claimed sums)
-    CM_HIP(hipEventSynchronize(ev_root3));
-    if (halo_pending) CM_CHECK(*pin_halo_err == 0, "sharded constraints: a previous-row neighbour lies outside the two ranges the halo exchange covers");
-    halo_pending = false;
-    complete_sliced(cm, sl2, pin_sub2);
-    CM_CHECK(memcmp(sl2.root.data(), pinned_words() + PIN_ROOT2, 32) == 0, "sharded interaction commitment: the device's tree top differs from the host's");
-    ch.mix_root(sl2.root);
-    const QM31 rho = ch.draw_felt();
-    CM_CHECK(rho == QM31::from_u32(pinned_words() + PIN_COEFF), "composition: device transcript diverged from the host channel");
-    QM31 cur(M31(1));
-    for (size_t g = powers.size(); g-- > 0;) { powers[g] = cur; cur = cur * rho; }   // host copy: the OODS check needs it
-    complete_sliced(cm, sl3, pin_sub3);
-    CM_CHECK(memcmp(sl3.root.data(), pinned_words() + PIN_STEP3 + 4, 32) == 0, "sharded composition commitment: the device's tree top differs from the host's");
-    P.trees[3].root = sl3.root;
-    ch.mix_root(sl3.root);
-    QM31 t;
-    oods = draw_oods_point(ch, &t);
-    CM_CHECK(t == QM31::from_u32(pinned_words() + PIN_STEP3), "oods: device transcript diverged from the host channel");
-  }
-  for (int c = 0; c < air::N_COMPONENTS; c++) {
-    CPoint<M31> step = point_at_index(subgroup_gen_index(clog[c]));
-    prev_points[clog[c]] = cadd(oods, CPoint<QM31>{QM31(step.x), QM31(-step.y)});
-  }
-  // mask sizes now ([oods] or [previous row, oods]), values below: the quotient tables are built while the evaluation kernels run
-  pf.sampled_values.resize(4);
-  for (int t = 0; t < 4; t++) {
-    pf.sampled_values[t].resize(n_cols_t[t]);
-    for (uint32_t c = 0; c < n_cols_t[t]; c++)
-      for (int k = (t == 2 && sidx_prev[2][c] != 0 ? 2 : 1); k > 0; k--) pf.sampled_values[t][c].push_back(QM31());
-  }
-  // ---- DEEP quotients of the own ROWS (host half: size groups, batches, tables — no sampled value needed yet) ----
-  std::vector<uint32_t> q_logs;
-  std::vector<ColumnSet> quotients;
-  struct QG { uint32_t log; std::vector<const uint32_t*> cols; std::vector<uint32_t> ci, si; std::vector<QuotientBatch> qb; std::vector<CPoint<QM31>> pts;
-              ColumnSet out_slice; size_t o_cols, o_out, o_ci, o_si, o_cc, o_qb, o_ep; };
-  std::vector<QG> gs;   // the quotient size groups, largest first; out_slice = this rank's rows of the four coordinate columns
-  // row-sharded part of FRI (first-layer tree + the large inner layers), see below
-  SlicedTree fri_first;
-  std::vector<std::unique_ptr<ShardedFriLayer>> sfl;
-  FriPhase fri;
-  {
-    struct QRef { int t; uint32_t c; };
-    std::map<uint32_t, std::vector<QRef>, std::greater<uint32_t>> qgroups;  // LDE log -> columns (tree-major order)
-    for (int t = 0; t < 4; t++)
-      for (uint32_t c = 0; c < n_cols_t[t]; c++) qgroups[col_log(t, c) + B].push_back({t, c});
-    using G = QG;
-    std::vector<uint8_t> blob;
-    auto qput = [&](const void* ptr, size_t bytes) {
-      size_t o = (blob.size() + 15) & ~(size_t)15;
-      blob.resize(o + bytes);
-      if (bytes && ptr) memcpy(blob.data() + o, ptr, bytes);
-      return o;
-    };
-    size_t n_jobs = 0;
-    for (auto& kv : qgroups) {
-      G g;
-      g.log = kv.first;
-      const uint64_t sl = (uint64_t)1 << (g.log - logN);
-      std::vector<std::vector<std::pair<uint32_t, uint32_t>>> batches;   // per batch: (column in group, sample slot)
-      for (uint32_t i = 0; i < kv.second.size(); i++) {
-        const QRef& rf = kv.second[i];
-        // this rank's row slice of the column
-        const uint32_t* p = rf.t == 0 ? P.trees[0].lde.ptrs[rf.c] + (uint64_t)R * sl : rf.t == 3 ? P.trees[3].lde.ptrs[rf.c] + (uint64_t)R * sl
-                            : rf.t == 1 ? sl1.slice[rf.c] : sl2.slice[rf.c];
-        g.cols.push_back(p);
-        const size_t ns = pf.sampled_values[rf.t][rf.c].size();
-        for (size_t k = 0; k < ns; k++) {
-          const bool is_prev = ns == 2 && k == 0;
-          CPoint<QM31> pt = is_prev ? prev_points[col_log(rf.t, rf.c)] : oods;
-          size_t bi = 0;
-          for (; bi < g.pts.size(); bi++) if (g.pts[bi].x == pt.x && g.pts[bi].y == pt.y) break;
-          if (bi == g.pts.size()) { g.pts.push_back(pt); batches.push_back({}); }
-          batches[bi].push_back({i, is_prev ? sidx_prev[rf.t][rf.c] : sidx_cur[rf.t][rf.c]});
-        }
-      }
-      if (framing().sample_batch_sorted) {   // framing.hpp `sample_batch`: batches ordered by point
-        std::vector<size_t> order(batches.size());
-        for (size_t i = 0; i < order.size(); i++) order[i] = i;
-        std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return secure_point_less(g.pts[a], g.pts[b]); });
-        auto pts0 = g.pts;
-        auto b0 = batches;
-        for (size_t i = 0; i < order.size(); i++) { g.pts[i] = pts0[order[i]]; batches[i] = b0[order[i]]; }
-      }
-      g.qb.resize(batches.size());
-      for (size_t bi = 0; bi < batches.size(); bi++) {
-        memset(&g.qb[bi], 0, sizeof(QuotientBatch));
-        g.qb[bi].begin = (uint32_t)g.ci.size();
-        for (auto& en : batches[bi]) { g.ci.push_back(en.first); g.si.push_back(en.second); }
-        g.qb[bi].end = (uint32_t)g.ci.size();
-        g.pts[bi].x.to_u32(g.qb[bi].point);
-        g.pts[bi].y.to_u32(g.qb[bi].point + 4);
-      }
-      g.out_slice.alloc(std::vector<uint32_t>(4, g.log - logN), st, false);
-      g.o_cols = qput(g.cols.data(), g.cols.size() * sizeof(void*));
-      g.o_out = qput(g.out_slice.ptrs.data(), 4 * sizeof(void*));
-      g.o_ci = qput(g.ci.data(), g.ci.size() * 4);
-      {
-        std::vector<const uint32_t*> ep;   // per entry: the column pointer itself (the two-rows kernel's scalar loads)
-        for (auto ci : g.ci) ep.push_back(g.cols[ci]);
-        g.o_ep = qput(ep.data(), ep.size() * sizeof(void*));
-      }
-      g.o_si = qput(g.si.data(), g.si.size() * 4);
-      g.o_cc = qput(nullptr, g.ci.size() * 16);
-      g.o_qb = qput(g.qb.data(), g.qb.size() * sizeof(QuotientBatch));
-      n_jobs += g.qb.size();
-      gs.push_back(std::move(g));
-    }
-    const size_t o_jobs = qput(nullptr, n_jobs * sizeof(QuotientCoefJob));
-    DevBuf d_blob(blob.size());
-    uint8_t* base = d_blob.as<uint8_t>();
+  // composition polynomial + tree 3 (prover.rs:114-120)
+  void composition() {
+    if (!tree_stream) draw_constraint_powers(ch, powers, d_powers, st);
+    ColumnSet acc_top;
+    constraint_quotients(acc_top);
     {
-      QuotientCoefJob* qj = (QuotientCoefJob*)(blob.data() + o_jobs);
-      size_t k = 0;
-      for (auto& g : gs)
-        for (size_t bi = 0; bi < g.qb.size(); bi++, k++) {
-          qj[k].qb = (QuotientBatch*)(base + g.o_qb) + bi;
-          qj[k].coef_c = (uint32_t*)(base + g.o_cc);
-          qj[k].sample_idx = (const uint32_t*)(base + g.o_si);
-        }
+      CommittedTree& t = P.trees[3];
+      t.coeffs = std::move(acc_top);
+      P.commit_enqueue(t, nullptr, true, st, /*with_merkle=*/false);   // LDE of the 4 coordinate columns on every rank (0.15 ms) ...
+      slice_replicated(cm, t.lde, sl3, nullptr, /*enqueue_only=*/tree_stream);   // ... Merkle hashing by row range
+      if (tree_stream) {
+        // root 3 -> the felt of the OODS point, on the device copy of the channel the coefficient step left (prover.hip oods_sampling)
+        shard_top(comm_c.recv_buf, N, ts + TS_ROOT3, ts + TS_SUB3, st);
+        chan_mix_root_draw(ts + TS_CHAN, ts + TS_ROOT3, ts + TS_STEP3, ts + TS_STEP3 + 4, st);
+        CM_HIP(hipMemcpyAsync(pin_sub3, ts + TS_SUB3, 8 * N * 4, hipMemcpyDeviceToHost, st));
+        CM_HIP(hipMemcpyAsync(pinned_words() + PIN_STEP3, ts + TS_STEP3, 48, hipMemcpyDeviceToHost, st));   // {felt[4], root 3 [8]}
+        static thread_local hipEvent_t ev = nullptr;   // root 3 comes back HERE, in front of the evaluation kernels enqueued next
+        CM_HIP(hipEventRecord(ev_root3 = thread_event(ev), st));
+      } else {
+        t.root = sl3.root;
+        ch.mix_root(sl3.root);
+      }
     }
-    stage_upload(d_blob.p, blob.data(), blob.size(), st);   // (behind the evaluation kernels, in front of the wait)
-    std::vector<std::pair<QuotientArgs, double>> qargs;
-    for (auto& g : gs) {
-      QuotientArgs a;
-      a.tw = view(*P.tw); a.log_size = g.log;
-      a.cols = (const uint32_t* const*)(base + g.o_cols);
-      a.out = (uint32_t* const*)(base + g.o_out);
-      a.col_index = (const uint32_t*)(base + g.o_ci);
-      a.entry_cols = (const uint32_t* const*)(base + g.o_ep);
-      a.coef_c = (const uint32_t*)(base + g.o_cc);
-      a.batches = (const QuotientBatch*)(base + g.o_qb);
-      a.n_batches = (uint32_t)g.qb.size();
-      a.n_rows = 1u << (g.log - logN);
-      a.row0 = R * a.n_rows;
-      qargs.push_back({a, (double)g.cols.size()});
+    P.tick("composition_commit");
+  }
+  // OODS sampling: own columns (+ trees 0 and 3 on every rank), values all-gathered; the DEEP-quotient plan is made meanwhile
+  void oods_sampling() {
+    if (!tree_stream) oods = draw_oods_point(ch);
+    // global sample slots: (tree, column, prev?) -> slot; owner of every slot
+    struct Slot { int t; uint32_t c; bool prev; int owner; const uint32_t* coeffs; uint32_t log; };
+    std::vector<Slot> slots;
+    std::vector<std::vector<uint32_t>> sidx_cur(4), sidx_prev(4);
+    n_cols_t[0] = P.trees[0].coeffs.size(); n_cols_t[1] = tr_logs.size(); n_cols_t[2] = it_logs.size(); n_cols_t[3] = 4;
+    for (int t = 0; t < 4; t++) { sidx_cur[t].assign(n_cols_t[t], 0); sidx_prev[t].assign(n_cols_t[t], 0); }
+    // where this rank holds the coefficients of every column it samples (trees 0 / 3: every rank; trees 1 / 2: the owner)
+    std::vector<std::vector<const uint32_t*>> cptr(4);
+    for (int t = 0; t < 4; t++) {
+      cptr[t].resize(n_cols_t[t]);
+      if (t == 0 || t == 3) { for (size_t c = 0; c < n_cols_t[t]; c++) cptr[t][c] = P.trees[t].coeffs.ptrs[c]; continue; }
+      const std::vector<int>& ow = t == 1 ? tr_owner : it_owner;
+      size_t li = 0;
+      for (size_t c = 0; c < n_cols_t[t]; c++) cptr[t][c] = (uint32_t)ow[c] == R ? (t == 1 ? own1 : own2).coeffs.ptrs[li++] : nullptr;
     }
-    // (round 6) the leaf layer of the first-layer FRI tree's subtree is written by the quotient kernel of the LARGEST size group,
-    // like the single-GPU prover's ("quot_leaf", prover.hip deep_quotients)
-    if (shard_fri_stop_log() < 99 && tune(T_QUOT_LEAF) != 0 && !qargs.empty() && (qargs.size() == 1 || qargs[1].first.log_size < qargs[0].first.log_size) &&
-        quotient_leaf_serves(qargs[0].first)) {
-      fri_first.local.leaf_prealloc.alloc((size_t)32 * qargs[0].first.n_rows);
-      qargs[0].first.leaf_hashes = fri_first.local.leaf_prealloc.u32();
-      fri_first.leaf_done = true;
+    for (int t = 0; t < 4; t++)
+      for (uint32_t c = 0; c < n_cols_t[t]; c++) {
+        sidx_cur[t][c] = (uint32_t)slots.size();
+        slots.push_back(Slot{t, c, false, col_owner_of(t, c), cptr[t][c], col_log(t, c)});
+      }
+    for (int c = 0; c < air::N_COMPONENTS; c++) {
+      int ni = air::component_info(c).n_interaction;
+      for (int k = ni - 4; k < ni; k++) {
+        const uint32_t gc = (uint32_t)(it0[c] + k);
+        sidx_prev[2][gc] = (uint32_t)slots.size();
+        slots.push_back(Slot{2, gc, true, it_owner[gc], cptr[2][gc], clog[c]});
+      }
     }
-    // ---- the sampled values: wait, gather, mix; then the quotient kernels ----
+    const size_t n_slots = slots.size();
+    d_oods_out.alloc(n_slots * 16);
+    std::map<uint32_t, CPoint<QM31>> prev_points;
+    std::vector<uint32_t> samples(4 * n_slots, 0);
+    // (d_oods_out: every slot is written by the upload of the gathered samples below)
+    // jobs = (log, prev?) groups of the slots this rank evaluates (trees 0 / 3: every rank, so that nobody waits for them)
+    std::map<std::pair<uint32_t, bool>, std::vector<uint32_t>> groups;
+    for (uint32_t s = 0; s < n_slots; s++)
+      if (slots[s].coeffs) groups[{slots[s].log, slots[s].prev}].push_back(s);
+    std::vector<const uint32_t*> table;
+    struct J { uint32_t log; bool prev; size_t off, n; std::vector<uint32_t> ids; };
+    std::vector<J> js;
+    for (auto& kv : groups) {
+      J j{kv.first.first, kv.first.second, table.size(), kv.second.size(), kv.second};
+      for (auto s : kv.second) table.push_back(slots[s].coeffs);
+      js.push_back(j);
+    }
+    DevBuf &d_table = d_oods_table = upload(table, st), &d_tmp = d_oods_tmp;
+    size_t n_tmp = table.size();
+    d_tmp.alloc(n_tmp * 16 + 16);
+    std::vector<EapJob> ej;
+    for (auto& j : js) {
+      CPoint<QM31> pt = oods;
+      EapJob e{j.log, (uint32_t)j.n, d_table.as<const uint32_t*>() + j.off, QM31(), QM31(), d_tmp.u32() + 4 * j.off};
+      if (j.prev) {
+        CPoint<M31> step = point_at_index(subgroup_gen_index(j.log));
+        if (tree_stream) { e.has_shift = true; e.shift_x = step.x.v; e.shift_y = (-step.y).v; }
+        else pt = cadd(oods, CPoint<QM31>{QM31(step.x), QM31(-step.y)});
+      }
+      e.px = pt.x; e.py = pt.y;
+      ej.push_back(e);
+    }
+    eval_at_point_multi(ej, st, tree_stream ? ts + TS_STEP3 : nullptr);
+    std::vector<uint32_t> tmp(4 * n_tmp);
+    const void* tmp_land = n_tmp ? stage_download_async(d_tmp.p, tmp.size() * 4, st) : nullptr;   // pinned: read after the synchronisation below
+    if (tree_stream) {
+      // host replay of the steps behind trees 2 and 3, in transcript order, as soon as root 3 is back — the evaluation kernels are
+      // still running (the one round trip since the claimed sums)
+      CM_HIP(hipEventSynchronize(ev_root3));
+      check_halo(/*synchronise=*/false);
+      complete_sliced(cm, sl2, pin_sub2);
+      CM_CHECK(memcmp(sl2.root.data(), pinned_words() + PIN_ROOT2, 32) == 0, "sharded interaction commitment: the device's tree top differs from the host's");
+      ch.mix_root(sl2.root);
+      const QM31 rho = ch.draw_felt();
+      CM_CHECK(rho == QM31::from_u32(pinned_words() + PIN_COEFF), "composition: device transcript diverged from the host channel");
+      QM31 pw(M31(1));
+      for (size_t g = powers.size(); g-- > 0;) { powers[g] = pw; pw = pw * rho; }   // host copy: the OODS check needs it
+      complete_sliced(cm, sl3, pin_sub3);
+      CM_CHECK(memcmp(sl3.root.data(), pinned_words() + PIN_STEP3 + 4, 32) == 0, "sharded composition commitment: the device's tree top differs from the host's");
+      P.trees[3].root = sl3.root;
+      ch.mix_root(sl3.root);
+      QM31 t;
+      oods = draw_oods_point(ch, &t);
+      CM_CHECK(t == QM31::from_u32(pinned_words() + PIN_STEP3), "oods: device transcript diverged from the host channel");
+    }
+    for (int c = 0; c < air::N_COMPONENTS; c++) {
+      CPoint<M31> step = point_at_index(subgroup_gen_index(clog[c]));
+      prev_points[clog[c]] = cadd(oods, CPoint<QM31>{QM31(step.x), QM31(-step.y)});
+    }
+    // mask sizes now ([oods] or [previous row, oods]), values below: the quotient tables are built while the evaluation kernels run
+    pf.sampled_values.resize(4);
+    for (int t = 0; t < 4; t++) {
+      pf.sampled_values[t].resize(n_cols_t[t]);
+      for (uint32_t c = 0; c < n_cols_t[t]; c++)
+        for (int k = (t == 2 && sidx_prev[2][c] != 0 ? 2 : 1); k > 0; k--) pf.sampled_values[t][c].push_back(QM31());
+    }
+    plan_deep_quotients(sidx_cur, sidx_prev, prev_points);
+    // ---- the sampled values: wait, gather, mix ----
     {
       CM_HIP(hipStreamSynchronize(st));
       if (n_tmp) memcpy(tmp.data(), tmp_land, tmp.size() * 4);
@@ -1489,8 +1423,35 @@ ProofData* prove_sharded(const DeviceInput& din, const cm_pcs_config& cfg, const
       ch.mix_felts(flat.data(), flat.size());
     }
     P.tick("oods_sampling");
+  }
+  // DEEP quotients of the own ROWS, host half (quotient_plan.hpp; no sampled value needed yet): plan, upload, launch arguments
+  void plan_deep_quotients(const std::vector<std::vector<uint32_t>>& sidx_cur, const std::vector<std::vector<uint32_t>>& sidx_prev,
+                           const std::map<uint32_t, CPoint<QM31>>& prev_points) {
+    std::vector<QuotientCol> qcols;
+    for (int t = 0; t < 4; t++)
+      for (uint32_t c = 0; c < n_cols_t[t]; c++) {
+        const uint32_t lde_log = col_log(t, c) + B;
+        const uint64_t sl = (uint64_t)1 << (lde_log - logN);
+        qcols.push_back({t, c, lde_log, /* this rank's row slice */ t == 0 || t == 3 ? P.trees[t].lde.ptrs[c] + (uint64_t)R * sl : t == 1 ? sl1.slice[c] : sl2.slice[c]});
+      }
+    QuotientPlan qp; const QuotientWindow win{(int)logN, R};   // this rank's rows
+    qp.build(qcols, pf.sampled_values, sidx_cur, sidx_prev, oods, prev_points, B, win, st);
+    d_qblob.alloc(qp.blob.size());
+    qp.bind(d_qblob.as<uint8_t>());
+    stage_upload(d_qblob.p, qp.blob.data(), qp.blob.size(), st);   // (behind the evaluation kernels, in front of the wait)
+    o_qjobs = qp.o_jobs; n_qjobs = qp.n_jobs; gs = std::move(qp.groups);
+    qargs = quotient_args(gs, d_qblob.as<uint8_t>(), *P.tw, win);
+    // "quot_leaf": the first-layer FRI subtree's leaf layer is written by the LARGEST group's quotient kernel (prover.hip deep_quotients)
+    if (shard_fri_stop_log() < 99 && quotient_leaf_wanted(qargs)) {
+      fri_first.local.leaf_prealloc.alloc((size_t)32 * qargs[0].first.n_rows);
+      qargs[0].first.leaf_hashes = fri_first.local.leaf_prealloc.u32();
+      fri_first.leaf_done = true;
+    }
+  }
+  // compute_fri_quotients: one launch per size group
+  void deep_quotients() {
     const QM31 qcoeff = ch.draw_felt();
-    quotient_coeffs((const QuotientCoefJob*)(base + o_jobs), (uint32_t)n_jobs, d_oods_out.u32(), qcoeff, st);
+    quotient_coeffs((const QuotientCoefJob*)(d_qblob.as<uint8_t>() + o_qjobs), (uint32_t)n_qjobs, d_oods_out.u32(), qcoeff, st);
     {
       // one kernel per size group, independent outputs: the small groups (latency-bound) together on one side stream first, the
       // large ones by descending size on streams of their own (the single-GPU prover's region)
@@ -1502,40 +1463,52 @@ ProofData* prove_sharded(const DeviceInput& din, const cm_pcs_config& cfg, const
       fkq.join();
     }
     for (auto& g : gs) q_logs.push_back(g.log);
-    // (d_blob is a temporary: pool blocks are reused in stream order, no host synchronisation)
+    d_qblob.release(); qargs.clear();   // (where d_blob's block ended: pool blocks are reused in stream order, no host synchronisation)
+    P.tick("quotients");
   }
-  P.tick("quotients");
-
   // ---- FRI commit.  Folds are pair-local (rows 2i, 2i + 1 of a layer give row i of the next), so a rank that holds rows
   // [r, r+1) * 2^l / N of a layer produces the same range of the next one with no exchange; a layer's tree is the rank's subtree +
   // a 32-byte all-gather + the top log2 N levels (SlicedTree, like the four commitment trees).  The first-layer tree (over the
   // quotient slices) and every inner layer above 2^stop rows are committed that way, with the transcript on the host channel;
   // then the current layer and the small quotient groups are all-gathered and FriPhase::commit finishes on every rank (device-side
   // transcript, k_fri_tail) — the replicated part is the latency-bound tail only. ----
-  const uint32_t last_log = cfg.log_last_layer_degree_bound + cfg.log_blowup_factor;
-  QM31 alpha_c;
-  uint32_t layer_log = q_logs[0] - 1;
-  size_t qi_next = 0;
-  ColumnSet cur;          // this rank's rows of the layer being built
-  bool cur_valid = false;
-  const bool shard_fri = shard_fri_stop_log() < 99;
-  // (round 6) "shard_fri_stream": the sharded layers stay ON THE STREAM — after a tree's 32-byte all-gather ONE kernel hashes the
-  // top log2 N levels over the N sub-roots, mixes the root into a device copy of the channel and draws the folding challenge
-  // (k_shard_top_step); the fold kernels read the challenge from device memory.  The host replays every step (top levels for the
-  // decommitment, mix_root, draw_felt) ONCE behind the last sharded layer and refuses the proof on a mismatch, instead of
-  // stopping the stream for a root and a challenge after every tree (7 round trips at the metric config).  With a host-blocking
-  // cm_comm the collective itself still waits; with the stream-ordered RCCL communicator nothing does.  0 = the host-driven form.
-  const bool fri_stream = shard_fri && tune(T_SHARD_FRI_STREAM) != 0 && !framing().hash_node_rfc;
-  DevBuf d_fs;                              // {device channel, per tree: challenge, root, sub-roots}: alive until the proof returns
-  std::vector<uint32_t> fri_back;           // the host copy of the slots, filled by fri_replay
-  const uint32_t* fri_back_land = nullptr;
-  hipEvent_t ev_fri_back = nullptr;
-  std::vector<SlicedTree*> fri_order;
-  size_t fri_slot_words = 0;
-  const uint32_t *rs_d_chan = nullptr, *rs_d_alpha_c = nullptr;
-  if (shard_fri) {
+  void fri_and_pow() {
+    last_log = cfg.log_last_layer_degree_bound + cfg.log_blowup_factor;
+    layer_log = q_logs[0] - 1;
+    shard_fri = shard_fri_stop_log() < 99;
+    // (round 6) "shard_fri_stream": the sharded layers stay ON THE STREAM — after a tree's 32-byte all-gather ONE kernel hashes the
+    // top log2 N levels over the N sub-roots, mixes the root into a device copy of the channel and draws the folding challenge
+    // (k_shard_top_step); the fold kernels read the challenge from device memory.  The host replays every step (top levels for the
+    // decommitment, mix_root, draw_felt) ONCE behind the last sharded layer and refuses the proof on a mismatch, instead of
+    // stopping the stream for a root and a challenge after every tree (7 round trips at the metric config).  With a host-blocking
+    // cm_comm the collective itself still waits; with the stream-ordered RCCL communicator nothing does.  0 = the host-driven form.
+    fri_stream = shard_fri && tune(T_SHARD_FRI_STREAM) != 0 && !framing().hash_node_rfc;
+    if (shard_fri) fri_sharded_layers();
+    fri_hand_over();
+    {
+      FriResume rs;
+      rs.layer = cur_valid ? &full_layer : nullptr;
+      rs.layer_log = layer_log;
+      rs.qi = qi_next;
+      rs.n_inner_before = (uint32_t)sfl.size();
+      rs.alpha_c = alpha_c;
+      rs.d_chan = rs_d_chan;
+      rs.d_alpha_c = rs_d_alpha_c;
+      fri.commit(P, cfg, quotients, q_logs, pf, [&] {
+        fri_replay();   // (fri_stream) the sharded layers' steps, in front of FriPhase's own replay
+        check_composition_at_oods(pf, tr0, it0, clog, hrel, powers, coff, oods);
+      }, shard_fri ? &rs : nullptr);
+    }
+    hm.mark("fri_commit returned");
+    P.tick("fri_commit");
+    pf.proof_of_work = grind_gpu(ch.digest.data(), cfg.pow_bits, st);
+    ch.mix_u64(pf.proof_of_work);
+    P.tick("pow");
+  }
+  // the first-layer tree and every layer above 2^stop rows, by row range
+  void fri_sharded_layers() {
     for (auto& g : gs)
-      for (int c = 0; c < 4; c++) { fri_first.lde_logs.push_back(g.log); fri_first.slice.push_back(g.out_slice.ptrs[c]); }
+      for (int c = 0; c < 4; c++) { fri_first.lde_logs.push_back(g.log); fri_first.slice.push_back(g.out.ptrs[c]); }
     const uint32_t stop = std::max(shard_fri_stop_log(), logN + 5);   // a slice keeps at least 2^5 rows
     const uint32_t n_slots = 1 + (layer_log > last_log ? layer_log - last_log : 0);   // first-layer tree + every possible inner layer
     const size_t slot_words = 4 + 8 + 8 * (size_t)N;                                     // {challenge, root, sub-roots} per tree
@@ -1586,7 +1559,7 @@ ProofData* prove_sharded(const DeviceInput& din, const cm_pcs_config& cfg, const
         sliced_prepare(cm, X.tree, st);
         uint32_t* leaves = sliced_leaf_target(X.tree);
         const uint32_t* circ[4] = {nullptr, nullptr, nullptr, nullptr};
-        if (n_groups) for (int c = 0; c < 4; c++) circ[c] = gs[qi_next].out_slice.ptrs[c];
+        if (n_groups) for (int c = 0; c < 4; c++) circ[c] = gs[qi_next].out.ptrs[c];
         const bool fused = leaves && (prev ? fold_line_leaf(X.slice.ptrs.data(), lsrc, n_groups ? circ : nullptr, prev->log, *P.tw, st, d_alpha(prev_slot), d_alpha(0), leaves, row0, n_loc)
                                            : fold_circle_leaf(X.slice.ptrs.data(), circ, gs[qi_next].log, *P.tw, st, d_alpha(0), leaves, row0, n_loc));
         if (fused) { X.tree.leaf_done = true; qi_next += n_groups; return; }
@@ -1594,7 +1567,7 @@ ProofData* prove_sharded(const DeviceInput& din, const cm_pcs_config& cfg, const
       bool blank = true;
       if (prev) { fold_line_rows(X.slice.ptrs.data(), lsrc, prev->log, *P.tw, prev_alpha, row0, n_loc, st, fri_stream ? d_alpha(prev_slot) : nullptr); blank = false; }
       for (size_t k = 0; k < n_groups; k++, qi_next++) {
-        const uint32_t* src[4] = {gs[qi_next].out_slice.ptrs[0], gs[qi_next].out_slice.ptrs[1], gs[qi_next].out_slice.ptrs[2], gs[qi_next].out_slice.ptrs[3]};
+        const uint32_t* src[4] = {gs[qi_next].out.ptrs[0], gs[qi_next].out.ptrs[1], gs[qi_next].out.ptrs[2], gs[qi_next].out.ptrs[3]};
         fold_circle_into_line_rows(X.slice.ptrs.data(), src, gs[qi_next].log, *P.tw, alpha_c, !blank, row0, n_loc, st, fri_stream ? d_alpha(0) : nullptr);
         blank = false;
       }
@@ -1630,24 +1603,20 @@ ProofData* prove_sharded(const DeviceInput& din, const cm_pcs_config& cfg, const
       // NOT here: the words travel to pinned memory behind an event, the replicated layers are enqueued first (FriPhase takes the
       // device channel and the circle-fold challenge from device memory: FriResume::d_chan / d_alpha_c) and the host replays while
       // they run (fri_replay below).  It used to stop the stream: ~70 us of idle GPU in the round-6 timeline.
-      fri_back.resize(order.size() * slot_words);
-      fri_back_land = (const uint32_t*)stage_download_async(d_slots, fri_back.size() * 4, st);
+      CM_CHECK(order.size() * slot_words <= PIN_WORDS - PIN_SHARD_FRI, "sharded fri: more layers than the pinned slot holds");
+      CM_HIP(hipMemcpyAsync(pinned_words() + PIN_SHARD_FRI, d_slots, order.size() * slot_words * 4, hipMemcpyDeviceToHost, st));
+      fri_back_land = pinned_words() + PIN_SHARD_FRI;
       static thread_local hipEvent_t ev = nullptr;
-      if (!ev) { CM_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); thread_event_owned(ev); }
-      CM_HIP(hipEventRecord(ev, st));
-      ev_fri_back = ev;
-      fri_order = order;
-      fri_slot_words = slot_words;
-      rs_d_chan = d_chan;
-      rs_d_alpha_c = d_alpha(0);
+      CM_HIP(hipEventRecord(ev_fri_back = thread_event(ev), st));
+      fri_order = order; fri_slot_words = slot_words;
+      rs_d_chan = d_chan; rs_d_alpha_c = d_alpha(0);
     } else pf.fri_first.commitment = fri_first.root;
   }
-  auto fri_replay = [&] {
-    if (!ev_fri_back) return;
+  void fri_replay() {
+    if (!ev_fri_back) return;   // (the host-driven form replayed every step where it happened)
     CM_HIP(hipEventSynchronize(ev_fri_back));
-    memcpy(fri_back.data(), fri_back_land, fri_back.size() * 4);   // (the landing buffer is reused by the next download)
     for (size_t k = 0; k < fri_order.size(); k++) {
-      const uint32_t* w = &fri_back[k * fri_slot_words];
+      const uint32_t* w = &fri_back_land[k * fri_slot_words];
       complete_sliced(cm, *fri_order[k], w + 12);
       CM_CHECK(memcmp(fri_order[k]->root.data(), w + 4, 32) == 0, "sharded fri: the device's tree top differs from the host's");
       ch.mix_root(fri_order[k]->root);
@@ -1655,209 +1624,190 @@ ProofData* prove_sharded(const DeviceInput& din, const cm_pcs_config& cfg, const
       CM_CHECK(a == QM31::from_u32(w), "sharded fri: the device transcript diverged from the host channel");
     }
     pf.fri_first.commitment = fri_first.root;
-  };
+  }
   // hand-over: the current layer's slices and the quotient groups not folded yet -> full columns on every rank
-  ColumnSet full_layer;
-  if (N == 1) {
-    // a lone rank's slices ARE the columns: the layer moves, the quotient groups not folded yet are aliased (their storage stays
-    // with `gs`, which the decommitment of the first-layer tree reads and which outlives `quotients`' users)
-    const size_t g0 = shard_fri ? qi_next : 0;
-    if (cur_valid) full_layer = std::move(cur);
-    for (size_t gi = 0; gi < gs.size(); gi++) {
-      quotients.emplace_back();
-      if (gi >= g0) { quotients.back().logs.assign(4, gs[gi].log); quotients.back().ptrs = gs[gi].out_slice.ptrs; }
-    }
-  } else {
-    const size_t g0 = shard_fri ? qi_next : 0;
-    uint64_t per_rank = 0;
-    if (cur_valid) per_rank += (uint64_t)4 << (layer_log - logN);
-    for (size_t gi = g0; gi < gs.size(); gi++) per_rank += (uint64_t)4 << (gs[gi].log - logN);
-    cm.need(per_rank * N);
-    {
-      std::vector<CopySeg> segs;
-      uint64_t off = 0;
-      if (cur_valid) for (int c = 0; c < 4; c++) { const uint64_t sl = (uint64_t)1 << (layer_log - logN); segs.push_back(CopySeg{cur.ptrs[c], comm_c.send_buf + off, sl}); off += sl; }
-      for (size_t gi = g0; gi < gs.size(); gi++)
-        for (int c = 0; c < 4; c++) { const uint64_t sl = (uint64_t)1 << (gs[gi].log - logN); segs.push_back(CopySeg{gs[gi].out_slice.ptrs[c], comm_c.send_buf + off, sl}); off += sl; }
-      copy_segments(segs, st);
-    }
-    cm.all_gather(per_rank);
-    {
-      std::vector<CopySeg> segs;
-      if (cur_valid) full_layer.alloc(std::vector<uint32_t>(4, layer_log), st, false);
+  void fri_hand_over() {
+    if (N == 1) {
+      // a lone rank's slices ARE the columns: the layer moves, the quotient groups not folded yet are aliased (their storage stays
+      // with `gs`, which the decommitment of the first-layer tree reads and which outlives `quotients`' users)
+      const size_t g0 = shard_fri ? qi_next : 0;
+      if (cur_valid) full_layer = std::move(cur);
       for (size_t gi = 0; gi < gs.size(); gi++) {
         quotients.emplace_back();
-        if (gi >= g0) quotients.back().alloc(std::vector<uint32_t>(4, gs[gi].log), st, false);
+        if (gi >= g0) { quotients.back().logs.assign(4, gs[gi].log); quotients.back().ptrs = gs[gi].out.ptrs; }
       }
-      for (uint32_t sr = 0; sr < N; sr++) {
-        uint64_t off = (uint64_t)sr * per_rank;
-        if (cur_valid) for (int c = 0; c < 4; c++) { const uint64_t sl = (uint64_t)1 << (layer_log - logN); segs.push_back(CopySeg{comm_c.recv_buf + off, full_layer.ptrs[c] + (uint64_t)sr * sl, sl}); off += sl; }
-        for (size_t gi = g0; gi < gs.size(); gi++)
-          for (int c = 0; c < 4; c++) {
-            const uint64_t sl = (uint64_t)1 << (gs[gi].log - logN);
-            segs.push_back(CopySeg{comm_c.recv_buf + off, quotients[gi].ptrs[c] + (uint64_t)sr * sl, sl});
-            off += sl;
-          }
-      }
-      copy_segments(segs, st);
-    }
-  }
-  {
-    FriResume rs;
-    rs.layer = cur_valid ? &full_layer : nullptr;
-    rs.layer_log = layer_log;
-    rs.qi = qi_next;
-    rs.n_inner_before = (uint32_t)sfl.size();
-    rs.alpha_c = alpha_c;
-    rs.d_chan = rs_d_chan;
-    rs.d_alpha_c = rs_d_alpha_c;
-    fri.commit(P, cfg, quotients, q_logs, pf, [&] {
-      fri_replay();   // (fri_stream) the sharded layers' steps, in front of FriPhase's own replay
-      check_composition_at_oods(pf, tr0, it0, clog, hrel, powers, coff, oods);
-    }, shard_fri ? &rs : nullptr);
-  }
-  hm.mark("fri_commit returned");
-  P.tick("fri_commit");
-  pf.proof_of_work = grind_gpu(ch.digest.data(), cfg.pow_bits, st);
-  ch.mix_u64(pf.proof_of_work);
-  P.tick("pow");
-
-  // ---- queries + decommitment ----
-  hm.mark("pow done");
-  Queries queries = Queries::draw(ch, cfg.n_queries, q_logs[0]);
-  std::map<uint32_t, std::vector<uint32_t>> qpos;
-  for (auto l : q_logs) qpos[l] = queries.fold(queries.log_domain_size - l).positions;
-  {
-    // two gathers: (A) the replicated FRI layers + the four commitment trees — enqueued as soon as it is planned, so that it runs while
-    // the host plans (B) the row-sharded FRI layers; one wait for both
-    GatherBatch gb, gbB;
-    fri.plan_decommit(queries, qpos, quotients, q_logs, gb);
-    hm.mark("decommit: queries + replicated plan");   // the replicated layers (and the first-layer tree when FRI is not sharded)
-    const SlicedTree* slt[4] = {&sl0, &sl1, &sl2, &sl3};
-    pf.decommitments.resize(4);
-    pf.queried_values.resize(4);
-    // sections in one fixed order on every rank: the four commitment trees, then the row-sharded FRI layers
-    std::vector<std::unique_ptr<ShardSection>> secs;
-    auto new_sec = [&]() -> ShardSection& { secs.emplace_back(new ShardSection()); return *secs.back(); };
-    for (int t = 0; t < 4; t++) {
-      ShardSection& sc = new_sec();
-      sc.d = &pf.decommitments[t]; sc.qv = &pf.queried_values[t]; sc.gb = &gb;
-      plan_sharded_decommit(*slt[t], cm, qpos, gb, sc.fetch, sc.sd);
-    }
-    hm.mark("decommit: four trees planned");
-    // pinned landing words of both gathers: A's size is known, B's is bounded (per sharded tree and query: two hashes and a
-    // handful of values per layer); a B beyond the bound — never seen — waits for A and takes the landing buffer for itself
-    const size_t wordsA = gb.total_words();
-    const size_t boundB = (sfl.size() + 1 + gs.size()) * (size_t)cfg.n_queries * 24 * 32;
-    uint32_t* const land = (uint32_t*)stage_landing((wordsA + boundB) * 4, st);
-    gb.enqueue(st, land);
-    pf.fri_inner.reserve(sfl.size() + fri.inner.size());   // sections keep pointers into the first entries: no reallocation later
-    pf.fri_inner.resize(sfl.size());
-    if (shard_fri) {
-      std::map<uint32_t, std::vector<uint32_t>> first_dpos;
-      for (auto& g : gs) {
-        ShardSection& sc = new_sec();
-        sc.wit = &pf.fri_first.fri_witness; sc.gb = &gbB;
-        std::vector<uint32_t> pos;
-        plan_fri_positions_sharded(cm, g.log, g.out_slice.ptrs.data(), qpos.at(g.log), pos, gbB, sc.fetch, sc.sd);
-        first_dpos[g.log] = std::move(pos);
-      }
+    } else {
+      const size_t g0 = shard_fri ? qi_next : 0;
+      uint64_t per_rank = 0;
+      if (cur_valid) per_rank += (uint64_t)4 << (layer_log - logN);
+      for (size_t gi = g0; gi < gs.size(); gi++) per_rank += (uint64_t)4 << (gs[gi].log - logN);
+      cm.need(per_rank * N);
       {
-        ShardSection& sc = new_sec();
-        sc.d = &pf.fri_first.decommitment; sc.gb = &gbB;
-        plan_sharded_decommit(fri_first, cm, first_dpos, gbB, sc.fetch, sc.sd);
+        std::vector<CopySeg> segs;
+        uint64_t off = 0;
+        if (cur_valid) for (int c = 0; c < 4; c++) { const uint64_t sl = (uint64_t)1 << (layer_log - logN); segs.push_back(CopySeg{cur.ptrs[c], comm_c.send_buf + off, sl}); off += sl; }
+        for (size_t gi = g0; gi < gs.size(); gi++)
+          for (int c = 0; c < 4; c++) { const uint64_t sl = (uint64_t)1 << (gs[gi].log - logN); segs.push_back(CopySeg{gs[gi].out.ptrs[c], comm_c.send_buf + off, sl}); off += sl; }
+        copy_segments(segs, st);
       }
-      Queries lq = queries.fold(1);
-      for (size_t i = 0; i < sfl.size(); i++) {
-        ShardedFriLayer& L = *sfl[i];
-        std::map<uint32_t, std::vector<uint32_t>> dpos;
+      cm.all_gather(per_rank);
+      {
+        std::vector<CopySeg> segs;
+        if (cur_valid) full_layer.alloc(std::vector<uint32_t>(4, layer_log), st, false);
+        for (size_t gi = 0; gi < gs.size(); gi++) {
+          quotients.emplace_back();
+          if (gi >= g0) quotients.back().alloc(std::vector<uint32_t>(4, gs[gi].log), st, false);
+        }
+        for (uint32_t sr = 0; sr < N; sr++) {
+          uint64_t off = (uint64_t)sr * per_rank;
+          if (cur_valid) for (int c = 0; c < 4; c++) { const uint64_t sl = (uint64_t)1 << (layer_log - logN); segs.push_back(CopySeg{comm_c.recv_buf + off, full_layer.ptrs[c] + (uint64_t)sr * sl, sl}); off += sl; }
+          for (size_t gi = g0; gi < gs.size(); gi++)
+            for (int c = 0; c < 4; c++) {
+              const uint64_t sl = (uint64_t)1 << (gs[gi].log - logN);
+              segs.push_back(CopySeg{comm_c.recv_buf + off, quotients[gi].ptrs[c] + (uint64_t)sr * sl, sl});
+              off += sl;
+            }
+        }
+        copy_segments(segs, st);
+      }
+    }
+  }
+  // queries + decommitment
+  void decommit() {
+    hm.mark("pow done");
+    Queries queries = Queries::draw(ch, cfg.n_queries, q_logs[0]);
+    std::map<uint32_t, std::vector<uint32_t>> qpos;
+    for (auto l : q_logs) qpos[l] = queries.fold(queries.log_domain_size - l).positions;
+    {
+      // two gathers: (A) the replicated FRI layers + the four commitment trees — enqueued as soon as it is planned, so that it runs while
+      // the host plans (B) the row-sharded FRI layers; one wait for both
+      GatherBatch gb, gbB;
+      fri.plan_decommit(queries, qpos, quotients, q_logs, gb);
+      hm.mark("decommit: queries + replicated plan");   // the replicated layers (and the first-layer tree when FRI is not sharded)
+      const SlicedTree* slt[4] = {&sl0, &sl1, &sl2, &sl3};
+      pf.decommitments.resize(4);
+      pf.queried_values.resize(4);
+      // sections in one fixed order on every rank: the four commitment trees, then the row-sharded FRI layers
+      std::vector<std::unique_ptr<ShardSection>> secs;
+      auto new_sec = [&]() -> ShardSection& { secs.emplace_back(new ShardSection()); return *secs.back(); };
+      for (int t = 0; t < 4; t++) {
+        ShardSection& sc = new_sec();
+        sc.d = &pf.decommitments[t]; sc.qv = &pf.queried_values[t]; sc.gb = &gb;
+        plan_sharded_decommit(*slt[t], cm, qpos, gb, sc.fetch, sc.sd);
+      }
+      hm.mark("decommit: four trees planned");
+      // pinned landing words of both gathers: A's size is known, B's is bounded (per sharded tree and query: two hashes and a
+      // handful of values per layer); a B beyond the bound — never seen — waits for A and takes the landing buffer for itself
+      const size_t wordsA = gb.total_words();
+      const size_t boundB = (sfl.size() + 1 + gs.size()) * (size_t)cfg.n_queries * 24 * 32;
+      uint32_t* const land = (uint32_t*)stage_landing((wordsA + boundB) * 4, st);
+      gb.enqueue(st, land);
+      pf.fri_inner.reserve(sfl.size() + fri.inner.size());   // sections keep pointers into the first entries: no reallocation later
+      pf.fri_inner.resize(sfl.size());
+      if (shard_fri) {
+        std::map<uint32_t, std::vector<uint32_t>> first_dpos;
+        for (auto& g : gs) {
+          ShardSection& sc = new_sec();
+          sc.wit = &pf.fri_first.fri_witness; sc.gb = &gbB;
+          std::vector<uint32_t> pos;
+          plan_fri_positions_sharded(cm, g.log, g.out.ptrs.data(), qpos.at(g.log), pos, gbB, sc.fetch, sc.sd);
+          first_dpos[g.log] = std::move(pos);
+        }
         {
           ShardSection& sc = new_sec();
-          sc.wit = &pf.fri_inner[i].fri_witness; sc.gb = &gbB;
-          plan_fri_positions_sharded(cm, L.log, L.slice.ptrs.data(), lq.positions, dpos[L.log], gbB, sc.fetch, sc.sd);
+          sc.d = &pf.fri_first.decommitment; sc.gb = &gbB;
+          plan_sharded_decommit(fri_first, cm, first_dpos, gbB, sc.fetch, sc.sd);
         }
-        ShardSection& sc = new_sec();
-        sc.d = &pf.fri_inner[i].decommitment; sc.gb = &gbB;
-        plan_sharded_decommit(L.tree, cm, dpos, gbB, sc.fetch, sc.sd);
-        pf.fri_inner[i].commitment = L.tree.root;
-        lq = lq.fold(1);
+        Queries lq = queries.fold(1);
+        for (size_t i = 0; i < sfl.size(); i++) {
+          ShardedFriLayer& L = *sfl[i];
+          std::map<uint32_t, std::vector<uint32_t>> dpos;
+          {
+            ShardSection& sc = new_sec();
+            sc.wit = &pf.fri_inner[i].fri_witness; sc.gb = &gbB;
+            plan_fri_positions_sharded(cm, L.log, L.slice.ptrs.data(), lq.positions, dpos[L.log], gbB, sc.fetch, sc.sd);
+          }
+          ShardSection& sc = new_sec();
+          sc.d = &pf.fri_inner[i].decommitment; sc.gb = &gbB;
+          plan_sharded_decommit(L.tree, cm, dpos, gbB, sc.fetch, sc.sd);
+          pf.fri_inner[i].commitment = L.tree.root;
+          lq = lq.fold(1);
+        }
       }
-    }
-    hm.mark("decommit: sharded FRI planned");
-    std::vector<uint32_t> keepA;
-    if (gbB.total_words() <= boundB) {
-      gbB.enqueue(st, land + wordsA);
-      CM_HIP(hipStreamSynchronize(st));
-    } else {
-      CM_HIP(hipStreamSynchronize(st));
-      keepA.assign(land, land + wordsA);
-      gb.words = keepA.data() + (gb.words - land); gb.hashes = keepA.data() + (gb.hashes - land); gb.run_out = keepA.data() + (gb.run_out - land);
-      gbB.run(st);
-    }
-    hm.mark("decommit: gather ran");
-    const FriLayerProofData* const inner_base = pf.fri_inner.data();
-    fri.finish_decommit(gb, pf);   // appends the replicated inner layers behind the sharded ones
-    CM_CHECK(pf.fri_inner.data() == inner_base, "sharded decommitment: fri_inner was reallocated under the section pointers");
-    // my items of every section, in script order -> all ranks (a lone rank has nobody to tell: it assembles straight from the gather)
-    auto fetched = [&](const ShardSection& sc, const std::pair<int, size_t>& f) -> const uint32_t* {
-      return f.first == 0 ? &sc.gb->hashes[8 * f.second] : f.first == 1 ? &sc.gb->run_out[f.second] : &sc.gb->words[f.second];
-    };
-    std::vector<uint32_t> all;
-    uint64_t maxw = 0;
-    if (N > 1) {
-      for (uint32_t k = 0; k < N; k++) {
-        uint64_t w = 0;
-        for (auto& sc : secs) w += sc->sd.words_of[k];
-        maxw = std::max(maxw, w);
+      hm.mark("decommit: sharded FRI planned");
+      std::vector<uint32_t> keepA;
+      if (gbB.total_words() <= boundB) {
+        gbB.enqueue(st, land + wordsA);
+        CM_HIP(hipStreamSynchronize(st));
+      } else {
+        CM_HIP(hipStreamSynchronize(st));
+        keepA.assign(land, land + wordsA);
+        gb.words = keepA.data() + (gb.words - land); gb.hashes = keepA.data() + (gb.hashes - land); gb.run_out = keepA.data() + (gb.run_out - land);
+        gbB.run(st);
       }
-      std::vector<uint32_t> mine_items;
-      mine_items.reserve(maxw);
+      hm.mark("decommit: gather ran");
+      const FriLayerProofData* const inner_base = pf.fri_inner.data();
+      fri.finish_decommit(gb, pf);   // appends the replicated inner layers behind the sharded ones
+      CM_CHECK(pf.fri_inner.data() == inner_base, "sharded decommitment: fri_inner was reallocated under the section pointers");
+      // my items of every section, in script order -> all ranks (a lone rank has nobody to tell: it assembles straight from the gather)
+      auto fetched = [&](const ShardSection& sc, const std::pair<int, size_t>& f) -> const uint32_t* {
+        return f.first == 0 ? &sc.gb->hashes[8 * f.second] : f.first == 1 ? &sc.gb->run_out[f.second] : &sc.gb->words[f.second];
+      };
+      std::vector<uint32_t> all;
+      uint64_t maxw = 0;
+      if (N > 1) {
+        for (uint32_t k = 0; k < N; k++) {
+          uint64_t w = 0;
+          for (auto& sc : secs) w += sc->sd.words_of[k];
+          maxw = std::max(maxw, w);
+        }
+        std::vector<uint32_t> mine_items;
+        mine_items.reserve(maxw);
+        for (auto& sc : secs) {
+          size_t fi = 0;
+          for (auto& item : sc->sd.script) {
+            if (item.kind == 2 || item.owner != R) continue;
+            const uint32_t* w = fetched(*sc, sc->fetch[fi++]);
+            mine_items.insert(mine_items.end(), w, w + item.count);
+          }
+        }
+        mine_items.resize(maxw, 0);
+        all = cm.gather_host(mine_items);
+      }
+      hm.mark("decommit: items gathered");
+      std::vector<size_t> cursor(N);
+      for (uint32_t k = 0; k < N; k++) cursor[k] = (size_t)k * maxw;
       for (auto& sc : secs) {
         size_t fi = 0;
+        {   // one pass over the 8-byte items sizes the section's vectors (a proof carries ~1 MB of witnesses: no regrowth while copying)
+          size_t nh = 0, nw = 0, nq = 0, nf = 0;
+          for (auto& item : sc->sd.script) {
+            if (item.kind == 0 || item.kind == 2) nh++;
+            else if (item.kind == 3) nf++;
+            else if (item.is_query) nq += item.count;
+            else nw += item.count;
+          }
+          if (sc->d) { sc->d->hash_witness.reserve(sc->d->hash_witness.size() + nh); sc->d->column_witness.reserve(sc->d->column_witness.size() + nw); }
+          if (sc->qv) sc->qv->reserve(sc->qv->size() + nq);
+          if (sc->wit) sc->wit->reserve(sc->wit->size() + nf);
+        }
         for (auto& item : sc->sd.script) {
-          if (item.kind == 2 || item.owner != R) continue;
-          const uint32_t* w = fetched(*sc, sc->fetch[fi++]);
-          mine_items.insert(mine_items.end(), w, w + item.count);
+          if (item.kind == 2) { sc->d->hash_witness.push_back(sc->sd.host_hashes[item.count]); continue; }
+          const uint32_t* w = item.owner == R ? fetched(*sc, sc->fetch[fi++]) : &all[cursor[item.owner]];   // own items: from the gather itself
+          cursor[item.owner] += item.count;
+          if (item.kind == 0) { Hash32 h; memcpy(h.data(), w, 32); sc->d->hash_witness.push_back(h); }
+          else if (item.kind == 3) sc->wit->push_back(QM31::from_u32(w));
+          else if (item.is_query) { if (sc->qv) sc->qv->insert(sc->qv->end(), w, w + item.count); }
+          else sc->d->column_witness.insert(sc->d->column_witness.end(), w, w + item.count);
         }
       }
-      mine_items.resize(maxw, 0);
-      all = cm.gather_host(mine_items);
+      pf.commitments = {sl0.root, sl1.root, sl2.root, sl3.root};
     }
-    hm.mark("decommit: items gathered");
-    std::vector<size_t> cursor(N);
-    for (uint32_t k = 0; k < N; k++) cursor[k] = (size_t)k * maxw;
-    for (auto& sc : secs) {
-      size_t fi = 0;
-      {   // one pass over the 8-byte items sizes the section's vectors (a proof carries ~1 MB of witnesses: no regrowth while copying)
-        size_t nh = 0, nw = 0, nq = 0, nf = 0;
-        for (auto& item : sc->sd.script) {
-          if (item.kind == 0 || item.kind == 2) nh++;
-          else if (item.kind == 3) nf++;
-          else if (item.is_query) nq += item.count;
-          else nw += item.count;
-        }
-        if (sc->d) { sc->d->hash_witness.reserve(sc->d->hash_witness.size() + nh); sc->d->column_witness.reserve(sc->d->column_witness.size() + nw); }
-        if (sc->qv) sc->qv->reserve(sc->qv->size() + nq);
-        if (sc->wit) sc->wit->reserve(sc->wit->size() + nf);
-      }
-      for (auto& item : sc->sd.script) {
-        if (item.kind == 2) { sc->d->hash_witness.push_back(sc->sd.host_hashes[item.count]); continue; }
-        const uint32_t* w = item.owner == R ? fetched(*sc, sc->fetch[fi++]) : &all[cursor[item.owner]];   // own items: from the gather itself
-        cursor[item.owner] += item.count;
-        if (item.kind == 0) { Hash32 h; memcpy(h.data(), w, 32); sc->d->hash_witness.push_back(h); }
-        else if (item.kind == 3) sc->wit->push_back(QM31::from_u32(w));
-        else if (item.is_query) { if (sc->qv) sc->qv->insert(sc->qv->end(), w, w + item.count); }
-        else sc->d->column_witness.insert(sc->d->column_witness.end(), w, w + item.count);
-      }
-    }
-    pf.commitments = {sl0.root, sl1.root, sl2.root, sl3.root};
+    hm.mark("decommit: assembled");
+    P.tick("decommit");
   }
-  hm.mark("decommit: assembled");
-  P.tick("decommit");
-  P.finish();
-  fork_join_check();
-  pf.phase_ms = P.phase_ms;
-  pf.steps = 0;
-  for (int i = 0; i < CM_N_OPCODE_COMPONENTS; i++) pf.steps += in.n_bundles[i];
-  return out.release();
+};
+
+ProofData* prove_sharded(const DeviceInput& din, const cm_pcs_config& cfg, const cm_comm& comm_c) {
+  return ShardedProver(din, cfg, comm_c).run();
 }

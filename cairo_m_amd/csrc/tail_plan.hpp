@@ -35,7 +35,7 @@ struct DeviceTail {
     if (!device_tail_enabled() || q_logs.empty() || !fri.have_first) return false;
     const uint32_t last_log = cfg.log_last_layer_degree_bound + cfg.log_blowup_factor;
     return cfg.n_queries >= 1 && cfg.n_queries <= TAIL_MAX_QUERIES && q_logs[0] < TAIL_MAX_SHIFTS && q_logs[0] >= 1 &&
-           (1u << last_log) <= TAIL_MAX_LAST && 4u << last_log <= PIN_WORDS - PIN_LAST_LAYER && cfg.pow_bits <= TAIL_MAX_POW_BITS &&
+           (1u << last_log) <= TAIL_MAX_LAST && 4u << last_log <= PIN_LAST_LAYER_END - PIN_LAST_LAYER && cfg.pow_bits <= TAIL_MAX_POW_BITS &&
            (fri.n_inner_ + 1) * 12 <= PIN_LAST_LAYER - PIN_ALPHAS;
   }
 
