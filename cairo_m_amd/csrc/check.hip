@@ -1,5 +1,7 @@
 // PCS-free AIR check of a whole segment (reference: debug_tools::assert_constraints, crates/prover/src/debug_tools/
-// assert_constraints.rs:24-60, and its relation_tracker): the prover's own trace-generation, histogram, preprocessed-column and
+// assert_constraints.rs:24-60).  Of the reference's relation_tracker this file has the per-relation SUMS (which relation does not
+// balance); the summary of the tuples that do not cancel is track.hip, which runs this check first and keeps its columns.
+// The prover's own trace-generation, histogram, preprocessed-column and
 // LogUp kernels on trace-domain buffers only — no twiddles, LDE, Merkle trees or FRI — then the check kernels of kernels_check.inc
 // for all 34 components and the public data's LogUp contribution per relation.  One host round trip at the end (two when a lookup
 // value was out of range).  Threading as cm_prove_device: the calling thread's main stream and device pool.
@@ -38,7 +40,7 @@ void set_message(cm_check_report& rep, const std::string& m) {
 
 }  // namespace
 
-void check_segment(const DeviceInput& din, const cm_relations* relations, cm_check_report& rep) {
+void check_segment(const DeviceInput& din, const cm_relations* relations, cm_check_report& rep, CheckColumns* keep) {
   static_assert(sizeof(cm_relations) == sizeof(DevRelations), "cm_relations must mirror DevRelations");
   static_assert(CM_N_COMPONENTS == air::N_COMPONENTS && CM_N_RELATIONS == air::N_RELATIONS, "report dimensions");
   static_assert(sizeof(cm_check_report) % 8 == 0 && offsetof(cm_check_report, row) == 16, "cm_check_report: plain words");
@@ -46,15 +48,21 @@ void check_segment(const DeviceInput& din, const cm_relations* relations, cm_che
   const hipStream_t st = thread_main_stream();
   const cm_prover_input& in = din.meta;
   constexpr int NC = air::N_COMPONENTS;
-  uint32_t clog[NC];
+  CheckColumns own;
+  CheckColumns& cols = keep ? *keep : own;
+  uint32_t* const clog = cols.clog;
   component_logs(in, clog);
   for (int c = 0; c < NC; c++) CM_CHECK(clog[c] <= 26, "component too large");
 
   // ---- preprocessed columns, execution trace + lookup multiplicities (as SegmentProver::trace_commit, on one stream) ----
-  ColumnSet pp_evals, tr_evals, it_evals;
+  ColumnSet& pp_evals = cols.pp;
+  ColumnSet& tr_evals = cols.tr;
+  ColumnSet it_evals;
   pp_evals.alloc(std::vector<uint32_t>(air::PREPROC_LOG, air::PREPROC_LOG + air::N_PREPROC), st);
   launch_preproc_all(pp_evals.ptrs.data(), st);
-  std::vector<size_t> tr0(NC), it0(NC);
+  std::vector<size_t>& tr0 = cols.tr0;
+  std::vector<size_t> it0(NC);
+  tr0.assign(NC, 0);
   {
     std::vector<uint32_t> tl, il;
     for (int c = 0; c < NC; c++) {
@@ -106,7 +114,7 @@ void check_segment(const DeviceInput& din, const cm_relations* relations, cm_che
 
   // ---- relations: the caller's, or drawn from a fresh default channel (assert_constraints.rs:42) ----
   DevRelations drel_h;
-  HostRelations hrel;
+  HostRelations& hrel = cols.hrel;
   if (relations) {
     memcpy(&drel_h, relations, sizeof(DevRelations));
     host_relations(drel_h, hrel);
@@ -115,7 +123,8 @@ void check_segment(const DeviceInput& din, const cm_relations* relations, cm_che
     draw_relations(ch, hrel, drel_h);
   }
   memcpy(&rep.relations, &drel_h, sizeof(DevRelations));
-  DevBuf drel(sizeof(DevRelations));
+  DevBuf& drel = cols.drel;
+  drel.alloc(sizeof(DevRelations));
   stage_upload(drel.p, &drel_h, sizeof(DevRelations), st);
   const DevRelations* const d_rels = drel.as<DevRelations>();
   const uint32_t* const* const d_pp = (const uint32_t* const*)pp_evals.dev();

@@ -1,4 +1,5 @@
-// PCS-free AIR check for gfx950 (reference: debug_tools/assert_constraints.rs, relation_tracker): one thread per TRACE-domain row.
+// PCS-free AIR check for gfx950 (reference: debug_tools/assert_constraints.rs; the relation tracker proper is kernels_track.inc):
+// one thread per TRACE-domain row.
 //   k_check<C>        : every constraint of component C tested for zero on every row (RowCheckEval); failing rows counted with a
 //                       wave ballot + one atomic per wave that saw one, the lowest (row, constraint) by a 64-bit atomicMin.  A row
 //                       that satisfies its constraints issues no atomic at all.

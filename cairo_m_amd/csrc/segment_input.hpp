@@ -49,6 +49,18 @@ inline void draw_relations(hostch::Channel& ch, HostRelations& hrel, DevRelation
 // receives its part per relation (registers, merkle, memory; zero for the others).  verifier.hip
 QM31 public_logup_sum(const PublicData& d, const HostRelations& rel, QM31* per_relation = nullptr);
 
+// What the AIR check (check.hip) built and the relation tracker (track.hip) reads after it: the trace-domain columns of trees 0
+// and 1, where each component's columns start, and the relations on both sides.
+struct CheckColumns {
+  ColumnSet pp, tr;
+  std::vector<size_t> tr0;
+  uint32_t clog[air::N_COMPONENTS];
+  DevBuf drel;
+  HostRelations hrel;
+};
+// The PCS-free AIR check of a whole segment; keep (optional) receives the columns instead of the check releasing them.
+void check_segment(const DeviceInput& din, const cm_relations* relations, cm_check_report& rep, CheckColumns* keep = nullptr);
+
 }  // namespace cm
 
 struct cm_device_input { cm::DeviceInput* d = nullptr; ~cm_device_input() { delete d; } };

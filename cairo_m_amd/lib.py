@@ -826,3 +826,107 @@ def _b_relation_sums(self, cid, trace_cols, preprocessed, log_size, rel_words):
 Backend.check = _b_check
 Backend.constraints_check = _b_constraints_check
 Backend.relation_sums = _b_relation_sums
+
+
+# ---- relation tracker (include/cairom_hip.h: cm_relation_entry; reference: debug_tools/relation_tracker.rs) ----------------
+MAX_RELATION_SIZE = 16
+COMPONENT_NAMES = ("AssertEqFpImm", "CallAbsImm", "JmpImm", "JnzFpImm", "Ret", "StoreImm", "StoreFpFp", "StoreFpImm", "DoubleDerefFpImm",
+                   "DoubleDerefFpFp", "StoreFramePointer", "U32StoreImm", "U32StoreAddFpImm", "U32StoreMulFpImm", "U32StoreDivFpImm",
+                   "U32StoreEqFpFp", "U32StoreEqFpImm", "U32StoreLtFpImm", "U32StoreLtFpFp", "U32StoreAddFpFp", "U32StoreSubFpFp",
+                   "U32StoreMulFpFp", "U32StoreDivFpFp", "U32StoreBitwiseFpFp", "U32StoreBitwiseFpImm", "StoreLeFpImm", "MemoryC", "MerkleC",
+                   "ClockUpdateC", "Poseidon2C", "RangeCheck8C", "RangeCheck16C", "RangeCheck20C", "BitwiseC", "PublicData")
+assert len(COMPONENT_NAMES) == N_COMPONENTS + 1
+
+
+class RelationEntry(C.Structure):
+    """One tuple of the tracker's summary (cm_relation_entry): net multiplicity (canonical M31, never 0), the lowest
+    (component, row) merged into it (component N_COMPONENTS = public data) and the number of entries merged."""
+    _fields_ = [("relation", C.c_uint32), ("multiplicity", C.c_uint32), ("n_values", C.c_uint32), ("first_component", C.c_uint32),
+                ("first_row", C.c_uint64), ("n_entries", C.c_uint64), ("values", C.c_uint32 * MAX_RELATION_SIZE)]
+
+    @property
+    def relation_name(self):
+        return RELATION_NAMES[self.relation]
+
+    @property
+    def tuple(self):
+        """the values without trailing zeros"""
+        return tuple(int(v) for v in self.values[:self.n_values])
+
+    @property
+    def signed_multiplicity(self):
+        m = int(self.multiplicity)
+        return m - P_M31 if m > P_M31 // 2 else m
+
+    def __repr__(self):
+        return (f"RelationEntry({self.relation_name}, {list(self.tuple)} -> {self.signed_multiplicity}, "
+                f"{COMPONENT_NAMES[self.first_component]} row {self.first_row}, {self.n_entries} entries)")
+
+
+class RelationSummary:
+    """What the tracker returns: .entries (at most cap of them, by relation id, then by grouping key), .n_total, .truncated,
+    .report (the CheckReport of the whole-segment call, None at the op level)."""
+
+    def __init__(self, entries, n_total, report=None):
+        self.entries, self.n_total, self.report = entries, n_total, report
+
+    @property
+    def truncated(self):
+        return self.n_total > len(self.entries)
+
+    def as_dict(self):
+        """{(relation name, values without trailing zeros): net multiplicity}"""
+        return {(e.relation_name, e.tuple): int(e.multiplicity) for e in self.entries}
+
+    def __str__(self):
+        lines, last = [], None
+        for e in self.entries:
+            if e.relation != last:
+                lines.append(e.relation_name)
+                last = e.relation
+            lines.append(f"  {list(e.tuple)} -> {e.signed_multiplicity}   ({COMPONENT_NAMES[e.first_component]} row {e.first_row}, "
+                         f"{e.n_entries} entries)")
+        if self.truncated:
+            lines.append(f"  ... {self.n_total - len(self.entries)} more")
+        return "\n".join(lines)
+
+
+def _relation_words(relations):
+    if relations is None:
+        return None
+    r = np.ascontiguousarray(relations, dtype=np.uint32)
+    assert r.size == RELATION_WORDS
+    return r
+
+
+def _b_track_relations(self, dev_or_host_input, relations=None, mask=0, cap=4096):
+    """The relation tracker on a whole segment: the check's passes, then the tuples of the tracked relations whose multiplicities
+    do not cancel, public data included.  mask 0 = the relations whose sums do not cancel; bit r = track relation r regardless."""
+    rep = CheckReport()
+    r = _relation_words(relations)
+    buf = (RelationEntry * max(cap, 1))()
+    n_total = C.c_uint64(0)
+    dev, own = dev_or_host_input, False
+    if hasattr(dev_or_host_input, "view"):
+        dev, own = self.upload_input(dev_or_host_input), True
+    try:
+        self._ck(self.L.cm_track_relations(dev, _p(r) if r is not None else None, C.c_uint32(mask), C.byref(rep),
+                                           buf if cap else None, C.c_uint64(cap), C.byref(n_total)))
+    finally:
+        if own:
+            self.free_input(dev)
+    return RelationSummary([buf[i] for i in range(min(n_total.value, cap))], n_total.value, rep)
+
+
+def _b_relation_entries(self, cid, trace_cols, preprocessed, log_size, rel_words, mask=0, cap=4096):
+    """the tracker's summary of ONE component's trace-domain columns (no public data); mask 0 = all 8 relations"""
+    r = _relation_words(rel_words)
+    buf = (RelationEntry * max(cap, 1))()
+    n_total = C.c_uint64(0)
+    self._ck(self.L.cm_relation_entries(C.c_int32(cid), self._harr(trace_cols), self._harr(preprocessed), C.c_uint32(log_size), _p(r),
+                                        C.c_uint32(mask), buf if cap else None, C.c_uint64(cap), C.byref(n_total), C.c_uint64(0)))
+    return RelationSummary([buf[i] for i in range(min(n_total.value, cap))], n_total.value)
+
+
+Backend.track_relations = _b_track_relations
+Backend.relation_entries = _b_relation_entries

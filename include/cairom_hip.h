@@ -27,8 +27,9 @@
 /* Revision of this header.  4: cm_comm.struct_size at offset 0 (breaking for cm_comm users).  5: cm_shard_plan* take the PCS
  * config and column-array capacities; cm_set_device_tail, cm_tail_list.  6: cm_runner_segment grows by initial_heap /
  * n_initial_heap at its END (a revision-5 caller must be recompiled: the library reads the two fields);
- * cm_host_segment_set_initial_heap.  7: cm_check_report, cm_check_constraints, cm_constraints_check, cm_relation_sums. */
-#define CM_ABI_REVISION 7
+ * cm_host_segment_set_initial_heap.  7: cm_check_report, cm_check_constraints, cm_constraints_check, cm_relation_sums.
+ * 8: cm_relation_entry, cm_track_relations, cm_relation_entries. */
+#define CM_ABI_REVISION 8
 
 #ifdef __cplusplus
 extern "C" {
@@ -519,7 +520,8 @@ int32_t cm_constraints_accumulate(int32_t component, const cm_handle* trace_lde,
                                   const cm_handle* preprocessed_lde, uint32_t log_size, const cm_relations* relations,
                                   const uint32_t* coeff_powers, const uint32_t claimed_sum[4], const cm_handle acc[4],
                                   cm_stream_t s);
-/* ---- PCS-free AIR check (reference: debug_tools::assert_constraints, relation_tracker) ------------------------------------
+/* ---- PCS-free AIR check (reference: debug_tools::assert_constraints; the per-relation sums of the report tell WHICH relation does
+ * not balance, cm_track_relations below is the reference's relation tracker and tells which tuples) ---------------------------
  * Builds the three traces of a segment on their trace domains only (no twiddles, LDE, Merkle trees or FRI), draws the relations
  * (from a default channel unless the caller passes them), and checks that every constraint of every component vanishes on every
  * row and that the LogUp sums cancel.  Verdict, in the order of precedence:
@@ -560,6 +562,37 @@ int32_t cm_constraints_check(int32_t component, const cm_handle* trace_cols, con
 /* sums[r] = sum over the component's rows and its entries of relation r of multiplicity / (sum_i alpha_r^i v_i - z_r) */
 int32_t cm_relation_sums(int32_t component, const cm_handle* trace_cols, const cm_handle* preprocessed, uint32_t log_size,
                          const cm_relations* relations, uint32_t sums[CM_N_RELATIONS][4], cm_stream_t s);
+/* ---- relation tracker (reference: debug_tools/relation_tracker.rs, RelationSummary::summarize_relations(..).cleaned()) --------
+ * An entry is one add_to_relation(relation, multiplicity, values) of a component on one trace-domain row (padding rows included;
+ * zero multiplicities contribute nothing), and for a whole segment also one term of the verifier's public-data LogUp sum
+ * (registers [pc, fp, 1] +1 and [pc, fp, clock + 1] -1, the two Merkle root tuples, per public memory cell one memory tuple and
+ * four Merkle leaf tuples).  Two entries are the same tuple when they belong to the same relation and their values are equal after
+ * removing trailing zeros (the LogUp denominator cannot see those).  The summary lists the tuples whose multiplicities do not sum
+ * to zero modulo P.  Tuples are grouped by their LogUp denominator under the relations of the call: two different tuples of one
+ * relation are merged with probability <= 16 / |QM31| ~ 2^-120 over drawn relations; degenerate caller-supplied relations
+ * (alpha = 0) merge tuples exactly as they blind the sum check. */
+typedef struct {
+  uint32_t relation;                 /* 0..7, the relation ids of cm_check_report */
+  uint32_t multiplicity;             /* net, canonical M31, never 0 (a consumer's -1 is P - 1) */
+  uint32_t n_values;                 /* after removing trailing zeros, 0..CM_MAX_RELATION_SIZE */
+  uint32_t first_component;          /* lowest (component, row) merged in; CM_N_COMPONENTS = public data (row 0) */
+  uint64_t first_row;
+  uint64_t n_entries;                /* entries merged into this tuple (zero multiplicities not counted) */
+  uint32_t values[CM_MAX_RELATION_SIZE];   /* zero beyond n_values */
+} cm_relation_entry;
+/* Whole segment: runs the passes of cm_check_constraints (report, optional, receives its verdict; the tracker runs whatever the
+ * verdict is), then the tracker.  relations NULL = drawn from a default channel, as the check.  relation_mask 0 = the relations
+ * whose sums do not cancel (a valid segment costs the check and nothing more); bit r set = track relation r regardless.
+ * entries[0, min(*n_total, cap)) are written; *n_total > cap means truncated, which is not an error (entries may be NULL when
+ * cap is 0).  Order: by relation id, then by the grouping key's words: deterministic for given input and relations.  The record
+ * buffers (88 bytes per entry of the largest tracked relation) come from the calling thread's device pool; when it cannot supply
+ * them the call fails with a message naming the bytes.  Threading as cm_check_constraints. */
+int32_t cm_track_relations(const cm_device_input* input, const cm_relations* relations, uint32_t relation_mask,
+                           cm_check_report* report, cm_relation_entry* entries, uint64_t cap, uint64_t* n_total);
+/* op level, beside cm_relation_sums: the summary of ONE component's columns (no public data); relation_mask 0 = all 8 */
+int32_t cm_relation_entries(int32_t component, const cm_handle* trace_cols, const cm_handle* preprocessed, uint32_t log_size,
+                            const cm_relations* relations, uint32_t relation_mask, cm_relation_entry* entries, uint64_t cap,
+                            uint64_t* n_total, cm_stream_t s);
 /* AccumulationOps::accumulate: dst[k][i] += src[k][i] (4 coordinate columns of n words); generate_secure_powers:
  * out[i] = felt^i for i < n (host array of 4 * n words).  Column::zeros = cm_col_alloc + cm_col_zero. */
 int32_t cm_accumulate(const cm_handle dst[4], const cm_handle src[4], uint64_t n, cm_stream_t s);

@@ -145,6 +145,19 @@ pub struct cm_check_report {
     pub relations: cm_relations,
     pub message: [c_char; 256],
 }
+/// One tuple of the relation tracker's summary (`cm_track_relations`, `cm_relation_entries`): net multiplicity (canonical M31,
+/// never 0), the lowest (component, row) merged into it (`CM_N_COMPONENTS` = public data) and the number of entries merged.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct cm_relation_entry {
+    pub relation: u32,
+    pub multiplicity: u32,
+    pub n_values: u32,
+    pub first_component: u32,
+    pub first_row: u64,
+    pub n_entries: u64,
+    pub values: [u32; CM_MAX_RELATION_SIZE],
+}
 /// One runner segment (crates/common/src/execution.rs:10-15) as plain arrays
 #[repr(C)]
 pub struct cm_runner_segment {
@@ -277,6 +290,8 @@ unsafe extern "C" {
     pub fn cm_constraints_accumulate(component: i32, trace_lde: *const cm_handle, interaction_lde: *const cm_handle, preprocessed_lde: *const cm_handle, log_size: u32, relations: *const cm_relations, coeff_powers: *const u32, claimed_sum: *const u32, acc: *const cm_handle, s: cm_stream_t) -> i32;
     pub fn cm_check_constraints(input: *const cm_device_input, relations: *const cm_relations, out: *mut cm_check_report) -> i32;
     pub fn cm_constraints_check(component: i32, trace_cols: *const cm_handle, interaction_cols: *const cm_handle, preprocessed: *const cm_handle, log_size: u32, relations: *const cm_relations, claimed_sum: *const u32, row_status: cm_handle, failing_rows: *mut u64, first_constraint: *mut i32, first_row: *mut u64, s: cm_stream_t) -> i32;
+    pub fn cm_track_relations(input: *const cm_device_input, relations: *const cm_relations, relation_mask: u32, report: *mut cm_check_report, entries: *mut cm_relation_entry, cap: u64, n_total: *mut u64) -> i32;
+    pub fn cm_relation_entries(component: i32, trace_cols: *const cm_handle, preprocessed: *const cm_handle, log_size: u32, relations: *const cm_relations, relation_mask: u32, entries: *mut cm_relation_entry, cap: u64, n_total: *mut u64, s: cm_stream_t) -> i32;
     pub fn cm_relation_sums(component: i32, trace_cols: *const cm_handle, preprocessed: *const cm_handle, log_size: u32, relations: *const cm_relations, sums: *mut [u32; 4], s: cm_stream_t) -> i32;
     pub fn cm_accumulate(dst: *const cm_handle, src: *const cm_handle, n: u64, s: cm_stream_t) -> i32;
     pub fn cm_generate_secure_powers(felt: *const u32, n: u64, out: *mut u32) -> i32;

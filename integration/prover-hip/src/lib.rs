@@ -233,3 +233,43 @@ pub fn assert_constraints(input: &mut ProverInput) -> Result<(), ConstraintFailu
     let message = unsafe { CStr::from_ptr(report.message.as_ptr()).to_string_lossy().into_owned() };
     Err(ConstraintFailure { report, message })
 }
+
+/// Twin of `debug_tools::relation_tracker::track_and_summarize_relations` (relation_tracker.rs:21-31, the `.cleaned()` summary) on
+/// the GPU: relation name -> the tuples (values without trailing zeros) whose multiplicities do not sum to zero, with their net
+/// multiplicity.  Only the relations whose sums do not cancel are tracked, so a valid input returns an empty map at the cost of
+/// `assert_constraints`.  The public data takes part with the terms of `PublicData::initial_logup_sum`.  `input` is consumed in
+/// place as by `prove_cairo_m_hip`.  A library error (no GPU, out of memory) panics.
+pub fn track_and_summarize_relations(input: &mut ProverInput) -> std::collections::BTreeMap<&'static str, Vec<(Vec<stwo_prover::core::fields::m31::M31>, stwo_prover::core::fields::m31::M31)>> {
+    use stwo_prover::core::fields::m31::M31;
+    const NAMES: [&str; CM_N_RELATIONS] =
+        ["registers", "memory", "merkle", "poseidon2", "range_check_8", "range_check_16", "range_check_20", "bitwise"];
+    ensure_init();
+    let flat = Flat::new(input, MemoryOrder::AscendingAddress);
+    let view = flat.view();
+    let mut dev: *mut cm_device_input = std::ptr::null_mut();
+    let rc = unsafe { cm_input_upload(&view, &mut dev) };
+    assert!(rc == 0, "cm_input_upload: {}", last_error());
+    let mut cap: u64 = 4096;
+    let mut entries: Vec<cm_relation_entry> = Vec::new();
+    loop {
+        entries.resize(cap as usize, unsafe { std::mem::zeroed() });
+        let mut n_total: u64 = 0;
+        let rc = unsafe { cm_track_relations(dev, std::ptr::null(), 0, std::ptr::null_mut(), entries.as_mut_ptr(), cap, &mut n_total) };
+        if rc != 0 {
+            unsafe { cm_input_free(dev) };
+            panic!("cm_track_relations: {}", last_error());
+        }
+        if n_total <= cap {
+            entries.truncate(n_total as usize);
+            break;
+        }
+        cap = n_total;
+    }
+    unsafe { cm_input_free(dev) };
+    let mut out: std::collections::BTreeMap<&'static str, Vec<(Vec<M31>, M31)>> = std::collections::BTreeMap::new();
+    for e in entries.iter() {
+        let values: Vec<M31> = e.values[..e.n_values as usize].iter().map(|v| M31::from_u32_unchecked(*v)).collect();
+        out.entry(NAMES[e.relation as usize]).or_default().push((values, M31::from_u32_unchecked(e.multiplicity)));
+    }
+    out
+}

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Cost of the PCS-free AIR check (cm_check_constraints) against a proof (cm_prove_device) of the same device-resident input, at
 the metric config (fibonacci 419 000: 4 190 012 steps) — alternating blocks in ONE process, so that clocks, pools and caches are
-shared by both sides — then the per-kernel split of the check (cm_kprof_report, a run of its own after the timed blocks) and, with
+shared by both sides — with a third leg, check + relation tracker on a tampered copy of the input (one prev_value changed: the
+memory relation is tracked), then the tracker with every relation forced (mask 0xFF) on the valid input, the per-kernel split of
+both tracker shapes and of the check (cm_kprof_report, a run of its own after the timed blocks) and, with
 --configs4, one check of configs[4] (all_opcodes_program(1_545_000), 2^26 rows).  Every timed call ends in a device synchronise
 (both entry points return after their last copy).  Prints one JSON object; --out writes it to a file too.
 
@@ -26,7 +28,7 @@ def main():
     ap.add_argument("--out")
     args = ap.parse_args()
     from cairo_m_amd import Backend
-    from cairo_m_amd.lib import synth_fibonacci, vm_segment
+    from cairo_m_amd.lib import ArrayInput, prover_input_arrays, synth_fibonacci, vm_segment
     from cairo_m_amd.workloads import all_opcodes_program
     be = Backend(0)
     inp = synth_fibonacci(419_000)
@@ -39,6 +41,40 @@ def main():
         assert rep.status == 0, rep.message
         return dt
 
+    # the tampered input of tests/test_gpu_track.py: prev_value of the destination access of StoreFpFp row 300 000
+    a = prover_input_arrays(inp.view)
+    i = int(a["bundles6"][300_000][10]) + 2
+    a["data_accesses"][i][2] = (int(a["data_accesses"][i][2]) + 1) % (2**31 - 1)
+    bad = ArrayInput(a)
+    dev_bad = be.upload_input(bad)
+
+    def track():
+        t = time.perf_counter()
+        s = be.track_relations(dev_bad)
+        dt = (time.perf_counter() - t) * 1e3
+        assert s.report.status == 3 and s.n_total == 2, str(s)
+        return dt
+
+    def track_all():
+        t = time.perf_counter()
+        s = be.track_relations(dev, mask=0xFF)
+        dt = (time.perf_counter() - t) * 1e3
+        assert s.report.status == 0 and s.n_total == 0, str(s)
+        return dt
+
+    def kprof(f, calls=3):
+        be.L.cm_kprof_enable(C.c_int32(1))
+        for _ in range(calls):
+            f()
+        buf = C.create_string_buffer(1 << 16)
+        be.L.cm_kprof_report(buf, C.c_size_t(len(buf)))
+        be.L.cm_kprof_enable(C.c_int32(0))
+        try:
+            rep = json.loads(buf.value.decode())
+        except ValueError:
+            return buf.value.decode()
+        return {k: v for k, v in rep.items() if k.startswith("k_track")}
+
     def prove():
         t = time.perf_counter()
         p = be.prove_device(dev)
@@ -49,16 +85,29 @@ def main():
     for _ in range(3):   # warm-up: code objects, the device pool's blocks of both shapes
         check()
         prove()
-    t_check, t_prove = [], []
+        track()
+    t_check, t_prove, t_track = [], [], []
+    legs = [(check, t_check), (prove, t_prove), (track, t_track)]
     for b in range(args.blocks):
-        order = (check, prove) if b % 2 == 0 else (prove, check)
-        for f in order:
-            dst = t_check if f is check else t_prove
+        for f, dst in legs[b % 3:] + legs[:b % 3]:
             dst.extend(f() for _ in range(args.per_block))
+    track_all()
+    t_all = [track_all() for _ in range(args.per_block)]
+
+    def stats(t):
+        return {"median": statistics.median(t), "min": min(t), "max": max(t)}
     out = {"steps": inp.steps, "blocks": args.blocks, "per_block": args.per_block,
-           "check_ms": {"median": statistics.median(t_check), "min": min(t_check), "max": max(t_check)},
-           "prove_ms": {"median": statistics.median(t_prove), "min": min(t_prove), "max": max(t_prove)}}
+           "check_ms": stats(t_check), "prove_ms": stats(t_prove), "track_tampered_ms": stats(t_track), "track_all_relations_ms": stats(t_all)}
     out["check_over_prove"] = out["check_ms"]["median"] / out["prove_ms"]["median"]
+    # per-kernel split of the tracker (bytes = algorithmic; k_track_net moves 32 bytes per record: records = bytes / 32 / calls)
+    out["track_tampered_kprof_3_calls"] = kprof(track)
+    out["track_all_relations_kprof_3_calls"] = kprof(track_all)
+    for key in ("track_tampered_kprof_3_calls", "track_all_relations_kprof_3_calls"):
+        k = out[key]
+        if isinstance(k, dict) and "k_track_net" in k:
+            out[key.replace("kprof_3_calls", "records")] = int(k["k_track_net"]["bytes"] / 32 / 3)
+            ms = sum(v["ms"] for n, v in k.items() if n != "k_track_recover")
+            out[key.replace("kprof_3_calls", "gbytes_per_s")] = sum(v["bytes"] for v in k.values()) / ms / 1e6 if ms else None
     # per-kernel split of the check (timing events on the launch stream: a run of its own)
     be.L.cm_kprof_enable(C.c_int32(1))
     for _ in range(3):
@@ -71,6 +120,7 @@ def main():
     except ValueError:
         out["check_kprof_3_calls"] = buf.value.decode()
     be.free_input(dev)
+    be.free_input(dev_bad)
     inp.free()
     if args.configs4:
         f, t = C.c_uint64(0), C.c_uint64(0)
