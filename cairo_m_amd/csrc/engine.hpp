@@ -160,6 +160,16 @@ void pool_trim();
 // everything back" means everything and a parked FRI phase can never be the reason an allocation fails.
 void set_thread_parked_release(std::function<void()> f);
 void release_thread_parked();
+// Accounting (pool.hip; C ABI: cm_mem_stats_get / cm_mem_reset_peak / cm_set_memory_budget).  The process-wide counters are
+// relaxed atomics; the calling thread's own pool keeps plain counters under the mutex its get / put hold anyway.
+size_t pool_round(size_t bytes);                   // the capacity class Pool::get asks the driver for
+struct ThreadMem { uint64_t live, reserved, mark_peak_live, peak_reserved, driver_allocs; };
+ThreadMem thread_mem();                            // the calling thread's pool, as it is now
+uint64_t thread_mem_mark();                        // high-water mark of its live bytes since the previous mark; starts a new one
+void thread_mem_reset_reserved_peak();             // peak_reserved := reserved
+uint64_t mem_budget();                             // 0 = none
+void mem_proof_enter();                            // proofs_in_flight of cm_mem_stats (every cm_prove* entry point)
+void mem_proof_leave();
 void stage_upload(void* dst, const void* src, size_t bytes, hipStream_t st);
 
 // The HIP device cm_init() selected (one device per process: one process per GPU).  hipSetDevice is per host

@@ -1,9 +1,11 @@
 // Device-memory caching pool + pinned upload ring.  Sized for a 288 GB part: freed blocks are kept
 // (never returned to the driver on the hot path) and reused best-fit, so a steady-state proof performs
-// zero hipMalloc/hipFree calls; cm_shutdown()/pool_trim() hands everything back.
+// zero hipMalloc/hipFree calls (counted since header revision 9, cm_proof_mem.driver_allocs: 0 for a repeated proof at the suite's
+// sizes, 1 for the third identical proof at the metric config — DESIGN 3.5); cm_shutdown()/pool_trim() hands everything back.
 #include <algorithm>
 #include "engine.hpp"
 #include "tail_device.hpp"
+#include "../../include/cairom_hip.h"
 #include <atomic>
 #include <map>
 #include <mutex>
@@ -16,6 +18,28 @@
 
 namespace cm {
 namespace {
+// ---- accounting (include/cairom_hip.h, cm_mem_stats) ---------------------------------------------------------------------
+// Process-wide sums over all thread pools.  Relaxed atomics: the numbers are statistics and admission inputs, nothing is ordered
+// by them.  A get / put adds one atomic add and one compare to what it did before; `reserved` only moves on the driver paths.
+struct MemGlobal {
+  std::atomic<uint64_t> live{0}, reserved{0}, peak_live{0}, peak_reserved{0}, pinned{0}, driver_allocs{0}, budget{0};
+  std::atomic<uint32_t> in_flight{0}, peak_in_flight{0};
+  std::atomic<int> budget_init{0};
+};
+MemGlobal& mg() { static MemGlobal* g = new MemGlobal(); return *g; }
+template <class T> inline void atomic_max(std::atomic<T>& a, T v) {
+  T cur = a.load(std::memory_order_relaxed);
+  while (v > cur && !a.compare_exchange_weak(cur, v, std::memory_order_relaxed)) {}
+}
+inline void g_live_add(uint64_t b) { atomic_max(mg().peak_live, mg().live.fetch_add(b, std::memory_order_relaxed) + b); }
+inline void g_live_sub(uint64_t b) { mg().live.fetch_sub(b, std::memory_order_relaxed); }
+inline void g_reserved_add(uint64_t b) { atomic_max(mg().peak_reserved, mg().reserved.fetch_add(b, std::memory_order_relaxed) + b); }
+inline void g_reserved_sub(uint64_t b) { mg().reserved.fetch_sub(b, std::memory_order_relaxed); }
+inline void pinned_add(size_t b) { mg().pinned.fetch_add(b, std::memory_order_relaxed); }
+inline void pinned_sub(size_t b) { mg().pinned.fetch_sub(b, std::memory_order_relaxed); }
+struct Pool;
+struct PoolRegistry { std::mutex mu; std::vector<Pool*> pools; };
+PoolRegistry& registry() { static PoolRegistry* r = new PoolRegistry(); return *r; }
 struct Pool {
   std::mutex mu;
   // Free blocks by capacity class.  A proof asks for the same ~1500 sizes every time and they fall into ~100 classes: a class
@@ -24,6 +48,8 @@ struct Pool {
   // the teardown of one proof is ~600 puts with the GPU idle).
   std::map<size_t, std::vector<void*>> free_;  // capacity -> blocks
   std::unordered_map<void*, size_t> cap_;      // every live or cached block
+  // this pool's share of the process-wide counters (under `mu`): what a proof reports about itself (cm_proof_mem)
+  uint64_t live = 0, reserved = 0, mark_peak_live = 0, peak_reserved = 0, driver_allocs = 0;
   static size_t round(size_t b) {
     if (b <= (1u << 20)) return (b + 511) & ~(size_t)511;
     return (b + ((size_t)1 << 21) - 1) & ~(((size_t)1 << 21) - 1);
@@ -37,6 +63,9 @@ struct Pool {
         if (!it->second.empty()) {
           void* p = it->second.back();
           it->second.pop_back();
+          live += it->first;
+          if (live > mark_peak_live) mark_peak_live = live;
+          g_live_add(it->first);
           return p;
         }
     }
@@ -50,18 +79,46 @@ struct Pool {
     if (e != hipSuccess) throw CmError(2, std::string("device allocation of ") + std::to_string(want) + " bytes failed: " + hipGetErrorString(e));
     std::lock_guard<std::mutex> lk(mu);
     cap_[p] = want;
+    live += want; reserved += want; driver_allocs++;
+    if (live > mark_peak_live) mark_peak_live = live;
+    if (reserved > peak_reserved) peak_reserved = reserved;
+    g_live_add(want); g_reserved_add(want);
+    mg().driver_allocs.fetch_add(1, std::memory_order_relaxed);
     return p;
   }
-  void put(void* p) {
+  // a block of THIS pool that another thread frees (a cm_device_input released by a thread other than its maker): it leaves
+  // the pool for the driver; false = not ours
+  bool drop_foreign(void* p) {
     std::lock_guard<std::mutex> lk(mu);
     auto it = cap_.find(p);
-    if (it == cap_.end()) { (void)hipFree(p); return; }
-    free_[it->second].push_back(p);
+    if (it == cap_.end()) return false;
+    live -= it->second; reserved -= it->second;
+    g_live_sub(it->second); g_reserved_sub(it->second);
+    cap_.erase(it);
+    return true;
+  }
+  void put(void* p) {
+    {
+      std::lock_guard<std::mutex> lk(mu);
+      auto it = cap_.find(p);
+      if (it != cap_.end()) {
+        free_[it->second].push_back(p);
+        live -= it->second;
+        g_live_sub(it->second);
+        return;
+      }
+    }
+    {   // (no two pool locks are ever held together)
+      PoolRegistry& r = registry();
+      std::lock_guard<std::mutex> lk(r.mu);
+      for (Pool* q : r.pools) if (q != this && q->drop_foreign(p)) break;
+    }
+    (void)hipFree(p);
   }
   void trim() {
     std::lock_guard<std::mutex> lk(mu);
     for (auto& kv : free_)
-      for (void* p : kv.second) { (void)hipFree(p); cap_.erase(p); }
+      for (void* p : kv.second) { (void)hipFree(p); cap_.erase(p); reserved -= kv.first; g_reserved_sub(kv.first); }
     free_.clear();
   }
 };
@@ -72,8 +129,15 @@ struct Pool {
 // of a host thread go back to the driver when that thread exits — prover threads that come and go would otherwise pin
 // a few GB of HBM each.
 struct PoolExitGuard { Pool* p = nullptr; ~PoolExitGuard() { if (p) p->trim(); } };
+Pool* new_registered_pool() {
+  Pool* p = new Pool();
+  PoolRegistry& r = registry();
+  std::lock_guard<std::mutex> lk(r.mu);
+  r.pools.push_back(p);
+  return p;
+}
 Pool& pool() {
-  static thread_local Pool* p = new Pool();
+  static thread_local Pool* p = new_registered_pool();
   static thread_local PoolExitGuard guard;
   guard.p = p;
   return *p;
@@ -90,7 +154,7 @@ struct Stage {
   std::vector<User> users;
   std::vector<hipEvent_t> spare;
   void ensure() {
-    if (!base) CM_HIP(hipHostMalloc((void**)&base, size, hipHostMallocDefault));
+    if (!base) { CM_HIP(hipHostMalloc((void**)&base, size, hipHostMallocDefault)); pinned_add(size); }
   }
 };
 Stage& stage() {   // ring wrap syncs only the owner's stream
@@ -104,7 +168,7 @@ Stage& stage() {   // ring wrap syncs only the owner's stream
         (void)hipEventSynchronize(u.ev); (void)hipEventDestroy(u.ev);
       }
       for (hipEvent_t e : own->spare) (void)hipEventDestroy(e);
-      if (own->base) (void)hipHostFree(own->base);
+      if (own->base) { (void)hipHostFree(own->base); pinned_sub(own->size); }
       delete own;
     });
   }
@@ -132,6 +196,35 @@ namespace { std::function<void()>& parked_release_fn() { static thread_local std
 void set_thread_parked_release(std::function<void()> f) { parked_release_fn() = std::move(f); }
 void release_thread_parked() { if (parked_release_fn()) parked_release_fn()(); }
 void pool_trim() { release_thread_parked(); pool().trim(); }
+size_t pool_round(size_t bytes) { return Pool::round(bytes); }
+ThreadMem thread_mem() {
+  Pool& p = pool();
+  std::lock_guard<std::mutex> lk(p.mu);
+  return ThreadMem{p.live, p.reserved, p.mark_peak_live, p.peak_reserved, p.driver_allocs};
+}
+uint64_t thread_mem_mark() {
+  Pool& p = pool();
+  std::lock_guard<std::mutex> lk(p.mu);
+  const uint64_t v = p.mark_peak_live;
+  p.mark_peak_live = p.live;
+  return v;
+}
+void thread_mem_reset_reserved_peak() {
+  Pool& p = pool();
+  std::lock_guard<std::mutex> lk(p.mu);
+  p.peak_reserved = p.reserved;
+}
+uint64_t mem_budget() {
+  MemGlobal& g = mg();
+  if (!g.budget_init.load(std::memory_order_acquire)) {   // CM_MEMORY_BUDGET: the initial value, read once
+    const char* e = getenv("CM_MEMORY_BUDGET");
+    int expected = 0;
+    if (g.budget_init.compare_exchange_strong(expected, 1) && e && *e) g.budget.store(strtoull(e, nullptr, 0), std::memory_order_relaxed);
+  }
+  return g.budget.load(std::memory_order_relaxed);
+}
+void mem_proof_enter() { atomic_max(mg().peak_in_flight, mg().in_flight.fetch_add(1, std::memory_order_relaxed) + 1); }
+void mem_proof_leave() { mg().in_flight.fetch_sub(1, std::memory_order_relaxed); }
 
 // The copy out of the ring as a KERNEL that reads the pinned words over PCIe: a hipMemcpyAsync of more than a few KB goes through
 // the SDMA engine, and a copy-engine command between two kernels of a compute stream costs ~10 us on either side of its 7 us
@@ -248,7 +341,7 @@ Landing& landing() {
   if (!l) {
     l = new Landing();
     Landing* own = l;
-    at_thread_exit([own] { if (own->base) (void)hipHostFree(own->base); delete own; });
+    at_thread_exit([own] { if (own->base) { (void)hipHostFree(own->base); pinned_sub(own->cap); } delete own; });
   }
   return *l;
 }
@@ -258,9 +351,11 @@ void* stage_landing(size_t bytes, hipStream_t st) { return const_cast<void*>(sta
 const void* stage_download_async(const void* src, size_t bytes, hipStream_t st) {
   Landing& l = landing();
   if (bytes > l.cap) {
-    if (l.base) { CM_HIP(hipStreamSynchronize(st)); CM_HIP(hipHostFree(l.base)); l.base = nullptr; }
-    l.cap = std::max(bytes * 2, (size_t)1 << 20);
-    CM_HIP(hipHostMalloc((void**)&l.base, l.cap, hipHostMallocDefault));
+    if (l.base) { CM_HIP(hipStreamSynchronize(st)); CM_HIP(hipHostFree(l.base)); l.base = nullptr; pinned_sub(l.cap); l.cap = 0; }
+    const size_t cap = std::max(bytes * 2, (size_t)1 << 20);
+    CM_HIP(hipHostMalloc((void**)&l.base, cap, hipHostMallocDefault));
+    l.cap = cap;
+    pinned_add(cap);
   }
   if (bytes && src) CM_HIP(hipMemcpyAsync(l.base, src, bytes, hipMemcpyDeviceToHost, st));
   return l.base;
@@ -275,14 +370,15 @@ void* tail_pinned(int which, size_t bytes) {
   if (!t) {
     t = new TailPinned();
     TailPinned* own = t;
-    at_thread_exit([own] { for (int i = 0; i < 2; i++) if (own->base[i]) (void)hipHostFree(own->base[i]); delete own; });
+    at_thread_exit([own] { for (int i = 0; i < 2; i++) if (own->base[i]) { (void)hipHostFree(own->base[i]); pinned_sub(own->cap[i]); } delete own; });
   }
   if (bytes > t->cap[which]) {
     // (a proof ends with a synchronised stream: nothing of the previous proof still reads or writes the old buffer)
-    if (t->base[which]) { CM_HIP(hipDeviceSynchronize()); CM_HIP(hipHostFree(t->base[which])); t->base[which] = nullptr; t->cap[which] = 0; }
+    if (t->base[which]) { CM_HIP(hipDeviceSynchronize()); CM_HIP(hipHostFree(t->base[which])); t->base[which] = nullptr; pinned_sub(t->cap[which]); t->cap[which] = 0; }
     const size_t cap = std::max(bytes + bytes / 2, (size_t)1 << 16);
     CM_HIP(hipHostMalloc((void**)&t->base[which], cap, hipHostMallocDefault));
     t->cap[which] = cap;
+    pinned_add(cap);
   }
   return t->base[which];
 }
@@ -296,8 +392,9 @@ uint32_t* pinned_words() {
   static thread_local uint32_t* p = nullptr;
   if (!p) {
     CM_HIP(hipHostMalloc((void**)&p, PIN_WORDS * 4, hipHostMallocDefault));
+    pinned_add(PIN_WORDS * 4);
     uint32_t* own = p;
-    at_thread_exit([own] { (void)hipHostFree(own); });
+    at_thread_exit([own] { (void)hipHostFree(own); pinned_sub(PIN_WORDS * 4); });
   }
   return p;
 }
@@ -606,3 +703,39 @@ Fork::~Fork() {
 }
 
 }  // namespace cm
+
+extern "C" int32_t cm_set_last_error(const char* msg);
+extern "C" {
+int32_t cm_mem_stats_get(cm_mem_stats* out) {
+  if (!out) return cm_set_last_error("cm_mem_stats_get: null argument");
+  if (out->struct_size < sizeof(cm_mem_stats)) return cm_set_last_error("cm_mem_stats_get: struct_size does not cover cm_mem_stats (set it to sizeof(cm_mem_stats))");
+  cm::MemGlobal& g = cm::mg();
+  cm_mem_stats s;
+  memset(&s, 0, sizeof(s));
+  s.struct_size = sizeof(s);
+  s.budget_bytes = cm::mem_budget();
+  s.proofs_in_flight = g.in_flight.load(std::memory_order_relaxed);
+  s.peak_proofs_in_flight = g.peak_in_flight.load(std::memory_order_relaxed);
+  s.live_bytes = g.live.load(std::memory_order_relaxed);
+  s.reserved_bytes = g.reserved.load(std::memory_order_relaxed);
+  s.peak_live_bytes = g.peak_live.load(std::memory_order_relaxed);
+  s.peak_reserved_bytes = g.peak_reserved.load(std::memory_order_relaxed);
+  s.pinned_host_bytes = g.pinned.load(std::memory_order_relaxed);
+  s.driver_allocs = g.driver_allocs.load(std::memory_order_relaxed);
+  memcpy(out, &s, sizeof(s));
+  return 0;
+}
+int32_t cm_mem_reset_peak(void) {
+  cm::MemGlobal& g = cm::mg();
+  g.peak_live.store(g.live.load(std::memory_order_relaxed), std::memory_order_relaxed);
+  g.peak_reserved.store(g.reserved.load(std::memory_order_relaxed), std::memory_order_relaxed);
+  g.peak_in_flight.store(g.in_flight.load(std::memory_order_relaxed), std::memory_order_relaxed);
+  g.driver_allocs.store(0, std::memory_order_relaxed);
+  return 0;
+}
+int32_t cm_set_memory_budget(uint64_t bytes) {
+  (void)cm::mem_budget();   // (the environment's initial value must not overwrite this one later)
+  cm::mg().budget.store(bytes, std::memory_order_relaxed);
+  return 0;
+}
+}

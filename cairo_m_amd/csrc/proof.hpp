@@ -76,6 +76,9 @@ struct ProofData {
   uint64_t cells = 0, steps = 0;
   std::vector<double> phase_ms;
   double total_ms = 0;
+  // device memory of the proving thread's pool during this proof (cm_proof_mem; zeros for a proof rebuilt from words)
+  uint64_t mem_start_live = 0, mem_peak_live = 0, mem_peak_reserved = 0, mem_input_bytes = 0, mem_driver_allocs = 0;
+  std::vector<uint64_t> phase_peak_live;   // one entry per phase_ms entry
 };
 
 // [{"op": "mix_u64", "digest": "<64 hex digits: the channel digest after the call>", "n_words": 2, "words": [..first <= 16..]}, ...]

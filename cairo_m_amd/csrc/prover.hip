@@ -189,6 +189,80 @@ static Twiddles* cached_twiddles(uint32_t R, hipStream_t st) {
   cache[R] = t;
   return t;
 }
+}  // namespace cm
+#include "mem_estimate.hpp"
+namespace cm {
+static MemSwitches mem_switches() { return MemSwitches{pp_cache_enabled(), tw_cache_enabled(), tune(T_DEFER_TEARDOWN) != 0}; }
+// ---- memory budget (cm_set_memory_budget) ----------------------------------------------------------------------------------
+// What one item needs: its resident input and the estimate's bound on what its proof adds to the proving thread's pool.
+struct ItemBytes { uint64_t input = 0, working = 0; };
+static ItemBytes item_bytes(const cm_prover_input& meta, uint64_t input_bytes, const cm_pcs_config& cfg, uint32_t world) {
+  uint32_t clog[air::N_COMPONENTS];
+  component_logs(meta, clog);
+  cm_mem_estimate e;
+  memset(&e, 0, sizeof(e));
+  cm_pcs_config c = cfg;
+  c.log_blowup_factor = std::min(std::max(c.log_blowup_factor, 1u), 4u);   // (an invalid config is refused by the prover itself)
+  for (auto& l : clog) l = std::min(l, 27u);
+  estimate_memory(clog, c, world, mem_switches(), e);
+  return ItemBytes{input_bytes, e.working_bytes};
+}
+// the third rule of the budget: an item that cannot fit alone fails before any GPU work for it
+static void check_item_fits(const ItemBytes& b, uint64_t budget, const char* who) {
+  if (budget && b.input + b.working > budget)
+    throw CmError(2, std::string(who) + ": the item needs input_bytes " + std::to_string(b.input) + " + working_bytes " + std::to_string(b.working) +
+                         " = " + std::to_string(b.input + b.working) + " bytes, the memory budget is " + std::to_string(budget));
+}
+// Admission by bytes for the pipelines (process-wide, like the budget): `inputs` = device inputs resident for them, `working` =
+// the estimates of the proofs running.  Nothing waits when no budget is set; when nothing is running the next item is always
+// admitted, so an item that fits alone can never wait for ever.
+struct Admission {
+  std::mutex mu;
+  std::condition_variable cv;
+  uint64_t inputs = 0, working = 0;
+  uint32_t running = 0;
+  void add_inputs(uint64_t b) { std::lock_guard<std::mutex> lk(mu); inputs += b; }
+  void sub_inputs(uint64_t b) { { std::lock_guard<std::mutex> lk(mu); inputs -= std::min(inputs, b); } cv.notify_all(); }
+  // a producer, before it makes a device input of `b` bytes (counted as resident from here on).  Never blocks: a producer that
+  // waits for room must keep releasing the inputs that come back to it — their release may be the room
+  bool try_admit_input(uint64_t b) {
+    std::lock_guard<std::mutex> lk(mu);
+    const uint64_t bud = mem_budget();
+    if (bud && inputs + working + b > bud && !(running == 0 && inputs == 0)) return false;
+    inputs += b;
+    return true;
+  }
+  // a worker, before it starts a proof whose estimate is `w`
+  void admit_proof(uint64_t w) {
+    std::unique_lock<std::mutex> lk(mu);
+    cv.wait(lk, [&] { const uint64_t bud = mem_budget(); return !bud || inputs + working + w <= bud || running == 0; });
+    working += w; running++;
+  }
+  void finish_proof(uint64_t w) {
+    { std::lock_guard<std::mutex> lk(mu); working -= std::min(working, w); running--; }
+    cv.notify_all();
+  }
+};
+static Admission& admission() { static Admission* a = new Admission(); return *a; }
+// One proof of a pipeline worker under the admission rules.  With a budget the worker gives back what its previous proof parked
+// before it waits (parked blocks are live bytes nobody admitted), and trims its pool when the process holds more than the budget.
+ProofData* prove(const DeviceInput& din, const cm_pcs_config& cfg);
+static ProofData* prove_admitted(const DeviceInput& din, const cm_pcs_config& cfg, const char* who) {
+  const uint64_t budget = mem_budget();
+  if (!budget) return prove(din, cfg);
+  const ItemBytes b = item_bytes(din.meta, device_input_bytes(din), cfg, 1);
+  check_item_fits(b, budget, who);
+  release_thread_parked();
+  {
+    cm_mem_stats s;
+    s.struct_size = sizeof(s);
+    if (cm_mem_stats_get(&s) == 0 && s.reserved_bytes > budget) pool_trim();
+  }
+  Admission& a = admission();
+  a.admit_proof(b.working);
+  struct Done { Admission& a; uint64_t w; ~Done() { release_thread_parked(); a.finish_proof(w); } } done{a, b.working};
+  return prove(din, cfg);
+}
 struct ProofTwiddles {   // per-proof tables in pool memory
   Twiddles t;
   DevBuf x, ix, y, iy, scratch;
@@ -392,6 +466,7 @@ struct SegmentProver {
     ht.mark("finish: phase events read");
     fork_join_check();
     pf.phase_ms = P.phase_ms;
+    P.report_memory(pf, device_input_bytes(din));
     pf.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - P.t0).count();
     pf.steps = 0;
     for (int i = 0; i < CM_N_OPCODE_COMPONENTS; i++) pf.steps += in.n_bundles[i];
@@ -1406,6 +1481,8 @@ ProofData* prove(const DeviceInput& din, const cm_pcs_config& cfg) {
   const auto t0 = now();
   ProofData* r;
   std::chrono::steady_clock::time_point t1;
+  if (const uint64_t budget = mem_budget()) check_item_fits(item_bytes(din.meta, device_input_bytes(din), cfg, 1), budget, "cm_prove");
+  struct InFlight { InFlight() { mem_proof_enter(); } ~InFlight() { mem_proof_leave(); } } mem_in_flight;
   {
     SegmentProver sp(din, cfg);
     if (marks) fprintf(stderr, "[host] %-40s %8.1f us\n", "(prover object constructed)", std::chrono::duration<double, std::micro>(now() - t0).count());
@@ -1585,6 +1662,10 @@ int32_t cm_prove_many(const cm_device_input* const* inputs, uint32_t n, const cm
   struct Shared { std::mutex mu; std::condition_variable cv; uint32_t done = 0, next = 0; int32_t rc = 0; std::string err; } sh;
   for (uint32_t i = 0; i < n; i++) outs[i] = nullptr;
   const uint32_t runners = inflight < n ? inflight : n;
+  // under a memory budget the caller's inputs count as resident for the whole call (cm::Admission)
+  uint64_t resident = 0;
+  if (cm::mem_budget()) for (uint32_t i = 0; i < n; i++) if (inputs[i] && inputs[i]->d) resident += cm::device_input_bytes(*inputs[i]->d);
+  struct Resident { uint64_t b; Resident(uint64_t b_) : b(b_) { if (b) cm::admission().add_inputs(b); } ~Resident() { if (b) cm::admission().sub_inputs(b); } } resident_scope(resident);
   // `runners` jobs, each pulling segment indices until none is left: exactly that many proofs are in flight
   for (uint32_t r = 0; r < runners; r++) {
     w.submit([&] {
@@ -1597,7 +1678,7 @@ int32_t cm_prove_many(const cm_device_input* const* inputs, uint32_t n, const cm
         std::string err;
         try {
           std::unique_ptr<cm_proof> p(new cm_proof());
-          p->d = cm::prove(*inputs[i]->d, cfg);
+          p->d = cm::prove_admitted(*inputs[i]->d, cfg, "cm_prove_many");
           outs[i] = p.release();
         } catch (const cm::CmError& e) { rc = e.code ? e.code : 1; err = e.what(); }
         catch (const std::exception& e) { rc = 1; err = e.what(); }
@@ -1626,8 +1707,10 @@ extern "C++" {
 // for plain uploads (6 ms of PCIe per 10 ms proof); the device adapter is ~13 ms of uploads, kernels and five host round trips per
 // segment while the GPU is busy proving, so runner segments get two.  An input is released by the producer that made it (its
 // device pool owns the blocks).
-template <class Produce>
-static int32_t prove_streamed(uint32_t n, Produce&& produce, const cm_pcs_config* config, uint32_t inflight, cm_proof** outs,
+// need(i, cfg, known): the bytes item i takes (cm::ItemBytes), for the memory budget; known = false when only an upper guess of the
+// input can be made before the item exists (runner segments: the refusal then happens in front of the proof, not the adapter)
+template <class Produce, class Need>
+static int32_t prove_streamed(uint32_t n, Produce&& produce, Need&& need, const cm_pcs_config* config, uint32_t inflight, cm_proof** outs,
                               uint32_t n_producers = 1) {
   if (!n) return 0;
   if (inflight < 1) inflight = 1;
@@ -1639,12 +1722,12 @@ static int32_t prove_streamed(uint32_t n, Produce&& produce, const cm_pcs_config
   for (uint32_t i = 0; i < n; i++) outs[i] = nullptr;
   cm::ProveWorkers& w = cm::prove_workers();
   w.ensure(inflight + n_producers - 1);
-  struct Job { uint32_t i; cm::DeviceInput* d; uint32_t pid; };
+  struct Job { uint32_t i; cm::DeviceInput* d; uint32_t pid; uint64_t bytes; };   // bytes: what cm::Admission counts as resident for it
   struct Shared {
     std::mutex mu;
     std::condition_variable cv;
     std::deque<Job> ready;                         // produced, not yet picked up
-    std::deque<cm::DeviceInput*> spent[3];         // proved: back to the producer that made them
+    std::deque<std::pair<cm::DeviceInput*, uint64_t>> spent[3];   // proved: back to the producer that made them (with Job::bytes)
     uint32_t outstanding[3] = {0, 0, 0};           // inputs of producer p that exist (being produced, ready, being proved, spent)
     uint32_t alive = 0, next_i = 0, workers_done = 0, producers_done = 0, n_producers = 1;
     uint32_t extra_done = 0;                       // library-thread producers that have left `sh` for good (counted under `mu`)
@@ -1671,14 +1754,14 @@ static int32_t prove_streamed(uint32_t n, Produce&& produce, const cm_pcs_config
         std::string err;
         try {
           std::unique_ptr<cm_proof> p(new cm_proof());
-          p->d = cm::prove(*job.d, cfg);
+          p->d = cm::prove_admitted(*job.d, cfg, "cm_prove_many (streamed)");
           outs[job.i] = p.release();
         } catch (const cm::CmError& e) { rc = e.code ? e.code : 1; err = e.what(); }
         catch (const std::exception& e) { rc = 1; err = e.what(); }
         catch (...) { rc = 1; err = "unknown error"; }
         std::lock_guard<std::mutex> lk(sh.mu);
         if (rc && !sh.rc) { sh.rc = rc; sh.err = err; }
-        sh.spent[job.pid].push_back(job.d);
+        sh.spent[job.pid].push_back({job.d, job.bytes});
         sh.cv.notify_all();
       }
       std::lock_guard<std::mutex> lk(sh.mu);
@@ -1687,15 +1770,15 @@ static int32_t prove_streamed(uint32_t n, Produce&& produce, const cm_pcs_config
     });
   }
   // one producer: takes the next index while a slot is free, makes the device input, hands it to the workers; frees what comes back
-  auto producer = [&sh, &produce, n, cap](uint32_t pid) {
+  auto producer = [&sh, &produce, &need, &cfg, n, cap](uint32_t pid) {
     cm::bind_thread_to_library_device();
     auto release_spent = [&](std::unique_lock<std::mutex>& lk) {   // lock held on entry and exit; the frees run outside of it
-      std::deque<cm::DeviceInput*> v;
+      std::deque<std::pair<cm::DeviceInput*, uint64_t>> v;
       v.swap(sh.spent[pid]);
       sh.alive -= (uint32_t)v.size();
       sh.outstanding[pid] -= (uint32_t)v.size();
       lk.unlock();
-      for (auto* d : v) delete d;
+      for (auto& d : v) { delete d.first; if (d.second) cm::admission().sub_inputs(d.second); }
       lk.lock();
       sh.cv.notify_all();
     };
@@ -1714,17 +1797,40 @@ static int32_t prove_streamed(uint32_t n, Produce&& produce, const cm_pcs_config
       cm::DeviceInput* d = nullptr;
       int32_t rc = 0;
       std::string err;
-      try { d = produce(i); }
+      uint64_t counted = 0;     // bytes cm::Admission holds as resident for this item
+      bool refused = false;     // over the memory budget on its own: this item fails, the others go on
+      try {
+        if (const uint64_t budget = cm::mem_budget()) {
+          bool known = true;
+          const cm::ItemBytes b = need(i, cfg, known);
+          if (known) { refused = true; cm::check_item_fits(b, budget, "cm_prove_many (streamed)"); refused = false; }
+          // while this producer waits for room, the inputs it is asked to release must still go back (a worker's proof ends,
+          // its input comes back here, and only its release makes the room)
+          while (!cm::admission().try_admit_input(b.input)) {
+            std::unique_lock<std::mutex> lk(sh.mu);
+            if (!sh.spent[pid].empty()) release_spent(lk);
+            else sh.cv.wait_for(lk, std::chrono::milliseconds(1));   // (a finished proof notifies; the limit covers other pipelines' proofs)
+          }
+          counted = b.input;
+        }
+        d = produce(i);
+        if (counted) {   // the real size, once the input exists
+          const uint64_t real = cm::device_input_bytes(*d);
+          if (real > counted) cm::admission().add_inputs(real - counted); else cm::admission().sub_inputs(counted - real);
+          counted = real;
+        }
+      }
       catch (const cm::CmError& e) { rc = e.code ? e.code : 1; err = e.what(); }
       catch (const std::exception& e) { rc = 1; err = e.what(); }
       catch (...) { rc = 1; err = "unknown error"; }
+      if (!d && counted) cm::admission().sub_inputs(counted);
       std::lock_guard<std::mutex> lk(sh.mu);
       if (!d) {   // this item cannot be made: report it, stop producing (the items already handed over are still proved)
         if (!sh.rc) { sh.rc = rc ? rc : 1; sh.err = err; }
-        sh.stop = true;
+        if (!refused) sh.stop = true;
         sh.alive--;
         sh.outstanding[pid]--;
-      } else sh.ready.push_back(Job{i, d, pid});
+      } else sh.ready.push_back(Job{i, d, pid, counted});
       sh.cv.notify_all();
     }
     std::unique_lock<std::mutex> lk(sh.mu);
@@ -1756,6 +1862,10 @@ int32_t cm_prove_many_host(const cm_prover_input* const* inputs, uint32_t n, con
   return prove_streamed(n, [&](uint32_t i) {
     CM_CHECK(inputs && inputs[i], "cm_prove_many_host: null input");
     return cm::upload_input(*inputs[i], cm::thread_main_stream());
+  }, [&](uint32_t i, const cm_pcs_config& cfg, bool& known) {
+    CM_CHECK(inputs && inputs[i], "cm_prove_many_host: null input");
+    known = true;
+    return cm::item_bytes(*inputs[i], cm::estimate_input_bytes(*inputs[i]), cfg, 1);
   }, config, inflight, outs);
 }
 int32_t cm_prove_many_segments(const cm_runner_segment* const* segments, uint32_t n, const cm_pcs_config* config, uint32_t inflight,
@@ -1763,6 +1873,15 @@ int32_t cm_prove_many_segments(const cm_runner_segment* const* segments, uint32_
   return prove_streamed(n, [&](uint32_t i) {
     CM_CHECK(segments && segments[i], "cm_prove_many_segments: null segment");
     return cm::adapt_segment_device(*segments[i]);
+  }, [&](uint32_t i, const cm_pcs_config&, bool& known) {
+    CM_CHECK(segments && segments[i], "cm_prove_many_segments: null segment");
+    // before the adapter has run only the step and access counts are known: one bundle per step, one data access and at most one
+    // clock update per logged access, boundary memory and its two Merkle paths from the cells the accesses can touch
+    known = false;
+    const cm_runner_segment& g = *segments[i];
+    const uint64_t cells = g.n_initial_memory + g.n_initial_heap + g.n_memory_trace;
+    return cm::ItemBytes{g.n_trace * sizeof(cm_bundle) + g.n_memory_trace * (sizeof(cm_data_access) + sizeof(cm_clock_update)) +
+                             2 * cells * sizeof(cm_memory_cell), 0};
   }, config, inflight, outs, /*n_producers=*/2);
 }
 // ---- per-component AIR ops (include/cairom_hip.h): the kernels of the whole-segment prover, one component
@@ -2038,6 +2157,50 @@ int32_t cm_kprof_report(char* buf, size_t buf_len) {
   s += "}";
   if (buf && buf_len) { size_t n = s.size() < buf_len - 1 ? s.size() : buf_len - 1; memcpy(buf, s.data(), n); buf[n] = 0; }
   return (int32_t)s.size();
+}
+int32_t cm_proof_memory(const cm_proof* p, cm_proof_mem* out) {
+  return pguard([&] {
+    CM_CHECK(p && p->d && out, "cm_proof_memory: null argument");
+    CM_CHECK(out->struct_size >= sizeof(cm_proof_mem), "cm_proof_memory: struct_size does not cover cm_proof_mem (set it to sizeof(cm_proof_mem))");
+    cm_proof_mem m;
+    memset(&m, 0, sizeof(m));
+    m.struct_size = sizeof(m);
+    const cm::ProofData& d = *p->d;
+    m.n_phases = (uint32_t)std::min<size_t>(d.phase_peak_live.size(), 32);
+    m.start_live_bytes = d.mem_start_live; m.peak_live_bytes = d.mem_peak_live; m.peak_reserved_bytes = d.mem_peak_reserved;
+    m.input_bytes = d.mem_input_bytes; m.driver_allocs = d.mem_driver_allocs;
+    for (uint32_t k = 0; k < m.n_phases; k++) m.phase_peak_live_bytes[k] = d.phase_peak_live[k];
+    memcpy(out, &m, sizeof(m));
+  });
+}
+extern "C++" {
+static void estimate_checked(const uint32_t* clog, const cm_pcs_config* config, uint32_t world, uint64_t input_bytes, cm_mem_estimate* out, const char* who) {
+  const std::string w(who);
+  CM_CHECK(clog && out, (w + ": null argument").c_str());
+  CM_CHECK(out->struct_size >= sizeof(cm_mem_estimate), (w + ": struct_size does not cover cm_mem_estimate (set it to sizeof(cm_mem_estimate))").c_str());
+  const cm_pcs_config cfg = config ? *config : default_cfg();
+  CM_CHECK(cfg.log_blowup_factor >= 1 && cfg.log_blowup_factor <= 4, (w + ": log_blowup_factor must be in 1..4").c_str());
+  CM_CHECK(world == 1 || world == 2 || world == 4 || world == 8, (w + ": world must be 1, 2, 4 or 8").c_str());
+  CM_CHECK(cfg.n_queries <= 4096, (w + ": n_queries must be at most 4096").c_str());
+  for (int c = 0; c < air::N_COMPONENTS; c++) CM_CHECK(clog[c] <= 26, (w + ": a component's log size exceeds 26").c_str());
+  cm_mem_estimate e;
+  memset(&e, 0, sizeof(e));
+  e.struct_size = sizeof(e);
+  cm::estimate_memory(clog, cfg, world, cm::mem_switches(), e);
+  e.input_bytes = input_bytes;
+  memcpy(out, &e, sizeof(e));
+}
+}
+int32_t cm_estimate_memory_logs(const uint32_t log_size[CM_N_COMPONENTS], const cm_pcs_config* config, uint32_t world, cm_mem_estimate* out) {
+  return pguard([&] { estimate_checked(log_size, config, world, 0, out, "cm_estimate_memory_logs"); });
+}
+int32_t cm_estimate_memory(const cm_prover_input* input, const cm_pcs_config* config, uint32_t world, cm_mem_estimate* out) {
+  return pguard([&] {
+    CM_CHECK(input && out, "cm_estimate_memory: null argument");
+    uint32_t clog[air::N_COMPONENTS];
+    cm::component_logs(*input, clog);
+    estimate_checked(clog, config, world, cm::estimate_input_bytes(*input), out, "cm_estimate_memory");
+  });
 }
 int32_t cm_proof_stats(const cm_proof* p, uint64_t* cells, uint64_t* steps, double* phase_ms, uint32_t n_phases) {
   if (cells) *cells = p->d->cells;

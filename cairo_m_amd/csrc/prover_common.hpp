@@ -109,13 +109,22 @@ struct Prover {
     evs.push_back(c[evs.size()]);
     return evs.back();
   }
+  // Memory of the proving thread's pool, sampled where the phases are marked: allocations are host-side events, so the mark a
+  // phase's tick takes is the high-water mark of what the host allocated while it enqueued that phase (cm_proof_mem).
+  std::vector<uint64_t> phase_peak_live;
+  uint64_t mem_start_live = 0, mem_start_allocs = 0;
   void start() {
     t0 = std::chrono::steady_clock::now();
     CM_HIP(hipEventRecord(next_event(), st));
+    const ThreadMem m = thread_mem();
+    mem_start_live = m.live; mem_start_allocs = m.driver_allocs;
+    (void)thread_mem_mark();
+    thread_mem_reset_reserved_peak();
   }
   void tick(const char* name) {
     static const bool trace = getenv("CM_HOST_TRACE") != nullptr;
     CM_HIP(hipEventRecord(next_event(), st));
+    phase_peak_live.push_back(thread_mem_mark());
     if (!trace) return;
     auto te = std::chrono::steady_clock::now();
     CM_HIP(hipStreamSynchronize(st));
@@ -131,6 +140,19 @@ struct Prover {
       CM_HIP(hipEventElapsedTime(&ms, evs[k - 1], evs[k]));
       phase_ms.push_back(ms);
     }
+    const uint64_t rest = thread_mem_mark();   // what the host allocated behind the last tick belongs to the last phase
+    if (!phase_peak_live.empty() && rest > phase_peak_live.back()) phase_peak_live.back() = rest;
+  }
+  // the proof's memory report, from the marks above (call behind finish())
+  void report_memory(ProofData& pf, uint64_t input_bytes) const {
+    const ThreadMem m = thread_mem();
+    pf.phase_peak_live = phase_peak_live;
+    pf.mem_start_live = mem_start_live;
+    pf.mem_peak_live = mem_start_live;
+    for (uint64_t v : phase_peak_live) pf.mem_peak_live = std::max(pf.mem_peak_live, v);
+    pf.mem_peak_reserved = m.peak_reserved;
+    pf.mem_driver_allocs = m.driver_allocs - mem_start_allocs;
+    pf.mem_input_bytes = input_bytes;
   }
 
   // IFFT src(evals, trace domain) -> tree.coeffs; LDE -> tree.lde; Merkle; mix root.

@@ -586,6 +586,7 @@ struct ShardedProver {
     P.finish();
     fork_join_check();
     pf.phase_ms = P.phase_ms;
+    P.report_memory(pf, device_input_bytes(din));
     pf.steps = 0;
     for (int i = 0; i < CM_N_OPCODE_COMPONENTS; i++) pf.steps += in.n_bundles[i];
     return out.release();
@@ -1809,5 +1810,8 @@ struct ShardedProver {
 };
 
 ProofData* prove_sharded(const DeviceInput& din, const cm_pcs_config& cfg, const cm_comm& comm_c) {
+  if (const uint64_t budget = mem_budget())   // a lone proof has nothing to wait for: it fits or it is refused before any GPU work
+    check_item_fits(item_bytes(din.meta, device_input_bytes(din), cfg, std::max(comm_c.world, 1u)), budget, "cm_prove_sharded");
+  struct InFlight { InFlight() { mem_proof_enter(); } ~InFlight() { mem_proof_leave(); } } mem_in_flight;
   return ShardedProver(din, cfg, comm_c).run();
 }

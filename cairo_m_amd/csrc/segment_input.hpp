@@ -21,6 +21,14 @@ struct DeviceInput {
   PublicData public_data;
 };
 
+// bytes of the pool blocks a resident input occupies: every array at its size, pool-rounded (an empty array is a 4-byte block)
+inline uint64_t device_input_bytes(const DeviceInput& d) {
+  uint64_t n = 0;
+  auto add = [&](const DevBuf& b) { if (b.p) n += pool_round(b.bytes); };
+  for (int i = 0; i < CM_N_OPCODE_COMPONENTS; i++) add(d.bundles[i]);
+  add(d.data_accesses); add(d.init_mem); add(d.fin_mem); add(d.clock_updates); add(d.init_tree); add(d.fin_tree);
+  return n;
+}
 // log2 rows of every component, known from the input lengths (Claim::log_sizes)
 inline void component_logs(const cm_prover_input& in, uint32_t* clog) {
   uint64_t nrows[air::N_COMPONENTS] = {0};

@@ -258,8 +258,20 @@ class Proof:
         cells, steps = C.c_uint64(0), C.c_uint64(0)
         ph = (C.c_double * 32)()
         n = self.L.cm_proof_stats(self.h, C.byref(cells), C.byref(steps), ph, C.c_uint32(32))
-        return {"cells": cells.value, "steps": steps.value,
-                "phase_ms": dict(zip(self.PHASES, [ph[i] for i in range(min(n, 32))]))}
+        out = {"cells": cells.value, "steps": steps.value,
+               "phase_ms": dict(zip(self.PHASES, [ph[i] for i in range(min(n, 32))]))}
+        if hasattr(self.L, "cm_proof_memory"):      # (CAIROM_HIP_LIB may name a build older than header revision 9)
+            out["memory"] = self.memory().as_dict(self.PHASES)
+        return out
+
+    def memory(self):
+        """cm_proof_memory: what this proof took from the proving thread's device pool (ProofMem)."""
+        m = ProofMem()
+        m.struct_size = C.sizeof(ProofMem)
+        rc = self.L.cm_proof_memory(self.h, C.byref(m))
+        if rc:
+            raise _lib_error(self.L, rc)
+        return m
 
     def verify(self, cfg=None):
         """verify_cairo_m(proof, pcs_config) on this proof (product-side verifier, host code): (status, message).
@@ -583,6 +595,85 @@ def _backend_mem_info(self):
 
 
 Backend.mem_info = _backend_mem_info
+
+
+# ---- device-memory accounting, estimate and budget (include/cairom_hip.h, revision 9) --------------------------
+N_COMPONENTS = 34
+
+
+class MemStats(C.Structure):
+    """cm_mem_stats: process-wide counters over all thread pools."""
+    _fields_ = [("struct_size", C.c_uint32), ("proofs_in_flight", C.c_uint32), ("peak_proofs_in_flight", C.c_uint32),
+                ("reserved0", C.c_uint32),
+                ("live_bytes", C.c_uint64), ("reserved_bytes", C.c_uint64), ("peak_live_bytes", C.c_uint64),
+                ("peak_reserved_bytes", C.c_uint64), ("pinned_host_bytes", C.c_uint64), ("driver_allocs", C.c_uint64),
+                ("budget_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n not in ("struct_size", "reserved0")}
+
+
+class ProofMem(C.Structure):
+    """cm_proof_mem: one proof's share of the proving thread's pool."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_phases", C.c_uint32),
+                ("start_live_bytes", C.c_uint64), ("peak_live_bytes", C.c_uint64), ("peak_reserved_bytes", C.c_uint64),
+                ("input_bytes", C.c_uint64), ("driver_allocs", C.c_uint64), ("phase_peak_live_bytes", C.c_uint64 * 32)]
+
+    def as_dict(self, phases=None):
+        d = {n: getattr(self, n) for n in ("start_live_bytes", "peak_live_bytes", "peak_reserved_bytes", "input_bytes", "driver_allocs")}
+        peaks = [self.phase_peak_live_bytes[i] for i in range(self.n_phases)]
+        d["phase_peak_live_bytes"] = dict(zip(phases, peaks)) if phases and len(phases) >= len(peaks) else peaks
+        return d
+
+
+class MemEstimate(C.Structure):
+    """cm_mem_estimate: input_bytes, working_bytes (upper bound of a lone proof's peak over its start), cached_bytes."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_uint32),
+                ("input_bytes", C.c_uint64), ("working_bytes", C.c_uint64), ("cached_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {"input_bytes": self.input_bytes, "working_bytes": self.working_bytes, "cached_bytes": self.cached_bytes}
+
+
+def mem_stats(lib=None):
+    """cm_mem_stats_get (host code: works without a GPU and before cm_init)."""
+    L = lib or load_library()
+    s = MemStats()
+    s.struct_size = C.sizeof(MemStats)
+    rc = L.cm_mem_stats_get(C.byref(s))
+    if rc:
+        raise _lib_error(L, rc)
+    return s
+
+
+def mem_reset_peak(lib=None):
+    (lib or load_library()).cm_mem_reset_peak()
+
+
+def set_memory_budget(n_bytes, lib=None):
+    """cm_set_memory_budget: 0 = none."""
+    (lib or load_library()).cm_set_memory_budget(C.c_uint64(int(n_bytes)))
+
+
+def estimate_memory(view=None, log_sizes=None, cfg=None, world=1, lib=None):
+    """cm_estimate_memory (view = a cm_prover_input*, e.g. HostInput.view) or cm_estimate_memory_logs (34 component log sizes)."""
+    L = lib or load_library()
+    e = MemEstimate()
+    e.struct_size = C.sizeof(MemEstimate)
+    if view is not None:
+        rc = L.cm_estimate_memory(view, _cfg(cfg), C.c_uint32(world), C.byref(e))
+    else:
+        logs = (C.c_uint32 * N_COMPONENTS)(*[int(x) for x in log_sizes])
+        rc = L.cm_estimate_memory_logs(logs, _cfg(cfg), C.c_uint32(world), C.byref(e))
+    if rc:
+        raise _lib_error(L, rc)
+    return e
+
+
+Backend.mem_stats = lambda self: mem_stats(self.L)
+Backend.mem_reset_peak = lambda self: mem_reset_peak(self.L)
+Backend.set_memory_budget = lambda self, n_bytes: set_memory_budget(n_bytes, self.L)
+Backend.estimate_memory = lambda self, view=None, log_sizes=None, cfg=None, world=1: estimate_memory(view, log_sizes, cfg, world, self.L)
 
 
 # ---- compiled-program JSON (crates/common/src/program.rs:143-170, instruction.rs:609-655) ----------------------

@@ -28,8 +28,10 @@
  * config and column-array capacities; cm_set_device_tail, cm_tail_list.  6: cm_runner_segment grows by initial_heap /
  * n_initial_heap at its END (a revision-5 caller must be recompiled: the library reads the two fields);
  * cm_host_segment_set_initial_heap.  7: cm_check_report, cm_check_constraints, cm_constraints_check, cm_relation_sums.
- * 8: cm_relation_entry, cm_track_relations, cm_relation_entries. */
-#define CM_ABI_REVISION 8
+ * 8: cm_relation_entry, cm_track_relations, cm_relation_entries.
+ * 9: cm_mem_stats, cm_proof_mem, cm_mem_estimate; cm_mem_stats_get, cm_mem_reset_peak, cm_proof_memory, cm_estimate_memory,
+ *    cm_estimate_memory_logs, cm_set_memory_budget. */
+#define CM_ABI_REVISION 9
 
 #ifdef __cplusplus
 extern "C" {
@@ -431,6 +433,65 @@ int32_t cm_proof_json(const cm_proof* p, const char** json_out, size_t* len_out)
 int32_t cm_proof_transcript(const cm_proof* p, const char** json_out, size_t* len_out);
 /* The four commitment roots (trees 0..3), 32 bytes each. */
 int32_t cm_proof_commitments(const cm_proof* p, uint8_t roots[4][32]);
+/* ---- device-memory accounting, estimate and budget (revision 9) --------------------------------------------------------------
+ * Every block a proof uses comes from a caching pool per host thread (cairo_m_amd/csrc/pool.hip).  The counters below are
+ * process-wide sums over all thread pools, kept with relaxed atomics on the pool's own paths (no lock, no driver call):
+ *   live_bytes      capacity of the blocks handed out and not yet given back (a proof's columns, a resident cm_device_input,
+ *                   what a finished proof parked for its successor, a cached preprocessed tree)
+ *   reserved_bytes  live + cached = everything the library holds from the driver through the pool
+ *   peak_*          high-water marks since the last cm_mem_reset_peak
+ *   driver_allocs   hipMalloc calls of the pool since the last reset (0 in a steady state of equal proofs)
+ *   pinned_host_bytes  the pinned host buffers of the threads that entered the library: upload ring, landing buffer, the
+ *                   device tail's two buffers, the fixed result words
+ * NOT counted (direct driver allocations outside the pool): caller-owned columns of cm_col_alloc, the process-wide twiddle tables
+ * of cm_set_twiddle_cache(1) (cm_mem_estimate.cached_bytes does include them), the proof-of-work result ring, the 128-byte flag
+ * words of a thread's side streams and the 4 bytes of the flag-synchronisation self-test, RCCL's own buffers.
+ * A struct's leading struct_size is sizeof as the CALLER compiled it (like cm_comm): set it before the call; the library writes
+ * at most that many bytes, and a size that does not cover the revision-9 fields is status 1. */
+typedef struct {
+  uint32_t struct_size, proofs_in_flight, peak_proofs_in_flight, reserved0;
+  uint64_t live_bytes, reserved_bytes, peak_live_bytes, peak_reserved_bytes, pinned_host_bytes, driver_allocs, budget_bytes;
+} cm_mem_stats;
+/* host code; works before cm_init and without a GPU (all zero) */
+int32_t cm_mem_stats_get(cm_mem_stats* out);
+/* peaks := current values, driver_allocs := 0, peak_proofs_in_flight := proofs_in_flight */
+int32_t cm_mem_reset_peak(void);
+/* What ONE proof took, measured on the proving thread's own pool (for cm_prove_sharded: this rank's numbers).  Phases are those
+ * of cm_proof_stats' phase_ms, same order and count.  A proof rebuilt by cm_proof_from_words reports zeros. */
+typedef struct {
+  uint32_t struct_size, n_phases;
+  uint64_t start_live_bytes;        /* the proving thread's pool at entry: caches, blocks parked by the previous proof */
+  uint64_t peak_live_bytes;         /* high-water mark of that pool during this proof */
+  uint64_t peak_reserved_bytes;
+  uint64_t input_bytes;             /* the cm_device_input it read (owned by another pool under cm_prove_many*) */
+  uint64_t driver_allocs;           /* hipMalloc calls this proof caused */
+  uint64_t phase_peak_live_bytes[32];   /* same order and count as cm_proof_stats' phase_ms */
+} cm_proof_mem;
+int32_t cm_proof_memory(const cm_proof* p, cm_proof_mem* out);
+/* Estimate (host code, no GPU): a closed formula of the 34 component log sizes, the PCS config, `world` (1 = cm_prove_device,
+ * 2 / 4 / 8 = one rank of cm_prove_sharded) and the memory-relevant switches in force (preprocessed / twiddle cache, deferred
+ * teardown).  working_bytes is an UPPER BOUND of peak_live_bytes - start_live_bytes of a lone proof, monotone in every log size
+ * and in log_blowup_factor; how tight it is is measured (tools/mem_report.py), not promised.  For world > 1 the bound does not
+ * yet credit what sharding saves.  log sizes above 26, a blowup outside 1..4 or a world that is not 1, 2, 4 or 8 are status 1. */
+typedef struct {
+  uint32_t struct_size, reserved0;
+  uint64_t input_bytes;     /* the resident cm_device_input */
+  uint64_t working_bytes;   /* upper bound of peak_live_bytes - start_live_bytes of a lone proof */
+  uint64_t cached_bytes;    /* what the preprocessed / twiddle caches and the parked teardown may hold between proofs */
+} cm_mem_estimate;
+int32_t cm_estimate_memory(const cm_prover_input* input, const cm_pcs_config* config, uint32_t world, cm_mem_estimate* out);
+/* the same from the component log sizes alone (plan a max_steps without having an input): input_bytes is 0 */
+int32_t cm_estimate_memory_logs(const uint32_t log_size[CM_N_COMPONENTS], const cm_pcs_config* config, uint32_t world,
+                                cm_mem_estimate* out);
+/* Budget for the pool's LIVE bytes, process-wide; 0 = none (default); env CM_MEMORY_BUDGET sets the initial value.  With a budget
+ * cm_prove_many, cm_prove_many_host and cm_prove_many_segments admit work by bytes as well as by `inflight`: the next device
+ * input is made, and the next proof started, only while resident inputs + the working_bytes of the proofs running + the new item
+ * fit; a worker gives its parked teardown back before it waits and trims its pool when reserved_bytes is over the budget; when
+ * nothing is running the next item is always admitted (no deadlock).  An item whose own input_bytes + working_bytes exceeds the
+ * budget fails with status 2 and a message naming both numbers, before any GPU work for it (cm_prove_many_segments: before its
+ * proof — its component sizes are only known once the device adapter has run); the other items are proved.  cm_prove_device,
+ * cm_prove_segment and cm_prove_sharded apply that last rule only.  Order of outs and proof bytes never depend on the budget. */
+int32_t cm_set_memory_budget(uint64_t bytes);
 /* ---- device-side adapter -----------------------------------------------------------------
  * One runner segment in the runner's own terms: the VM trace, the memory access log and the memory at
  * segment start (crates/runner/src/vm/mod.rs:306-375, crates/common/src/execution.rs:28-66).

@@ -145,6 +145,45 @@ pub struct cm_check_report {
     pub relations: cm_relations,
     pub message: [c_char; 256],
 }
+/// Process-wide device-memory counters over all thread pools (`cm_mem_stats_get`); `struct_size` = `size_of::<cm_mem_stats>()`.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct cm_mem_stats {
+    pub struct_size: u32,
+    pub proofs_in_flight: u32,
+    pub peak_proofs_in_flight: u32,
+    pub reserved0: u32,
+    pub live_bytes: u64,
+    pub reserved_bytes: u64,
+    pub peak_live_bytes: u64,
+    pub peak_reserved_bytes: u64,
+    pub pinned_host_bytes: u64,
+    pub driver_allocs: u64,
+    pub budget_bytes: u64,
+}
+/// What one proof took from the proving thread's device pool (`cm_proof_memory`); phases as `cm_proof_stats`.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct cm_proof_mem {
+    pub struct_size: u32,
+    pub n_phases: u32,
+    pub start_live_bytes: u64,
+    pub peak_live_bytes: u64,
+    pub peak_reserved_bytes: u64,
+    pub input_bytes: u64,
+    pub driver_allocs: u64,
+    pub phase_peak_live_bytes: [u64; 32],
+}
+/// Host-side estimate of a proof's device memory (`cm_estimate_memory`): `working_bytes` is an upper bound.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct cm_mem_estimate {
+    pub struct_size: u32,
+    pub reserved0: u32,
+    pub input_bytes: u64,
+    pub working_bytes: u64,
+    pub cached_bytes: u64,
+}
 /// One tuple of the relation tracker's summary (`cm_track_relations`, `cm_relation_entries`): net multiplicity (canonical M31,
 /// never 0), the lowest (component, row) merged into it (`CM_N_COMPONENTS` = public data) and the number of entries merged.
 #[repr(C)]
@@ -300,5 +339,11 @@ unsafe extern "C" {
     pub fn cm_kprof_enable(on: i32) -> i32;
     pub fn cm_kprof_report(buf: *mut c_char, buf_len: usize) -> i32;
     pub fn cm_kprof_filter(name: *const c_char) -> i32;
+    pub fn cm_mem_stats_get(out: *mut cm_mem_stats) -> i32;
+    pub fn cm_mem_reset_peak() -> i32;
+    pub fn cm_proof_memory(p: *const cm_proof, out: *mut cm_proof_mem) -> i32;
+    pub fn cm_estimate_memory(input: *const cm_prover_input, config: *const cm_pcs_config, world: u32, out: *mut cm_mem_estimate) -> i32;
+    pub fn cm_estimate_memory_logs(log_size: *const u32, config: *const cm_pcs_config, world: u32, out: *mut cm_mem_estimate) -> i32;
+    pub fn cm_set_memory_budget(bytes: u64) -> i32;
     pub fn cm_proof_stats(p: *const cm_proof, cells: *mut u64, steps: *mut u64, phase_ms: *mut f64, n_phases: u32) -> i32;
 }

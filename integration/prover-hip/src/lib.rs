@@ -273,3 +273,38 @@ pub fn track_and_summarize_relations(input: &mut ProverInput) -> std::collection
     }
     out
 }
+
+/// Device memory a proof of `input` needs under `config` (`None` = REGULAR_96_BITS), computed on the host without a GPU:
+/// `(input_bytes, working_bytes, cached_bytes)`.  `working_bytes` is an upper bound of what one proof adds to its thread's device
+/// pool; a host that keeps several proofs in flight sizes `set_memory_budget` from it.  `world` = 1 for `prove_cairo_m_hip`,
+/// 2 / 4 / 8 for one rank of a sharded proof.
+pub fn estimate_memory(input: &mut ProverInput, config: Option<cm_pcs_config>, world: u32) -> Result<(u64, u64, u64), String> {
+    let flat = Flat::new(input, MemoryOrder::AscendingAddress);
+    let view = flat.view();
+    let mut e: cm_mem_estimate = unsafe { std::mem::zeroed() };
+    e.struct_size = std::mem::size_of::<cm_mem_estimate>() as u32;
+    let cfg_ptr = match config.as_ref() {
+        Some(c) => c as *const cm_pcs_config,
+        None => std::ptr::null(),
+    };
+    let rc = unsafe { cm_estimate_memory(&view, cfg_ptr, world, &mut e) };
+    if rc != 0 {
+        return Err(last_error());
+    }
+    Ok((e.input_bytes, e.working_bytes, e.cached_bytes))
+}
+
+/// Bytes the proof pipelines (`cm_prove_many*`) may keep live in device memory, process-wide; 0 = no budget.
+pub fn set_memory_budget(bytes: u64) {
+    let rc = unsafe { cm_set_memory_budget(bytes) };
+    assert!(rc == 0, "cm_set_memory_budget: {}", last_error());
+}
+
+/// The process-wide device-memory counters (live / reserved bytes, their peaks, driver allocations, proofs in flight).
+pub fn memory_stats() -> cm_mem_stats {
+    let mut s: cm_mem_stats = unsafe { std::mem::zeroed() };
+    s.struct_size = std::mem::size_of::<cm_mem_stats>() as u32;
+    let rc = unsafe { cm_mem_stats_get(&mut s) };
+    assert!(rc == 0, "cm_mem_stats_get: {}", last_error());
+    s
+}
