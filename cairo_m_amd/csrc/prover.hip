@@ -6,6 +6,8 @@
 #include "../../include/cairom_hip.h"
 #include "prover_common.hpp"
 #include "quotient_plan.hpp"
+#include "constraint_plan.hpp"
+#include "proof_context.hpp"
 #include "air_kernels.hpp"
 #include "gpu_air.hpp"
 #include "point_eval.hpp"
@@ -275,15 +277,7 @@ struct ProofTwiddles {   // per-proof tables in pool memory
   }
 };
 
-// coset_vanishing of CanonicCoset(log).coset at p (QM31 or M31 point)
-template <class F>
-static F coset_vanishing_canonic(uint32_t log, CPoint<F> p) {
-  // shift = -initial + step/2 = 0 for a canonic (odds) coset: initial = G_{2^(log+1)} = step/2
-  F x = p.x;
-  for (uint32_t i = 1; i < log; i++) x = double_x(x);
-  return x;
-}
-
+// (coset_vanishing_canonic, zero_ranges: constraint_plan.hpp)
 // (component_logs: segment_input.hpp)
 // ---- transcript steps shared by the single-GPU and the sharded prover ------------------------------------------------------
 // PcsConfig::mix_into + PublicData::mix_into (prover.rs:33-36, 62-66)
@@ -347,25 +341,6 @@ static CPoint<QM31> draw_oods_point(Channel& ch, QM31* t_out = nullptr) {
   p.y = (t + t) * iv;
   return p;
 }
-// up to three device ranges zeroed by ONE launch (the constraints phase clears two accumulator sets and the slot buffer right in
-// front of its kernels: three dependent hipMemsetAsync = three packets on the critical path behind the interaction tree)
-struct ZeroRanges { uint4* p[3]; uint64_t n16[3]; };
-__global__ void __launch_bounds__(256) k_zero_ranges(ZeroRanges z) {
-  for (int r = 0; r < 3; r++)
-    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < z.n16[r]; i += (uint64_t)gridDim.x * 256) z.p[r][i] = make_uint4(0, 0, 0, 0);
-}
-static void zero_ranges(void* const p[3], const size_t bytes[3], hipStream_t st) {
-  ZeroRanges z;
-  uint64_t total = 0;
-  for (int r = 0; r < 3; r++) {
-    CM_CHECK(((uintptr_t)p[r] & 15) == 0 && (bytes[r] & 15) == 0, "zero_ranges: ranges must be 16-byte aligned");
-    z.p[r] = (uint4*)p[r]; z.n16[r] = bytes[r] / 16; total += z.n16[r];
-  }
-  if (!total) return;
-  const unsigned blocks = (unsigned)std::min<uint64_t>((total + 255) / 256, 256 * 16);
-  hipLaunchKernelGGL(k_zero_ranges, dim3(blocks), dim3(256), 0, st, z);
-  CM_HIP(hipGetLastError());
-}
 // side streams a fork region spreads its large launches over (A/B: CM_FORK_WIDTH; the join costs one barrier packet per used stream)
 static int fork_width(int dflt) {
   const int w = tune(T_FORK_WIDTH);
@@ -386,20 +361,10 @@ struct HostTrace {
     t = n;
   }
 };
-// the PcsConfig ranges both provers accept (max_log: the largest trace column)
-static void check_pcs_config(const cm_pcs_config& cfg, uint32_t max_log) {
-  CM_CHECK(cfg.n_queries >= 1 && cfg.n_queries <= 4096, "PcsConfig: n_queries must be in 1..4096");
-  CM_CHECK(cfg.pow_bits <= 64, "PcsConfig: pow_bits must be at most 64");
-  CM_CHECK(cfg.log_last_layer_degree_bound <= max_log, "PcsConfig: log_last_layer_degree_bound exceeds the largest trace column");
-}
+// (check_pcs_config, ProofContext, mix_claim, channel_words, DrainOnExit: proof_context.hpp)
 // One segment proof on one GPU: the phases of prove_cairo_m (prover.rs:23-147) in transcript order.  Each phase enqueues its
 // kernels and returns at the next point where the transcript needs a device result; what crosses a phase boundary is a member.
-struct SegmentProver {
-  const DeviceInput& din;
-  const cm_prover_input& in;
-  const cm_pcs_config cfg;
-  std::unique_ptr<ProofData> out;
-  ProofData& pf;
+struct SegmentProver : ProofContext {
   HostTrace ht{"[host]", 40, "CM_HOST_TRACE", "CM_HOST_MARKS"};
   struct DtorMark { HostTrace* ht; const char* what; ~DtorMark() { ht->mark(what); } };   // (CM_HOST_MARKS: where the teardown goes)
   DtorMark dm_p{&ht, "~ everything else (P: trees, events)"};
@@ -407,22 +372,15 @@ struct SegmentProver {
   DtorMark dm_after_p{&ht, "~ twiddles .. step buffers"};
   hipStream_t st;
   Channel& ch;
-  uint32_t clog[air::N_COMPONENTS];          // log2 rows of every component
-  uint32_t max_log = 0, comp_log = 0;        // largest component; composition polynomial = max_log + 1
-  std::vector<int> by_size, by_size_all;     // launch orders: opcode components / all components by descending size
+  std::vector<int> by_size;                  // launch order of the opcode components: by_size_all without the builtins
   ProofTwiddles own_tw;
   std::unique_ptr<Fork> tw_fork;
   ColumnSet pp_evals, tr_evals;              // preprocessed / execution-trace evaluations (trace domain)
-  std::vector<size_t> tr0, it0;              // first column of every component in trees 1 / 2
-  HostRelations hrel;
   DevBuf drel;                               // DevRelations
-  std::vector<size_t> coff;                  // first constraint of every component
-  std::vector<QM31> powers;                  // random-coefficient powers, one per constraint
-  DevBuf d_powers;
+  DevBuf d_powers;                           // `powers` on the device
   DevBuf d_step1;                            // device-side transcript step after tree 1: {root[8], nonce[2], n_sent, error, z0[4]}
   DevBuf d_step2;                            // device-side transcript step after tree 2: {channel[16], coefficient[4], root[8]}
   DevBuf d_ctab;                             // composition: every small table of the constraints phase, ONE upload
-  CPoint<QM31> oods;
   DtorMark dm_q{&ht, "~ oods buffers, quotients"};
   DevBuf d_oods_table, d_oods_out, d_qblob;  // sampling pointer table, sampled values, DEEP-quotient plan
   size_t o_qjobs = 0, n_qjobs = 0;
@@ -441,14 +399,9 @@ struct SegmentProver {
   std::vector<QuotientGroup> qg;             // DEEP-quotient size groups (quotient_plan.hpp)
   AffinityScope cpu_scope;   // the calling thread sits next to the GPU for this proof only (pool.hip)
   SegmentProver(const DeviceInput& din_, const cm_pcs_config& cfg_)
-      : din(din_), in(din_.meta), cfg(cfg_), out(new ProofData()), pf(*out), st(nullptr), ch(P.ch) {
-    pf.config = cfg;
-    bind_thread_to_library_device();
-    if (g_transcript_log.load()) P.ch.log.p = &pf.transcript;
-    P.cfg = cfg;
-    P.st = thread_main_stream();
+      : ProofContext(din_, cfg_), st(nullptr), ch(P.ch) {
+    start(P);
     st = P.st;
-    P.start();
   }
   ProofData* run() {
     setup();
@@ -462,14 +415,9 @@ struct SegmentProver {
 
     kprof_close_run();   // a run of timed launches still open on this thread
     ht.mark("finish: entered");
-    P.finish();
-    ht.mark("finish: phase events read");
-    fork_join_check();
-    pf.phase_ms = P.phase_ms;
-    P.report_memory(pf, device_input_bytes(din));
+    finish_common(P);
+    ht.mark("finish: phase events read, fork/join checked");
     pf.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - P.t0).count();
-    pf.steps = 0;
-    for (int i = 0; i < CM_N_OPCODE_COMPONENTS; i++) pf.steps += in.n_bundles[i];
     if (pp_cache_enabled()) {
       tl_pp_cache.tree = std::move(P.trees[0]);
       tl_pp_cache.evals = std::move(pp_evals);
@@ -506,18 +454,9 @@ struct SegmentProver {
 
   // component sizes, twiddles (side stream), transcript setup (prover.rs:33-66)
   void setup() {
-    // ---- component log sizes (known from the input lengths) ----
-    component_logs(in, clog);
-    max_log = 0;
-    for (int c = 0; c < air::N_COMPONENTS; c++) max_log = std::max(max_log, clog[c]);
-    for (int c = 0; c < air::N_COMPONENTS; c++) CM_CHECK(clog[c] <= 26, "component too large");
-    // launch orders: components by descending size (stable)
-    for (int c = 0; c < air::N_COMPONENTS; c++) { by_size_all.push_back(c); if (c < air::N_OPCODE_COMPONENTS) by_size.push_back(c); }
-    auto bigger = [&](int x, int y) { return clog[x] > clog[y]; };
-    std::stable_sort(by_size.begin(), by_size.end(), bigger);
-    std::stable_sort(by_size_all.begin(), by_size_all.end(), bigger);
-    comp_log = max_log + 1;
-    check_pcs_config(cfg, max_log);
+    size_components();
+    column_offsets();
+    for (int c : by_size_all) if (c < air::N_OPCODE_COMPONENTS) by_size.push_back(c);
     if (tw_cache_enabled()) P.tw = cached_twiddles(comp_log + cfg.log_blowup_factor, st);
     else {
       tw_fork.reset(new Fork(st));
@@ -538,10 +477,7 @@ struct SegmentProver {
     // ---- tree 0: preprocessed trace (prover.rs:70-73) ----
     std::unique_ptr<Fork> pp_fork;
     hipStream_t tree0_stream = nullptr;
-    struct DrainOnExit {   // an exception between the fork and the join must not return tree 0's buffers to the pool under its kernels
-      hipStream_t& s; bool joined = false;
-      ~DrainOnExit() { if (s && !joined) (void)hipStreamSynchronize(s); }
-    } tree0_guard{tree0_stream};
+    DrainOnExit tree0_guard;   // an exception between the fork and the join must not return tree 0's buffers to the pool under its kernels
     bool build_tree0 = false;
     if (pp_cache_enabled() && tl_pp_cache.valid && tl_pp_cache.log_blowup == cfg.log_blowup_factor) {
       P.trees[0] = std::move(tl_pp_cache.tree);  // both handed back at the end of the proof
@@ -568,16 +504,7 @@ struct SegmentProver {
     ht.mark("preprocessed gpu done");
 
     // ---- tree 1: execution trace (prover.rs:77-82; Claim::write_trace) ----
-    tr0.assign(air::N_COMPONENTS, 0);
-    it0.assign(air::N_COMPONENTS, 0);
-    {
-      std::vector<uint32_t> logs;
-      for (int c = 0; c < air::N_COMPONENTS; c++) {
-        tr0[c] = logs.size();
-        for (int k = 0; k < air::component_info(c).n_trace; k++) logs.push_back(clog[c]);
-      }
-      tr_evals.alloc(logs, st);
-    }
+    tr_evals.alloc(tr_logs, st);
     DevBuf flag(4);   // range-check / bitwise lookup out of range: read back with the tree-1 root (no round trip of its own)
     uint32_t* flag_host = pinned_words();
     {
@@ -650,13 +577,13 @@ struct SegmentProver {
       // four high-priority chains cutting into them cost 0.5-1 ms per proof (9.6 -> 10.1-10.8 with four in flight).
       const int t0_prio = tune(T_TREE0_PRIO);
       if (t0_prio != 0 && g_proofs_in_flight.load(std::memory_order_relaxed) <= 1) {
-        tree0_stream = thread_priority_stream(t0_prio);
+        tree0_guard.s = tree0_stream = thread_priority_stream(t0_prio);
         hipEvent_t e = Prover::pipe_event();
         CM_HIP(hipEventRecord(e, st));                       // trace generation launched, twiddles joined
         CM_HIP(hipStreamWaitEvent(tree0_stream, e, 0));
       } else {
         pp_fork.reset(new Fork(st));
-        tree0_stream = pp_fork->stream(Fork::N - 1);   // the side stream waits for THIS point of the main stream (trace generation done)
+        tree0_guard.s = tree0_stream = pp_fork->stream(Fork::N - 1);   // the side stream waits for THIS point of the main stream (trace generation done)
       }
     }
     P.tick("trace_gen");
@@ -693,15 +620,14 @@ struct SegmentProver {
       memcpy(P.trees[0].root.data(), pinned_words() + PIN_ROOT0, 32);
       ch.mix_root(P.trees[0].root);
     }
-    for (int c = 0; c < air::N_COMPONENTS; c++) { pf.claim_log_sizes.push_back(clog[c]); ch.mix_u64(clog[c]); }
+    mix_claim(ch, pf, clog);
     // Everything from root 1 to the relation challenges happens on the device, right behind the tree (k_step_pow_relations:
     // mix_root, interaction proof of work, mix_u64(nonce), Relations::draw + alpha powers): the LogUp kernels start without a
     // host round trip.  The host replays the steps from the copied-back root / nonce when it waits for the claimed sums.
     {
       static_assert(sizeof(DevRelations) == 4 * 4 * (air::N_RELATIONS + air::N_RELATIONS * air::MAX_REL_SIZE), "DevRelations layout");
       uint32_t cw[9];
-      memcpy(cw, ch.digest.data(), 32);
-      cw[8] = ch.n_sent;
+      channel_words(ch, cw);
       drel.alloc(sizeof(DevRelations));
       d_step1.alloc(16 * 4);
       uint32_t* rel = drel.u32();
@@ -731,16 +657,9 @@ struct SegmentProver {
     Prover::DeferredCols late;
     Prover::CommitPrep tree2_prep;
     bool tree2_prepared = false;
-    {
-      std::vector<uint32_t> logs;
-      for (int c = 0; c < air::N_COMPONENTS; c++) {
-        it0[c] = logs.size();
-        for (int k = 0; k < air::component_info(c).n_interaction; k++) logs.push_back(clog[c]);
-      }
-      ht.mark("interaction: entered");
-      it_evals.alloc(logs, st);
-      ht.mark("interaction: columns allocated");
-    }
+    ht.mark("interaction: entered");
+    it_evals.alloc(it_logs, st);
+    ht.mark("interaction: columns allocated");
     {
       tail_scratch.emplace_back(air::N_COMPONENTS * 16);
       uint32_t* const d_sums = tail_scratch.back().u32();
@@ -860,54 +779,21 @@ struct SegmentProver {
     // ---- stwo prove: composition polynomial.  Everything that does not depend on the random coefficient (accumulators,
     // slots, per-component arguments, their uploads and memsets) is prepared and enqueued here, behind the tree-2 kernels;
     // the root is read back, the coefficient drawn and its powers uploaded right before the launches. ----
-    size_t total_constraints = 0;
-    coff.assign(air::N_COMPONENTS, 0);
-    for (int c = 0; c < air::N_COMPONENTS; c++) { coff[c] = total_constraints; total_constraints += air::component_info(c).n_constraints; }
-    powers.assign(total_constraints, QM31());
+    const size_t total_constraints = powers.size();
     d_powers.alloc(16 * total_constraints);
-    // accumulators: 4 columns per evaluation log.  The top size gets its own ColumnSet (it becomes the coefficient
-    // set of tree 3), all smaller sizes share one — two pointer-table uploads and two memsets instead of one pair
-    // per size.
-    struct AccRef { ColumnSet* set; size_t first; uint32_t* const* dev() const { return set->dev(first); } };
-    std::map<uint32_t, AccRef> accs;  // evaluation log -> its 4 accumulator columns
-    std::set<uint32_t> acc_interpolated;   // evaluation logs whose accumulator is interpolated inside the constraints region
-    std::map<uint32_t, std::vector<int>> cgroups;
-    for (int c = 0; c < air::N_COMPONENTS; c++) cgroups[clog[c] + 1].push_back(c);
-    ColumnSet acc_top, acc_rest;
-    {
-      std::vector<uint32_t> rest_logs;
-      for (auto& kv : cgroups)
-        if (kv.first != comp_log) { accs[kv.first] = AccRef{&acc_rest, rest_logs.size()}; rest_logs.insert(rest_logs.end(), 4, kv.first); }
-      CM_CHECK(cgroups.count(comp_log), "composition polynomial log size mismatch");
-      accs[comp_log] = AccRef{&acc_top, 0};
-      // (pointer tables: in the phase's one upload below; zeroing: one launch together with the slot buffer)
-      acc_top.alloc(std::vector<uint32_t>(4, comp_log), st, false);
-      if (!rest_logs.empty()) acc_rest.alloc(rest_logs, st, false);
-    }
-    // The constraints are evaluated on CanonicCoset(log + 1).  With log_blowup_factor = 1 (REGULAR_96_BITS) that is the
-    // committed LDE domain and the kernels read the committed columns; with a larger blowup every polynomial is evaluated
-    // on its (log + 1) domain separately (Stwo does the same: `poly.evaluate(eval_domain)`), at the cost of one more forward
-    // transform per column and its memory.
+    // the accumulators of every evaluation log (constraint_plan.hpp): pointer tables in the phase's one upload below, zeroing in
+    // one launch together with the slot buffer
+    ConstraintAccumulators acc;
+    acc.plan(clog, comp_log, [](int) { return true; });
+    CM_CHECK(acc.cgroups.count(comp_log), "composition polynomial log size mismatch");
+    acc.alloc(st, /*upload_ptrs=*/false, /*top_contiguous=*/false);
+    const std::map<uint32_t, std::vector<int>>& cgroups = acc.cgroups;
+    ColumnSet &acc_top = acc.top, &acc_rest = acc.rest;
     CM_CHECK(cfg.log_blowup_factor >= 1 && cfg.log_blowup_factor <= 4, "PcsConfig: log_blowup_factor must be in 1..4");
     ColumnSet cdom[3];   // evaluation-domain copies of trees 0..2 (only when log_blowup_factor > 1)
     if (cfg.log_blowup_factor > 1) {
-      for (int t = 0; t < 3; t++) {
-        std::vector<uint32_t> logs(P.trees[t].coeffs.logs);
-        for (auto& l : logs) l += 1;
-        cdom[t].alloc(logs, st);
-        std::vector<const uint32_t*> table;
-        struct Grp { uint32_t log, n; size_t off; };
-        std::vector<Grp> grps;
-        for (auto& kv : by_log(P.trees[t].coeffs.logs)) {
-          grps.push_back(Grp{kv.first, (uint32_t)kv.second.size(), table.size()});
-          for (auto i : kv.second) table.push_back(P.trees[t].coeffs.ptrs[i]);
-          for (auto i : kv.second) table.push_back(cdom[t].ptrs[i]);
-        }
-        DevBuf d_table = upload(table, st);
-        const uint32_t** dt = d_table.as<const uint32_t*>();
-        for (auto& g : grps) evaluate((const uint32_t* const*)(dt + g.off), (uint32_t* const*)(dt + g.off + g.n), g.n, g.log, g.log + 1, *P.tw, st);
-        CM_HIP(hipStreamSynchronize(st));   // d_table is a temporary
-      }
+      const ColumnSet* const src[3] = {&P.trees[0].coeffs, &P.trees[1].coeffs, &P.trees[2].coeffs};
+      eval_domain_copies(cdom, src, *P.tw, st);
     }
     auto cdom_cols = [&](int t, size_t first) -> const uint32_t* const* {
       return (const uint32_t* const*)(cfg.log_blowup_factor > 1 ? cdom[t].dev(first) : P.trees[t].lde.dev(first));
@@ -935,11 +821,7 @@ struct SegmentProver {
       if (slot_words)
         for (auto& g : sgroups)
           for (uint32_t k = 0; k < 4 * g.n; k++) slot_tab[g.tab0 + k] = slots.u32() + g.off_words + ((size_t)k << g.el);
-      {
-        void* const zp[3] = {acc_top.buf.p, acc_rest.buf.p ? acc_rest.buf.p : acc_top.buf.p, slots.p};
-        const size_t zb[3] = {acc_top.buf.bytes & ~(size_t)15, acc_rest.buf.p ? (acc_rest.buf.bytes & ~(size_t)15) : 0, (slot_words * 4 + 15) & ~(size_t)15};
-        zero_ranges(zp, zb, st);
-      }
+      acc.zero(slots.p, slot_words, st);
       // ONE device table for the phase: [acc_top pointers | acc_rest pointers | slot table | small-component arguments | their ids];
       // its address is known before the arguments (which point into it) are built
       const size_t o_top = 0, o_rest = 64, o_slot = (o_rest + acc_rest.ptrs.size() * sizeof(void*) + 15) & ~(size_t)15;
@@ -958,21 +840,12 @@ struct SegmentProver {
       uint32_t small_max_log = 0;
       for (auto it = cgroups.rbegin(); it != cgroups.rend(); ++it) {
         for (int c : it->second) {
-          const air::ComponentInfo& info = air::component_info(c);
           ConstraintArgs& a = cargs[c];
           a.tr = cdom_cols(1, tr0[c]);
           a.it = cdom_cols(2, it0[c]);
           a.pp = cdom_cols(0, 0);
-          a.rels = drel.as<DevRelations>();
-          a.coeff = d_powers.u32() + 4 * coff[c];
-          a.acc = slot_of[c] >= 0 ? d_slot_tab + 4 * slot_of[c] : accs.at(it->first).dev();
-          a.log_size = clog[c];
-          a.n_base = info.n_base_constraints;
-          (pf.claimed_sums[c] * inv(M31::from_u32(1u << clog[c]))).to_u32(a.cumsum_shift);
-          for (uint32_t k = 0; k < 2; k++) {
-            CPoint<M31> p = point_at_index(domain_index_at(clog[c] + 1, k));
-            a.denom_inv[k] = inv(coset_vanishing_canonic<M31>(clog[c], p)).v;
-          }
+          a.acc = slot_of[c] >= 0 ? d_slot_tab + 4 * slot_of[c] : acc.of(it->first);
+          fill_constraint_args(a, c, clog[c], pf.claimed_sums[c], drel.as<DevRelations>(), d_powers.u32() + 4 * coff[c]);
           // a small component either owns a private slot or is alone in its size group: no accumulator is shared inside the batch
           if (clog[c] <= SMALL_COMPONENT_MAX_LOG && !no_small_batch() && (slot_of[c] >= 0 || it->second.size() == 1)) {
             small_args.push_back(a);
@@ -998,8 +871,7 @@ struct SegmentProver {
       // host replays both steps on its own channel when root 3 comes back (oods_sampling) and checks the coefficients agree.
       {
         uint32_t cw[9];
-        memcpy(cw, ch.digest.data(), 32);
-        cw[8] = ch.n_sent;
+        channel_words(ch, cw);
         d_step2.alloc(4 * (16 + 4 + 8));
         uint32_t* d_chan = d_step2.u32();
         chan_init_mix_root_draw(cw, d_chan, P.trees[2].merkle.layers[0].u32(), d_chan + 16, d_chan + 20, st);
@@ -1025,12 +897,8 @@ struct SegmentProver {
       ht.mark("constraints: small batch launched");
       int gi = 0, small_rr = 0;
       static const bool early_interp = getenv("CM_NO_EARLY_ACC_INTERP") == nullptr;   // A/B switch
-      // A WIDE component of few rows (poseidon2: 443 columns, 426 constraints on 2^10 evaluation rows) is one long program per row
-      // on four blocks: ~0.33 ms of pure latency.  In size order it was enqueued last and ran ALONE behind the large kernels
-      // (round-5 timeline: 5570 -> 5905 us of a region that the large groups had left at ~5720).  Launched first it hides under
-      // them.  "cons_wide_first" = 0: the plain size order (A/B).
-      const bool wide_first = tune(T_CONS_WIDE_FIRST) != 0;
-      auto is_wide = [&](int c) { return wide_first && air::component_info(c).n_trace >= 128 && clog[c] <= 14; };
+      // the wide component of few rows first (round-5 timeline: 5570 -> 5905 us of a region that the large groups had left at ~5720)
+      auto is_wide = [&](int c) { return is_wide_component(c, clog); };
       std::vector<hipStream_t> cstream(air::N_COMPONENTS, nullptr);
       for (auto it = cgroups.rbegin(); it != cgroups.rend(); ++it, ++gi)
         for (int c : it->second) {
@@ -1051,43 +919,29 @@ struct SegmentProver {
         // DomainEvaluationAccumulator::finalize starts here for such a group: its accumulator is interpolated on the same
         // stream right behind its constraint kernels — no second fork/join region for the large accumulators
         if (one_stream && early_interp) {
-          interpolate(accs.at(it->first).dev(), 4, it->first, *P.tw, fk.stream(gi == 0 ? Fork::main_or(cplan[0]) : cplan[gi % 4]));
-          acc_interpolated.insert(it->first);
+          interpolate(acc.of(it->first), 4, it->first, *P.tw, fk.stream(gi == 0 ? Fork::main_or(cplan[0]) : cplan[gi % 4]));
+          acc.interpolated.insert(it->first);
         }
         ht.mark("constraints: size group launched");
       }
       fk.join();
       kreg.close();
-      for (auto& g : sgroups) sum_slots(accs.at(g.el).dev(), slots.u32() + g.off_words, g.n, g.el, st);
+      for (auto& g : sgroups) sum_slots(acc.of(g.el), slots.u32() + g.off_words, g.n, g.el, st);
     }
     P.tick("constraints");
-    // DomainEvaluationAccumulator::finalize.  Stwo walks the sizes upward: interpolate(vals_l + evaluate_l(cur)).
-    // Interpolation is linear and interpolate_l(evaluate_l(cur)) is cur zero-padded (coefficient bases nest),
-    // so the same coefficients come from interpolating every accumulator at its OWN size (independent, on side
-    // streams) and adding the zero-padded coefficient vectors — field arithmetic is exact, the result is
-    // bit-identical, and the extend/add chain over the large domains disappears.
+    // DomainEvaluationAccumulator::finalize (constraint_plan.hpp)
     {
       CommittedTree& t = P.trees[3];
-      if (acc_interpolated.empty()) {
+      if (acc.interpolated.empty()) {   // nothing interpolated inside the region (CM_NO_EARLY_ACC_INTERP): every size on a side stream of its own
         Fork fk(st);
         int k = 0;
-        for (auto it = accs.rbegin(); it != accs.rend(); ++it, ++k) interpolate(it->second.dev(), 4, it->first, *P.tw, fk.stream(k));
+        for (auto it = cgroups.rbegin(); it != cgroups.rend(); ++it, ++k) {
+          interpolate(acc.of(it->first), 4, it->first, *P.tw, fk.stream(k));
+          acc.interpolated.insert(it->first);
+        }
         fk.join();
-      } else {   // what is left are the slotted / batched small sizes: a handful of single-launch transforms, in a row
-        for (auto it = accs.rbegin(); it != accs.rend(); ++it)
-          if (!acc_interpolated.count(it->first)) interpolate(it->second.dev(), 4, it->first, *P.tw, st);
       }
-      {
-        AddColumnsSrc as;
-        as.n = 0;
-        for (auto& kv : accs)
-          if (kv.first != comp_log) {
-            CM_CHECK(as.n < 28, "composition: too many accumulator sizes");
-            as.log[as.n] = kv.first;
-            as.src[as.n++] = (const uint32_t* const*)kv.second.dev();
-          }
-        add_columns_multi(acc_top.dev(), as, 4, st);
-      }
+      finalize_accumulators(acc, *P.tw, st);
       t.coeffs = std::move(acc_top);
       oods_prepare();   // needs tree 3's coefficient pointers, nothing of its commitment
       KProfAloneScope kprof_alone_scope;   // (measurement only: the composition tree has the GPU to itself, kprof.hpp)
@@ -2022,16 +1876,8 @@ int32_t cm_constraints_accumulate(int32_t c, const cm_handle* trace_lde, const c
     stage_upload(drel.p, relations, sizeof(DevRelations), st);
     ConstraintArgs a;
     a.tr = (const uint32_t* const*)d_tr; a.it = (const uint32_t* const*)d_it; a.pp = (const uint32_t* const*)d_pp;
-    a.rels = drel.as<DevRelations>();
-    a.coeff = d_coeff;
     a.acc = d_acc;
-    a.log_size = log_size;
-    a.n_base = info.n_base_constraints;
-    (QM31::from_u32(claimed_sum) * inv(M31::from_u32(1u << log_size))).to_u32(a.cumsum_shift);
-    for (uint32_t k = 0; k < 2; k++) {
-      CPoint<M31> pt = point_at_index(domain_index_at(log_size + 1, k));
-      a.denom_inv[k] = inv(coset_vanishing_canonic<M31>(log_size, pt)).v;
-    }
+    fill_constraint_args(a, c, log_size, QM31::from_u32(claimed_sum), drel.as<DevRelations>(), d_coeff);
     launch_constraints(c, a, st);
     CM_HIP(hipStreamSynchronize(st));
   });

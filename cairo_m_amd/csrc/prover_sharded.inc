@@ -490,19 +490,16 @@ static uint32_t shard_fri_stop_log() { return (uint32_t)tune(T_SHARD_FRI_STOP_LO
 // is a member, declared in the order in which it is made: members die in reverse order, and that order is behaviour (every Fork
 // dies before `P`; see the guards).  The private methods named like the old lambdas (commit_own, sums_arrive, check_halo,
 // fri_replay, check_flags) are where a later phase finishes an earlier phase's wait.
-struct ShardedProver {
+struct ShardedProver : ProofContext {
   HostTrace hm{"[shard]", 44, "CM_SHARD_MARKS"};   // host time between the marks of one sharded proof (development aid)
-  const DeviceInput& din; const cm_prover_input& in;
-  const cm_pcs_config cfg; const cm_comm& comm_c;
-  std::unique_ptr<ProofData> out; ProofData& pf;
+  const cm_comm& comm_c;
   AffinityScope cpu_scope;   // restored when the proof returns (pool.hip)
   Prover P;
   hipStream_t st; Channel& ch; ShardComm cm;
   const uint32_t N, R, B;                    // ranks, this rank, log_blowup_factor
-  uint32_t logN = 0, clog[air::N_COMPONENTS], max_log = 0, comp_log = 0;
+  uint32_t logN = 0;
   ShardPlan plan;
   const std::vector<int>&tr_owner, &it_owner;   // plan.tr_owner / plan.it_owner
-  std::vector<int> by_size;   // launch order of the fork regions: components by descending size (stable), as in the single-GPU prover
   bool tree_stream = false;   // "shard_tree_stream", see setup()
   // the device words of the tree_stream transcript steps (d_ts) ...
   enum : uint32_t { TS_CHAN = 0, TS_COEFF = 16, TS_ROOT2_LOG = 20, TS_ROOT1 = 32, TS_SUB1 = 40, TS_STEP1 = 104, TS_ROOT2 = 120, TS_SUB2 = 128,
@@ -519,12 +516,12 @@ struct ShardedProver {
   std::unique_ptr<Fork> tw_fork; hipStream_t s0 = nullptr;   // twiddles, constant columns, tree 0's transforms (setup .. trace_commit)
   // An exception between a fork and its join must not hand the buffers declared in FRONT of these guards (own_tw, P.trees[0]) back
   // to the pool under the side stream's kernels: the guards are declared behind them, so they drain first.
-  struct DrainOnExit { hipStream_t s = nullptr; bool joined = false; ~DrainOnExit() { if (s && !joined) (void)hipStreamSynchronize(s); } } s0_guard;
+  DrainOnExit s0_guard;
   std::unique_ptr<Fork> pp_fork; DrainOnExit pp_guard;   // tree_stream: tree 0's chain (IFFT, LDE, subtree) forks behind the trace kernels
   // ---- trace_commit ----
   SlicedTree sl0, sl1, sl2, sl3; SlicedLater sl0_later; ColumnSet pp_evals;
-  std::vector<size_t> tr0, it0, ltr0, lit0;   // first column of every component: trees 1 / 2, global and among this rank's own
-  std::vector<uint32_t> tr_logs, it_logs, ltr_logs, lit_logs;
+  std::vector<size_t> ltr0, lit0;   // first column of every component among this rank's own columns of trees 1 / 2 (global: tr0 / it0)
+  std::vector<uint32_t> ltr_logs, lit_logs;
   std::vector<int> ltr_of, lit_of;      // global column -> index among this rank's own columns (-1: somebody else's)
   // split components: this rank's ROW slice of every trace / interaction column (trace domain, plain row order: row r = bundle r)
   struct SplitComp { int c; uint32_t slog; ColumnSet tr_slice, it_slice, cum_lde, cum_prev; };
@@ -533,7 +530,7 @@ struct ShardedProver {
   static constexpr size_t HW = ((size_t)1 << 8) + ((size_t)1 << 16) + ((size_t)1 << 20) + ((size_t)1 << 18);
   DevBuf hist, hist_sum, flag;   // (kept until the proof returns, as ever: the pool then hands later phases the same blocks)
   CommittedTree own1, own2;       // coefficients + full LDE of the OWN columns of trees 1 and 2
-  HostRelations hrel; DevBuf drel;
+  DevBuf drel;
   // ---- interaction ----
   std::vector<int> my_comps; DevBuf d_sums;   // components whose cumulative-sum columns (and claimed sum) this rank computes
   std::vector<DevBuf> tail_scratch;     // scratch of the LogUp tail when it runs on a side stream: alive until the host has seen the sums
@@ -542,10 +539,8 @@ struct ShardedProver {
   bool sums_gathered = false, halo_pending = false;
   hipEvent_t ev_sums = nullptr, ev_root3 = nullptr, ev_fri_back = nullptr;
   ColumnSet it_evals;
-  std::vector<size_t> coff;             // first constraint of every component
-  std::vector<QM31> powers; DevBuf d_powers;
+  DevBuf d_powers;                      // `powers` on the device
   // ---- oods_sampling / deep_quotients ----
-  CPoint<QM31> oods;
   size_t n_cols_t[4] = {0, 0, 0, 0};
   DevBuf d_oods_out, d_oods_table, d_oods_tmp;   // (kept until the proof returns, like hist)
   std::vector<uint32_t> q_logs; std::vector<ColumnSet> quotients;
@@ -563,16 +558,12 @@ struct ShardedProver {
   std::vector<SlicedTree*> fri_order; const uint32_t *rs_d_chan = nullptr, *rs_d_alpha_c = nullptr;
   ColumnSet full_layer;   // the hand-over layer, whole, on every rank
   ShardedProver(const DeviceInput& din_, const cm_pcs_config& cfg_, const cm_comm& comm_)
-      : din(din_), in(din_.meta), cfg(cfg_), comm_c(comm_), out(new ProofData()), pf(*out), st(nullptr), ch(P.ch),
+      : ProofContext(din_, cfg_), comm_c(comm_), st(nullptr), ch(P.ch),
         cm{&comm_, nullptr, comm_.world, comm_.rank, 0}, N(comm_.world), R(comm_.rank), B(cfg_.log_blowup_factor),
         tr_owner(plan.tr_owner), it_owner(plan.it_owner) {
-    pf.config = cfg;
-    bind_thread_to_library_device();
     release_thread_parked();   // a single-GPU proof of this thread may have parked its FRI phase and quotient columns (prover.hip)
-    if (g_transcript_log.load()) P.ch.log.p = &pf.transcript;
-    P.cfg = cfg;
-    st = cm.st = P.st = thread_main_stream();
-    P.start();
+    start(P);
+    st = cm.st = P.st;
   }
   ProofData* run() {
     setup();
@@ -583,12 +574,7 @@ struct ShardedProver {
     deep_quotients();
     fri_and_pow();
     decommit();
-    P.finish();
-    fork_join_check();
-    pf.phase_ms = P.phase_ms;
-    P.report_memory(pf, device_input_bytes(din));
-    pf.steps = 0;
-    for (int i = 0; i < CM_N_OPCODE_COMPONENTS; i++) pf.steps += in.n_bundles[i];
+    finish_common(P);
     return out.release();
   }
 
@@ -609,13 +595,9 @@ struct ShardedProver {
     // polynomials on the (log + 1) domain separately, as Stwo and the single-GPU prover do — and components stay whole (the
     // row-range constraints of a split component read the committed LDE slices the exchange leaves on every rank).
     CM_CHECK(B >= 1 && B <= 4, "PcsConfig: log_blowup_factor must be in 1..4");
-    component_logs(in, clog);
-    for (int c = 0; c < air::N_COMPONENTS; c++) { max_log = std::max(max_log, clog[c]); CM_CHECK(clog[c] <= 26, "component too large"); }
-    check_pcs_config(cfg, max_log);
-    comp_log = max_log + 1;
+    size_components();
+    column_offsets();
     plan = make_shard_plan(clog, N, /*allow_split=*/B == 1);
-    for (int c = 0; c < air::N_COMPONENTS; c++) by_size.push_back(c);
-    std::stable_sort(by_size.begin(), by_size.end(), [&](int x, int y) { return clog[x] > clog[y]; });
     // (round 6) "shard_tree_stream": the commitment trees' transcript steps stay ON THE STREAM like the sharded FRI layers' — behind a
     // tree's sub-root all-gather k_shard_top hashes the top log2 N levels on the device and the single-GPU prover's transcript kernels
     // take the root from there: k_step_pow_relations behind tree 1 (mix_root, interaction proof of work, Relations::draw -> the LogUp
@@ -675,21 +657,18 @@ struct ShardedProver {
     }
     P.tick("preprocessed");
 
-    // ---- column bookkeeping of trees 1 and 2: global order, owner of every column, local (own) column sets ----
-    tr0.assign(air::N_COMPONENTS, 0); it0.assign(air::N_COMPONENTS, 0); ltr0.assign(air::N_COMPONENTS, 0); lit0.assign(air::N_COMPONENTS, 0);
+    // ---- column bookkeeping of trees 1 and 2: owner of every column (global order: column_offsets), local (own) column sets ----
+    ltr0.assign(air::N_COMPONENTS, 0); lit0.assign(air::N_COMPONENTS, 0);
     for (int c = 0; c < air::N_COMPONENTS; c++) {
-      tr0[c] = tr_logs.size(); it0[c] = it_logs.size();
       ltr0[c] = ltr_logs.size(); lit0[c] = lit_logs.size();   // (meaningful for whole components of this rank: their columns are consecutive)
       for (int k = 0; k < air::component_info(c).n_trace; k++) {
-        const bool own = (uint32_t)tr_owner[tr_logs.size()] == R;
+        const bool own = (uint32_t)tr_owner[tr0[c] + k] == R;
         ltr_of.push_back(own ? (int)ltr_logs.size() : -1);
-        tr_logs.push_back(clog[c]);
         if (own) ltr_logs.push_back(clog[c]);
       }
       for (int k = 0; k < air::component_info(c).n_interaction; k++) {
-        const bool own = (uint32_t)it_owner[it_logs.size()] == R;
+        const bool own = (uint32_t)it_owner[it0[c] + k] == R;
         lit_of.push_back(own ? (int)lit_logs.size() : -1);
-        it_logs.push_back(clog[c]);
         if (own) lit_logs.push_back(clog[c]);
       }
     }
@@ -714,7 +693,7 @@ struct ShardedProver {
         Fork fk(st);   // (round 5) whole components: trace + histogram in one launch each, on side streams (histogram adds commute)
         if (!small_trace.empty()) launch_trace_hist_small(d_small_trace.as<SmallTraceJob>(), (uint32_t)small_trace.size(), din.data_accesses.p, h, fk.stream(Fork::N - 2));
         int spos = 0;
-        for (int c : by_size) {   // large components first: the largest on the main stream
+        for (int c : by_size_all) {   // large components first: the largest on the main stream
           if (c >= air::N_OPCODE_COMPONENTS || !mine(c) || clog[c] <= SMALL_COMPONENT_MAX_LOG) continue;
           launch_opcode_trace_hist(c, din.bundles[c].p, (uint32_t)in.n_bundles[c], din.data_accesses.p, clog[c], tr_evals.dev(ltr0[c]), h,
                                    fk.stream(spos == 0 ? Fork::main_or(0) : spos % (Fork::N - 2)));
@@ -810,13 +789,12 @@ struct ShardedProver {
       complete_sliced(cm, sl0, sl0_later);   // root 0 arrives behind tree 1's transforms; the GPU is busy with tree 1's subtree
       P.trees[0].root = sl0.root;
       ch.mix_root(sl0.root);
-      for (int c = 0; c < air::N_COMPONENTS; c++) { pf.claim_log_sizes.push_back(clog[c]); ch.mix_u64(clog[c]); }
+      mix_claim(ch, pf, clog);
       // root 1 -> interaction proof of work -> relation challenges, all behind the all-gather (prover.hip trace_commit)
       static_assert(sizeof(DevRelations) == 4 * 4 * (air::N_RELATIONS + air::N_RELATIONS * air::MAX_REL_SIZE), "DevRelations layout");
       shard_top(comm_c.recv_buf, N, ts + TS_ROOT1, ts + TS_SUB1, st);
       uint32_t cw[9];
-      memcpy(cw, ch.digest.data(), 32);
-      cw[8] = ch.n_sent;
+      channel_words(ch, cw);
       step_pow_relations(cw, ts + TS_ROOT1, INTERACTION_POW_BITS, air::N_RELATIONS, air::MAX_REL_SIZE, drel.u32(), drel.u32() + 4 * air::N_RELATIONS,
                          ts + TS_STEP1, st);
       CM_HIP(hipMemcpyAsync(pin_sub1, ts + TS_SUB1, 8 * N * 4, hipMemcpyDeviceToHost, st));
@@ -825,7 +803,7 @@ struct ShardedProver {
     } else {
       commit_own(own1, &tr_evals, false, false, tr_logs, tr_owner, sl1);
       // transcript order (prover.rs:70-82): root 0 (mixed above), claim, root 1
-      for (int c = 0; c < air::N_COMPONENTS; c++) { pf.claim_log_sizes.push_back(clog[c]); ch.mix_u64(clog[c]); }
+      mix_claim(ch, pf, clog);
       ch.mix_root(sl1.root);
       P.tick("trace_commit");
 
@@ -885,7 +863,7 @@ struct ShardedProver {
         jobs[k].log_size = clog[c];
       }
       int spos = 0;
-      for (int c : by_size) {
+      for (int c : by_size_all) {
         if (plan.cum_owner(c) != (int)R || split(c) || clog[c] <= SMALL_COMPONENT_MAX_LOG) continue;   // (split: generated above, by rows)
         launch_logup(c, (const uint32_t* const*)tr_evals.dev(ltr0[c]), (const uint32_t* const*)pp_evals.dev(), clog[c], drel.as<DevRelations>(),
                      it_evals.dev(lit0[c]), fk.stream(small_jobs.empty() && spos == 0 ? Fork::MAIN : 1 + spos % 2));
@@ -1075,10 +1053,7 @@ struct ShardedProver {
     }
     if (!tree_stream) sums_arrive();
     P.tick("interaction_gen");
-    size_t total_constraints = 0;
-    coff.assign(air::N_COMPONENTS, 0);
-    for (int c = 0; c < air::N_COMPONENTS; c++) { coff[c] = total_constraints; total_constraints += air::component_info(c).n_constraints; }
-    powers.resize(total_constraints);
+    const size_t total_constraints = powers.size();
     d_powers.alloc(16 * total_constraints);
     {
       own2.coeffs = std::move(it_evals);   // interpolated in place, every size group right in front of its extension
@@ -1089,8 +1064,7 @@ struct ShardedProver {
         // without the host having seen the root
         shard_top(comm_c.recv_buf, N, ts + TS_ROOT2, ts + TS_SUB2, st);
         uint32_t cw[9];
-        memcpy(cw, ch.digest.data(), 32);
-        cw[8] = ch.n_sent;
+        channel_words(ch, cw);
         chan_init_mix_root_draw(cw, ts + TS_CHAN, ts + TS_ROOT2, ts + TS_COEFF, ts + TS_ROOT2_LOG, st);
         coeff_powers(ts + TS_COEFF, d_powers.u32(), (uint32_t)total_constraints, st);
         static_assert(PIN_COEFF + 4 == PIN_ROOT2 && TS_COEFF + 4 == TS_ROOT2_LOG, "{coefficient, root 2} come back in one copy");
@@ -1109,44 +1083,18 @@ struct ShardedProver {
   }
   // constraints of the own components -> acc_top: the composition polynomial's coefficients, partial sums reduced across the ranks
   void constraint_quotients(ColumnSet& acc_top) {
-    std::map<uint32_t, std::vector<int>> cgroups;   // evaluation log -> own components
-    for (int c = 0; c < air::N_COMPONENTS; c++) if (mine(c) || split(c)) cgroups[clog[c] + 1].push_back(c);   // split: every rank, its rows
     std::vector<DevBuf> split_tabs;   // column tables of the split components (alive until the launches are enqueued and drained)
     // B > 1: the own polynomials of trees 0..2 on their (log + 1) evaluation domains
     ColumnSet cdom[3];
     if (B > 1) {
-      ColumnSet* src[3] = {&P.trees[0].coeffs, &own1.coeffs, &own2.coeffs};
-      for (int t = 0; t < 3; t++) {
-        std::vector<uint32_t> logs(src[t]->logs);
-        for (auto& l : logs) l += 1;
-        cdom[t].alloc(logs, st);
-        std::vector<const uint32_t*> table;
-        struct Grp { uint32_t log, n; size_t off; };
-        std::vector<Grp> grps;
-        for (auto& kv : by_log(src[t]->logs)) {
-          grps.push_back(Grp{kv.first, (uint32_t)kv.second.size(), table.size()});
-          for (auto i : kv.second) table.push_back(src[t]->ptrs[i]);
-          for (auto i : kv.second) table.push_back(cdom[t].ptrs[i]);
-        }
-        DevBuf d_table = upload(table, st);
-        const uint32_t** dt = d_table.as<const uint32_t*>();
-        for (auto& g : grps) evaluate((const uint32_t* const*)(dt + g.off), (uint32_t* const*)(dt + g.off + g.n), g.n, g.log, g.log + 1, *P.tw, st);
-        // (d_table is a temporary: pool blocks are reused in stream order, no host synchronisation)
-      }
+      const ColumnSet* const src[3] = {&P.trees[0].coeffs, &own1.coeffs, &own2.coeffs};
+      eval_domain_copies(cdom, src, *P.tw, st);
     }
-    acc_top.alloc(std::vector<uint32_t>(4, comp_log), st, true, /* contiguous: exchanged as one block */ true);
-    // (round 6) every smaller size shares ONE column set — one pointer-table upload — and the three buffers the phase clears
-    // (acc_top, acc_rest, the slots) are zeroed by one launch: it used to be an upload + a memset per size, ~20 packets of ~5 us in a
-    // row on the main stream behind the interaction tree
-    ColumnSet acc_rest;
-    std::map<uint32_t, size_t> acc_at;   // evaluation log -> first of its four columns in acc_rest
-    {
-      std::vector<uint32_t> rest_logs;
-      for (auto& kv : cgroups)
-        if (kv.first != comp_log) { acc_at[kv.first] = rest_logs.size(); rest_logs.insert(rest_logs.end(), 4, kv.first); }
-      if (!rest_logs.empty()) acc_rest.alloc(rest_logs, st);
-    }
-    auto acc_of = [&](uint32_t el) -> uint32_t* const* { return el == comp_log ? acc_top.dev() : acc_rest.dev(acc_at.at(el)); };
+    // the accumulators of every evaluation log with own components (constraint_plan.hpp); split components: every rank, its rows
+    ConstraintAccumulators acc;
+    acc.plan(clog, comp_log, [this](int c) { return mine(c) || split(c); });
+    acc.alloc(st, /*upload_ptrs=*/true, /*top_contiguous: exchanged as one block*/ true);
+    const std::map<uint32_t, std::vector<int>>& cgroups = acc.cgroups;
     // small components (idle ones are 16 padding rows: pure launch latency): private accumulator slots, ONE batched launch,
     // slots summed afterwards — as in the single-GPU prover
     std::vector<ConstraintArgs> small_args;
@@ -1164,11 +1112,7 @@ struct ShardedProver {
     }
     DevBuf slots(((slot_words * 4 + 15) & ~(size_t)15) + 16);
     std::vector<uint32_t*> slot_tab;
-    {
-      void* const zp[3] = {acc_top.buf.p, acc_rest.buf.p ? acc_rest.buf.p : acc_top.buf.p, slots.p};
-      const size_t zb[3] = {acc_top.buf.bytes & ~(size_t)15, acc_rest.buf.p ? (acc_rest.buf.bytes & ~(size_t)15) : 0, (slot_words * 4 + 15) & ~(size_t)15};
-      zero_ranges(zp, zb, st);
-    }
+    acc.zero(slots.p, slot_words, st);
     std::map<int, size_t> slot_tab_at;
     for (auto& kv : slot_off) {
       slot_tab_at[kv.first] = slot_tab.size();
@@ -1204,22 +1148,13 @@ struct ShardedProver {
           a.it = (const uint32_t* const*)(B > 1 ? cdom[2].dev(lit0[c]) : own2.lde.dev(lit0[c]));
         }
         a.pp = (const uint32_t* const*)(B > 1 ? cdom[0].dev() : P.trees[0].lde.dev());
-        a.rels = drel.as<DevRelations>();
-        a.coeff = d_powers.u32() + 4 * coff[c];
         const bool small = slot_off.count(c) != 0;
-        a.acc = small ? d_slot_tab.as<uint32_t*>() + slot_tab_at[c] : acc_of(it->first);
-        a.log_size = clog[c];
-        a.n_base = info.n_base_constraints;
-        (pf.claimed_sums[c] * inv(M31::from_u32(1u << clog[c]))).to_u32(a.cumsum_shift);
-        for (uint32_t k = 0; k < 2; k++) {
-          CPoint<M31> p = point_at_index(domain_index_at(clog[c] + 1, k));
-          a.denom_inv[k] = inv(coset_vanishing_canonic<M31>(clog[c], p)).v;
-        }
+        a.acc = small ? d_slot_tab.as<uint32_t*>() + slot_tab_at[c] : acc.of(it->first);
+        fill_constraint_args(a, c, clog[c], pf.claimed_sums[c], drel.as<DevRelations>(), d_powers.u32() + 4 * coff[c]);
         if (small) { small_args.push_back(a); small_cids.push_back(c); small_max_log = std::max(small_max_log, clog[c]); }
         else big_jobs.push_back({c, a});
       }
     DevBuf d_small_args = upload(small_args, st), d_small_cids = upload(small_cids, st);
-    std::set<uint32_t> acc_interpolated;
     {
       // (round 6) one fork region like the single-GPU prover's (prover.hip composition): the batched small components first on a side
       // stream (latency-bound, hidden under the large kernels), a WIDE component of few rows (poseidon2: one long program per row on
@@ -1235,7 +1170,7 @@ struct ShardedProver {
         const uint32_t el = clog[j.first] + 1;
         if (!group_stream.count(el)) { const int gi = (int)group_stream.size(); group_stream[el] = gi == 0 ? Fork::MAIN : gi % 4; }
       }
-      auto is_wide = [&](int c) { return tune(T_CONS_WIDE_FIRST) != 0 && air::component_info(c).n_trace >= 128 && clog[c] <= 14; };
+      auto is_wide = [&](int c) { return is_wide_component(c, clog); };
       for (auto& j : big_jobs) if (is_wide(j.first)) launch_constraints(j.first, j.second, fk.stream(group_stream.at(clog[j.first] + 1)));
       for (auto& gs_ : group_stream) {
         const uint32_t el = gs_.first;
@@ -1243,40 +1178,30 @@ struct ShardedProver {
         bool has_small = false;
         for (auto& g : sgroups) has_small = has_small || g.el == el;
         if (!has_small) {
-          interpolate(acc_of(el), 4, el, *P.tw, fk.stream(gs_.second));
-          acc_interpolated.insert(el);
+          interpolate(acc.of(el), 4, el, *P.tw, fk.stream(gs_.second));
+          acc.interpolated.insert(el);
         }
       }
       fk.join();
     }
     if (!small_args.empty()) {
-      for (auto& g : sgroups) sum_slots(acc_of(g.el), slots.u32() + g.off_words, g.n, g.el, st);
+      for (auto& g : sgroups) sum_slots(acc.of(g.el), slots.u32() + g.off_words, g.n, g.el, st);
     }
     P.tick("constraints");
     // interpolate every partial accumulator at its own size and add the zero-padded coefficient vectors (linear: the
     // partial sums of all ranks add up to the coefficients the single-GPU prover computes); ONE launch adds all of them
-    if (!acc_interpolated.count(comp_log)) interpolate(acc_top.dev(), 4, comp_log, *P.tw, st);
-    {
-      AddColumnsSrc as;
-      as.n = 0;
-      for (auto& kv : acc_at) {
-        if (!acc_interpolated.count(kv.first)) interpolate(acc_of(kv.first), 4, kv.first, *P.tw, st);
-        CM_CHECK(as.n < 28, "composition: too many accumulator sizes");
-        as.log[as.n] = kv.first;
-        as.src[as.n++] = (const uint32_t* const*)acc_of(kv.first);
-      }
-      if (as.n) add_columns_multi(acc_top.dev(), as, 4, st);
-    }
+    finalize_accumulators(acc, *P.tw, st);
     // reduce across ranks: slices of the (4 x 2^comp_log)-word buffer go to their owner, are summed mod P, and come back
     if (N > 1) {   // (a lone rank's coefficients are the sum: two 64 MB copies and two collectives less)
       const uint64_t W = (uint64_t)4 << comp_log, sl = W / N;
       cm.need(W);
-      CM_HIP(hipMemcpyAsync(comm_c.send_buf, acc_top.buf.p, W * 4, hipMemcpyDeviceToDevice, st));
+      CM_HIP(hipMemcpyAsync(comm_c.send_buf, acc.top.buf.p, W * 4, hipMemcpyDeviceToDevice, st));
       cm.all_to_all_v(std::vector<uint64_t>(N, sl), std::vector<uint64_t>(N, sl));
       sum_copies(comm_c.recv_buf, N, sl, sl, comm_c.send_buf, true, st);
       cm.all_gather(sl);
-      CM_HIP(hipMemcpyAsync(acc_top.buf.p, comm_c.recv_buf, W * 4, hipMemcpyDeviceToDevice, st));
+      CM_HIP(hipMemcpyAsync(acc.top.buf.p, comm_c.recv_buf, W * 4, hipMemcpyDeviceToDevice, st));
     }
+    acc_top = std::move(acc.top);
   }
   // composition polynomial + tree 3 (prover.rs:114-120)
   void composition() {
@@ -1533,8 +1458,7 @@ struct ShardedProver {
       d_chan = d_fs.u32();
       d_slots = d_chan + 16;
       uint32_t cw[16] = {0};
-      memcpy(cw, ch.digest.data(), 32);
-      cw[8] = ch.n_sent;
+      channel_words(ch, cw);
       stage_upload(d_chan, cw, sizeof(cw), st);
     }
     alpha_c = tree_step(fri_first);
