@@ -17,8 +17,13 @@
 #include "../../include/cairom_hip.h"
 #include "engine.hpp"
 #include "host_adapter.hpp"
+#include "proof.hpp"
 #include <hipcub/hipcub.hpp>
 #include <stdlib.h>
+#include <stdio.h>
+#include <chrono>
+#include <memory>
+#include <mutex>
 
 namespace cm {
 
@@ -255,62 +260,88 @@ __global__ void k_tree_advance(TreeState* stt, const uint32_t* __restrict__ firs
   stt->node_off += parents;
   stt->n = parents;
 }
+// Everything one tree build holds until its stream has been waited for.  a = the leaves (index, value, multiplicity; `cap`
+// entries allocated, the live count is TreeState::n in `state`), b = the other half of the level ping-pong.
+struct TreeJob {
+  DevBuf a[3], b[3], first, ppos, state, tmp;
+  DevBuf* root_src = nullptr;   // the value array that holds the root after the last level
+};
+// Device-pointer form: the leaves already sit in job.a and job.state holds {live leaves, 0}.  Enqueues every level and the copies of
+// the final TreeState and of the root into pin3[0..2] (pinned words); waits for nothing.
+void partial_merkle_tree_enqueue(TreeJob& j, uint32_t cap, DevBuf& nodes_out, uint32_t* pin3, hipStream_t st) {
+  CM_CHECK(cap > 0, "partial merkle tree: no leaves");
+  const std::vector<uint32_t>& dflt = host::poseidon2_default_hashes();
+  for (int k = 0; k < 3; k++) j.b[k].alloc((size_t)cap * 4);
+  j.first.alloc((size_t)cap * 4); j.ppos.alloc((size_t)cap * 4);
+  // every level has at most as many nodes as the one below: cap * TREE_HEIGHT bounds the total
+  nodes_out.alloc((size_t)cap * air::TREE_HEIGHT * sizeof(cm_merkle_node));
+  DevBuf* cur[3] = {&j.a[0], &j.a[1], &j.a[2]};
+  DevBuf* nxt[3] = {&j.b[0], &j.b[1], &j.b[2]};
+  size_t tmp_bytes = 0;
+  CM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, j.first.u32(), j.ppos.u32(), (int)cap, st));
+  j.tmp.alloc(tmp_bytes ? tmp_bytes : 4);
+  for (uint32_t depth = air::TREE_HEIGHT; depth >= 1; depth--) {
+    hipLaunchKernelGGL(k_tree_flags, grid1(cap), dim3(256), 0, st, cur[0]->u32(), j.state.as<TreeState>(), cap, j.first.u32());
+    CM_HIP(hipcub::DeviceScan::ExclusiveSum(j.tmp.p, tmp_bytes, j.first.u32(), j.ppos.u32(), (int)cap, st));
+    hipLaunchKernelGGL(k_tree_level, grid1(cap), dim3(256), 0, st, cur[0]->u32(), cur[1]->u32(), cur[2]->u32(), j.first.u32(), j.ppos.u32(),
+                       j.state.as<TreeState>(), cap, depth, dflt[depth], nodes_out.as<cm_merkle_node>(), nxt[0]->u32(), nxt[1]->u32(), nxt[2]->u32());
+    hipLaunchKernelGGL(k_tree_advance, dim3(1), dim3(64), 0, st, j.state.as<TreeState>(), j.first.u32(), j.ppos.u32());
+    for (int k = 0; k < 3; k++) std::swap(cur[k], nxt[k]);
+  }
+  j.root_src = cur[1];
+  CM_HIP(hipMemcpyAsync(pin3, j.state.p, sizeof(TreeState), hipMemcpyDeviceToHost, st));
+  CM_HIP(hipMemcpyAsync(pin3 + 2, j.root_src->p, 4, hipMemcpyDeviceToHost, st));
+  CM_HIP(hipGetLastError());
+}
 // leaves: (address << 2 | i, value_i, mult) sorted by address; returns the root; nodes + count stay on the device
 uint32_t build_partial_merkle_tree_device(const std::vector<uint32_t>& idx_h, const std::vector<uint32_t>& val_h,
                                           const std::vector<uint32_t>& mult_h, DevBuf& nodes_out, uint64_t& n_nodes, hipStream_t st) {
   const uint32_t cap = (uint32_t)idx_h.size();
   CM_CHECK(cap > 0, "partial merkle tree: no leaves");
-  const std::vector<uint32_t>& dflt = host::poseidon2_default_hashes();
-  DevBuf a_idx = upload(idx_h, st), a_val = upload(val_h, st), a_mult = upload(mult_h, st);
-  DevBuf b_idx((size_t)cap * 4), b_val((size_t)cap * 4), b_mult((size_t)cap * 4), d_first((size_t)cap * 4), d_ppos((size_t)cap * 4), d_st(sizeof(TreeState));
-  // every level has at most as many nodes as the one below: cap * TREE_HEIGHT bounds the total
-  nodes_out.alloc((size_t)cap * air::TREE_HEIGHT * sizeof(cm_merkle_node));
+  TreeJob j;
+  j.a[0] = upload(idx_h, st); j.a[1] = upload(val_h, st); j.a[2] = upload(mult_h, st);
+  j.state.alloc(sizeof(TreeState));
   TreeState s0{cap, 0};
-  stage_upload(d_st.p, &s0, sizeof(s0), st);
-  DevBuf* cur[3] = {&a_idx, &a_val, &a_mult};
-  DevBuf* nxt[3] = {&b_idx, &b_val, &b_mult};
-  size_t tmp_bytes = 0;
-  CM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_first.u32(), d_ppos.u32(), (int)cap, st));
-  DevBuf tmp(tmp_bytes ? tmp_bytes : 4);
-  for (uint32_t depth = air::TREE_HEIGHT; depth >= 1; depth--) {
-    hipLaunchKernelGGL(k_tree_flags, grid1(cap), dim3(256), 0, st, cur[0]->u32(), d_st.as<TreeState>(), cap, d_first.u32());
-    CM_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, tmp_bytes, d_first.u32(), d_ppos.u32(), (int)cap, st));
-    hipLaunchKernelGGL(k_tree_level, grid1(cap), dim3(256), 0, st, cur[0]->u32(), cur[1]->u32(), cur[2]->u32(), d_first.u32(), d_ppos.u32(),
-                       d_st.as<TreeState>(), cap, depth, dflt[depth], nodes_out.as<cm_merkle_node>(), nxt[0]->u32(), nxt[1]->u32(), nxt[2]->u32());
-    hipLaunchKernelGGL(k_tree_advance, dim3(1), dim3(64), 0, st, d_st.as<TreeState>(), d_first.u32(), d_ppos.u32());
-    for (int k = 0; k < 3; k++) std::swap(cur[k], nxt[k]);
-  }
-  TreeState fin;
-  uint32_t root = 0;
-  CM_HIP(hipMemcpyAsync(&fin, d_st.p, sizeof(fin), hipMemcpyDeviceToHost, st));
-  CM_HIP(hipMemcpyAsync(&root, cur[1]->p, 4, hipMemcpyDeviceToHost, st));
-  CM_HIP(hipGetLastError());
+  stage_upload(j.state.p, &s0, sizeof(s0), st);
+  uint32_t* const pin3 = pinned_words() + PIN_LAST_LAYER + 56;
+  partial_merkle_tree_enqueue(j, cap, nodes_out, pin3, st);
   CM_HIP(hipStreamSynchronize(st));
-  CM_CHECK(fin.n == 1, "partial merkle tree: did not converge to one root");
-  n_nodes = fin.node_off;
-  return root;
+  CM_CHECK(pin3[0] == 1, "partial merkle tree: did not converge to one root");
+  n_nodes = pin3[1];
+  return pin3[2];
 }
 
-
 }  // namespace
+}  // namespace cm
+#include "adapter_run.inc"   // the device tail of a run (cm_run): struct Run, RunTailIn, run_tail()
+namespace cm {
 
-// host tail shared with the host adapter: boundary memory rows, public multiplicities, partial Merkle trees
-DeviceInput* adapt_segment_device(const cm_runner_segment& seg) {
+// One segment through the adapter.  run == null: the memory at segment start comes from `seg` and the tail (step 5) finishes on
+// the host, shared with the host adapter: boundary memory rows, public multiplicities, partial Merkle trees.  run != null: the
+// memory is the run's device-resident image (seg.initial_* are ignored) and the tail stays on the device (adapter_run.inc).
+static DeviceInput* adapt_impl(const cm_runner_segment& seg, Run* run, uint64_t n_memory_end, uint64_t n_heap_end) {
   bind_thread_to_library_device();
   hipStream_t st = thread_main_stream();
   CM_CHECK(seg.n_trace >= 2, "adapter: empty trace");
-  const uint32_t n_steps = (uint32_t)(seg.n_trace - 1), n_mem = (uint32_t)seg.n_memory_trace, n_init = (uint32_t)seg.n_initial_memory;
+  const uint32_t n_steps = (uint32_t)(seg.n_trace - 1), n_mem = (uint32_t)seg.n_memory_trace;
+  const uint32_t n_init = run ? run->n_lo : (uint32_t)seg.n_initial_memory;
   CM_CHECK(seg.n_memory_trace < (1ull << 32) && seg.n_trace < (1ull << 32), "adapter: segment too large");
   CM_CHECK(seg.n_memory_trace >= 1, "adapter: empty memory trace");
   // ---- upload the runner output ----
-  const uint32_t n_heap = (uint32_t)seg.n_initial_heap;
-  CM_CHECK(seg.n_initial_memory + seg.n_initial_heap <= (uint64_t)host::MAX_ADDRESS + 1, "adapter: locals and heap overlap");
-  DevBuf d_trace(seg.n_trace * 8), d_mem((size_t)n_mem * 20 + 4), d_init((size_t)n_init * 16 + 4), d_heap((size_t)n_heap * 16 + 4), d_err(8);
+  const uint32_t n_heap = run ? run->n_hi : (uint32_t)seg.n_initial_heap;
+  CM_CHECK((uint64_t)n_init + n_heap <= (uint64_t)host::MAX_ADDRESS + 1 && (run || seg.n_initial_memory + seg.n_initial_heap <= (uint64_t)host::MAX_ADDRESS + 1),
+           "adapter: locals and heap overlap");
+  DevBuf d_trace(seg.n_trace * 8), d_mem((size_t)n_mem * 20 + 4), d_init, d_heap, d_err(8);
   CM_HIP(hipMemcpyAsync(d_trace.p, seg.trace, seg.n_trace * 8, hipMemcpyHostToDevice, st));
   if (n_mem) CM_HIP(hipMemcpyAsync(d_mem.p, seg.memory_trace, (size_t)n_mem * 20, hipMemcpyHostToDevice, st));
-  if (n_init) CM_HIP(hipMemcpyAsync(d_init.p, seg.initial_memory, (size_t)n_init * 16, hipMemcpyHostToDevice, st));
-  if (n_heap) CM_HIP(hipMemcpyAsync(d_heap.p, seg.initial_heap, (size_t)n_heap * 16, hipMemcpyHostToDevice, st));
-  const InitMem init{d_init.u32(), n_init, d_heap.u32(), n_heap};
+  if (!run) {
+    d_init.alloc((size_t)n_init * 16 + 4); d_heap.alloc((size_t)n_heap * 16 + 4);
+    if (n_init) CM_HIP(hipMemcpyAsync(d_init.p, seg.initial_memory, (size_t)n_init * 16, hipMemcpyHostToDevice, st));
+    if (n_heap) CM_HIP(hipMemcpyAsync(d_heap.p, seg.initial_heap, (size_t)n_heap * 16, hipMemcpyHostToDevice, st));
+  } else {
+    run->wait_on(st);   // the previous segment's advance may have been enqueued from another thread's stream
+  }
+  const InitMem init = run ? InitMem{run->lo.u32(), n_init, run->hi.u32(), n_heap} : InitMem{d_init.u32(), n_init, d_heap.u32(), n_heap};
   OpTable tab;
   memset(&tab, 0, sizeof(tab));
   for (uint32_t op = 0; op < 64; op++) {
@@ -323,7 +354,7 @@ DeviceInput* adapt_segment_device(const cm_runner_segment& seg) {
   // ---- 1. per-step counts and offsets (one 64-bit scan: log entries | operand accesses) ----
   CM_HIP(hipMemsetAsync(d_err.p, 0, 8, st));
   DevBuf d_info((size_t)n_steps * 4 + 4), d_off((size_t)n_steps * 8 + 8);
-  hipLaunchKernelGGL(k_step_counts, grid1(n_steps), dim3(256), 0, st, d_trace.u32(), n_steps, d_init.u32(), n_init, tab, d_info.u32(),
+  hipLaunchKernelGGL(k_step_counts, grid1(n_steps), dim3(256), 0, st, d_trace.u32(), n_steps, init.lo, n_init, tab, d_info.u32(),
                      d_off.as<unsigned long long>(), d_err.u32());
   // (the last step's own counts are needed for the totals: keep them before the in-place scan)
   uint32_t* const pin = pinned_words() + PIN_LAST_LAYER;   // no proof runs on this thread while it adapts a segment
@@ -397,14 +428,14 @@ DeviceInput* adapt_segment_device(const cm_runner_segment& seg) {
   }
   DevBuf bundles[CM_N_OPCODE_COMPONENTS];
   BundleDst dst;
-  uint32_t run = 0;
+  uint32_t row0 = 0;
   for (int c = 0; c < CM_N_OPCODE_COMPONENTS; c++) {
     bundles[c].alloc(counts[c] * sizeof(cm_bundle) + 4);
     dst.p[c] = bundles[c].as<cm_bundle>();
-    dst.start[c] = run;
-    run += (uint32_t)counts[c];
+    dst.start[c] = row0;
+    row0 += (uint32_t)counts[c];
   }
-  dst.start[CM_N_OPCODE_COMPONENTS] = run;
+  dst.start[CM_N_OPCODE_COMPONENTS] = row0;
   DevBuf d_acc((size_t)n_acc * sizeof(cm_data_access) + 4);
   hipLaunchKernelGGL(k_step_pos, grid1(n_steps), dim3(256), 0, st, d_steps_sorted.u32(), n_steps, d_steps.u32());   // (the iota is spent)
   hipLaunchKernelGGL(k_bundles, grid1(n_steps), dim3(256), 0, st, d_steps.u32(), n_steps, d_trace.u32(), d_info.u32(),
@@ -413,10 +444,17 @@ DeviceInput* adapt_segment_device(const cm_runner_segment& seg) {
   DevBuf d_cells((size_t)n_cells * sizeof(CellRec) + 16);
   hipLaunchKernelGGL(k_cells, grid1(n_mem), dim3(256), 0, st, d_saddr.u32(), d_se.u32(), n_mem, d_head.u32(), d_hrank.u32(), d_eclk.u32(),
                      d_cells.as<CellRec>());
+  if (run) {
+    RunTailIn t{seg, n_steps, n_mem, n_cells, n_acc, n_cu, counts, bundles, d_acc, d_cu, d_mem, d_cells, n_memory_end, n_heap_end};
+    return run_tail(*run, t, st);
+  }
   std::vector<CellRec> cells(n_cells);
   CM_HIP(hipMemcpyAsync(cells.data(), d_cells.p, (size_t)n_cells * sizeof(CellRec), hipMemcpyDeviceToHost, st));
   CM_HIP(hipGetLastError());
   CM_HIP(hipStreamSynchronize(st));
+  // CM_ADAPTER_TAIL_LOG=1: the host time of this tail, one line per segment on stderr (tools/run_report.py)
+  static const bool tail_log = getenv("CM_ADAPTER_TAIL_LOG") != nullptr;
+  const auto tail_t0 = std::chrono::steady_clock::now();
   std::map<uint32_t, host::MemState> initial_memory, final_memory;
   for (uint32_t a = 0; a < n_init; a++) {
     host::MemState s{{seg.initial_memory[4 * (size_t)a], seg.initial_memory[4 * (size_t)a + 1], seg.initial_memory[4 * (size_t)a + 2],
@@ -462,7 +500,20 @@ DeviceInput* adapt_segment_device(const cm_runner_segment& seg) {
   meta.data_accesses = nullptr; meta.n_data_accesses = n_acc;
   meta.clock_updates = nullptr; meta.n_clock_updates = n_cu;
   if (device_trees) { meta.n_initial_tree = n_init_tree; meta.n_final_tree = n_fin_tree; }
-  return make_device_input(meta, bundles, d_acc, d_cu, device_trees ? &init_tree_dev : nullptr, device_trees ? &fin_tree_dev : nullptr);
+  DeviceInput* din = make_device_input(meta, bundles, d_acc, d_cu, device_trees ? &init_tree_dev : nullptr, device_trees ? &fin_tree_dev : nullptr);
+  if (tail_log)
+    fprintf(stderr, "cm_adapter_tail_host_ms %.3f rows %zu\n",
+            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tail_t0).count(), initial_memory.size());
+  return din;
+}
+DeviceInput* adapt_segment_device(const cm_runner_segment& seg) { return adapt_impl(seg, nullptr, 0, 0); }
+DeviceInput* run_adapt_next(Run& run, const cm_run_segment& rs) {
+  run_check_ends(run, rs.n_memory_end, rs.n_heap_end);
+  cm_runner_segment seg;
+  memset(&seg, 0, sizeof(seg));
+  seg.trace = rs.trace; seg.n_trace = rs.n_trace; seg.memory_trace = rs.memory_trace; seg.n_memory_trace = rs.n_memory_trace;
+  for (int i = 0; i < 2; i++) { seg.program_range[i] = run.ranges[i]; seg.input_range[i] = run.ranges[2 + i]; seg.output_range[i] = run.ranges[4 + i]; }
+  return adapt_impl(seg, &run, rs.n_memory_end, rs.n_heap_end);
 }
 
 }  // namespace cm

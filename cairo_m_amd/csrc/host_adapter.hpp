@@ -103,6 +103,7 @@ struct Segment {
   std::vector<MemEntry> memory_trace;
   std::vector<Cell> initial_memory;            // dense: address i -> cell (the locals: program, frames)
   std::vector<Cell> initial_heap;              // dense from the top: index i -> cell at MAX_ADDRESS - i (runner/src/vm/mod.rs:205-221)
+  size_t end_memory = 0, end_heap = 0;         // lengths of the VM's two vectors when the segment ended
 };
 constexpr uint32_t MAX_ADDRESS = (1u << 28) - 1;   // crates/common/src/lib.rs MAX_ADDRESS: the heap grows downwards from here
 
@@ -265,6 +266,7 @@ inline std::vector<Segment> run_program(const std::vector<std::vector<uint32_t>>
     s.memory_trace.swap(vm.log);
     s.initial_memory = initial;
     s.initial_heap = initial_heap;
+    s.end_memory = vm.mem.size(); s.end_heap = vm.heap.size();
     bool done = vm.pc == vm.final_pc;
     segs.push_back(std::move(s));
     if (done) break;

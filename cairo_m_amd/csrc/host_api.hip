@@ -93,6 +93,11 @@ int32_t cm_synth_fibonacci_segment(uint32_t n, uint64_t max_steps, uint32_t segm
   return build_segment(cm::host::fibonacci_loop_program(), 0, {n}, 1, max_steps, segment_index, out, nullptr);
 }
 const cm_runner_segment* cm_host_segment_view(const cm_host_segment* h) { return &h->view; }
+int32_t cm_host_segment_end_lengths(const cm_host_segment* h, uint64_t* n_memory_end, uint64_t* n_heap_end) {
+  if (!h || !n_memory_end || !n_heap_end) return cm_set_last_error("cm_host_segment_end_lengths: null argument");
+  *n_memory_end = h->seg.end_memory; *n_heap_end = h->seg.end_heap;
+  return 0;
+}
 int32_t cm_host_segment_free(cm_host_segment* h) { delete h; return 0; }
 // ---- runner artifacts (wire formats of the reference) ---------------------------------------
 // trace file: per state `fp` then `pc`, little-endian u32 (crates/common/src/execution.rs:28-40; reader
@@ -133,6 +138,7 @@ int32_t cm_segment_from_artifacts(const uint8_t* trace, uint64_t trace_len, cons
   for (uint64_t i = 0; i < trace_len / 8; i++) { h->trace.push_back(get_le32(trace + 8 * i + 4)); h->trace.push_back(get_le32(trace + 8 * i)); }
   for (uint64_t i = 0; i < (mem_len - hdr) / 4; i++) h->mem.push_back(get_le32(mem + hdr + 4 * i));
   h->init.assign(initial_memory, initial_memory + 4 * n_initial_memory);
+  h->seg.end_memory = n_initial_memory;
   cm_runner_segment& v = h->view;
   v.trace = h->trace.data(); v.n_trace = trace_len / 8;
   v.memory_trace = h->mem.data(); v.n_memory_trace = (mem_len - hdr) / 20;
@@ -150,6 +156,7 @@ int32_t cm_host_segment_set_initial_heap(cm_host_segment* h, const uint32_t* ini
   if (n_initial_heap + h->view.n_initial_memory > (uint64_t)cm::host::MAX_ADDRESS + 1) return cm_set_last_error("cm_host_segment_set_initial_heap: locals and heap overlap");
   h->heap.assign(initial_heap, initial_heap + 4 * n_initial_heap);
   h->view.initial_heap = h->heap.data(); h->view.n_initial_heap = n_initial_heap;
+  h->seg.end_heap = n_initial_heap;
   return 0;
 }
 const cm_prover_input* cm_host_input_view(const cm_host_input* h) { return &h->view; }

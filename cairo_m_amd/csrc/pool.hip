@@ -72,6 +72,7 @@ struct Pool {
     void* p = nullptr;
     hipError_t e = hipMalloc(&p, want);
     if (e != hipSuccess) {
+      (void)hipGetLastError();   // (the failed attempt must not stay behind as the thread's last error: the retry may succeed)
       release_thread_parked();   // a previous proof's deferred teardown (prover.hip) goes back to the pool first ...
       trim();                    // ... and the pool back to the driver
       e = hipMalloc(&p, want);

@@ -31,7 +31,10 @@ namespace cm {
 
 // (log_size_for, DeviceInput: segment_input.hpp)
 
-static PublicData make_public_data(const cm_prover_input& in) {  // PublicData::new (public_data.rs:244-272)
+// PublicData::new (public_data.rs:244-272) in two halves: the registers, clock and roots from the input's scalars, and the entries
+// of the three public ranges — from the host rows (make_public_data) or gathered on the device by a run's adapter
+// (public_data_from_entries)
+static PublicData public_data_scalars(const cm_prover_input& in) {
   PublicData d;
   d.initial_pc = in.initial_pc; d.initial_fp = in.initial_fp; d.final_pc = in.final_pc; d.final_fp = in.final_fp;
   uint64_t steps = 0;
@@ -40,6 +43,27 @@ static PublicData make_public_data(const cm_prover_input& in) {  // PublicData::
   d.initial_root = in.initial_root; d.final_root = in.final_root;
   for (uint32_t w : {d.initial_pc, d.initial_fp, d.final_pc, d.final_fp, d.initial_root, d.final_root})
     CM_CHECK(w < P, "ProverInput: a public register / root word is not a canonical M31");
+  return d;
+}
+static void check_public_entry(const PublicEntry& e) {
+  CM_CHECK(e.addr < P && e.clock < P && e.value[0] < P && e.value[1] < P && e.value[2] < P && e.value[3] < P,
+           "ProverInput: a public memory entry is not made of canonical M31 words");
+}
+// entries = program, input, output laid end to end, one per address of each range (present = 0 where the boundary memory has no cell)
+static PublicData public_data_from_entries(const cm_prover_input& in, const PublicEntry* entries) {
+  PublicData d = public_data_scalars(in);
+  const PublicEntry* e = entries;
+  auto take = [&](std::vector<PublicEntry>& v, const uint32_t range[2]) {
+    const uint32_t n = range[1] > range[0] ? range[1] - range[0] : 0u;
+    v.assign(e, e + n);
+    for (const PublicEntry& x : v) if (x.present) check_public_entry(x);
+    e += n;
+  };
+  take(d.program, in.program_range); take(d.input, in.input_range); take(d.output, in.output_range);
+  return d;
+}
+static PublicData make_public_data(const cm_prover_input& in) {
+  PublicData d = public_data_scalars(in);
   std::map<uint32_t, const cm_memory_cell*> init, fin;
   for (uint64_t i = 0; i < in.n_initial_memory; i++) init[in.initial_memory[i].address] = &in.initial_memory[i];
   for (uint64_t i = 0; i < in.n_final_memory; i++) fin[in.final_memory[i].address] = &in.final_memory[i];
@@ -50,8 +74,7 @@ static PublicData make_public_data(const cm_prover_input& in) {  // PublicData::
       auto it = m.find(a);
       if (it != m.end()) {
         e.present = 1; e.addr = a; for (int k = 0; k < 4; k++) e.value[k] = it->second->value[k]; e.clock = it->second->clock;
-        CM_CHECK(a < P && e.clock < P && e.value[0] < P && e.value[1] < P && e.value[2] < P && e.value[3] < P,
-                 "ProverInput: a public memory entry is not made of canonical M31 words");
+        check_public_entry(e);
       }
       v.push_back(e);
     }
@@ -118,7 +141,30 @@ DeviceInput* make_device_input(const cm_prover_input& meta, DevBuf (&bundles)[CM
   CM_HIP(hipDeviceSynchronize());   // NULL-stream copies above; the prover's streams are non-blocking
   return d;
 }
+// a run's adapter (adapter_run.inc): every array already lives in the calling thread's pool and its stream has been waited for;
+// no copy, no wait here
+DeviceInput* make_device_input_resident(const cm_prover_input& meta, DevBuf (&bundles)[CM_N_OPCODE_COMPONENTS], DevBuf& data_accesses, DevBuf& clock_updates,
+                                        DevBuf& init_mem, DevBuf& fin_mem, DevBuf& init_tree, DevBuf& fin_tree, const PublicEntry* entries) {
+  std::unique_ptr<DeviceInput> d(new DeviceInput());
+  d->meta = meta;   // (every pointer of it is null)
+  d->public_data = public_data_from_entries(meta, entries);
+  for (int i = 0; i < CM_N_OPCODE_COMPONENTS; i++) d->bundles[i] = std::move(bundles[i]);
+  d->data_accesses = std::move(data_accesses);
+  d->clock_updates = std::move(clock_updates);
+  d->init_mem = std::move(init_mem); d->fin_mem = std::move(fin_mem);
+  d->init_tree = std::move(init_tree); d->fin_tree = std::move(fin_tree);
+  return d.release();
+}
 DeviceInput* adapt_segment_device(const cm_runner_segment& seg);  // adapter_device.hip
+// the run object (adapter_run.inc)
+struct Run;
+Run* run_begin(const uint32_t* initial_memory, uint64_t n_initial_memory, const uint32_t* initial_heap, uint64_t n_initial_heap, const uint32_t ranges[6]);
+DeviceInput* run_adapt_next(Run& run, const cm_run_segment& seg);
+void run_memory(Run& r, uint32_t* locals, uint64_t cap_l, uint64_t* n_l, uint32_t* heap, uint64_t cap_h, uint64_t* n_h);
+uint64_t run_image_bytes(const Run& r);
+uint64_t run_rows_bound(const Run& r, uint64_t n_memory_trace);
+std::mutex& run_mutex(Run& r);
+void run_free(Run* r);
 // copy a device-resident input back to the host (tests)
 void download_input(const DeviceInput& d, host::ProverInputOwned& o) {
   CM_HIP(hipDeviceSynchronize());
@@ -1737,6 +1783,99 @@ int32_t cm_prove_many_segments(const cm_runner_segment* const* segments, uint32_
     return cm::ItemBytes{g.n_trace * sizeof(cm_bundle) + g.n_memory_trace * (sizeof(cm_data_access) + sizeof(cm_clock_update)) +
                              2 * cells * sizeof(cm_memory_cell), 0};
   }, config, inflight, outs, /*n_producers=*/2);
+}
+// ---- a whole run (header revision 10): memory carried on the device, chained segment proofs --------------------------------
+struct cm_run { cm::Run* r = nullptr; ~cm_run() { cm::run_free(r); } };
+int32_t cm_run_begin(const uint32_t* initial_memory, uint64_t n_initial_memory, const uint32_t* initial_heap, uint64_t n_initial_heap,
+                     const uint32_t ranges[6], cm_run** out) {
+  return pguard([&] {
+    CM_CHECK(out, "cm_run_begin: null output");
+    std::unique_ptr<cm_run> h(new cm_run());
+    h->r = cm::run_begin(initial_memory, n_initial_memory, initial_heap, n_initial_heap, ranges);
+    *out = h.release();
+  });
+}
+static void check_run_segment(const cm_run_segment* seg, const char* who) {
+  CM_CHECK(seg, (std::string(who) + ": null segment").c_str());
+  CM_CHECK(seg->trace && seg->memory_trace, (std::string(who) + ": null trace or memory trace").c_str());
+}
+int32_t cm_run_adapt_next(cm_run* r, const cm_run_segment* seg, cm_device_input** out) {
+  return pguard([&] {
+    CM_CHECK(r && r->r && out, "cm_run_adapt_next: null argument");
+    check_run_segment(seg, "cm_run_adapt_next");
+    std::lock_guard<std::mutex> lk(cm::run_mutex(*r->r));
+    std::unique_ptr<cm_device_input> h(new cm_device_input());
+    h->d = cm::run_adapt_next(*r->r, *seg);
+    *out = h.release();
+  });
+}
+int32_t cm_run_memory(const cm_run* r, uint32_t* locals, uint64_t cap_l, uint64_t* n_l, uint32_t* heap, uint64_t cap_h, uint64_t* n_h) {
+  return pguard([&] {
+    CM_CHECK(r && r->r, "cm_run_memory: null run");
+    std::lock_guard<std::mutex> lk(cm::run_mutex(*r->r));
+    cm::run_memory(*r->r, locals, cap_l, n_l, heap, cap_h, n_h);
+  });
+}
+int32_t cm_run_free(cm_run* r) { delete r; return 0; }
+int32_t cm_prove_run(cm_run* r, const cm_run_segment* const* segs, uint32_t n, const cm_pcs_config* config, uint32_t inflight, cm_proof** outs) {
+  if (!r || !r->r || (n && (!segs || !outs))) return cm_set_last_error("cm_prove_run: null argument");
+  // the image is serial: ONE producer (the calling thread) adapts the segments in order, the workers prove behind it
+  std::lock_guard<std::mutex> lk(cm::run_mutex(*r->r));
+  return prove_streamed(n, [&](uint32_t i) {
+    check_run_segment(segs[i], "cm_prove_run");
+    return cm::run_adapt_next(*r->r, *segs[i]);
+  }, [&](uint32_t i, const cm_pcs_config&, bool& known) {
+    check_run_segment(segs[i], "cm_prove_run");
+    known = false;   // as for cm_prove_many_segments: the component sizes exist once the adapter has run
+    const cm_run_segment& g = *segs[i];
+    const uint64_t cells = cm::run_rows_bound(*r->r, g.n_memory_trace);   // (the image as it is now: this thread is its only writer)
+    return cm::ItemBytes{g.n_trace * sizeof(cm_bundle) + g.n_memory_trace * (sizeof(cm_data_access) + sizeof(cm_clock_update)) +
+                             2 * cells * sizeof(cm_memory_cell), 0};
+  }, config, inflight, outs, /*n_producers=*/1);
+}
+int32_t cm_proof_public_data(const cm_proof* p, cm_public_data* out) {
+  return pguard([&] {
+    CM_CHECK(p && p->d && out, "cm_proof_public_data: null argument");
+    CM_CHECK(out->struct_size >= sizeof(cm_public_data), "cm_proof_public_data: struct_size does not cover cm_public_data (set it to sizeof(cm_public_data))");
+    const cm::PublicData& d = p->d->public_data;
+    cm_public_data o;
+    memset(&o, 0, sizeof(o));
+    o.struct_size = sizeof(o);
+    o.initial_pc = d.initial_pc; o.initial_fp = d.initial_fp; o.final_pc = d.final_pc; o.final_fp = d.final_fp; o.clock = d.clock;
+    o.initial_root = d.initial_root; o.final_root = d.final_root;
+    o.n_program = (uint32_t)d.program.size(); o.n_input = (uint32_t)d.input.size(); o.n_output = (uint32_t)d.output.size();
+    memcpy(out, &o, sizeof(o));
+  });
+}
+int32_t cm_proof_public_entries(const cm_proof* p, uint32_t which, uint32_t* out, uint64_t cap_entries, uint64_t* n_entries) {
+  return pguard([&] {
+    CM_CHECK(p && p->d && n_entries && which <= 2, "cm_proof_public_entries: null argument, or `which` is not 0 (program), 1 (input) or 2 (output)");
+    const cm::PublicData& d = p->d->public_data;
+    const std::vector<cm::PublicEntry>& v = which == 0 ? d.program : which == 1 ? d.input : d.output;
+    *n_entries = v.size();
+    if (!out) return;
+    CM_CHECK(cap_entries >= v.size(), "cm_proof_public_entries: the output array is too small (the count is reported)");
+    static_assert(sizeof(cm::PublicEntry) == 28, "seven words per public entry");
+    if (!v.empty()) memcpy(out, v.data(), v.size() * sizeof(cm::PublicEntry));
+  });
+}
+// host code: every proof verifies, and each segment starts where its predecessor stopped (crates/prover/tests/prover.rs:198-243;
+// the registers are the execution boundary of public_data.rs:192-227)
+int32_t cm_verify_run(const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected) {
+  return pguard([&] {
+    CM_CHECK(n >= 1 && proofs, "cm_verify_run: no proofs");
+    for (uint32_t i = 0; i < n; i++) {
+      CM_CHECK(proofs[i] && proofs[i]->d, "cm_verify_run: null proof");
+      const std::string e = cm::verify_proof(*proofs[i]->d, expected ? *expected : default_cfg());
+      if (!e.empty()) throw cm::CmError(11, "run: segment " + std::to_string(i) + ": verification failed: " + e);
+    }
+    for (uint32_t i = 1; i < n; i++) {
+      const cm::PublicData &a = proofs[i - 1]->d->public_data, &b = proofs[i]->d->public_data;
+      const char* field = b.initial_pc != a.final_pc ? "pc" : b.initial_fp != a.final_fp ? "fp" : b.initial_root != a.final_root ? "root" : nullptr;
+      if (field)
+        throw cm::CmError(11, "run: segment " + std::to_string(i) + " initial_" + field + " != segment " + std::to_string(i - 1) + " final_" + field);
+    }
+  });
 }
 // ---- per-component AIR ops (include/cairom_hip.h): the kernels of the whole-segment prover, one component
 // at a time on caller-owned columns --------------------------------------------------------------------------------

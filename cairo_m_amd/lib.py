@@ -281,6 +281,27 @@ class Proof:
         self.L.cm_last_error(buf, C.c_size_t(512))
         return rc, buf.value.decode(errors="replace") if rc else ""
 
+    def public_data(self):
+        """cm_proof_public_data + cm_proof_public_entries (revision 10): the registers, clock and memory roots the proof is about,
+        and the public entries of the three ranges as (n, 7) arrays of (present, address, value[4], clock)."""
+        d = PublicDataC()
+        d.struct_size = C.sizeof(PublicDataC)
+        rc = self.L.cm_proof_public_data(self.h, C.byref(d))
+        if rc:
+            raise _lib_error(self.L, rc)
+        out = {n: getattr(d, n) for n in ("initial_pc", "initial_fp", "final_pc", "final_fp", "clock", "initial_root", "final_root")}
+        for which, name in enumerate(("program", "input", "output")):
+            n = C.c_uint64(0)
+            rc = self.L.cm_proof_public_entries(self.h, C.c_uint32(which), None, C.c_uint64(0), C.byref(n))
+            if rc:
+                raise _lib_error(self.L, rc)
+            a = np.zeros((n.value, 7), dtype=np.uint32)
+            rc = self.L.cm_proof_public_entries(self.h, C.c_uint32(which), _p(a), C.c_uint64(n.value), C.byref(n))
+            if rc:
+                raise _lib_error(self.L, rc)
+            out[name] = a
+        return out
+
     def transcript(self):
         """cm_proof_transcript: the Fiat-Shamir steps of this proof (list of {"op", "digest", "n_words", "words"}); empty
         unless set_transcript_log(True) was in force when it was made."""
@@ -595,6 +616,125 @@ def _backend_mem_info(self):
 
 
 Backend.mem_info = _backend_mem_info
+
+
+# ---- a whole run (include/cairom_hip.h, revision 10): memory carried on the device, chained segment proofs ------
+class PublicDataC(C.Structure):
+    """cm_public_data"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_uint32),
+                ("initial_pc", C.c_uint32), ("initial_fp", C.c_uint32), ("final_pc", C.c_uint32), ("final_fp", C.c_uint32),
+                ("clock", C.c_uint32), ("initial_root", C.c_uint32), ("final_root", C.c_uint32),
+                ("n_program", C.c_uint32), ("n_input", C.c_uint32), ("n_output", C.c_uint32)]
+
+
+class RunSegmentC(C.Structure):
+    """cm_run_segment"""
+    _fields_ = [("trace", C.c_void_p), ("n_trace", C.c_uint64), ("memory_trace", C.c_void_p), ("n_memory_trace", C.c_uint64),
+                ("n_memory_end", C.c_uint64), ("n_heap_end", C.c_uint64)]
+
+
+def segment_end_lengths(host_segment):
+    """cm_host_segment_end_lengths: cells in the synthetic VM's locals / heap vectors when the segment ended."""
+    a, b = C.c_uint64(0), C.c_uint64(0)
+    rc = host_segment.L.cm_host_segment_end_lengths(host_segment.h, C.byref(a), C.byref(b))
+    if rc:
+        raise _lib_error(host_segment.L, rc)
+    return a.value, b.value
+
+
+def run_segment(host_segment, n_memory_end=None, n_heap_end=None):
+    """cm_run_segment over a HostSegment's trace and log (the HostSegment must outlive it); the end lengths default to the
+    synthetic VM's own."""
+    v = C.cast(host_segment.view, C.POINTER(RunnerSegmentView)).contents
+    ends = segment_end_lengths(host_segment)
+    return RunSegmentC(v.trace, v.n_trace, v.memory_trace, v.n_memory_trace,
+                       ends[0] if n_memory_end is None else n_memory_end, ends[1] if n_heap_end is None else n_heap_end)
+
+
+class Run:
+    """cm_run: a program's memory kept on the device from segment to segment."""
+
+    def __init__(self, backend, initial_memory, initial_heap, ranges):
+        self.B, self.L = backend, backend.L
+        lo = np.ascontiguousarray(initial_memory, dtype=np.uint32).reshape(-1, 4)
+        hi = np.ascontiguousarray(initial_heap, dtype=np.uint32).reshape(-1, 4)
+        h = C.c_void_p()
+        backend._ck(self.L.cm_run_begin(_p(lo), C.c_uint64(lo.shape[0]), _p(hi), C.c_uint64(hi.shape[0]),
+                                        (C.c_uint32 * 6)(*[int(x) for x in ranges]), C.byref(h)))
+        self.h = h
+
+    @classmethod
+    def from_segment(cls, backend, host_segment):
+        """the run that starts with this segment: its initial memory, heap and ranges"""
+        a = runner_segment_arrays(host_segment.view)
+        return cls(backend, a["initial_memory"], a["initial_heap"], a["ranges"])
+
+    def adapt_next(self, seg):
+        """cm_run_adapt_next: seg = a RunSegmentC (run_segment) or a HostSegment; returns the device input, advances the image."""
+        if not isinstance(seg, RunSegmentC):
+            seg = run_segment(seg)
+        h = C.c_void_p()
+        self.B._ck(self.L.cm_run_adapt_next(self.h, C.byref(seg), C.byref(h)))
+        return h
+
+    def lengths(self):
+        """cm_run_memory without arrays: (cells in the locals, cells in the heap)"""
+        nl, nh = C.c_uint64(0), C.c_uint64(0)
+        self.B._ck(self.L.cm_run_memory(self.h, None, C.c_uint64(0), C.byref(nl), None, C.c_uint64(0), C.byref(nh)))
+        return nl.value, nh.value
+
+    def memory(self):
+        """cm_run_memory: (locals (n, 4), heap (n, 4)); heap index i = the cell at 2^28 - 1 - i"""
+        nl, nh = (C.c_uint64(x) for x in self.lengths())
+        lo, hi = np.zeros((nl.value, 4), dtype=np.uint32), np.zeros((nh.value, 4), dtype=np.uint32)
+        self.B._ck(self.L.cm_run_memory(self.h, _p(lo), C.c_uint64(nl.value), C.byref(nl), _p(hi), C.c_uint64(nh.value), C.byref(nh)))
+        return lo, hi
+
+    def prove(self, segs, inflight=3, cfg=None):
+        """cm_prove_run: the next segments of this run (RunSegmentC or HostSegment each), proved in order of `segs`."""
+        segs = [s if isinstance(s, RunSegmentC) else run_segment(s) for s in segs]
+        n = len(segs)
+        ins = (C.c_void_p * n)(*[C.addressof(s) for s in segs])
+        outs = (C.c_void_p * n)()
+        rc = self.L.cm_prove_run(self.h, ins, C.c_uint32(n), _cfg(cfg), C.c_uint32(inflight), outs)
+        proofs = [Proof(self.L, C.c_void_p(outs[i])) if outs[i] else None for i in range(n)]
+        if rc != 0:
+            try:
+                self.B._ck(rc)
+            except CmError as e:
+                e.partial = proofs
+                raise
+        return proofs
+
+    def free(self):
+        if self.h:
+            self.L.cm_run_free(self.h)
+            self.h = None
+
+
+def prove_run(backend, host_segments, inflight=3, cfg=None):
+    """A whole run from its runner segments: one cm_run from the first segment's memory, every segment through cm_prove_run."""
+    run = Run.from_segment(backend, host_segments[0])
+    try:
+        return run.prove(host_segments, inflight, cfg)
+    finally:
+        run.free()
+
+
+def verify_run(proofs, cfg=None, lib=None):
+    """cm_verify_run (host code): (status, message); 0 = every proof verifies and each starts where its predecessor stopped."""
+    L = lib or proofs[0].L
+    n = len(proofs)
+    hs = (C.c_void_p * n)(*[p.h.value if isinstance(p.h, C.c_void_p) else p.h for p in proofs])
+    rc = L.cm_verify_run(hs, C.c_uint32(n), _cfg(cfg))
+    buf = C.create_string_buffer(1024)
+    L.cm_last_error(buf, C.c_size_t(1024))
+    return rc, buf.value.decode(errors="replace") if rc else ""
+
+
+Backend.run_begin = lambda self, initial_memory, initial_heap, ranges: Run(self, initial_memory, initial_heap, ranges)
+Backend.prove_run = lambda self, host_segments, inflight=3, cfg=None: prove_run(self, host_segments, inflight, cfg)
+Backend.verify_run = lambda self, proofs, cfg=None: verify_run(proofs, cfg, self.L)
 
 
 # ---- device-memory accounting, estimate and budget (include/cairom_hip.h, revision 9) --------------------------

@@ -30,8 +30,10 @@
  * cm_host_segment_set_initial_heap.  7: cm_check_report, cm_check_constraints, cm_constraints_check, cm_relation_sums.
  * 8: cm_relation_entry, cm_track_relations, cm_relation_entries.
  * 9: cm_mem_stats, cm_proof_mem, cm_mem_estimate; cm_mem_stats_get, cm_mem_reset_peak, cm_proof_memory, cm_estimate_memory,
- *    cm_estimate_memory_logs, cm_set_memory_budget. */
-#define CM_ABI_REVISION 9
+ *    cm_estimate_memory_logs, cm_set_memory_budget.
+ * 10: a whole run (additive): cm_run, cm_run_segment, cm_public_data; cm_run_begin, cm_run_adapt_next, cm_run_memory, cm_run_free,
+ *    cm_prove_run, cm_proof_public_data, cm_proof_public_entries, cm_verify_run, cm_host_segment_end_lengths. */
+#define CM_ABI_REVISION 10
 
 #ifdef __cplusplus
 extern "C" {
@@ -516,6 +518,59 @@ int32_t cm_adapt_segment_device(const cm_runner_segment* seg, cm_device_input** 
 /* streaming ingest from runner segments: see cm_prove_many_host */
 int32_t cm_prove_many_segments(const cm_runner_segment* const* segments, uint32_t n, const cm_pcs_config* config, uint32_t inflight,
                                cm_proof** outs);
+/* ---- a whole run (revision 10) ----------------------------------------------------------------------------------------
+ * The reference cuts a run into segments at max_steps and chains them by public data: segment i's final registers and final
+ * memory root are segment i + 1's initial ones (crates/prover/tests/prover.rs:198-243, public_data.rs:192-227).  A cm_run keeps
+ * the program's memory ON THE DEVICE between segments, so a segment brings only its trace and its memory log; the image is
+ * uploaded once (cm_run_begin) and lives in the device pool of the thread that made it (cm_mem_stats counts it).
+ *
+ * cm_run_begin: the memory at the start of the run — locals dense from address 0, heap dense from MAX_ADDRESS downwards (the two
+ * arrays of cm_runner_segment; NULL / 0 for none) — and ranges = program, input, output [start, end).
+ * cm_run_adapt_next: the same cm_device_input cm_adapt_segment_device makes for this segment with this memory at its start; then
+ * the image advances to the memory at the segment's end: each region grows to the given end length (the lengths of the runner's
+ * two vectors when the segment ends), a touched cell inside a region takes its last logged value, an untouched one keeps its
+ * value (zero where the region grew over it), a touched cell outside both regions is a read of an untouched cell and is not
+ * carried.  Status 1, with the run left as it was: an end length below the current one; regions that overlap; a touched cell
+ * outside both regions whose last value is not zero; every input error of cm_adapt_segment_device.
+ * The boundary memory, both partial Merkle trees (from CM_ADAPTER_DEVICE_TREE_MIN rows up, default 2048; below it the rows are
+ * downloaded and hashed on the host), the public entries and the advance are built on the calling thread's stream: no
+ * NULL-stream copy, no device-wide wait; three host round trips with data per segment and one wait behind the tree nodes'
+ * copy or upload.
+ * cm_run_memory: the image as it is now; n_l / n_h always receive the lengths, an array is filled when it is not NULL (status 1
+ * when its capacity, in cells, is too small).  Calls on one run are serialised; they may come from different threads. */
+typedef struct cm_run cm_run;
+typedef struct {
+  const uint32_t* trace;           /* as cm_runner_segment */
+  uint64_t n_trace;
+  const uint32_t* memory_trace;
+  uint64_t n_memory_trace;
+  uint64_t n_memory_end, n_heap_end;   /* cells in the runner's locals / heap vectors when the segment ends */
+} cm_run_segment;
+int32_t cm_run_begin(const uint32_t* initial_memory, uint64_t n_initial_memory, const uint32_t* initial_heap, uint64_t n_initial_heap,
+                     const uint32_t ranges[6], cm_run** out);
+int32_t cm_run_adapt_next(cm_run* r, const cm_run_segment* seg, cm_device_input** out);
+int32_t cm_run_memory(const cm_run* r, uint32_t* locals, uint64_t cap_l, uint64_t* n_l, uint32_t* heap, uint64_t cap_h, uint64_t* n_h);
+int32_t cm_run_free(cm_run* r);
+/* The next n segments of the run, proved: the calling thread adapts them in order (the image is serial) while up to `inflight`
+ * library workers prove.  Error contract, order of outs, memory-budget admission as cm_prove_many_segments; at most inflight + 1
+ * inputs are resident.  A segment that cannot be adapted fails the call, leaves the image at that segment's start and stops the
+ * ingest; the run may be continued by a later cm_prove_run or cm_run_adapt_next. */
+int32_t cm_prove_run(cm_run* r, const cm_run_segment* const* segs, uint32_t n, const cm_pcs_config* config, uint32_t inflight,
+                     cm_proof** outs);
+/* A proof's public data (public_data.rs:192-227).  Set struct_size = sizeof(cm_public_data) before the call. */
+typedef struct {
+  uint32_t struct_size, reserved0;
+  uint32_t initial_pc, initial_fp, final_pc, final_fp, clock, initial_root, final_root;
+  uint32_t n_program, n_input, n_output;   /* public entries: one per address of each range */
+} cm_public_data;
+int32_t cm_proof_public_data(const cm_proof* p, cm_public_data* out);
+/* which: 0 program, 1 input, 2 output.  *n_entries always receives the count; out (NULL = count only) receives seven words per
+ * entry: present, address, value[4], clock (all zero where the boundary memory has no such cell). */
+int32_t cm_proof_public_entries(const cm_proof* p, uint32_t which, uint32_t* out, uint64_t cap_entries, uint64_t* n_entries);
+/* Host code, no GPU: every proof passes cm_verify_proof, and for every i > 0 the initial pc, fp and memory root of proof i equal
+ * the final ones of proof i - 1.  Status 11; the message names the link and the field, e.g.
+ * "run: segment 3 initial_root != segment 2 final_root", or "run: segment 3: verification failed: ...". */
+int32_t cm_verify_run(const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected);
 /* Copy a device-resident ProverInput back (tests: device adapter vs host adapter). */
 int32_t cm_device_input_download(const cm_device_input* in, cm_host_input** out);
 /* The synthetic VM's raw output for one segment (what cm_vm_run feeds to the host adapter). */
@@ -525,6 +580,9 @@ int32_t cm_vm_segment(const uint32_t* instr_words, const uint32_t* instr_lens, u
                       uint32_t segment_index, cm_host_segment** out, uint32_t* n_segments_out);
 int32_t cm_synth_fibonacci_segment(uint32_t n, uint64_t max_steps, uint32_t segment_index, cm_host_segment** out);
 const cm_runner_segment* cm_host_segment_view(const cm_host_segment* h);
+/* (revision 10) cells in the synthetic VM's locals / heap vectors when the segment ended: cm_run_segment.n_memory_end / n_heap_end
+ * (a segment built from artifacts reports its initial lengths) */
+int32_t cm_host_segment_end_lengths(const cm_host_segment* h, uint64_t* n_memory_end, uint64_t* n_heap_end);
 /* Runner artifact wire formats (crates/common/src/execution.rs:28-66, crates/prover/src/adapter/io.rs:38-80):
  * trace = (fp, pc) little-endian u32 pairs; memory trace = [u32 program_length header] + (address, v0..v3)
  * records.  out == NULL only reports *len.  The reference does not serialise the initial memory and the public

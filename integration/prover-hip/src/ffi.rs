@@ -237,6 +237,38 @@ pub const CM_COMM_STREAM_ORDERED: u32 = 1;
 pub struct cm_rccl_comm {
     _private: [u8; 0],
 }
+/// (revision 10) a run: the program's memory kept on the device from segment to segment
+#[repr(C)]
+pub struct cm_run {
+    _private: [u8; 0],
+}
+/// One segment of a run: trace and memory log as in `cm_runner_segment`, plus the lengths of the runner's two memory vectors
+/// when the segment ends
+#[repr(C)]
+pub struct cm_run_segment {
+    pub trace: *const u32,
+    pub n_trace: u64,
+    pub memory_trace: *const u32,
+    pub n_memory_trace: u64,
+    pub n_memory_end: u64,
+    pub n_heap_end: u64,
+}
+/// A proof's public data (public_data.rs:192-227); set `struct_size` before the call
+#[repr(C)]
+pub struct cm_public_data {
+    pub struct_size: u32,
+    pub reserved0: u32,
+    pub initial_pc: u32,
+    pub initial_fp: u32,
+    pub final_pc: u32,
+    pub final_fp: u32,
+    pub clock: u32,
+    pub initial_root: u32,
+    pub final_root: u32,
+    pub n_program: u32,
+    pub n_input: u32,
+    pub n_output: u32,
+}
 
 unsafe extern "C" {
     pub fn cm_init(device: i32) -> i32;
@@ -300,6 +332,15 @@ unsafe extern "C" {
     pub fn cm_prove_many(inputs: *const *const cm_device_input, n: u32, config: *const cm_pcs_config, inflight: u32, outs: *mut *mut cm_proof) -> i32;
     pub fn cm_prove_many_host(inputs: *const *const cm_prover_input, n: u32, config: *const cm_pcs_config, inflight: u32, outs: *mut *mut cm_proof) -> i32;
     pub fn cm_prove_many_segments(segments: *const *const cm_runner_segment, n: u32, config: *const cm_pcs_config, inflight: u32, outs: *mut *mut cm_proof) -> i32;
+    pub fn cm_run_begin(initial_memory: *const u32, n_initial_memory: u64, initial_heap: *const u32, n_initial_heap: u64, ranges: *const u32, out: *mut *mut cm_run) -> i32;
+    pub fn cm_run_adapt_next(r: *mut cm_run, seg: *const cm_run_segment, out: *mut *mut cm_device_input) -> i32;
+    pub fn cm_run_memory(r: *const cm_run, locals: *mut u32, cap_l: u64, n_l: *mut u64, heap: *mut u32, cap_h: u64, n_h: *mut u64) -> i32;
+    pub fn cm_run_free(r: *mut cm_run) -> i32;
+    pub fn cm_prove_run(r: *mut cm_run, segs: *const *const cm_run_segment, n: u32, config: *const cm_pcs_config, inflight: u32, outs: *mut *mut cm_proof) -> i32;
+    pub fn cm_proof_public_data(p: *const cm_proof, out: *mut cm_public_data) -> i32;
+    pub fn cm_proof_public_entries(p: *const cm_proof, which: u32, out: *mut u32, cap_entries: u64, n_entries: *mut u64) -> i32;
+    pub fn cm_verify_run(proofs: *const *const cm_proof, n: u32, expected: *const cm_pcs_config) -> i32;
+    pub fn cm_host_segment_end_lengths(h: *const cm_host_segment, n_memory_end: *mut u64, n_heap_end: *mut u64) -> i32;
     pub fn cm_set_preprocessed_cache(on: i32) -> i32;
     pub fn cm_set_twiddle_cache(on: i32) -> i32;
     pub fn cm_set_device_tail(on: i32) -> i32;

@@ -160,6 +160,69 @@ pub fn prove_segments_hip(
         .collect()
 }
 
+/// One segment of a run in the runner's own terms: `(pc, fp)` pairs, the memory log (five words per access) and the lengths of
+/// the runner's locals / heap vectors when the segment ends.
+pub struct RunSegment<'a> {
+    pub trace: &'a [u32],
+    pub memory_trace: &'a [u32],
+    pub n_memory_end: u64,
+    pub n_heap_end: u64,
+}
+
+/// A whole run (`cm_prove_run`, header revision 10): the memory at the start of the run is uploaded once and carried on the
+/// device; every segment brings only its trace and its log.  `ranges` = program, input, output `[start, end)`.  The proofs come
+/// back in segment order and chain: `cm_verify_run` has checked that each starts where its predecessor stopped.
+pub fn prove_run_hip(
+    initial_memory: &[u32],
+    initial_heap: &[u32],
+    ranges: [u32; 6],
+    segments: &[RunSegment],
+    pcs_config: Option<PcsConfig>,
+    inflight: u32,
+) -> Result<Vec<Proof<Blake2sMerkleHasher>>, ProvingError> {
+    ensure_init();
+    let cfg = pcs(&pcs_config.unwrap_or(REGULAR_96_BITS));
+    let mut run: *mut cm_run = std::ptr::null_mut();
+    let rc = unsafe {
+        cm_run_begin(initial_memory.as_ptr(), (initial_memory.len() / 4) as u64, initial_heap.as_ptr(), (initial_heap.len() / 4) as u64, ranges.as_ptr(), &mut run)
+    };
+    assert!(rc == 0, "cm_run_begin: {}", last_error());
+    let views: Vec<cm_run_segment> = segments
+        .iter()
+        .map(|s| cm_run_segment {
+            trace: s.trace.as_ptr(),
+            n_trace: (s.trace.len() / 2) as u64,
+            memory_trace: s.memory_trace.as_ptr(),
+            n_memory_trace: (s.memory_trace.len() / 5) as u64,
+            n_memory_end: s.n_memory_end,
+            n_heap_end: s.n_heap_end,
+        })
+        .collect();
+    let ptrs: Vec<*const cm_run_segment> = views.iter().map(|v| v as *const cm_run_segment).collect();
+    let mut outs: Vec<*mut cm_proof> = vec![std::ptr::null_mut(); segments.len()];
+    let rc = unsafe { cm_prove_run(run, ptrs.as_ptr(), ptrs.len() as u32, &cfg, inflight, outs.as_mut_ptr()) };
+    unsafe { cm_run_free(run) };
+    let handles: Vec<ProofHandle> = outs.into_iter().filter(|p| !p.is_null()).map(ProofHandle).collect();   // freed on drop
+    match rc {
+        0 => {}
+        10 => return Err(ProvingError::Stwo(StwoProvingError::ConstraintsNotSatisfied)),
+        _ => panic!("libcairom_hip: status {rc}: {}", last_error()),
+    }
+    let raw: Vec<*const cm_proof> = handles.iter().map(|h| h.0 as *const cm_proof).collect();
+    let rc = unsafe { cm_verify_run(raw.as_ptr(), raw.len() as u32, &cfg) };
+    assert!(rc == 0, "cm_verify_run: {}", last_error());
+    handles
+        .iter()
+        .map(|h| {
+            let (mut ptr, mut len) = (std::ptr::null(), 0usize);
+            let rc = unsafe { cm_proof_json(h.0, &mut ptr, &mut len) };
+            assert!(rc == 0, "cm_proof_json: {}", last_error());
+            let json = unsafe { std::slice::from_raw_parts(ptr as *const u8, len) };
+            Ok(sonic_rs::from_slice(json).expect("libcairom_hip returned a malformed Proof JSON"))
+        })
+        .collect()
+}
+
 /// `verify_cairo_m::<Blake2sMerkleChannel>` stays the reference's own function: the value returned above is an ordinary
 /// `Proof<Blake2sMerkleHasher>`.  This helper is the library-side verifier (host code, no GPU) for callers that want the
 /// check without Stwo: same acceptance conditions, error mapped onto the reference's enum.
