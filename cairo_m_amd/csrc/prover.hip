@@ -1439,6 +1439,7 @@ ProveWorkers& prove_workers() { static ProveWorkers* w = new ProveWorkers(); ret
 }  // namespace
 }  // namespace cm
 
+#include "verify_device.hpp"
 namespace cm {
 std::string verify_proof(const ProofData& pf, const cm_pcs_config& expected);                 // verifier.hip
 bool proof_from_words(const uint32_t* w, uint64_t n, ProofData& p, std::string& err);
@@ -1876,6 +1877,56 @@ int32_t cm_verify_run(const cm_proof* const* proofs, uint32_t n, const cm_pcs_co
         throw cm::CmError(11, "run: segment " + std::to_string(i) + " initial_" + field + " != segment " + std::to_string(i - 1) + " final_" + field);
     }
   });
+}
+// The same verdicts from the GPU, for a whole batch (verify_device.hip): results[i] = what cm_verify_proof says about proofs[i]
+static int32_t verify_many_impl(const char* who, const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected,
+                                std::vector<cm::VerifyOutcome>& out, cm_stream_t s) {
+  return pguard([&] {
+    CM_CHECK(n >= 1 && proofs, std::string(who) + ": no proofs");
+    std::vector<const cm::ProofData*> pd(n);
+    for (uint32_t i = 0; i < n; i++) {
+      CM_CHECK(proofs[i] && proofs[i]->d, std::string(who) + ": null proof");
+      pd[i] = proofs[i]->d;
+    }
+    cm::verify_many_device(pd.data(), n, expected ? *expected : default_cfg(), out, (hipStream_t)(uintptr_t)s);
+  });
+}
+int32_t cm_verify_many(const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected, cm_verify_result* results, cm_stream_t s) {
+  std::vector<cm::VerifyOutcome> out;
+  const int32_t rc = verify_many_impl("cm_verify_many", proofs, n, expected, out, s);
+  if (rc) return rc;
+  int64_t first = -1;
+  for (uint32_t i = 0; i < n; i++) {
+    const bool ok = out[i].message.empty();
+    if (!ok && first < 0) first = i;
+    if (!results) continue;
+    memset(&results[i], 0, sizeof(cm_verify_result));
+    if (ok) continue;
+    results[i].status = 11;
+    results[i].check = out[i].check;
+    snprintf(results[i].message, sizeof(results[i].message), "verification failed: %s", out[i].message.c_str());
+  }
+  if (first < 0) return 0;
+  cm_set_last_error(("proof " + std::to_string(first) + ": verification failed: " + out[first].message).c_str());
+  return 11;
+}
+int32_t cm_verify_run_device(const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected) {
+  std::vector<cm::VerifyOutcome> out;
+  const int32_t rc = verify_many_impl("cm_verify_run_device", proofs, n, expected, out, 0);
+  if (rc) return rc;
+  return pguard([&] {
+    for (uint32_t i = 0; i < n; i++)
+      if (!out[i].message.empty()) throw cm::CmError(11, "run: segment " + std::to_string(i) + ": verification failed: " + out[i].message);
+    for (uint32_t i = 1; i < n; i++) {
+      const cm::PublicData &a = proofs[i - 1]->d->public_data, &b = proofs[i]->d->public_data;
+      const char* field = b.initial_pc != a.final_pc ? "pc" : b.initial_fp != a.final_fp ? "fp" : b.initial_root != a.final_root ? "root" : nullptr;
+      if (field)
+        throw cm::CmError(11, "run: segment " + std::to_string(i) + " initial_" + field + " != segment " + std::to_string(i - 1) + " final_" + field);
+    }
+  });
+}
+int32_t cm_verify_many_timing(double ms[4]) {
+  return pguard([&] { CM_CHECK(ms, "cm_verify_many_timing: null output"); cm::verify_many_timing(ms); });
 }
 // ---- per-component AIR ops (include/cairom_hip.h): the kernels of the whole-segment prover, one component
 // at a time on caller-owned columns --------------------------------------------------------------------------------

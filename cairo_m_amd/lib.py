@@ -721,12 +721,44 @@ def prove_run(backend, host_segments, inflight=3, cfg=None):
         run.free()
 
 
-def verify_run(proofs, cfg=None, lib=None):
-    """cm_verify_run (host code): (status, message); 0 = every proof verifies and each starts where its predecessor stopped."""
+class VerifyResultC(C.Structure):
+    """cm_verify_result: one proof's verdict from cm_verify_many"""
+    _fields_ = [("status", C.c_int32), ("check", C.c_int32), ("message", C.c_char * 160)]
+
+
+def _proof_handles(proofs):
+    return (C.c_void_p * len(proofs))(*[p.h.value if isinstance(p.h, C.c_void_p) else p.h for p in proofs])
+
+
+def verify_many(proofs, cfg=None, lib=None, stream=0, checks=False):
+    """cm_verify_many (GPU, no CPU fallback): every proof's verdict from one batch — [(status, message)], the host verifier's own
+    status and words per proof (checks=True: (status, message, CM_VERIFY_* id)).  Raises CmError for everything that is not a
+    verdict (no device, no proofs)."""
     L = lib or proofs[0].L
     n = len(proofs)
-    hs = (C.c_void_p * n)(*[p.h.value if isinstance(p.h, C.c_void_p) else p.h for p in proofs])
-    rc = L.cm_verify_run(hs, C.c_uint32(n), _cfg(cfg))
+    res = (VerifyResultC * max(n, 1))()
+    rc = L.cm_verify_many(_proof_handles(proofs), C.c_uint32(n), _cfg(cfg), res, C.c_uint64(stream))
+    if rc not in (0, 11):
+        raise _lib_error(L, rc)
+    out = [(r.status, r.message.decode(errors="replace")) + ((r.check,) if checks else ()) for r in res[:n]]
+    return out
+
+
+def verify_many_timing(lib=None):
+    """cm_verify_many_timing: where the calling thread's last cm_verify_many spent its time (ms)"""
+    L = lib or load_library()
+    ms = (C.c_double * 4)()
+    L.cm_verify_many_timing(ms)
+    return dict(zip(("plan", "upload", "kernels", "download"), list(ms)))
+
+
+def verify_run(proofs, cfg=None, lib=None, device=False):
+    """cm_verify_run (host code; device=True: cm_verify_run_device, the proofs checked on the GPU in one batch): (status, message);
+    0 = every proof verifies and each starts where its predecessor stopped."""
+    L = lib or proofs[0].L
+    n = len(proofs)
+    hs = _proof_handles(proofs)
+    rc = (L.cm_verify_run_device if device else L.cm_verify_run)(hs, C.c_uint32(n), _cfg(cfg))
     buf = C.create_string_buffer(1024)
     L.cm_last_error(buf, C.c_size_t(1024))
     return rc, buf.value.decode(errors="replace") if rc else ""
@@ -734,7 +766,8 @@ def verify_run(proofs, cfg=None, lib=None):
 
 Backend.run_begin = lambda self, initial_memory, initial_heap, ranges: Run(self, initial_memory, initial_heap, ranges)
 Backend.prove_run = lambda self, host_segments, inflight=3, cfg=None: prove_run(self, host_segments, inflight, cfg)
-Backend.verify_run = lambda self, proofs, cfg=None: verify_run(proofs, cfg, self.L)
+Backend.verify_run = lambda self, proofs, cfg=None, device=False: verify_run(proofs, cfg, self.L, device)
+Backend.verify_many = lambda self, proofs, cfg=None: verify_many(proofs, cfg, self.L)
 
 
 # ---- device-memory accounting, estimate and budget (include/cairom_hip.h, revision 9) --------------------------

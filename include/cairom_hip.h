@@ -32,7 +32,9 @@
  * 9: cm_mem_stats, cm_proof_mem, cm_mem_estimate; cm_mem_stats_get, cm_mem_reset_peak, cm_proof_memory, cm_estimate_memory,
  *    cm_estimate_memory_logs, cm_set_memory_budget.
  * 10: a whole run (additive): cm_run, cm_run_segment, cm_public_data; cm_run_begin, cm_run_adapt_next, cm_run_memory, cm_run_free,
- *    cm_prove_run, cm_proof_public_data, cm_proof_public_entries, cm_verify_run, cm_host_segment_end_lengths. */
+ *    cm_prove_run, cm_proof_public_data, cm_proof_public_entries, cm_verify_run, cm_host_segment_end_lengths.
+ *    Still 10 (additive: new symbols and one struct, nothing moved): cm_verify_result, CM_VERIFY_*, cm_verify_many,
+ *    cm_verify_run_device, cm_verify_many_timing. */
 #define CM_ABI_REVISION 10
 
 #ifdef __cplusplus
@@ -571,6 +573,42 @@ int32_t cm_proof_public_entries(const cm_proof* p, uint32_t which, uint32_t* out
  * the final ones of proof i - 1.  Status 11; the message names the link and the field, e.g.
  * "run: segment 3 initial_root != segment 2 final_root", or "run: segment 3: verification failed: ...". */
 int32_t cm_verify_run(const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected);
+/* ---- batched verification on the GPU (additive to revision 10) -------------------------------------------------------------
+ * cm_verify_many verifies n independent proofs in one batch.  Per proof the host replays the transcript and does every check in
+ * front of the queries (cm_verify_proof's own code), then plans the query phase as flat tables; the GPU computes the DEEP-quotient
+ * answers, folds the FRI layers and hashes every decommitment path of every tree of every proof (one upload, four launches on
+ * stream s, one download).  There is no CPU fallback: without a GPU the status is cm_init's (3).  The verdict and the words are
+ * the host verifier's: results[i].status / message equal what cm_verify_proof(proofs[i], expected) returns and leaves in
+ * cm_last_error() — the EARLIEST failed check in the host's order, whose id (below, numbered in that order) is results[i].check.
+ * Returns 0 when every proof is accepted; otherwise 11 and cm_last_error() reads "proof <i>: <message>" for the lowest rejected
+ * i.  n == 0, a null array or a null proof: status 1.  The framing in force (cm_set_framing) is honoured.  The call keeps
+ * nothing: its device buffers come from the calling thread's pool and are back there when it returns.  A level of one tree
+ * holds at most 1024 nodes on the device (that is n_queries <= 512); more is status 1. */
+#define CM_VERIFY_STRUCTURE 1            /* InvalidStructure..., config and shape */
+#define CM_VERIFY_POW_INTERACTION 2      /* ProofOfWork(interaction) */
+#define CM_VERIFY_LOGUP_SUM 3            /* InvalidLogupSum */
+#define CM_VERIFY_OODS 4                 /* OodsNotMatching */
+#define CM_VERIFY_FRI_STRUCTURE 5        /* Fri(InvalidNumFriLayers), Fri(LastLayerDegreeInvalid) */
+#define CM_VERIFY_POW 6                  /* ProofOfWork */
+#define CM_VERIFY_MERKLE 7               /* Merkle(tree 0..3): ... */
+#define CM_VERIFY_QUERIED_VALUES 8       /* InvalidStructure(queried values) */
+#define CM_VERIFY_FRI_FIRST_EVALS 9      /* Fri(FirstLayerEvaluationsInvalid) */
+#define CM_VERIFY_FRI_FIRST_COMMITMENT 10 /* Fri(FirstLayerCommitmentInvalid): ... */
+#define CM_VERIFY_FRI_INNER_EVALS 11     /* Fri(InnerLayerEvaluationsInvalid), layer by layer in front of ... */
+#define CM_VERIFY_FRI_INNER_COMMITMENT 12 /* ... Fri(InnerLayerCommitmentInvalid <i>): ... of the same layer */
+#define CM_VERIFY_FRI_LAST_EVALS 13      /* Fri(LastLayerEvaluationsInvalid) */
+typedef struct cm_verify_result {
+  int32_t status;      /* 0 = accepted, 11 = rejected (same code cm_verify_proof returns) */
+  int32_t check;       /* 0, or the CM_VERIFY_* id of the failed check */
+  char    message[160];/* exactly the string the host verifier gives for this proof, NUL-terminated */
+} cm_verify_result;
+int32_t cm_verify_many(const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected, cm_verify_result* results,
+                       cm_stream_t s);
+/* cm_verify_many plus the register / root chain check of cm_verify_run, with cm_verify_run's messages. */
+int32_t cm_verify_run_device(const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected);
+/* Where the calling thread's last cm_verify_many / cm_verify_run_device spent its time, in milliseconds: 0 host planning,
+ * 1 upload, 2 kernels, 3 download of the result words (1-3 from events on the stream). */
+int32_t cm_verify_many_timing(double ms[4]);
 /* Copy a device-resident ProverInput back (tests: device adapter vs host adapter). */
 int32_t cm_device_input_download(const cm_device_input* in, cm_host_input** out);
 /* The synthetic VM's raw output for one segment (what cm_vm_run feeds to the host adapter). */

@@ -253,6 +253,14 @@ pub struct cm_run_segment {
     pub n_memory_end: u64,
     pub n_heap_end: u64,
 }
+/// One proof's verdict from `cm_verify_many`: the host verifier's status and words, and the CM_VERIFY_* id of the failed check
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct cm_verify_result {
+    pub status: i32,
+    pub check: i32,
+    pub message: [c_char; 160],
+}
 /// A proof's public data (public_data.rs:192-227); set `struct_size` before the call
 #[repr(C)]
 pub struct cm_public_data {
@@ -340,6 +348,9 @@ unsafe extern "C" {
     pub fn cm_proof_public_data(p: *const cm_proof, out: *mut cm_public_data) -> i32;
     pub fn cm_proof_public_entries(p: *const cm_proof, which: u32, out: *mut u32, cap_entries: u64, n_entries: *mut u64) -> i32;
     pub fn cm_verify_run(proofs: *const *const cm_proof, n: u32, expected: *const cm_pcs_config) -> i32;
+    pub fn cm_verify_many(proofs: *const *const cm_proof, n: u32, expected: *const cm_pcs_config, results: *mut cm_verify_result, s: cm_stream_t) -> i32;
+    pub fn cm_verify_run_device(proofs: *const *const cm_proof, n: u32, expected: *const cm_pcs_config) -> i32;
+    pub fn cm_verify_many_timing(ms: *mut f64) -> i32;
     pub fn cm_host_segment_end_lengths(h: *const cm_host_segment, n_memory_end: *mut u64, n_heap_end: *mut u64) -> i32;
     pub fn cm_set_preprocessed_cache(on: i32) -> i32;
     pub fn cm_set_twiddle_cache(on: i32) -> i32;

@@ -237,6 +237,32 @@ pub fn verify_words_hip(proof: &ProofHandleRef, pcs_config: Option<PcsConfig>) -
         _ => Err(VerificationError::Stwo(StwoVerificationError::InvalidStructure(last_error()))),
     }
 }
+/// `cm_verify_many`: the same verdicts for a whole batch of library proofs, computed on the GPU in one call (the host plans, the
+/// device hashes every decommitment path and folds the FRI layers).  One entry per proof, in order; the error carries the words
+/// `cm_verify_proof` would have left for that proof.  Panics when the batch cannot be run at all (no GPU, null proof).
+pub fn verify_cairo_m_many(proofs: &[ProofHandleRef], pcs_config: Option<PcsConfig>) -> Vec<Result<(), VerificationError>> {
+    ensure_init();
+    let cfg = pcs(&pcs_config.unwrap_or(REGULAR_96_BITS));
+    let raw: Vec<*const cm_proof> = proofs.iter().map(|p| p.0).collect();
+    let mut results = vec![cm_verify_result { status: 0, check: 0, message: [0; 160] }; raw.len()];
+    let rc = unsafe { cm_verify_many(raw.as_ptr(), raw.len() as u32, &cfg, results.as_mut_ptr(), 0) };
+    assert!(rc == 0 || rc == 11, "cm_verify_many: status {rc}: {}", last_error());
+    results
+        .iter()
+        .map(|r| {
+            if r.status == 0 {
+                return Ok(());
+            }
+            let msg = unsafe { std::ffi::CStr::from_ptr(r.message.as_ptr()) }.to_string_lossy().into_owned();
+            Err(match r.check {
+                3 => VerificationError::InvalidLogupSum,
+                2 | 6 => VerificationError::Stwo(StwoVerificationError::ProofOfWork),
+                4 => VerificationError::Stwo(StwoVerificationError::OodsNotMatching),
+                _ => VerificationError::Stwo(StwoVerificationError::InvalidStructure(msg)),
+            })
+        })
+        .collect()
+}
 /// Borrowed library proof object (e.g. kept by a caller that proves many segments and verifies them later).
 pub struct ProofHandleRef(pub *const cm_proof);
 
