@@ -1834,6 +1834,26 @@ int32_t cm_prove_run(cm_run* r, const cm_run_segment* const* segs, uint32_t n, c
                              2 * cells * sizeof(cm_memory_cell), 0};
   }, config, inflight, outs, /*n_producers=*/1);
 }
+// The same walk with the PCS-free check (check.hip) and the link diff (link.hip) in the place of the proof: every verdict is
+// collected, only a segment that cannot be adapted ends the call.  Segment i - 1's input lives until link i has been looked at.
+int32_t cm_check_run(cm_run* r, const cm_run_segment* const* segs, uint32_t n, const cm_relations* relations, cm_run_check* out,
+                     cm_link_cell* cells, uint64_t cap_per_link) {
+  return pguard([&] {
+    CM_CHECK(r && r->r && (!n || (segs && out)), "cm_check_run: null argument");
+    CM_CHECK(cells || cap_per_link == 0, "cm_check_run: null cells with a capacity");
+    std::lock_guard<std::mutex> lk(cm::run_mutex(*r->r));
+    if (n) memset(out, 0, (size_t)n * sizeof(cm_run_check));
+    std::unique_ptr<cm::DeviceInput> prev;
+    for (uint32_t i = 0; i < n; i++) {
+      check_run_segment(segs[i], "cm_check_run");
+      std::unique_ptr<cm::DeviceInput> cur(cm::run_adapt_next(*r->r, *segs[i]));
+      cm::check_segment(*cur, relations, out[i].check);
+      if (prev) cm::check_link_into(*prev, *cur, i, out[i], cells, cap_per_link);
+      prev = std::move(cur);
+    }
+    cm_set_last_error(cm::run_check_summary(out, n, true).c_str());
+  });
+}
 int32_t cm_proof_public_data(const cm_proof* p, cm_public_data* out) {
   return pguard([&] {
     CM_CHECK(p && p->d && out, "cm_proof_public_data: null argument");

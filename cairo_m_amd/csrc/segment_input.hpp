@@ -5,6 +5,7 @@
 #include "prover_common.hpp"
 #include "gpu_air.hpp"
 #include "point_eval.hpp"
+#include <string>
 
 namespace cm {
 
@@ -68,6 +69,15 @@ struct CheckColumns {
 };
 // The PCS-free AIR check of a whole segment; keep (optional) receives the columns instead of the check releasing them.
 void check_segment(const DeviceInput& din, const cm_relations* relations, cm_check_report& rep, CheckColumns* keep = nullptr);
+
+// Link diff of a run (link.hip): prev's final boundary memory against next's initial one.  rep.struct_size is kept; seg_index = the
+// index of `next` in its run (the report's first sentence names it).  cells: room for `cap` records; n_total: all there are.
+void link_diff(const DeviceInput& prev, const DeviceInput& next, uint32_t seg_index, cm_link_report& rep, cm_link_cell* cells, uint64_t cap,
+               uint64_t& n_total);
+// link i of a checked run into its record: cells + i * cap_per_link receive the cells
+void check_link_into(const DeviceInput& prev, const DeviceInput& next, uint32_t i, cm_run_check& rec, cm_link_cell* cells, uint64_t cap_per_link);
+// the line cm_check_run / cm_check_chain leave for cm_last_error(): the first bad link or segment, or empty
+std::string run_check_summary(const cm_run_check* out, uint32_t n, bool with_air);
 
 }  // namespace cm
 

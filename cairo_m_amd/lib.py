@@ -1194,3 +1194,192 @@ def _b_relation_entries(self, cid, trace_cols, preprocessed, log_size, rel_words
 
 Backend.track_relations = _b_track_relations
 Backend.relation_entries = _b_relation_entries
+
+
+# ---- a whole run, checked before it is proved (include/cairom_hip.h: cm_link_diff, cm_check_chain, cm_check_run) -----------
+LINK_KINDS = {1: "changed", 2: "only in next", 3: "only in prev"}
+
+
+class LinkCell(C.Structure):
+    """cm_link_cell: one cell that makes a link's roots differ — kind 1 present in both with different values, 2 present only in
+    the later segment's initial memory, 3 only in the earlier segment's final memory."""
+    _fields_ = [("kind", C.c_uint32), ("address", C.c_uint32), ("prev_value", C.c_uint32 * 4), ("next_value", C.c_uint32 * 4),
+                ("prev_clock", C.c_uint32)]
+
+    def words(self):
+        return [self.kind, self.address] + list(self.prev_value) + list(self.next_value) + [self.prev_clock]
+
+    def __repr__(self):
+        return (f"LinkCell({LINK_KINDS.get(self.kind, self.kind)}, address {self.address}, {list(self.prev_value)} -> "
+                f"{list(self.next_value)}, prev clock {self.prev_clock})")
+
+
+class _LinkReportC(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_uint32),
+                ("prev_final_pc", C.c_uint32), ("prev_final_fp", C.c_uint32), ("next_initial_pc", C.c_uint32), ("next_initial_fp", C.c_uint32),
+                ("pc_equal", C.c_uint32), ("fp_equal", C.c_uint32), ("roots_equal", C.c_uint32), ("reserved1", C.c_uint32),
+                ("prev_final_root", C.c_uint32), ("next_initial_root", C.c_uint32),
+                ("n_changed", C.c_uint64), ("n_only_next", C.c_uint64), ("n_only_prev", C.c_uint64), ("n_zero_only", C.c_uint64),
+                ("message", C.c_char * 160)]
+
+
+class LinkReport(_LinkReportC):
+    """cm_link_report: registers and roots on both sides of a link, per-kind totals of the listed cells, the count of cells that
+    are present on one side only with an all-zero value (they do not change the root and are not listed), and the message."""
+
+    @property
+    def message(self):
+        return _LinkReportC.message.__get__(self).decode(errors="replace")
+
+    @property
+    def first_sentence(self):
+        """cm_verify_run's words for this link, "" when registers and roots chain"""
+        m = self.message
+        return m.split(". ")[0] if m.startswith("run: ") else ""
+
+    @property
+    def n_total(self):
+        return self.n_changed + self.n_only_next + self.n_only_prev
+
+    @property
+    def ok(self):
+        return bool(self.pc_equal and self.fp_equal and self.roots_equal and self.n_total == 0)
+
+    def __repr__(self):
+        return f"LinkReport(ok={self.ok}, message={self.message!r})"
+
+
+class RunCheckC(C.Structure):
+    """cm_run_check: one segment's record of cm_check_run / cm_check_chain"""
+    _fields_ = [("check", CheckReport), ("link", LinkReport), ("link_cells_written", C.c_uint64), ("link_cells_total", C.c_uint64)]
+
+
+class LinkDiff:
+    """One link: .report (LinkReport), .cells (the first `cap` LinkCells in ascending address order), .n_total, .truncated."""
+
+    def __init__(self, report, cells, n_total):
+        self.report, self.cells, self.n_total = report, cells, n_total
+
+    @property
+    def truncated(self):
+        return self.n_total > len(self.cells)
+
+    def cell_words(self):
+        """(len(cells), 11) u32: kind, address, prev_value[4], next_value[4], prev_clock"""
+        return np.array([c.words() for c in self.cells], dtype=np.uint32).reshape(-1, 11)
+
+    def __repr__(self):
+        return f"LinkDiff({self.report.message!r}, {len(self.cells)} of {self.n_total} cells)"
+
+
+class SegmentCheck:
+    """One segment of a checked run: .check (CheckReport, None from check_chain), .link (LinkDiff, None for the first segment)."""
+
+    def __init__(self, check, link):
+        self.check, self.link = check, link
+
+    @property
+    def ok(self):
+        return (self.check is None or self.check.status == 0) and (self.link is None or self.link.report.ok)
+
+
+class RunCheck:
+    """What Run.check / check_run / check_chain return: .segments (SegmentCheck each), .summary (the library's one line about the
+    first bad link or segment, "" when the run will prove and chain), .ok."""
+
+    def __init__(self, segments, summary):
+        self.segments, self.summary = segments, summary
+
+    @property
+    def ok(self):
+        return all(s.ok for s in self.segments)
+
+    def __repr__(self):
+        return f"RunCheck(ok={self.ok}, summary={self.summary!r}, {len(self.segments)} segments)"
+
+
+def _copy_struct(cls, src):
+    out = cls()
+    C.memmove(C.byref(out), C.byref(src), C.sizeof(cls))
+    return out
+
+
+def _run_check_result(L, recs, cells, n, cap, with_air):
+    buf = C.create_string_buffer(1024)
+    L.cm_last_error(buf, C.c_size_t(1024))
+    segs = []
+    for i in range(n):
+        link = None
+        if i > 0:
+            got = [_copy_struct(LinkCell, cells[i * cap + k]) for k in range(recs[i].link_cells_written)]
+            link = LinkDiff(_copy_struct(LinkReport, recs[i].link), got, recs[i].link_cells_total)
+        segs.append(SegmentCheck(_copy_struct(CheckReport, recs[i].check) if with_air else None, link))
+    return RunCheck(segs, buf.value.decode(errors="replace"))
+
+
+def link_diff(prev, next, cap=64, lib=None):
+    """cm_link_diff: the cells that make `next`'s initial root differ from `prev`'s final root (two device inputs, e.g. of
+    Backend.adapt_segment / Run.adapt_next) -> LinkDiff.  The report's first sentence numbers prev 0 and next 1."""
+    L = lib or load_library()
+    rep = LinkReport()
+    rep.struct_size = C.sizeof(LinkReport)
+    buf = (LinkCell * max(cap, 1))()
+    n_total = C.c_uint64(0)
+    rc = L.cm_link_diff(prev, next, C.byref(rep), buf if cap else None, C.c_uint64(cap), C.byref(n_total))
+    if rc:
+        raise _lib_error(L, rc)
+    return LinkDiff(rep, [_copy_struct(LinkCell, buf[i]) for i in range(min(n_total.value, cap))], n_total.value)
+
+
+def check_chain(dev_inputs, cap=64, lib=None):
+    """cm_check_chain: the links of segments adapted one by one (device inputs in run order) -> RunCheck without AIR reports."""
+    L = lib or load_library()
+    n = len(dev_inputs)
+    ins = (C.c_void_p * n)(*[d.value if isinstance(d, C.c_void_p) else d for d in dev_inputs])
+    recs = (RunCheckC * max(n, 1))()
+    cells = (LinkCell * max(n * cap, 1))()
+    rc = L.cm_check_chain(ins, C.c_uint32(n), recs, cells if cap else None, C.c_uint64(cap))
+    if rc:
+        raise _lib_error(L, rc)
+    return _run_check_result(L, recs, cells, n, cap, False)
+
+
+def _run_check(self, segs, relations=None, cap=64):
+    """cm_check_run: the next segments of this run (RunSegmentC or HostSegment each) adapted, AIR-checked and link-diffed instead
+    of proved -> RunCheck; the image advances as under prove().  A segment that cannot be adapted raises CmError with the records
+    in front of it as e.partial (a RunCheck) and leaves the image at that segment's start."""
+    segs = [s if isinstance(s, RunSegmentC) else run_segment(s) for s in segs]
+    n = len(segs)
+    ins = (C.c_void_p * n)(*[C.addressof(s) for s in segs])
+    recs = (RunCheckC * max(n, 1))()
+    cells = (LinkCell * max(n * cap, 1))()
+    r = _relation_words(relations)
+    rc = self.L.cm_check_run(self.h, ins, C.c_uint32(n), _p(r) if r is not None else None, recs, cells if cap else None, C.c_uint64(cap))
+    if rc != 0:
+        try:
+            self.B._ck(rc)
+        except CmError as e:
+            done = 0
+            while done < n and any(recs[done].check.relations):    # (a record the call reached holds the relations it used)
+                done += 1
+            e.partial = _run_check_result(self.L, recs, cells, done, cap, True)
+            raise
+    return _run_check_result(self.L, recs, cells, n, cap, True)
+
+
+Run.check = _run_check
+
+
+def check_run(backend, host_segments, relations=None, cap=64):
+    """A whole run checked from its runner segments: makes and frees its own Run, so a later prove_run starts from the run's
+    beginning."""
+    run = Run.from_segment(backend, host_segments[0])
+    try:
+        return run.check(host_segments, relations, cap)
+    finally:
+        run.free()
+
+
+Backend.check_run = lambda self, host_segments, relations=None, cap=64: check_run(self, host_segments, relations, cap)
+Backend.check_chain = lambda self, dev_inputs, cap=64: check_chain(dev_inputs, cap, self.L)
+Backend.link_diff = lambda self, prev, next, cap=64: link_diff(prev, next, cap, self.L)

@@ -34,7 +34,8 @@
  * 10: a whole run (additive): cm_run, cm_run_segment, cm_public_data; cm_run_begin, cm_run_adapt_next, cm_run_memory, cm_run_free,
  *    cm_prove_run, cm_proof_public_data, cm_proof_public_entries, cm_verify_run, cm_host_segment_end_lengths.
  *    Still 10 (additive: new symbols and one struct, nothing moved): cm_verify_result, CM_VERIFY_*, cm_verify_many,
- *    cm_verify_run_device, cm_verify_many_timing. */
+ *    cm_verify_run_device, cm_verify_many_timing; cm_link_cell, cm_link_report, cm_run_check, cm_link_diff, cm_check_chain,
+ *    cm_check_run. */
 #define CM_ABI_REVISION 10
 
 #ifdef __cplusplus
@@ -609,6 +610,8 @@ int32_t cm_verify_run_device(const cm_proof* const* proofs, uint32_t n, const cm
 /* Where the calling thread's last cm_verify_many / cm_verify_run_device spent its time, in milliseconds: 0 host planning,
  * 1 upload, 2 kernels, 3 download of the result words (1-3 from events on the stream). */
 int32_t cm_verify_many_timing(double ms[4]);
+/* (Checking a whole run BEFORE proving it — cm_link_diff, cm_check_chain, cm_check_run — is declared behind the relation tracker
+ * below: its records embed cm_check_report.) */
 /* Copy a device-resident ProverInput back (tests: device adapter vs host adapter). */
 int32_t cm_device_input_download(const cm_device_input* in, cm_host_input** out);
 /* The synthetic VM's raw output for one segment (what cm_vm_run feeds to the host adapter). */
@@ -750,6 +753,64 @@ int32_t cm_track_relations(const cm_device_input* input, const cm_relations* rel
 int32_t cm_relation_entries(int32_t component, const cm_handle* trace_cols, const cm_handle* preprocessed, uint32_t log_size,
                             const cm_relations* relations, uint32_t relation_mask, cm_relation_entry* entries, uint64_t cap,
                             uint64_t* n_total, cm_stream_t s);
+/* ---- a whole run, checked before it is proved (additive to revision 10: new symbols and structs, nothing moved) ---------------
+ * A run can be invalid in a way no single-segment check sees: its LINKS.  A segment that first-writes a cell beyond the memory it
+ * was handed enters that cell into its initial tree with the written value (adapter/memory.rs:493-503), so its initial root is
+ * not its predecessor's final root, and cm_verify_run refuses the proved run naming two 31-bit roots.  cm_link_diff names the
+ * cells instead, from the two device inputs, without proving anything.
+ *
+ * cm_link_diff compares prev's FINAL boundary memory with next's INITIAL boundary memory (both in ascending address order, both
+ * stay where they are) on the calling thread's stream and pool (threading as cm_check_constraints).  Only the four value words of
+ * a cell are leaves of the partial Merkle tree; clocks and multiplicities are not compared.  An absent leaf hashes like a zero
+ * leaf (adapter/merkle.rs: missing nodes take the default hash of their depth, and the default leaf is 0), so a cell present on
+ * one side only with value (0, 0, 0, 0) does not change the root: such cells are counted in n_zero_only and are NOT listed.
+ * Contract, for inputs whose roots belong to their memories: roots_equal <=> *n_total == 0.
+ * cells[0, min(*n_total, cap)) are written in ascending address order; *n_total > cap means truncated, which is not an error;
+ * cells may be NULL when cap is 0.  The result is deterministic: its order comes from addresses and a scan.
+ * message: first the sentence cm_verify_run would give for this link — for the first field that differs, initial_pc, then
+ * initial_fp, then initial_root ("run: segment 1 initial_root != segment 0 final_root"; cm_link_diff numbers prev 0 and next 1,
+ * cm_check_run / cm_check_chain use the segments' own indices), nothing when all three are equal — then, when cells are listed,
+ * ". <n> cells differ: <a> changed, <b> new, <c> gone; first address <x>" (without the ". " when the first sentence is empty).
+ * Without a GPU the status is cm_init's (3).  Set struct_size = sizeof(cm_link_report) before cm_link_diff. */
+typedef struct {
+  uint32_t kind;            /* 1 present in both, values differ; 2 present only in next's initial memory; 3 only in prev's final memory */
+  uint32_t address;
+  uint32_t prev_value[4];   /* zero for kind 2 */
+  uint32_t next_value[4];   /* zero for kind 3 */
+  uint32_t prev_clock;      /* clock of prev's final row (the last access of the cell in prev); zero for kind 2 */
+} cm_link_cell;             /* sizeof = 44 */
+typedef struct {
+  uint32_t struct_size, reserved0;
+  uint32_t prev_final_pc, prev_final_fp, next_initial_pc, next_initial_fp;
+  uint32_t pc_equal, fp_equal, roots_equal, reserved1;
+  uint32_t prev_final_root, next_initial_root;
+  uint64_t n_changed, n_only_next, n_only_prev;   /* totals of kind 1, 2, 3: their sum is *n_total */
+  uint64_t n_zero_only;                           /* present on one side only, all-zero value: not listed */
+  char message[160];
+} cm_link_report;           /* sizeof = 240 */
+int32_t cm_link_diff(const cm_device_input* prev, const cm_device_input* next, cm_link_report* report, cm_link_cell* cells, uint64_t cap,
+                     uint64_t* n_total);
+/* One record per segment of a checked run: the AIR verdict of segment i (cm_check_constraints' report; all zero from
+ * cm_check_chain), the link between segment i - 1 and i (all zero for i = 0; struct_size is set by the library), and how many of
+ * the link's cells were written to cells[i * cap_per_link ...] out of how many there are. */
+typedef struct {
+  cm_check_report check;
+  cm_link_report link;
+  uint64_t link_cells_written, link_cells_total;
+} cm_run_check;             /* sizeof = sizeof(cm_check_report) + 240 + 16 = 8432 */
+/* The links of n segments adapted one by one (cm_adapt_segment_device, cm_input_upload): out = n records, cells = n * cap_per_link
+ * cells (NULL when cap_per_link is 0).  Returns 0 when the call ran; the verdicts are in out, and cm_last_error() holds a one-line
+ * summary of the first bad link ("link 3: run: segment 3 initial_root != ...") or is empty. */
+int32_t cm_check_chain(const cm_device_input* const* inputs, uint32_t n, cm_run_check* out, cm_link_cell* cells, uint64_t cap_per_link);
+/* The next n segments of a run, checked instead of proved.  Segment i goes through cm_run_adapt_next (the image advances exactly
+ * as under cm_prove_run), then the passes of cm_check_constraints run on its input (relations as there: NULL = drawn from a
+ * default channel), then, for i > 0, cm_link_diff against segment i - 1's input, which is kept until then and freed after: at most
+ * two inputs are resident.  The call does NOT stop at a bad verdict: it returns 0 when it ran, out holds every verdict, and
+ * cm_last_error() holds a one-line summary of the first bad link or segment in run order ("link 2: ...", "segment 2: ...") or is
+ * empty.  It does stop at a segment that cannot be adapted, with cm_run_adapt_next's own status and contract: the records in
+ * front of it are filled, the image is left at that segment's start, and the run may be continued from there. */
+int32_t cm_check_run(cm_run* r, const cm_run_segment* const* segs, uint32_t n, const cm_relations* relations, cm_run_check* out,
+                     cm_link_cell* cells, uint64_t cap_per_link);
 /* AccumulationOps::accumulate: dst[k][i] += src[k][i] (4 coordinate columns of n words); generate_secure_powers:
  * out[i] = felt^i for i < n (host array of 4 * n words).  Column::zeros = cm_col_alloc + cm_col_zero. */
 int32_t cm_accumulate(const cm_handle dst[4], const cm_handle src[4], uint64_t n, cm_stream_t s);

@@ -277,6 +277,49 @@ pub struct cm_public_data {
     pub n_input: u32,
     pub n_output: u32,
 }
+/// One cell that makes a link's roots differ (`cm_link_diff`): kind 1 present on both sides with different values, 2 present only
+/// in the later segment's initial memory, 3 only in the earlier segment's final memory
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct cm_link_cell {
+    pub kind: u32,
+    pub address: u32,
+    pub prev_value: [u32; 4],
+    pub next_value: [u32; 4],
+    pub prev_clock: u32,
+}
+/// Registers and roots on both sides of a link, totals per kind, the cells present on one side only with an all-zero value (not
+/// listed: they do not change the root), and the message; set `struct_size` before `cm_link_diff`
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct cm_link_report {
+    pub struct_size: u32,
+    pub reserved0: u32,
+    pub prev_final_pc: u32,
+    pub prev_final_fp: u32,
+    pub next_initial_pc: u32,
+    pub next_initial_fp: u32,
+    pub pc_equal: u32,
+    pub fp_equal: u32,
+    pub roots_equal: u32,
+    pub reserved1: u32,
+    pub prev_final_root: u32,
+    pub next_initial_root: u32,
+    pub n_changed: u64,
+    pub n_only_next: u64,
+    pub n_only_prev: u64,
+    pub n_zero_only: u64,
+    pub message: [c_char; 160],
+}
+/// One segment's record of `cm_check_run` / `cm_check_chain`: its AIR verdict, the link to its predecessor, the cells written
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct cm_run_check {
+    pub check: cm_check_report,
+    pub link: cm_link_report,
+    pub link_cells_written: u64,
+    pub link_cells_total: u64,
+}
 
 unsafe extern "C" {
     pub fn cm_init(device: i32) -> i32;
@@ -383,6 +426,9 @@ unsafe extern "C" {
     pub fn cm_constraints_check(component: i32, trace_cols: *const cm_handle, interaction_cols: *const cm_handle, preprocessed: *const cm_handle, log_size: u32, relations: *const cm_relations, claimed_sum: *const u32, row_status: cm_handle, failing_rows: *mut u64, first_constraint: *mut i32, first_row: *mut u64, s: cm_stream_t) -> i32;
     pub fn cm_track_relations(input: *const cm_device_input, relations: *const cm_relations, relation_mask: u32, report: *mut cm_check_report, entries: *mut cm_relation_entry, cap: u64, n_total: *mut u64) -> i32;
     pub fn cm_relation_entries(component: i32, trace_cols: *const cm_handle, preprocessed: *const cm_handle, log_size: u32, relations: *const cm_relations, relation_mask: u32, entries: *mut cm_relation_entry, cap: u64, n_total: *mut u64, s: cm_stream_t) -> i32;
+    pub fn cm_link_diff(prev: *const cm_device_input, next: *const cm_device_input, report: *mut cm_link_report, cells: *mut cm_link_cell, cap: u64, n_total: *mut u64) -> i32;
+    pub fn cm_check_chain(inputs: *const *const cm_device_input, n: u32, out: *mut cm_run_check, cells: *mut cm_link_cell, cap_per_link: u64) -> i32;
+    pub fn cm_check_run(r: *mut cm_run, segs: *const *const cm_run_segment, n: u32, relations: *const cm_relations, out: *mut cm_run_check, cells: *mut cm_link_cell, cap_per_link: u64) -> i32;
     pub fn cm_relation_sums(component: i32, trace_cols: *const cm_handle, preprocessed: *const cm_handle, log_size: u32, relations: *const cm_relations, sums: *mut [u32; 4], s: cm_stream_t) -> i32;
     pub fn cm_accumulate(dst: *const cm_handle, src: *const cm_handle, n: u64, s: cm_stream_t) -> i32;
     pub fn cm_generate_secure_powers(felt: *const u32, n: u64, out: *mut u32) -> i32;

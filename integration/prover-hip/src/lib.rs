@@ -323,6 +323,74 @@ pub fn assert_constraints(input: &mut ProverInput) -> Result<(), ConstraintFailu
     Err(ConstraintFailure { report, message })
 }
 
+/// Why `assert_run_constraints` rejected a run: every segment's record (AIR report, link report, cell counts), the cells of every
+/// link (`cap_per_link` slots per segment, `link_cells_written` of them filled) and the library's one-line summary of the first
+/// bad link or segment.
+#[derive(Clone)]
+pub struct RunConstraintFailure {
+    pub records: Vec<cm_run_check>,
+    pub cells: Vec<cm_link_cell>,
+    pub cap_per_link: usize,
+    pub message: String,
+}
+impl std::fmt::Debug for RunConstraintFailure {
+    fn fmt(&self, f: &mut std::fmt::Formatter<'_>) -> std::fmt::Result {
+        write!(f, "RunConstraintFailure({})", self.message)
+    }
+}
+impl RunConstraintFailure {
+    /// the listed cells of the link between segment `i - 1` and segment `i`
+    pub fn link_cells(&self, i: usize) -> &[cm_link_cell] {
+        let n = self.records[i].link_cells_written as usize;
+        &self.cells[i * self.cap_per_link..i * self.cap_per_link + n]
+    }
+}
+
+/// `assert_constraints` for a whole run, before any proof is made (`cm_check_run`): every segment is adapted with the memory
+/// carried on the device as under `prove_run_hip`, its AIR is checked, and its initial boundary memory is compared with its
+/// predecessor's final one.  `Ok` means the run will prove and chain; the error names the segment, constraint and row, or the link
+/// and the cells that make its roots differ (at most `cap_per_link` of them per link).  A library error (no GPU, a segment that
+/// cannot be adapted) panics.
+pub fn assert_run_constraints(
+    initial_memory: &[u32],
+    initial_heap: &[u32],
+    ranges: [u32; 6],
+    segments: &[RunSegment],
+    cap_per_link: usize,
+) -> Result<(), RunConstraintFailure> {
+    ensure_init();
+    let mut run: *mut cm_run = std::ptr::null_mut();
+    let rc = unsafe {
+        cm_run_begin(initial_memory.as_ptr(), (initial_memory.len() / 4) as u64, initial_heap.as_ptr(), (initial_heap.len() / 4) as u64, ranges.as_ptr(), &mut run)
+    };
+    assert!(rc == 0, "cm_run_begin: {}", last_error());
+    let views: Vec<cm_run_segment> = segments
+        .iter()
+        .map(|s| cm_run_segment {
+            trace: s.trace.as_ptr(),
+            n_trace: (s.trace.len() / 2) as u64,
+            memory_trace: s.memory_trace.as_ptr(),
+            n_memory_trace: (s.memory_trace.len() / 5) as u64,
+            n_memory_end: s.n_memory_end,
+            n_heap_end: s.n_heap_end,
+        })
+        .collect();
+    let ptrs: Vec<*const cm_run_segment> = views.iter().map(|v| v as *const cm_run_segment).collect();
+    let mut records: Vec<cm_run_check> = vec![unsafe { std::mem::zeroed() }; segments.len()];
+    let mut cells: Vec<cm_link_cell> = vec![cm_link_cell::default(); segments.len() * cap_per_link];
+    let cells_ptr = if cap_per_link == 0 { std::ptr::null_mut() } else { cells.as_mut_ptr() };
+    let rc = unsafe { cm_check_run(run, ptrs.as_ptr(), ptrs.len() as u32, std::ptr::null(), records.as_mut_ptr(), cells_ptr, cap_per_link as u64) };
+    unsafe { cm_run_free(run) };
+    assert!(rc == 0, "cm_check_run: status {rc}: {}", last_error());
+    let bad = records.iter().enumerate().any(|(i, r)| {
+        r.check.status != 0 || (i > 0 && (r.link.pc_equal == 0 || r.link.fp_equal == 0 || r.link.roots_equal == 0 || r.link_cells_total != 0))
+    });
+    if !bad {
+        return Ok(());
+    }
+    Err(RunConstraintFailure { records, cells, cap_per_link, message: last_error() })
+}
+
 /// Twin of `debug_tools::relation_tracker::track_and_summarize_relations` (relation_tracker.rs:21-31, the `.cleaned()` summary) on
 /// the GPU: relation name -> the tuples (values without trailing zeros) whose multiplicities do not sum to zero, with their net
 /// multiplicity.  Only the relations whose sums do not cancel are tracked, so a valid input returns an empty map at the cost of
