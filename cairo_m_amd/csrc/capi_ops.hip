@@ -218,12 +218,20 @@ int32_t cm_accumulate_quotients(uint32_t log_size, const cm_handle* cols, uint32
     }
     std::vector<uint32_t*> o(4);
     for (int k = 0; k < 4; k++) o[k] = P32(out[k]);
+    // per entry: the column pointer itself, as quotient_plan.hpp resolves it for the prover — the op then runs the kernel the
+    // "quot_rows" tuning key selects (k_quotients_rows<2> by default) and not only the one-row kernel's 8-wide loop
+    std::vector<const uint32_t*> ep(col_index.size());
+    for (size_t e = 0; e < col_index.size(); e++) {
+      CM_CHECK(col_index[e] < n_cols, "cm_accumulate_quotients: column index out of range");
+      ep[e] = c[col_index[e]];
+    }
     DevBuf dcols = upload(c, S(s)), dci = upload(col_index, S(s)), dcc = upload(coef_c, S(s)), dqb = upload(qb, S(s)),
-           dout = upload(o, S(s));
+           dout = upload(o, S(s)), dep = upload(ep, S(s));
     QuotientArgs a;
     a.tw = view(*(Twiddles*)(uintptr_t)tw); a.log_size = log_size; a.cols = dcols.as<const uint32_t*>();
     a.col_index = dci.u32(); a.coef_c = dcc.u32(); a.batches = dqb.as<QuotientBatch>(); a.n_batches = b->n_batches;
     a.out = dout.as<uint32_t*>();
+    a.entry_cols = dep.as<const uint32_t*>();
     launch_quotients(a, (double)n_cols, S(s));
     CM_HIP(hipStreamSynchronize(S(s)));
   });

@@ -131,6 +131,18 @@ static Relations relations_from_words(const uint32_t* w) {   // layout of cm_rel
   return r;
 }
 // interaction columns (n_interaction x 2^log words into dst) and claimed sum of one component
+// The preprocessed columns and their extensions are constants of the AIR: the per-component entry points below are called once
+// per component and setting by the tests, and rebuilding seven columns of up to 2^20 rows (and their 2^21-point extensions) on
+// every call was ~0.6 s of each.
+static Col lde_by_one(const Col& evals) { Col c = evals; uint32_t lg = ilog2(c.size()); return evaluate(interpolate(std::move(c)), lg + 1); }
+static const std::vector<Col>& pp_cached() {
+  static const std::vector<Col> pp = preprocessed_columns();
+  return pp;
+}
+static const std::vector<Col>& pp_lde_cached() {
+  static const std::vector<Col> ext = [] { std::vector<Col> e; for (auto& c : pp_cached()) e.push_back(lde_by_one(c)); return e; }();
+  return ext;
+}
 int orc_component_interaction(const cm_prover_input* in, int cid, const uint32_t* rel_words, uint32_t* dst, uint64_t dst_cap,
                               uint32_t* claimed_sum) {
   try {
@@ -138,8 +150,7 @@ int orc_component_interaction(const cm_prover_input* in, int cid, const uint32_t
     std::vector<ComponentTrace> cts = write_traces(*in, err);
     if (!err.empty()) { g_err = err; return 1; }
     ComponentTrace& ct = cts[cid];
-    std::vector<Col> pp = preprocessed_columns();
-    gen_interaction_dispatch(ct, relations_from_words(rel_words), pp);
+    gen_interaction_dispatch(ct, relations_from_words(rel_words), pp_cached());
     uint64_t need = ct.interaction.size() << ct.log_size;
     if (dst_cap < need) { g_err = "buffer too small"; return 2; }
     for (size_t c = 0; c < ct.interaction.size(); c++) memcpy(dst + (c << ct.log_size), ct.interaction[c].data(), (size_t)4 << ct.log_size);
@@ -156,12 +167,11 @@ int orc_component_constraints(const cm_prover_input* in, int cid, const uint32_t
     if (!err.empty()) { g_err = err; return 1; }
     ComponentTrace& ct = cts[cid];
     Relations rel = relations_from_words(rel_words);
-    std::vector<Col> pp = preprocessed_columns();
-    gen_interaction_dispatch(ct, rel, pp);
+    gen_interaction_dispatch(ct, rel, pp_cached());
     PcsProver pcs;
     pcs.trees.resize(3);
-    auto lde = [](const Col& evals) { Col c = evals; uint32_t lg = ilog2(c.size()); return evaluate(interpolate(std::move(c)), lg + 1); };
-    for (auto& c : pp) pcs.trees[0].evals.push_back(lde(c));
+    auto lde = [](const Col& evals) { return lde_by_one(evals); };
+    pcs.trees[0].evals = pp_lde_cached();
     for (auto& c : ct.trace) pcs.trees[1].evals.push_back(lde(c));
     for (auto& c : ct.interaction) pcs.trees[2].evals.push_back(lde(c));
     const air::ComponentInfo& info = air::component_info(cid);
