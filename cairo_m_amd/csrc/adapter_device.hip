@@ -17,6 +17,7 @@
 #include "../../include/cairom_hip.h"
 #include "engine.hpp"
 #include "host_adapter.hpp"
+#include "mem_open.hpp"
 #include "proof.hpp"
 #include <hipcub/hipcub.hpp>
 #include <stdlib.h>

@@ -22,6 +22,11 @@ struct Run {
   uint64_t cap_lo = 0, cap_hi = 0;  // cells allocated
   uint32_t ranges[6] = {0, 0, 0, 0, 0, 0};
   hipEvent_t ev = nullptr;          // behind the last work enqueued on the image
+  // the image's own partial Merkle tree (node list, exact size) for cm_run_open_memory: built on first use, dropped — not
+  // rebuilt — when the image advances; empty otherwise, so a run that never opens a cell pays nothing for it
+  DevBuf img_tree;
+  uint64_t n_img_tree = 0;
+  uint32_t img_root = 0;
   std::mutex mu;                    // one call at a time
   void mark(hipStream_t st) { CM_HIP(hipEventRecord(ev, st)); }
   void wait_on(hipStream_t st) { CM_HIP(hipStreamWaitEvent(st, ev, 0)); }
@@ -329,6 +334,7 @@ DeviceInput* run_tail(Run& run, RunTailIn& t, hipStream_t st) {
   DeviceInput* din = make_device_input_resident(meta, t.bundles, t.d_acc, t.d_cu, init_rows, fin_rows, tree[0], tree[1],
                                                 reinterpret_cast<const PublicEntry*>(land + pub_off));
   // ---- the advance, behind everything that read the old image ----
+  run.img_tree.release(); run.n_img_tree = 0;   // (its readers were waited for inside cm_run_open_memory)
   run.n_lo = end.n_lo; run.n_hi = end.n_hi;
   hipLaunchKernelGGL(k_run_advance, grid1(n_cells), dim3(256), 0, st, cells, n_cells, t.d_mem.u32(), end, run.lo.as<uint4>(), run.hi.as<uint4>());
   run.mark(st);
@@ -369,6 +375,38 @@ void run_memory(Run& r, uint32_t* locals, uint64_t cap_l, uint64_t* n_l, uint32_
   if (want_l) CM_HIP(hipMemcpyAsync(locals, r.lo.p, (size_t)r.n_lo * 16, hipMemcpyDeviceToHost, st));
   if (want_h) CM_HIP(hipMemcpyAsync(heap, r.hi.p, (size_t)r.n_hi * 16, hipMemcpyDeviceToHost, st));
   CM_HIP(hipStreamSynchronize(st));
+}
+// Openings under the root of the image as it is now (mem_open.hip): the leaves of every image cell (k_image_leaves) through the
+// device tree builder on first use — one round trip for the tree's size and root, one wait behind its copy into a right-sized
+// block — then one round trip per call for the records.
+void run_open_memory(Run& r, const uint32_t* addresses, uint64_t n, cm_mem_opening* out, uint32_t* root) {
+  bind_thread_to_library_device();
+  hipStream_t st = thread_main_stream();
+  const uint64_t cells = (uint64_t)r.n_lo + r.n_hi;
+  CM_CHECK(cells > 0, "cm_run_open_memory: the image is empty: there is no tree to open");
+  if (!r.img_tree.p) {
+    r.wait_on(st);   // the last advance may have been enqueued from another thread's stream
+    const uint32_t cap = (uint32_t)(4 * cells);
+    TreeJob j;
+    for (int k = 0; k < 3; k++) j.a[k].alloc((size_t)cap * 4);
+    j.state.alloc(sizeof(TreeState));
+    const TreeState s0{cap, 0};
+    stage_upload(j.state.p, &s0, sizeof(s0), st);
+    image_leaves_enqueue(r.lo.u32(), r.n_lo, r.hi.u32(), r.n_hi, j.a[0].u32(), j.a[1].u32(), j.a[2].u32(), st);
+    DevBuf nodes;
+    uint32_t* const pin3 = pinned_words() + PIN_LAST_LAYER + 56;
+    partial_merkle_tree_enqueue(j, cap, nodes, pin3, st);
+    CM_HIP(hipStreamSynchronize(st));
+    CM_CHECK(pin3[0] == 1, "partial merkle tree: did not converge to one root");
+    const uint64_t n_nodes = pin3[1];
+    const uint32_t img_root = pin3[2];
+    DevBuf exact(n_nodes * sizeof(cm_merkle_node) + 4);   // (the builder's block is sized for 30 nodes per leaf: see run_tail)
+    CM_HIP(hipMemcpyAsync(exact.p, nodes.p, n_nodes * sizeof(cm_merkle_node), hipMemcpyDeviceToDevice, st));
+    CM_HIP(hipStreamSynchronize(st));
+    r.img_tree = std::move(exact); r.n_img_tree = n_nodes; r.img_root = img_root;
+  }
+  *root = r.img_root;
+  open_paths(r.img_tree.as<cm_merkle_node>(), r.n_img_tree, addresses, n, out, st);
 }
 // an upper bound of the boundary-memory rows of the next segment, for the memory budget: the image and every logged access
 uint64_t run_rows_bound(const Run& r, uint64_t n_memory_trace) {

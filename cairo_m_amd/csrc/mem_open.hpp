@@ -1,0 +1,19 @@
+// Memory openings (mem_open.hip): what the run adapter (adapter_run.inc) needs of them.
+#pragma once
+#include "../../include/cairom_hip.h"
+#include "engine.hpp"
+
+namespace cm {
+
+// the leaves (4a + i, value_i, 1) of an image — lo dense from address 0, hi[i] = the cell at MAX_ADDRESS - i — in ascending index
+// order, 4 * (n_lo + n_hi) of them, for partial_merkle_tree_enqueue's device-pointer form.  Enqueued; waits for nothing.
+void image_leaves_enqueue(const uint32_t* lo, uint32_t n_lo, const uint32_t* hi, uint32_t n_hi, uint32_t* idx, uint32_t* val, uint32_t* mult,
+                          hipStream_t st);
+// out[i] = the opening of addresses[i] under the tree whose node list (depth 30..1, ascending index inside a depth) is `nodes`:
+// one upload, two launches, one download on `st`, which is waited for.  The addresses are below 2^28 (the caller checked).
+void open_paths(const cm_merkle_node* nodes, uint64_t n_nodes, const uint32_t* addresses, uint64_t n, cm_mem_opening* out, hipStream_t st);
+// status 1 unless (addresses, out) can take n openings and every address is below 2^28; status 3 without a device
+void open_require_device(const char* who);
+void open_check_addresses(const char* who, const uint32_t* addresses, uint64_t n, const cm_mem_opening* out);
+
+}  // namespace cm

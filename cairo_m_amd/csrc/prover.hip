@@ -164,6 +164,9 @@ void run_memory(Run& r, uint32_t* locals, uint64_t cap_l, uint64_t* n_l, uint32_
 uint64_t run_image_bytes(const Run& r);
 uint64_t run_rows_bound(const Run& r, uint64_t n_memory_trace);
 std::mutex& run_mutex(Run& r);
+void run_open_memory(Run& r, const uint32_t* addresses, uint64_t n, cm_mem_opening* out, uint32_t* root);
+void open_require_device(const char* who);   // mem_open.hip
+void open_check_addresses(const char* who, const uint32_t* addresses, uint64_t n, const cm_mem_opening* out);
 void run_free(Run* r);
 // copy a device-resident input back to the host (tests)
 void download_input(const DeviceInput& d, host::ProverInputOwned& o) {
@@ -1815,6 +1818,16 @@ int32_t cm_run_memory(const cm_run* r, uint32_t* locals, uint64_t cap_l, uint64_
     CM_CHECK(r && r->r, "cm_run_memory: null run");
     std::lock_guard<std::mutex> lk(cm::run_mutex(*r->r));
     cm::run_memory(*r->r, locals, cap_l, n_l, heap, cap_h, n_h);
+  });
+}
+// openings under the root of the image as it is now (mem_open.hip, adapter_run.inc); every refusal comes before the first write
+int32_t cm_run_open_memory(cm_run* r, const uint32_t* addresses, uint64_t n, cm_mem_opening* out, uint32_t* root) {
+  return pguard([&] {
+    cm::open_require_device("cm_run_open_memory");
+    CM_CHECK(r && r->r && root, "cm_run_open_memory: null argument");
+    cm::open_check_addresses("cm_run_open_memory", addresses, n, out);
+    std::lock_guard<std::mutex> lk(cm::run_mutex(*r->r));
+    cm::run_open_memory(*r->r, addresses, n, out, root);
   });
 }
 int32_t cm_run_free(cm_run* r) { delete r; return 0; }

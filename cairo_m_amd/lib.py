@@ -1383,3 +1383,89 @@ def check_run(backend, host_segments, relations=None, cap=64):
 Backend.check_run = lambda self, host_segments, relations=None, cap=64: check_run(self, host_segments, relations, cap)
 Backend.check_chain = lambda self, dev_inputs, cap=64: check_chain(dev_inputs, cap, self.L)
 Backend.link_diff = lambda self, prev, next, cap=64: link_diff(prev, next, cap, self.L)
+
+
+# ---- memory openings (include/cairom_hip.h, additive to revision 10) ----------------------------------------------
+ADDRESS_SPACE = 1 << 28
+
+
+class MemOpening(C.Structure):
+    """cm_mem_opening: one cell's value and its authentication path under a memory root (siblings[k] = depth 28 - k)."""
+    _fields_ = [("address", C.c_uint32), ("present", C.c_uint32), ("value", C.c_uint32 * 4), ("siblings", C.c_uint32 * 28)]
+
+    def words(self):
+        return [self.address, self.present] + list(self.value) + list(self.siblings)
+
+    @classmethod
+    def from_words(cls, words):
+        w = [int(x) for x in words]
+        return cls(w[0], w[1], (C.c_uint32 * 4)(*w[2:6]), (C.c_uint32 * 28)(*w[6:34]))
+
+    def __repr__(self):
+        return f"MemOpening(address={self.address}, present={self.present}, value={tuple(self.value)})"
+
+
+def _opening_array(openings):
+    """openings (a list of MemOpening, a ctypes array of them, or an (n, 34) word array) -> (ctypes array, n)"""
+    if isinstance(openings, C.Array):
+        return openings, len(openings)
+    if isinstance(openings, np.ndarray):
+        openings = [MemOpening.from_words(r) for r in openings.reshape(-1, 34)]
+    n = len(openings)
+    buf = (MemOpening * max(n, 1))()
+    for i, o in enumerate(openings):
+        C.memmove(C.byref(buf, i * C.sizeof(MemOpening)), C.byref(o), C.sizeof(MemOpening))
+    return buf, n
+
+
+def _open_call(L, fn, head, addresses):
+    a = np.ascontiguousarray(np.array(addresses, dtype=np.uint64).reshape(-1))
+    if a.size and int(a.max()) >= 1 << 32:
+        raise ValueError("an address does not fit 32 bits")
+    a = a.astype(np.uint32)
+    n = a.shape[0]
+    buf = (MemOpening * max(n, 1))()
+    root = C.c_uint32(0)
+    rc = fn(*head, _p(a) if n else None, C.c_uint64(n), buf if n else None, C.byref(root))
+    if rc:
+        raise _lib_error(L, rc)
+    return [_copy_struct(MemOpening, buf[i]) for i in range(n)], root.value
+
+
+def _backend_open_memory(self, dev_input, which, addresses):
+    """cm_input_open_memory: the openings of `addresses` under the input's initial (which = 0) or final (1) tree, built on the GPU
+    -> ([MemOpening], root)."""
+    return _open_call(self.L, self.L.cm_input_open_memory, (dev_input, C.c_uint32(which)), addresses)
+
+
+def _run_open(self, addresses):
+    """cm_run_open_memory: openings under the root of the image as it is now -> ([MemOpening], root).  The image's tree is built
+    on first use and dropped when the image advances."""
+    return _open_call(self.L, self.L.cm_run_open_memory, (self.h,), addresses)
+
+
+def verify_openings(root, openings, lib=None, stream=0):
+    """cm_verify_memory_openings (GPU, batched) -> [bool], one per opening."""
+    L = lib or load_library()
+    buf, n = _opening_array(openings)
+    ok = (C.c_uint8 * max(n, 1))()
+    rc = L.cm_verify_memory_openings(C.c_uint32(root), buf if n else None, C.c_uint64(n), ok if n else None, C.c_uint64(stream))
+    if rc:
+        raise _lib_error(L, rc)
+    return [bool(ok[i]) for i in range(n)]
+
+
+def verify_opening(root, opening, lib=None):
+    """cm_verify_memory_opening (host code, no GPU) -> (status, message): (0, "") accepted, (11, why) rejected."""
+    L = lib or load_library()
+    rc = L.cm_verify_memory_opening(C.c_uint32(root), C.byref(opening))
+    if not rc:
+        return 0, ""
+    buf = C.create_string_buffer(512)
+    L.cm_last_error(buf, C.c_size_t(512))
+    return rc, buf.value.decode(errors="replace")
+
+
+Backend.open_memory = _backend_open_memory
+Backend.verify_openings = lambda self, root, openings, stream=0: verify_openings(root, openings, self.L, stream)
+Run.open = _run_open

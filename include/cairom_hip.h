@@ -35,7 +35,9 @@
  *    cm_prove_run, cm_proof_public_data, cm_proof_public_entries, cm_verify_run, cm_host_segment_end_lengths.
  *    Still 10 (additive: new symbols and one struct, nothing moved): cm_verify_result, CM_VERIFY_*, cm_verify_many,
  *    cm_verify_run_device, cm_verify_many_timing; cm_link_cell, cm_link_report, cm_run_check, cm_link_diff, cm_check_chain,
- *    cm_check_run. */
+ *    cm_check_run.
+ *    Still 10 (additive: four new functions and one struct, nothing moved): cm_mem_opening, cm_input_open_memory, cm_run_open_memory,
+ *    cm_verify_memory_openings, cm_verify_memory_opening. */
 #define CM_ABI_REVISION 10
 
 #ifdef __cplusplus
@@ -811,6 +813,45 @@ int32_t cm_check_chain(const cm_device_input* const* inputs, uint32_t n, cm_run_
  * front of it are filled, the image is left at that segment's start, and the run may be continued from there. */
 int32_t cm_check_run(cm_run* r, const cm_run_segment* const* segs, uint32_t n, const cm_relations* relations, cm_run_check* out,
                      cm_link_cell* cells, uint64_t cap_per_link);
+/* ---- memory openings (additive to revision 10: new symbols and one struct, nothing moved) --------------------------------------
+ * A memory root commits to every cell; an opening is one cell's value plus its authentication path, checkable without the
+ * memory: a heap result outside the output range, a checkpoint image shown to be the one the proofs end in, one cell for a bridge.
+ * The tree (adapter/merkle.rs:183-295) has height 30: cell a < 2^28 owns the leaves 4a .. 4a + 3, the four words of its value;
+ * h29_0 = H(v0, v1), h29_1 = H(v2, v3), n28 = H(h29_0, h29_1) is the node of depth 28 with index a; above it there is one sibling
+ * per depth 28 .. 1 (at depth d the path's node has index a >> (28 - d) and is the right child when that index is odd).  A node
+ * the tree does not hold is the default hash of its depth (default[30] = 0, default[d] = H(default[d + 1], default[d + 1])), so the
+ * root is a function of the non-zero cells only: an absent cell opens as the value (0, 0, 0, 0), and a cell the tree holds with
+ * that value may be claimed with present = 1 or 0 alike.  Multiplicities enter no hash.
+ *
+ * cm_input_open_memory / cm_run_open_memory build out[i] = the opening of addresses[i] on the GPU, on the calling thread's stream
+ * and pool (threading as cm_link_diff): the addresses go up, two launches bisect the tree's node list (ordered by depth 30 .. 1,
+ * then by index), the records come back: one host round trip per call.  Addresses may repeat and come in any order; the same
+ * call gives the same bytes.  n == 0 is status 0 (out may be NULL) and *root is still written.  Status 1, with nothing written
+ * to out: an address >= 2^28, which > 1, a NULL argument, a run whose image is empty.  Without a GPU the status is cm_init's (3).
+ * cm_verify_memory_openings recomputes the 31 hashes of every record on the GPU, one lane per record (upload, one launch,
+ * download on stream s; 0 = the calling thread's own stream): ok[i] = 1 when record i hashes to `root`.  A record with an address
+ * >= 2^28, present > 1, a word >= P, or present = 0 with a non-zero value gets ok[i] = 0; it does not fail the call.
+ * cm_verify_memory_opening is the same check of one record in host code, for a light client: it needs no GPU. */
+typedef struct {
+  uint32_t address;
+  uint32_t present;         /* 1: the tree holds the cell; 0: absent, value is (0, 0, 0, 0) */
+  uint32_t value[4];
+  uint32_t siblings[28];    /* siblings[k] = the sibling at depth 28 - k */
+} cm_mem_opening;           /* sizeof = 136 */
+/* which: 0 = the input's initial tree, 1 = its final tree.  *root receives that tree's root. */
+int32_t cm_input_open_memory(const cm_device_input* in, uint32_t which, const uint32_t* addresses, uint64_t n, cm_mem_opening* out,
+                             uint32_t* root);
+/* Under the root of the run's image as it is now (= the final root of the last adapted segment = the initial root of the next).
+ * The image's tree is built on first use (every image cell through the device tree builder: one more round trip and one wait)
+ * and dropped, not rebuilt, when the image advances; cm_mem_stats counts it while it lives.  A run that never calls this pays
+ * nothing for it.  Serialised with the other calls on the run. */
+int32_t cm_run_open_memory(cm_run* r, const uint32_t* addresses, uint64_t n, cm_mem_opening* out, uint32_t* root);
+/* GPU, batched: ok[i] in {0, 1}; returns 0 when it ran. */
+int32_t cm_verify_memory_openings(uint32_t root, const cm_mem_opening* openings, uint64_t n, uint8_t* ok, cm_stream_t s);
+/* Host code, no GPU: 0 accepted, 11 rejected.  cm_last_error() then reads "memory opening of address <a>: " and what is wrong:
+ * the field that makes the record malformed with its depth (a value word: depth 30; "the sibling at depth <d>"), or, for a
+ * well-formed record, "the path hashes to root <x>, not <y>". */
+int32_t cm_verify_memory_opening(uint32_t root, const cm_mem_opening* opening);
 /* AccumulationOps::accumulate: dst[k][i] += src[k][i] (4 coordinate columns of n words); generate_secure_powers:
  * out[i] = felt^i for i < n (host array of 4 * n words).  Column::zeros = cm_col_alloc + cm_col_zero. */
 int32_t cm_accumulate(const cm_handle dst[4], const cm_handle src[4], uint64_t n, cm_stream_t s);

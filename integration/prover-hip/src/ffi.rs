@@ -320,6 +320,17 @@ pub struct cm_run_check {
     pub link_cells_written: u64,
     pub link_cells_total: u64,
 }
+/// One cell's value and its authentication path under a 31-bit memory root (`cm_input_open_memory`, `cm_run_open_memory`):
+/// `siblings[k]` is the sibling at depth 28 - k; an absent cell (`present` = 0) opens as the value (0, 0, 0, 0)
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct cm_mem_opening {
+    pub address: u32,
+    pub present: u32,
+    pub value: [u32; 4],
+    pub siblings: [u32; 28],
+}
+pub type CmMemOpening = cm_mem_opening;
 
 unsafe extern "C" {
     pub fn cm_init(device: i32) -> i32;
@@ -429,6 +440,10 @@ unsafe extern "C" {
     pub fn cm_link_diff(prev: *const cm_device_input, next: *const cm_device_input, report: *mut cm_link_report, cells: *mut cm_link_cell, cap: u64, n_total: *mut u64) -> i32;
     pub fn cm_check_chain(inputs: *const *const cm_device_input, n: u32, out: *mut cm_run_check, cells: *mut cm_link_cell, cap_per_link: u64) -> i32;
     pub fn cm_check_run(r: *mut cm_run, segs: *const *const cm_run_segment, n: u32, relations: *const cm_relations, out: *mut cm_run_check, cells: *mut cm_link_cell, cap_per_link: u64) -> i32;
+    pub fn cm_input_open_memory(input: *const cm_device_input, which: u32, addresses: *const u32, n: u64, out: *mut cm_mem_opening, root: *mut u32) -> i32;
+    pub fn cm_run_open_memory(r: *mut cm_run, addresses: *const u32, n: u64, out: *mut cm_mem_opening, root: *mut u32) -> i32;
+    pub fn cm_verify_memory_openings(root: u32, openings: *const cm_mem_opening, n: u64, ok: *mut u8, s: cm_stream_t) -> i32;
+    pub fn cm_verify_memory_opening(root: u32, opening: *const cm_mem_opening) -> i32;
     pub fn cm_relation_sums(component: i32, trace_cols: *const cm_handle, preprocessed: *const cm_handle, log_size: u32, relations: *const cm_relations, sums: *mut [u32; 4], s: cm_stream_t) -> i32;
     pub fn cm_accumulate(dst: *const cm_handle, src: *const cm_handle, n: u64, s: cm_stream_t) -> i32;
     pub fn cm_generate_secure_powers(felt: *const u32, n: u64, out: *mut u32) -> i32;

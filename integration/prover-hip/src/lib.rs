@@ -391,6 +391,34 @@ pub fn assert_run_constraints(
     Err(RunConstraintFailure { records, cells, cap_per_link, message: last_error() })
 }
 
+/// The openings of `addresses` under the initial (`which` = 0) or final (1) memory root of a device-resident input
+/// (`cm_input_open_memory`), built on the GPU: the records and that root.  Every address is below 2^28; an absent cell opens as
+/// the value zero.  A record is checked without the memory by `verify_memory_openings` (GPU, batched) or by
+/// `ffi::cm_verify_memory_opening` (host code).
+pub fn open_memory(input: *const cm_device_input, which: u32, addresses: &[u32]) -> Result<(Vec<CmMemOpening>, u32), String> {
+    ensure_init();
+    let mut out: Vec<CmMemOpening> = vec![unsafe { std::mem::zeroed() }; addresses.len()];
+    let mut root: u32 = 0;
+    let out_ptr = if addresses.is_empty() { std::ptr::null_mut() } else { out.as_mut_ptr() };
+    let rc = unsafe { cm_input_open_memory(input, which, addresses.as_ptr(), addresses.len() as u64, out_ptr, &mut root) };
+    if rc != 0 {
+        return Err(last_error());
+    }
+    Ok((out, root))
+}
+
+/// Every opening checked against `root` on the GPU in one batch (`cm_verify_memory_openings`): one verdict per record; a malformed
+/// record is a `false`, not an error.
+pub fn verify_memory_openings(root: u32, openings: &[CmMemOpening]) -> Result<Vec<bool>, String> {
+    ensure_init();
+    let mut ok: Vec<u8> = vec![0; openings.len()];
+    let rc = unsafe { cm_verify_memory_openings(root, openings.as_ptr(), openings.len() as u64, ok.as_mut_ptr(), 0) };
+    if rc != 0 {
+        return Err(last_error());
+    }
+    Ok(ok.iter().map(|v| *v != 0).collect())
+}
+
 /// Twin of `debug_tools::relation_tracker::track_and_summarize_relations` (relation_tracker.rs:21-31, the `.cleaned()` summary) on
 /// the GPU: relation name -> the tuples (values without trailing zeros) whose multiplicities do not sum to zero, with their net
 /// multiplicity.  Only the relations whose sums do not cancel are tracked, so a valid input returns an empty map at the cost of

@@ -1,0 +1,104 @@
+#!/usr/bin/env python3
+"""Measurement of the memory openings (cm_run_open_memory, cm_verify_memory_openings, cm_verify_memory_opening) for a maintainer
+with a GPU: on an image of --cells cells (locals and a heap, random values) it opens --queries random addresses.
+
+    python tools/open_report.py --out profiles/<set>_open_report.json
+
+One process, one GPU session.  Recorded, wall ms:
+  open_first   cm_run_open_memory on a fresh run: the image's tree is built (every cell through the device tree builder), then the
+               paths are extracted;
+  open_cached  the same call again with the tree cached: upload of the addresses, two launches, download of the records;
+  verify_gpu   cm_verify_memory_openings over the records (upload, one launch, download);
+  verify_host  a loop of the host cm_verify_memory_opening over the same records in the same process (one ctypes call each).
+No threshold: these are first measurements."""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def stats(v):
+    return {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4), "n": len(v)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cells", type=int, default=1 << 18)
+    ap.add_argument("--heap", type=int, default=1 << 12, help="cells of the image that lie in the heap")
+    ap.add_argument("--queries", type=int, default=1 << 16)
+    ap.add_argument("--runs", type=int, default=3, help="fresh runs (each gives one open_first)")
+    ap.add_argument("--calls", type=int, default=5, help="timed calls of the cached opening and of the GPU verifier per run")
+    ap.add_argument("--out")
+    a = ap.parse_args()
+    from cairo_m_amd import Backend
+    from cairo_m_amd.lib import MemOpening
+    be = Backend(0)
+    L = be.L
+    rng = np.random.default_rng(1)
+    p = (1 << 31) - 1
+    lo = rng.integers(0, p, (a.cells - a.heap, 4)).astype(np.uint32)
+    hp = rng.integers(0, p, (a.heap, 4)).astype(np.uint32)
+    lo[0] = [11, 0, 0, 0]
+    # half of the queries inside the image, half anywhere in the address space (mostly absent cells)
+    inside = np.concatenate([rng.integers(0, lo.shape[0], a.queries // 4), (1 << 28) - 1 - rng.integers(0, a.heap, a.queries // 4)])
+    addrs = np.concatenate([inside, rng.integers(0, 1 << 28, a.queries - inside.size)]).astype(np.uint32)
+    rng.shuffle(addrs)
+    t = {"open_first": [], "open_cached": [], "verify_gpu": [], "verify_host": []}
+    n_ok = None
+    for r in range(a.runs + 1):                                                   # (run 0 warms the pool and the code objects)
+        run = be.run_begin(lo, hp, [0, 1, 1, 1, 1, 1])
+        n = addrs.shape[0]
+        ap_, buf, again = addrs.ctypes.data_as(C.c_void_p), (MemOpening * n)(), (MemOpening * n)()
+        ok, root, root2 = (C.c_uint8 * n)(), C.c_uint32(0), C.c_uint32(0)
+
+        def timed(fn, *args):                                                     # the C call alone, without the Python wrappers' copies
+            t0 = time.perf_counter()
+            rc = fn(*args)
+            dt = (time.perf_counter() - t0) * 1e3
+            assert rc == 0, rc
+            return dt
+
+        first = timed(L.cm_run_open_memory, run.h, ap_, C.c_uint64(n), buf, C.byref(root))
+        cached = [timed(L.cm_run_open_memory, run.h, ap_, C.c_uint64(n), again, C.byref(root2)) for _ in range(a.calls)]
+        assert root2.value == root.value and bytes(again) == bytes(buf)
+        gpu = [timed(L.cm_verify_memory_openings, root, buf, C.c_uint64(n), ok, C.c_uint64(0)) for _ in range(a.calls)]
+        assert all(ok)
+        n_ok = n
+        root = root.value
+        run.free()
+        if r == 0:
+            continue
+        t["open_first"].append(first)
+        t["open_cached"] += cached
+        t["verify_gpu"] += gpu
+        if r == 1:                                                                # the host loop once: it is seconds long
+            fn, size, base = L.cm_verify_memory_opening, C.sizeof(MemOpening), C.addressof(buf)
+            fn.argtypes = [C.c_uint32, C.c_void_p]
+            t0 = time.perf_counter()
+            bad = 0
+            for i in range(n):
+                bad += fn(root, base + i * size)
+            t["verify_host"].append((time.perf_counter() - t0) * 1e3)
+            fn.argtypes = None
+            assert bad == 0
+    rep = {"cells": a.cells, "heap_cells": a.heap, "queries": a.queries, "accepted": n_ok, "ms": {k: stats(v) for k, v in t.items()}}
+    rep["tree_build_ms"] = round(rep["ms"]["open_first"]["median"] - rep["ms"]["open_cached"]["median"], 4)
+    rep["verify_host_over_gpu"] = round(rep["ms"]["verify_host"]["median"] / rep["ms"]["verify_gpu"]["median"], 2)
+    rep["us_per_opening"] = {k: round(1e3 * rep["ms"][k]["median"] / a.queries, 4) for k in ("open_cached", "verify_gpu", "verify_host")}
+    text = json.dumps(rep, indent=1)
+    print(text)
+    if a.out:
+        open(a.out, "w").write(text + "\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
