@@ -50,6 +50,11 @@ def test_hip_witness_equals_reference_derived_cells(backend):
     assert np.array_equal(got, GOLD["poseidon2"][:, :192])
     for h in cols:
         backend.col_free(h)
+    # the four multiplicity columns against bincounts of the reference closures' recorded lookup_data (air_lookup_vectors.npz)
+    from tests.test_gpu_air_edge_golden import check_histogram
+    lookups = np.load(os.path.join(ROOT, "tests", "golden", "air_lookup_vectors.npz"))
+    assert int(lookups["iters"][0]) == int(GOLD["iters"][0]) and int(lookups["seed"][0]) == int(GOLD["seed"][0])
+    check_histogram(backend, dev, lookups, "all-opcode program")
     backend.free_input(dev)
     inp.free()
 

@@ -21,7 +21,8 @@ finalize_last prefix-sums the LAST column over the rows), plus `rel_z`, `rel_alp
 tests/test_gpu_logup_golden.py feeds the reference-derived TRACE (air_witness_vectors.npz) to the HIP k_logup through
 cm_interaction_write and compares.
 
-Usage (build container only):  python tools/rsref/rs_logup.py"""
+Usage (build container only):  python tools/rsref/rs_logup.py [--program all|edge] [--out PATH]
+(`--program edge`: tests/edge_programs.py::edge_program -> tests/golden/air_logup_edge.npz, opcode components + memory)"""
 import os
 import random
 import re
@@ -221,10 +222,10 @@ def logup_table(src, name, per_row, n_rows, relations):
     return cum
 
 
-def main():
+def main(program="all", out_path=None):
     from cairo_m_amd.lib import prover_input_arrays, vm_run
-    from cairo_m_amd.workloads import all_opcodes_program
-    prog, steps = all_opcodes_program(W.ITERS, W.SEED)
+    assert program in ("all", "edge"), "div0 is witness-only"
+    prog, steps, params, edges = W.load_program(program)
     inp = vm_run(prog, entry_pc=0, args=(), n_returns=0)
     arrs = prover_input_arrays(inp.view)
     consts = opcode_constants()
@@ -234,8 +235,8 @@ def main():
     relations = Relations()
     for k in REL_ORDER:
         setattr(relations, k, Relation(rel_z[k], rel_a[k]))
-    out = {"iters": np.array([W.ITERS]), "seed": np.array([W.SEED]),
-           "rel_z": np.array([rel_z[k] for k in REL_ORDER], dtype=np.uint32), "rel_alpha": np.array([rel_a[k] for k in REL_ORDER], dtype=np.uint32)}
+    out = {"iters": np.array([W.ITERS]), "seed": np.array([W.SEED])} if edges is None else {"steps": params["steps"], "program": params["program"]}
+    out.update({"rel_z": np.array([rel_z[k] for k in REL_ORDER], dtype=np.uint32), "rel_alpha": np.array([rel_a[k] for k in REL_ORDER], dtype=np.uint32)})
     for cid, fname in enumerate(W.OPCODE_FILES):
         bundles = arrs[f"bundles{cid}"]
         lookups = []
@@ -248,11 +249,19 @@ def main():
     # the builtins with a regular closure (rows as in rs_witness.py: memory, merkle, synthetic clock updates)
     consts2, mem, tree, cu = W.builtin_inputs(arrs, consts)
     for name, rows in (("memory", mem), ("merkle", tree), ("clock_update", cu)):
+        if edges is not None and name != "memory":
+            continue           # merkle: ~8000 rows of QM31 words that do not compress, and no row of it carries an opcode operand
         lookups = []
         cols = W.interpret_builtin(name, rows, len(rows), consts2, keep_lookup=lookups)
         src = strip_comments(open(f"{REF}/prover/src/components/{name}.rs").read())
         out[name] = logup_columns(src, lookups, cols.shape[1], len(rows), consts2, relations)
         print(f"   {name:28s} {len(rows):4d} live rows, {out[name].shape[0]} LogUp columns x {cols.shape[1]} rows")
+    if edges is not None:      # the edge program: the 26 opcode components and memory only
+        inp.free()
+        path = out_path or os.path.join(ROOT, "tests", "golden", "air_logup_edge.npz")
+        np.savez_compressed(path, **out)
+        print("wrote", path, os.path.getsize(path), "bytes")
+        return
     # poseidon2: the 200 hash inputs of the witness golden (rs_poseidon2.py), its closure through the full interpreter
     import rs_poseidon2 as P2
     p2src, p2interp, p2g = P2.make_interp()
@@ -283,10 +292,10 @@ def main():
         out[name + "_values"], out[name + "_mults"] = vals.astype(np.uint32), mults.astype(np.uint32)
         print(f"   {name:28s} {n_tab:4d} rows, {out[name].shape[0]} LogUp column")
     inp.free()
-    path = os.path.join(ROOT, "tests", "golden", "air_logup_vectors.npz")
+    path = out_path or os.path.join(ROOT, "tests", "golden", "air_logup_vectors.npz")
     np.savez_compressed(path, **out)
     print("wrote", path, os.path.getsize(path), "bytes")
 
 
 if __name__ == "__main__":
-    main()
+    W.cli(main)

@@ -16,7 +16,9 @@ same program through the VM + adapter, asks the oracle for each component's trac
 (live AND padding rows).  store_fp_fp / store_fp_imm derive per-lane hints in a closure over the unpacked bundles in
 front of the row closure: both closures are interpreted (interpret_prepacked).
 
-Usage (build container only):  python tools/rsref/rs_witness.py
+Usage (build container only):  python tools/rsref/rs_witness.py [--program all|edge|div0] [--out PATH] [--lookups PATH]
+`--program edge` / `div0` run tests/edge_programs.py instead and write tests/golden/air_witness_edge.npz / air_witness_div0.npz:
+the same cells plus the program, its `edges` table and the closures' range-check / bitwise `lookup_data`.
 """
 import os
 import re
@@ -276,32 +278,97 @@ def builtin_inputs(arrs, consts):
     return consts2, mem, tree, cu
 
 
-def main():
+LOOKUP_KINDS = ("range_check_8", "range_check_16", "range_check_20", "bitwise")
+
+
+def load_program(name):
+    """-> (program, steps, parameters stored with the vectors, edges or None).  `all`: the all-opcode program of the two
+    original fixtures; `edge` / `div0`: tests/edge_programs.py (stored with the vectors word by word, so that a test can tell a
+    changed generator from a changed witness)."""
+    if name == "all":
+        from cairo_m_amd.workloads import all_opcodes_program
+        prog, steps = all_opcodes_program(ITERS, SEED)
+        return prog, steps, {"iters": np.array([ITERS]), "seed": np.array([SEED]), "steps": np.array([steps])}, None
+    from tests.edge_programs import div_by_zero_program, edge_program
+    prog, steps, edges = {"edge": edge_program, "div0": div_by_zero_program}[name]()
+    words = np.full((len(prog), 7), -1, dtype=np.int64)
+    for k, ins in enumerate(prog):
+        words[k, 0], words[k, 1:1 + len(ins)] = len(ins), ins
+    params = {"steps": np.array([steps]), "program": words, "edge_names": np.array([e[0] for e in edges]),
+              "edge_cid": np.array([e[1] for e in edges]), "edge_row": np.array([e[2] for e in edges])}
+    return prog, steps, params, edges
+
+
+def lookup_rows(cid, lookups):
+    """the closure's `lookup_data` of one component as rows (component id, tuple...) per kind, every lane of every packed row
+    (padding lanes included: the reference counts their range-check and bitwise look-ups like any other)"""
+    out = {}
+    for kind in LOOKUP_KINDS:
+        rows = []
+        for ld in lookups:
+            for idx in sorted(getattr(ld, kind).d):
+                val = getattr(ld, kind).d[idx]
+                vals = val if isinstance(val, (list, tuple)) else [val]
+                for lane in range(N_LANES):
+                    rows.append([cid] + [v.lanes[lane].v for v in vals])
+        out[kind] = rows
+    return out
+
+
+DEFAULT_OUT = {"all": "air_witness_vectors.npz", "edge": "air_witness_edge.npz", "div0": "air_witness_div0.npz"}
+
+
+def main(program="all", out_path=None, lookups_path=None):
     from cairo_m_amd.lib import prover_input_arrays, vm_run
-    from cairo_m_amd.workloads import all_opcodes_program
-    prog, steps = all_opcodes_program(ITERS, SEED)
+    prog, steps, out, edges = load_program(program)
     inp = vm_run(prog, entry_pc=0, args=(), n_returns=0)
     assert inp.steps == steps
     arrs = prover_input_arrays(inp.view)
     consts = opcode_constants()
-    out = {"iters": np.array([ITERS]), "seed": np.array([SEED]), "steps": np.array([steps])}
+    lookup = {k: [] for k in LOOKUP_KINDS}
     for cid, fname in enumerate(OPCODE_FILES):
-        cols = interpret_component(fname, arrs[f"bundles{cid}"], arrs["data_accesses"], consts)
+        kept = [] if edges is not None or lookups_path else None
+        cols = interpret_component(fname, arrs[f"bundles{cid}"], arrs["data_accesses"], consts, keep_lookup=kept)
         if cols is None:       # store_fp_fp / store_fp_imm: per-lane hints computed in a pre-pack closure
-            cols = interpret_prepacked(fname, arrs[f"bundles{cid}"], arrs["data_accesses"], consts)
+            cols = interpret_prepacked(fname, arrs[f"bundles{cid}"], arrs["data_accesses"], consts, keep_lookup=kept)
         out[fname] = cols
+        if kept is not None:
+            for k, rows in lookup_rows(cid, kept).items():
+                lookup[k] += rows
         print(f"{cid:2d} {fname:28s} {arrs[f'bundles{cid}'].shape[0]:4d} live rows -> {cols.shape[0]} columns x {cols.shape[1]} rows")
     # builtins with a regular closure: memory (rows = initial ++ final cells), merkle (initial ++ final tree nodes), clock_update
     consts2, mem, tree, cu = builtin_inputs(arrs, consts)
     for name, rows in (("memory", mem), ("merkle", tree), ("clock_update", cu)):
+        if edges is not None and name == "clock_update":
+            continue           # synthetic entries, not this program's: pinned once, with the all-opcode vectors
         out[name] = interpret_builtin(name, rows, len(rows), consts2)
         print(f"   {name:28s} {len(rows):4d} live rows -> {out[name].shape[0]} columns x {out[name].shape[1]} rows")
-    out["clock_update_input"] = cu.astype(np.uint32)
+    if edges is None:
+        out["clock_update_input"] = cu.astype(np.uint32)
+    else:
+        for k in LOOKUP_KINDS:
+            out["lookup_" + k] = np.array(lookup[k], dtype=np.uint32).reshape(len(lookup[k]), -1)
     inp.free()
-    path = os.path.join(ROOT, "tests", "golden", "air_witness_vectors.npz")
+    if lookups_path:           # the all-opcode program's look-ups go to a file of their own: its witness fixture stays as it is
+        np.savez_compressed(lookups_path, iters=out["iters"], seed=out["seed"],
+                            **{"lookup_" + k: np.array(lookup[k], dtype=np.uint32).reshape(len(lookup[k]), -1) for k in LOOKUP_KINDS})
+        print("wrote", lookups_path, os.path.getsize(lookups_path), "bytes")
+    path = out_path or os.path.join(ROOT, "tests", "golden", DEFAULT_OUT[program])
     np.savez_compressed(path, **out)
     print("wrote", path, os.path.getsize(path), "bytes")
 
 
+def cli(main_fn, with_lookups=False):
+    import argparse
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--program", choices=("all", "edge", "div0"), default="all")
+    ap.add_argument("--out", default=None, help="output path (default: the fixture under tests/golden/)")
+    if with_lookups:
+        ap.add_argument("--lookups", default=None, help="with --program all: also write the closures' range-check / bitwise "
+                        "lookup_data there (tests/golden/air_lookup_vectors.npz)")
+    a = ap.parse_args()
+    main_fn(a.program, a.out, *([a.lookups] if with_lookups else []))
+
+
 if __name__ == "__main__":
-    main()
+    cli(main, with_lookups=True)
