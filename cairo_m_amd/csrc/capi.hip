@@ -3,6 +3,7 @@
 // engine, map C++ exceptions to status codes + a thread-local error string.
 #include "../../include/cairom_hip.h"
 #include "engine.hpp"
+#include "fft_pass.hpp"
 #include "merkle_tree.hpp"
 #include "framing.hpp"
 #include <string.h>
@@ -276,6 +277,24 @@ int32_t cm_interpolate_extend(const cm_handle* evals, const cm_handle* coeffs, c
     DevBuf dl = upload(ptrs(lde, n_cols), S(s));
     interpolate_extend(de.as<const uint32_t*>(), dc.as<uint32_t*>(), dl.as<uint32_t*>(), n_cols, log_n, *(Twiddles*)(uintptr_t)tw, S(s));
     CM_HIP(hipStreamSynchronize(S(s)));
+  });
+}
+int32_t cm_fft_plan(uint32_t log_n, uint32_t out[8][4], uint32_t* n_passes) {
+  return guard([&] {
+    CM_CHECK(out && n_passes, "cm_fft_plan: null output");
+    CM_CHECK(log_n >= 1 && log_n <= 28, "cm_fft_plan: log size out of range (1..28)");
+    static_assert(FFT_MAX_PASSES == 8, "cm_fft_plan's out[8][4]");
+    FftPassShape p[FFT_MAX_PASSES];
+    const uint32_t np = fft_plan(log_n, p);
+    for (uint32_t i = 0; i < np; i++) { out[i][0] = p[i].lo; out[i][1] = p[i].hi; out[i][2] = p[i].tile_log; out[i][3] = p[i].M; }
+    *n_passes = np;
+  });
+}
+int32_t cm_fft_extend_fused(uint32_t log_n, uint32_t* fused) {
+  return guard([&] {
+    CM_CHECK(fused, "cm_fft_extend_fused: null output");
+    CM_CHECK(log_n >= 1 && log_n <= 27, "cm_fft_extend_fused: log size out of range (1..27)");
+    *fused = fft_extend_fused(log_n) ? 1u : 0u;
   });
 }
 int32_t cm_eval_at_point(const cm_handle* coeffs, uint32_t n_cols, uint32_t log_n, const uint32_t pt_xy[8],

@@ -27,4 +27,14 @@ struct FftPassArgs {
 uint32_t fft_pass_rb_tile_log(uint32_t W, uint32_t lo);
 void launch_fft_pass_rb(bool inverse, const FftPassArgs& a, uint32_t tile_log, uint32_t ntiles, uint32_t ncols, hipStream_t st);
 
+// The shape of a 2^n transform (n <= 28), decided on the host without a GPU call (kernels_poly.hip): passes in layer order (an
+// inverse transform runs them first to last, a forward one last to first), per pass the layers [lo, hi), the tile log of the
+// kernel that runs it (0 = the generic LDS-sweep kernel) and M.  Returns the number of passes.  Every launch goes through it,
+// and cm_fft_plan / cm_fft_extend_fused hand it to the tests, so what they read is what runs.
+constexpr uint32_t FFT_MAX_PASSES = 8;
+struct FftPassShape { uint32_t lo, hi, tile_log, M; };
+uint32_t fft_plan(uint32_t n, FftPassShape out[FFT_MAX_PASSES]);
+// whether interpolate_extend takes the fused sweep (k_fft_fused_rb) at 2^n rows under the current tuning ("fft_fused")
+bool fft_extend_fused(uint32_t n);
+
 }  // namespace cm

@@ -5,10 +5,10 @@
 // every thread keeps 2^E of them in registers, applying up to E layers (radix 2^E) before the tile is re-distributed
 // through LDS.  Three shapes are instantiated:
 //
-//   TL = 11, E = 3   256 threads, 8 KiB tile     strided passes of 1..7 layers (M >= 4: 64-B runs and longer)
+//   TL = 11, E = 3   256 threads, 8 KiB tile     strided passes of 1..5 layers (M >= 6: 256-B runs and longer)
 //   TL = 12, E = 4   256 threads, 16 KiB tile    the contiguous pass: 12 layers in three radix-16 rounds
 //   TL = 13, E = 5   256 threads, 32 KiB tile    contiguous pass of 13 layers (5 + 3 + 5) for 22-layer transforms
-//   TL = 14, E = 4   1024 threads, 64 KiB tile   strided passes of 6..10 layers (two blocks per CU in the 160 KiB LDS)
+//   TL = 14, E = 4   1024 threads, 64 KiB tile   strided passes of 6..9 layers (two blocks per CU in the 160 KiB LDS)
 //
 // so that a 2^21 / 2^22 transform is TWO sweeps over HBM (12 + 9 / 13 + 9 layers) instead of three (11 + 5 + 5 /
 // 11 + 6 + 5) and a layer costs fewer LDS exchanges (a pass of 9-13 layers has 3 rounds; the radix-8 form needed 4).
@@ -296,8 +296,6 @@ static void launch_w(const FftPassArgs& a, uint32_t tile_log, uint32_t ntiles, u
       case 3: launch_one<INV, 3, 11, 3>(a, ntiles, ncols, st); break;
       case 4: launch_one<INV, 4, 11, 3>(a, ntiles, ncols, st); break;
       case 5: launch_one<INV, 5, 11, 3>(a, ntiles, ncols, st); break;
-      case 6: launch_one<INV, 6, 11, 3>(a, ntiles, ncols, st); break;
-      case 7: launch_one<INV, 7, 11, 3>(a, ntiles, ncols, st); break;
       case 11: launch_one<INV, 11, 11, 3>(a, ntiles, ncols, st); break;
       default: break;
     }
@@ -311,7 +309,6 @@ static void launch_w(const FftPassArgs& a, uint32_t tile_log, uint32_t ntiles, u
       case 7: launch_one<INV, 7, 14, 4>(a, ntiles, ncols, st); break;
       case 8: launch_one<INV, 8, 14, 4>(a, ntiles, ncols, st); break;
       case 9: launch_one<INV, 9, 14, 4>(a, ntiles, ncols, st); break;
-      case 10: launch_one<INV, 10, 14, 4>(a, ntiles, ncols, st); break;
       default: break;
     }
   }
@@ -319,11 +316,11 @@ static void launch_w(const FftPassArgs& a, uint32_t tile_log, uint32_t ntiles, u
 // tile log the register-blocked kernels serve a pass with, 0 = none (the generic LDS-sweep kernel takes it)
 // Strided passes: the longer the contiguous runs (2^M words), the closer the pass gets to the HBM stream rate — measured on
 // 64 columns x 2^22 (tools/fft_lab.hip): 64-B runs (M = 4) 3.5 TB/s, 128-B runs 4.4 TB/s, 256-B runs 5.0 TB/s read + write.
-// So passes of 6 layers and more use the 2^14 tile (M = 8..4), shorter ones the 2^11 tile (M >= 6).
+// So passes of 6 to 9 layers use the 2^14 tile (M = 8..5), shorter ones the 2^11 tile (M >= 6).
 uint32_t fft_pass_rb_tile_log(uint32_t W, uint32_t lo) {
   if (lo == 0) return (W >= 11 && W <= 13) ? W : 0u;
-  if (W >= 6 && W <= 10 && lo >= 14 - W) return 14u;
-  if (W >= 1 && W <= 7 && lo >= 11 - W) return 11u;
+  if (W >= 6 && W <= 9 && lo >= 14 - W) return 14u;
+  if (W >= 1 && W <= 5 && lo >= 11 - W) return 11u;
   return 0u;
 }
 void launch_fft_pass_rb(bool inverse, const FftPassArgs& a, uint32_t tile_log, uint32_t ntiles, uint32_t ncols, hipStream_t st) {

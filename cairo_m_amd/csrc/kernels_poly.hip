@@ -462,28 +462,43 @@ constexpr uint32_t FFT_TILE_LOG = 11;        // tile of the generic LDS-sweep ke
 constexpr uint32_t FFT_CONTIG_LOG = 12;      // layers of the contiguous pass: three radix-16 rounds (13 = 5 + 3 + 5 when that saves a sweep)
 constexpr uint32_t FFT_MAX_STRIDED_W = 9;    // a strided pass carries up to 9 layers (2^9 x 2^5 tile: 128-B runs, 64 KiB of LDS)
 
+// fft_plan is the ONE place that decides the shape of a transform: the passes and, per pass, the kernel (tile log of the
+// register-blocked kernels, 0 = the generic LDS-sweep kernel) and M.  launch_pass, interpolate_extend and the host-only
+// cm_fft_plan / cm_fft_extend_fused (what the tests read) all go through it.
+static FftPassShape fft_pass_shape(uint32_t lo, uint32_t hi) {
+  const uint32_t W = hi - lo;
+  const uint32_t rb = fft_pass_rb_tile_log(W, lo);
+  uint32_t M = 0;
+  if (rb) M = rb - W;
+  else if (lo > 0) { M = FFT_TILE_LOG - W; if (M > lo) M = lo; }
+  return {lo, hi, rb, M};
+}
 // Plan: layers [0, k0) in one contiguous pass, the rest in as few strided passes of <= 9 layers as possible, balanced.
 // Measured on 64 columns x 2^22 (tools/fft_lab.hip, us forward / inverse): contiguous 11 layers 616 / 681, 12 layers
-// 544 / 598, 13 layers 604 / 707; strided (2^14 tile) 6 layers 371, 7: 407, 8: 405 / 423, 9: 472 / 496, 10 (64-B runs):
-// 618 / 872.  So k0 = 12, except that a transform with exactly 22 layers takes 13 + 9 instead of 12 + 10.
+// 544 / 598, 13 layers 604 / 707; strided (2^14 tile) 6 layers 371, 7: 407, 8: 405 / 423, 9: 472 / 496; 10 layers
+// (64-B runs) measured 618 / 872 before that instantiation was removed.  So k0 = 12, except that a transform with exactly 22
+// layers takes 13 + 9 instead of 12 + 10.
 // A 2^21 transform is 12 + 9, a 2^22 one 13 + 9: two sweeps over HBM where the radix-8 plan (11 + 5 + 5 / 11 + 6 + 5) made
 // three.  CM_FFT_OLD_PLAN=1 restores the 11-layer contiguous pass and <= 7-layer strided passes (A/B).
-static void plan_passes(uint32_t n, std::vector<std::pair<uint32_t, uint32_t>>& passes) {
+uint32_t fft_plan(uint32_t n, FftPassShape out[FFT_MAX_PASSES]) {
   static const bool old_plan = getenv("CM_FFT_OLD_PLAN") != nullptr;
   uint32_t contig = old_plan ? 11u : FFT_CONTIG_LOG;
   const uint32_t max_w = old_plan ? 7u : FFT_MAX_STRIDED_W;
   if (!old_plan && n == contig + max_w + 1) contig++;
   uint32_t k0 = n < contig ? n : contig;
-  passes.push_back({0, k0});
+  uint32_t np_out = 0;
+  out[np_out++] = fft_pass_shape(0, k0);
   uint32_t rest = n - k0;
-  if (rest == 0) return;
+  if (rest == 0) return np_out;
   uint32_t np = (rest + max_w - 1) / max_w;
+  CM_CHECK(1 + np <= FFT_MAX_PASSES, "fft_plan: log size out of range");
   uint32_t lo = k0;
   for (uint32_t i = 0; i < np; i++) {
     uint32_t w = (rest - (lo - k0) + (np - i) - 1) / (np - i);
-    passes.push_back({lo, lo + w});
+    out[np_out++] = fft_pass_shape(lo, lo + w);
     lo += w;
   }
+  return np_out;
 }
 template <bool INV>
 static void launch_pass(const uint32_t* const* d_src, uint32_t* const* d_dst, uint32_t ncols, uint32_t n, uint32_t lo,
@@ -494,10 +509,8 @@ static void launch_pass(const uint32_t* const* d_src, uint32_t* const* d_dst, ui
   a.ytw = INV ? tw.iytw : tw.ytw;
   a.R = tw.R; a.n = n; a.lo = lo; a.hi = hi;
   uint32_t W = hi - lo;
-  const uint32_t rb = fft_pass_rb_tile_log(W, lo);
-  uint32_t M = 0;
-  if (rb) M = rb - W;
-  else if (lo > 0) { M = FFT_TILE_LOG - W; if (M > lo) M = lo; }
+  const FftPassShape shape = fft_pass_shape(lo, hi);
+  const uint32_t rb = shape.tile_log, M = shape.M;
   a.M = M; a.in_len = in_len; a.scale = scale;
   uint32_t tile_log = W + M;
   uint32_t ntiles = 1u << (n - tile_log);
@@ -513,12 +526,12 @@ void interpolate_oop(const uint32_t* const* d_src, uint32_t* const* d_dst, uint3
                      hipStream_t st) {
   CM_CHECK(n >= 1 && n <= tw.R, "interpolate: log size exceeds twiddle table");
   if (ncols == 0) return;
-  std::vector<std::pair<uint32_t, uint32_t>> passes;
-  plan_passes(n, passes);
+  FftPassShape passes[FFT_MAX_PASSES];
+  const uint32_t np = fft_plan(n, passes);
   uint32_t inv_n = inv(M31::from_u32(1u << n)).v;
-  for (size_t i = 0; i < passes.size(); i++) {
-    bool last = i + 1 == passes.size();
-    launch_pass<true>(i == 0 ? d_src : (const uint32_t* const*)d_dst, d_dst, ncols, n, passes[i].first, passes[i].second,
+  for (uint32_t i = 0; i < np; i++) {
+    bool last = i + 1 == np;
+    launch_pass<true>(i == 0 ? d_src : (const uint32_t* const*)d_dst, d_dst, ncols, n, passes[i].lo, passes[i].hi,
                       1u << n, last ? inv_n : 1u, tw, st);
   }
   CM_HIP(hipGetLastError());
@@ -530,12 +543,12 @@ void evaluate(const uint32_t* const* d_src, uint32_t* const* d_dst, uint32_t nco
               const Twiddles& tw, hipStream_t st) {
   CM_CHECK(n_out >= n_in && n_out <= tw.R && n_out >= 1, "evaluate: bad log sizes");
   if (ncols == 0) return;
-  std::vector<std::pair<uint32_t, uint32_t>> passes;
-  plan_passes(n_out, passes);
-  for (size_t k = passes.size(); k-- > 0;) {
-    bool first = k + 1 == passes.size();
-    launch_pass<false>(first ? d_src : (const uint32_t* const*)d_dst, d_dst, ncols, n_out, passes[k].first,
-                       passes[k].second, first ? (1u << n_in) : (1u << n_out), 1u, tw, st);
+  FftPassShape passes[FFT_MAX_PASSES];
+  const uint32_t np = fft_plan(n_out, passes);
+  for (uint32_t k = np; k-- > 0;) {
+    bool first = k + 1 == np;
+    launch_pass<false>(first ? d_src : (const uint32_t* const*)d_dst, d_dst, ncols, n_out, passes[k].lo,
+                       passes[k].hi, first ? (1u << n_in) : (1u << n_out), 1u, tw, st);
   }
   CM_HIP(hipGetLastError());
 }
@@ -543,18 +556,22 @@ void evaluate(const uint32_t* const* d_src, uint32_t* const* d_dst, uint32_t nco
 // log_blowup_factor = 1.  For 2^18 .. 2^21 rows the last pass of the inverse transform and the first pass of the forward one are
 // ONE sweep (k_fft_fused_rb, kernels_fft.hip): [0,12) inverse | [12,n) inverse + top layer + [12,n) forward of both halves |
 // [0,12) forward.  d_src may equal d_coeffs (in place).  CM_FFT_FUSED=0: the two transforms one after the other (A/B).
-bool fft_fused_serves(uint32_t W);
 void launch_fft_fused_rb(const FftPassArgs& inv, const FftPassArgs& fwd, uint32_t ntiles, uint32_t ncols, hipStream_t st);
+bool fft_fused_serves(uint32_t W);
+// whether interpolate_extend takes the fused sweep at 2^n rows under the current tuning ("fft_fused") and plan
+bool fft_extend_fused(uint32_t n) {
+  if (tune(T_FFT_FUSED) == 0 || n <= FFT_CONTIG_LOG || n > 28) return false;
+  const uint32_t W = n - FFT_CONTIG_LOG;
+  FftPassShape passes[FFT_MAX_PASSES];
+  const uint32_t np = fft_plan(n, passes);
+  return fft_fused_serves(W) && np == 2 && passes[0].hi == FFT_CONTIG_LOG && passes[1].tile_log == 14;
+}
 void interpolate_extend(const uint32_t* const* d_src, uint32_t* const* d_coeffs, uint32_t* const* d_lde, uint32_t ncols, uint32_t n,
                         const Twiddles& tw, hipStream_t st) {
-  const bool fused_on = tune(T_FFT_FUSED) != 0;
   CM_CHECK(n >= 1 && n + 1 <= tw.R, "interpolate_extend: log size exceeds twiddle table");
   if (ncols == 0) return;
   const uint32_t W = n > FFT_CONTIG_LOG ? n - FFT_CONTIG_LOG : 0;
-  std::vector<std::pair<uint32_t, uint32_t>> passes;
-  plan_passes(n, passes);
-  const bool fused = fused_on && fft_fused_serves(W) && passes.size() == 2 && passes[0].second == FFT_CONTIG_LOG &&
-                     fft_pass_rb_tile_log(W, FFT_CONTIG_LOG) == 14;
+  const bool fused = fft_extend_fused(n);
   if (!fused) {
     interpolate_oop(d_src, d_coeffs, ncols, n, tw, st);
     evaluate((const uint32_t* const*)d_coeffs, d_lde, ncols, n, n + 1, tw, st);

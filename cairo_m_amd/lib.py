@@ -29,6 +29,28 @@ def _p(a):
     return a.ctypes.data_as(_u32p)
 
 
+def fft_plan(log_n, lib=None):
+    """cm_fft_plan: the passes of a 2^log_n transform as (lo, hi, tile_log, M) tuples in layer order (tile_log 0 = the generic
+    kernel).  Host code: needs no GPU."""
+    L = lib or load_library()
+    out = ((C.c_uint32 * 4) * 8)()
+    n = C.c_uint32(0)
+    rc = L.cm_fft_plan(C.c_uint32(log_n), out, C.byref(n))
+    if rc != 0:
+        raise _lib_error(L, rc)
+    return [tuple(out[i]) for i in range(n.value)]
+
+
+def fft_extend_fused(log_n, lib=None):
+    """cm_fft_extend_fused: whether cm_interpolate_extend takes the fused sweep at 2^log_n rows.  Host code: needs no GPU."""
+    L = lib or load_library()
+    f = C.c_uint32(0)
+    rc = L.cm_fft_extend_fused(C.c_uint32(log_n), C.byref(f))
+    if rc != 0:
+        raise _lib_error(L, rc)
+    return bool(f.value)
+
+
 class Backend:
     """Host-side handle on the HIP backend.  One instance per process / GPU."""
 

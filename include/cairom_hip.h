@@ -37,7 +37,8 @@
  *    cm_verify_run_device, cm_verify_many_timing; cm_link_cell, cm_link_report, cm_run_check, cm_link_diff, cm_check_chain,
  *    cm_check_run.
  *    Still 10 (additive: four new functions and one struct, nothing moved): cm_mem_opening, cm_input_open_memory, cm_run_open_memory,
- *    cm_verify_memory_openings, cm_verify_memory_opening. */
+ *    cm_verify_memory_openings, cm_verify_memory_opening.
+ *    Still 10 (additive: two host-only queries): cm_fft_plan, cm_fft_extend_fused. */
 #define CM_ABI_REVISION 10
 
 #ifdef __cplusplus
@@ -128,6 +129,15 @@ int32_t cm_evaluate(const cm_handle* coeffs, uint32_t n_cols, uint32_t log_n, ui
  * pass are one sweep over HBM.  evals[i] may equal coeffs[i] (in place). */
 int32_t cm_interpolate_extend(const cm_handle* evals, const cm_handle* coeffs, const cm_handle* lde, uint32_t n_cols, uint32_t log_n,
                               cm_handle tw, cm_stream_t s);
+/* The shape of a 2^log_n transform (1 <= log_n <= 28) as cm_interpolate / cm_evaluate run it: host code only, no GPU is
+ * touched or initialised.  out[i] = { lo, hi, tile_log, M } of pass i in layer order (the inverse transform runs the passes
+ * first to last, the forward one last to first): butterfly layers [lo, hi), the tile log of the register-blocked kernel that
+ * runs them (11, 12, 13 or 14; 0 = the generic LDS-sweep kernel) and M, the log of a tile's contiguous run.  The launches
+ * read the same function, so this is what runs.  CM_FFT_OLD_PLAN=1 in the environment (read once) selects the older plan. */
+int32_t cm_fft_plan(uint32_t log_n, uint32_t out[8][4], uint32_t* n_passes);
+/* *fused = 1 when cm_interpolate_extend takes the fused sweep at 2^log_n rows (1 <= log_n <= 27) under the current plan and
+ * tuning ("fft_fused"), 0 when it runs the two transforms one after the other.  Host code only. */
+int32_t cm_fft_extend_fused(uint32_t log_n, uint32_t* fused);
 /* PolyOps::eval_at_point for n_cols polynomials at one QM31 circle point (x[4], y[4]);
  * out = n_cols * 4 u32 (host). */
 int32_t cm_eval_at_point(const cm_handle* coeffs, uint32_t n_cols, uint32_t log_n, const uint32_t pt_xy[8],

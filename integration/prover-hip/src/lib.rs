@@ -419,6 +419,28 @@ pub fn verify_memory_openings(root: u32, openings: &[CmMemOpening]) -> Result<Ve
     Ok(ok.iter().map(|v| *v != 0).collect())
 }
 
+/// The passes of a 2^`log_n` transform as the library runs it (`cm_fft_plan`), in layer order: `[lo, hi, tile_log, M]` per pass,
+/// `tile_log` 0 = the generic kernel.  Host code: touches no GPU.
+pub fn fft_plan(log_n: u32) -> Result<Vec<[u32; 4]>, String> {
+    let mut out = [[0u32; 4]; 8];
+    let mut n: u32 = 0;
+    let rc = unsafe { cm_fft_plan(log_n, out.as_mut_ptr(), &mut n) };
+    if rc != 0 {
+        return Err(last_error());
+    }
+    Ok(out[..n as usize].to_vec())
+}
+
+/// Whether `cm_interpolate_extend` takes the fused sweep at 2^`log_n` rows under the current tuning (`cm_fft_extend_fused`).
+pub fn fft_extend_fused(log_n: u32) -> Result<bool, String> {
+    let mut fused: u32 = 0;
+    let rc = unsafe { cm_fft_extend_fused(log_n, &mut fused) };
+    if rc != 0 {
+        return Err(last_error());
+    }
+    Ok(fused != 0)
+}
+
 /// Twin of `debug_tools::relation_tracker::track_and_summarize_relations` (relation_tracker.rs:21-31, the `.cleaned()` summary) on
 /// the GPU: relation name -> the tuples (values without trailing zeros) whose multiplicities do not sum to zero, with their net
 /// multiplicity.  Only the relations whose sums do not cancel are tracked, so a valid input returns an empty map at the cost of

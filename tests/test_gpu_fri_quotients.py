@@ -104,26 +104,54 @@ def test_fold_line_leaves(backend, oracle, log_n, mode):
     backend.twiddles_free(tw)
 
 
-@pytest.mark.parametrize("log_n,n_cols", [(3, 1), (6, 5), (11, 40), (14, 7)])
-def test_accumulate_quotients(backend, oracle, log_n, n_cols):
-    """Two sample points (the OODS point and its mask-shifted neighbour): every column is sampled at point 0,
-    every third column also at point 1 — the shape Cairo-M's interaction columns produce."""
-    rng = np.random.default_rng(60 + log_n)
+def _quotients_against_the_oracle(backend, oracle, log_n, n_cols, strides, seed):
+    """batch k samples every strides[k]-th column at a random point of its own; the accumulated quotients against the oracle's"""
+    rng = np.random.default_rng(seed)
     tw = backend.twiddles(log_n)
     cols = [rng.integers(0, P, size=1 << log_n, dtype=np.uint32) for _ in range(n_cols)]
-    points = rng.integers(0, P, size=(2, 8), dtype=np.uint32)
-    b0 = list(range(n_cols))
-    b1 = list(range(0, n_cols, 3))
-    col_index = np.array(b0 + b1, dtype=np.uint32)
-    batch_off = np.array([0, len(b0), len(b0) + len(b1)], dtype=np.uint32)
+    points = rng.integers(0, P, size=(len(strides), 8), dtype=np.uint32)
+    batches = [list(range(0, n_cols, k)) for k in strides]
+    col_index = np.array(sum(batches, []), dtype=np.uint32)
+    batch_off = np.cumsum([0] + [len(b) for b in batches]).astype(np.uint32)
     values = rng.integers(0, P, size=(col_index.size, 4), dtype=np.uint32)
     coeff = rng.integers(0, P, size=4, dtype=np.uint32)
     hs = [backend.upload(c) for c in cols]
     ho = [backend.col_alloc(1 << log_n) for _ in range(4)]
-    backend.accumulate_quotients(log_n, hs, points, batch_off, col_index, values, coeff, ho, tw)
-    got = np.stack([backend.download(h, 1 << log_n) for h in ho])
-    exp = oracle.accumulate_quotients(log_n, cols, points, batch_off, col_index, values, coeff)
-    assert np.array_equal(got, exp)
-    for h in hs + ho:
-        backend.col_free(h)
-    backend.twiddles_free(tw)
+    try:
+        backend.accumulate_quotients(log_n, hs, points, batch_off, col_index, values, coeff, ho, tw)
+        got = np.stack([backend.download(h, 1 << log_n) for h in ho])
+        exp = oracle.accumulate_quotients(log_n, cols, points, batch_off, col_index, values, coeff)
+        assert np.array_equal(got, exp)
+    finally:
+        for h in hs + ho:
+            backend.col_free(h)
+        backend.twiddles_free(tw)
+
+
+# 9 | 10 and 13 | 14: the sizes on either side of the thresholds between k_quotients<64>, <8> and the per-row kernels
+@pytest.mark.parametrize("log_n,n_cols", [(3, 1), (6, 5), (11, 40), (14, 7), (9, 9), (10, 9), (13, 9)])
+def test_accumulate_quotients(backend, oracle, log_n, n_cols):
+    """Two sample points (the OODS point and its mask-shifted neighbour): every column is sampled at point 0,
+    every third column also at point 1 — the shape Cairo-M's interaction columns produce."""
+    _quotients_against_the_oracle(backend, oracle, log_n, n_cols, (1, 3), 60 + log_n)
+
+
+@pytest.mark.parametrize("quot_rows", [2, 4])
+@pytest.mark.parametrize("n_batches", [1, 2, 3])
+def test_accumulate_quotients_batch_counts(backend, oracle, n_batches, quot_rows):
+    """2^14 rows, 5 columns, one, two and three sample batches under "quot_rows" 2 and 4: k_quotients_rows<2> / <4> serve one
+    and two batches, and with a third the launch falls to k_quotients<1>.  The third batch is built as the second: every second
+    column at a further random point."""
+    import ctypes as C
+    L = backend.L
+    assert L.cm_set_tuning(b"quot_rows", C.c_int32(quot_rows)) == 0
+    try:
+        _quotients_against_the_oracle(backend, oracle, 14, 5, (1, 3, 2)[:n_batches], 6000 + 10 * n_batches + quot_rows)
+    finally:
+        L.cm_set_tuning(b"quot_rows", C.c_int32(2))
+
+
+def test_accumulate_quotients_three_wide_batches(backend, oracle):
+    """Three batches of 45, 15 and 23 entries at 2^14 rows: k_quotients<1> with a third batch walks its 16-wide groups, an
+    8-wide group and single-entry tails (45 = 2 * 16 + 8 + 5, 15 = 8 + 7, 23 = 16 + 7)."""
+    _quotients_against_the_oracle(backend, oracle, 14, 45, (1, 3, 2), 6100)

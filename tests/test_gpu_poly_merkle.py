@@ -5,6 +5,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from tests.fft_op_sizes import EVALUATE_EXTEND_LOGS, EVALUATE_PADDED, EXTEND_LOGS, INTERPOLATE_LOGS
+
 P = 2**31 - 1
 pytestmark = pytest.mark.gpu
 
@@ -57,7 +59,56 @@ def test_interpolate_evaluate_parity_full_size(backend, oracle, log_n):
     backend.twiddles_free(tw)
 
 
-@pytest.mark.parametrize("log_n", [4, 12, 17, 18, 19, 20, 21, 22])
+@pytest.mark.parametrize("log_n", INTERPOLATE_LOGS)
+def test_interpolate_evaluate_every_plan(backend, oracle, log_n):
+    """Every log size 1..24, so that every kernel the transform plan can select runs once in each direction against the oracle
+    (tests/test_fft_plan_cpu.py proves on the CPU that these sizes reach them all: the 2^11 tile at 1..5 strided layers, the 2^14
+    tile at 6..9 unfused, the three-pass plans of 2^23 = 12 + 6 + 5 and 2^24 = 12 + 6 + 6).  cm_interpolate and cm_evaluate onto
+    the double domain equal the oracle word for word; cm_evaluate onto the same domain returns the evaluations.  Two columns up
+    to 2^22, one at 2^23 and 2^24; 2^24 has no extension (the forward transform of 2^24 is its round trip and 23 -> 24).
+    The oracle takes 0.8 s to interpolate and 0.7 s to evaluate one 2^24 column on the GPU machine's CPU (0.25 / 0.21 s at 2^23);
+    the 2^23 and 2^24 cases take 1.1 and 0.9 s each."""
+    rng = np.random.default_rng(7100 + log_n)
+    extend = log_n in EVALUATE_EXTEND_LOGS
+    tw = backend.twiddles(log_n + 1 if extend else max(log_n, 2))
+    cols = rand_cols(rng, 2 if log_n <= 22 else 1, log_n)
+    hs = [backend.upload(c) for c in cols]
+    backend.interpolate(hs, log_n, tw)
+    coeffs = [backend.download(h, 1 << log_n) for h in hs]
+    for got, c in zip(coeffs, cols):
+        assert np.array_equal(got, oracle.interpolate(c))
+    outs = [backend.col_alloc(2 << log_n if extend else 1 << log_n) for _ in cols]
+    if extend:
+        backend.evaluate(hs, log_n, log_n + 1, tw, outs)
+        for o, cf in zip(outs, coeffs):
+            assert np.array_equal(backend.download(o, 2 << log_n), oracle.evaluate(cf, log_n + 1))
+    backend.evaluate(hs, log_n, log_n, tw, outs)
+    for o, c in zip(outs, cols):
+        assert np.array_equal(backend.download(o, 1 << log_n), c)
+    for h in hs + outs:
+        backend.col_free(h)
+    backend.twiddles_free(tw)
+
+
+@pytest.mark.parametrize("n_in,n_out", EVALUATE_PADDED)
+def test_evaluate_zero_padded(backend, oracle, n_in, n_out):
+    """cm_evaluate with n_out > n_in + 1: the first pass to run reads implicit zeros beyond 2^n_in (in_len) instead of padded
+    columns, in the generic-free plans of 2^12 (one pass), 2^14 (2^11-tile strided pass first), 2^19 and 2^20 (2^14-tile pass)."""
+    rng = np.random.default_rng(7200 + n_out)
+    tw = backend.twiddles(n_out)
+    cols = rand_cols(rng, 2, n_in)
+    hs = [backend.upload(c) for c in cols]
+    # poison the outputs: a word the kernel skips must not pass for a zero it computed
+    outs = [backend.upload(np.full(1 << n_out, 0x5A5A5A5A, dtype=np.uint32)) for _ in cols]
+    backend.evaluate(hs, n_in, n_out, tw, outs)
+    for o, c in zip(outs, cols):
+        assert np.array_equal(backend.download(o, 1 << n_out), oracle.evaluate(c, n_out))
+    for h in hs + outs:
+        backend.col_free(h)
+    backend.twiddles_free(tw)
+
+
+@pytest.mark.parametrize("log_n", EXTEND_LOGS)
 @pytest.mark.parametrize("in_place", [False, True])
 def test_interpolate_extend_parity(backend, oracle, log_n, in_place):
     """extend_evals in one call (cm_interpolate_extend): 2^18..2^21 go through the fused sweep (last inverse pass + top layer +
@@ -104,10 +155,12 @@ def test_lde_roundtrip_large(backend):
     backend.twiddles_free(tw)
 
 
-@pytest.mark.parametrize("log_n", [3, 9, 10, 11, 15])
+@pytest.mark.parametrize("log_n", [3, 9, 10, 11, 15, 12, 13, 21])
 def test_eval_at_point_parity(backend, oracle, log_n):
+    """EAP_LOW_BITS = 12: 2^12 and 2^13 are the sizes whose high half is empty / one bit; 2^21 (two columns) hands
+    k_reduce_partials 512 chunks per column, more than its 256 threads."""
     rng = np.random.default_rng(5 + log_n)
-    cols = rand_cols(rng, 4, log_n)
+    cols = rand_cols(rng, 4 if log_n < 21 else 2, log_n)
     hs = [backend.upload(c) for c in cols]
     pt = rng.integers(0, P, size=8, dtype=np.uint32)
     got = backend.eval_at_point(hs, log_n, pt)

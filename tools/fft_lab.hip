@@ -21,14 +21,14 @@ int main() {
   CK(hipMalloc(&d_ptrs, ncols * 8));
   CK(hipMemcpy(d_ptrs, ptrs.data(), ncols * 8, hipMemcpyHostToDevice));
   struct Case { const char* name; bool inv; uint32_t lo, hi, tl; } cases[] = {
-      {"fwd  contiguous 11 (TL11 r8)", false, 0, 11, 11}, {"fwd  strided 5 (TL11 M=6)", false, 11, 16, 11}, {"fwd  strided 6 (TL11 M=5)", false, 16, 22, 11},
+      {"fwd  contiguous 11 (TL11 r8)", false, 0, 11, 11}, {"fwd  strided 5 (TL11 M=6)", false, 11, 16, 11},
       {"inv  contiguous 11 (TL11 r8)", true, 0, 11, 11}, {"inv  strided 5 (TL11 M=6)", true, 11, 16, 11},
       {"fwd  contiguous 12 (TL12 r16)", false, 0, 12, 12}, {"inv  contiguous 12 (TL12 r16)", true, 0, 12, 12},
       {"fwd  contiguous 13 (TL13 r32)", false, 0, 13, 13}, {"inv  contiguous 13 (TL13 r32)", true, 0, 13, 13},
       {"fwd  strided 9 (TL14 M=5)", false, 13, 22, 14}, {"inv  strided 9 (TL14 M=5)", true, 13, 22, 14},
       {"fwd  strided 8 (TL14 M=6)", false, 13, 21, 14}, {"inv  strided 8 (TL14 M=6)", true, 13, 21, 14},
-      {"fwd  strided 7 (TL14 M=7)", false, 13, 20, 14}, {"fwd  strided 6 (TL14 M=8)", false, 13, 19, 14},
-      {"fwd  strided 7 (TL11 M=4)", false, 13, 20, 11}, {"fwd  strided 6 (TL11 M=5)", false, 13, 19, 11}};
+      {"fwd  strided 7 (TL14 M=7)", false, 13, 20, 14}, {"fwd  strided 6 (TL14 M=8)", false, 13, 19, 14}};
+  // (the 2^11 tile at 6 and 7 layers, M = 5 / 4, measured slower than the 2^14 tile here and is no longer instantiated)
   hipEvent_t e0, e1;
   CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
   for (auto& c : cases) {
