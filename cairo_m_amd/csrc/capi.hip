@@ -329,6 +329,58 @@ int32_t cm_merkle_commit(const cm_handle* cols, const uint32_t* col_logs, uint32
     t.root(root, S(s));
   });
 }
+int32_t cm_merkle_commit_layers(const cm_handle* cols, const uint32_t* col_logs, uint32_t n_cols, uint8_t root[32], uint32_t* layers_out,
+                                uint64_t cap_words, cm_stream_t s) {
+  return guard([&] {
+    CM_CHECK(root && layers_out, "cm_merkle_commit_layers: null output");
+    std::vector<const uint32_t*> c(n_cols);
+    std::vector<uint32_t> logs(col_logs, col_logs + n_cols);
+    for (uint32_t i = 0; i < n_cols; i++) c[i] = P32(cols[i]);
+    MerkleTree t;
+    t.commit(c, logs, S(s));
+    t.root(root, S(s));   // (waits for the stream)
+    const size_t max_log = t.layers.size() - 1;
+    CM_CHECK(cap_words >= (((uint64_t)2 << max_log) - 1) * 8, "cm_merkle_commit_layers: output buffer too small");
+    // the buffers the decommitment gathers from, as they are: largest layer first
+    uint32_t* dst = layers_out;
+    for (size_t l = max_log + 1; l-- > 0;) {
+      const size_t bytes = (size_t)32 << l;
+      CM_CHECK(t.layers[l].p && t.layers[l].bytes >= bytes, "cm_merkle_commit_layers: the commitment left a layer without a buffer");
+      CM_HIP(hipMemcpy(dst, t.layers[l].p, bytes, hipMemcpyDeviceToHost));
+      dst += (size_t)8 << l;
+    }
+  });
+}
+int32_t cm_merkle_plan(const uint32_t* col_logs, uint32_t n_cols, uint32_t out[][CM_MERKLE_PLAN_WORDS], uint32_t cap_launches,
+                       uint32_t* n_launches) {
+  return guard([&] {
+    CM_CHECK(out && n_launches && (col_logs || !n_cols), "cm_merkle_plan: null argument");
+    static_assert(CM_MERKLE_PLAN_WORDS == 9 + MERKLE_PLAN_MAX_LAYERS, "cm_merkle_plan's record");
+    // MerkleTree::prepare's order: by size, descending (only the logs matter here)
+    std::vector<uint32_t> logs(col_logs, col_logs + n_cols);
+    for (uint32_t l : logs) CM_CHECK(l < 32, "merkle tree: column of 2^32 rows or more");
+    std::stable_sort(logs.begin(), logs.end(), [](uint32_t a, uint32_t b) { return a > b; });
+    MerkleLaunchPlan recs[MERKLE_PLAN_MAX_LAUNCHES];
+    const uint32_t n = merkle_plan(logs.data(), logs.size(), recs);
+    CM_CHECK(n <= cap_launches, "cm_merkle_plan: output buffer too small");
+    for (uint32_t i = 0; i < n; i++) {
+      const MerkleLaunchPlan& r = recs[i];
+      uint32_t* w = out[i];
+      memset(w, 0, sizeof(uint32_t) * CM_MERKLE_PLAN_WORDS);
+      w[0] = r.kind; w[1] = r.hi; w[2] = r.lo; w[3] = r.has_prev; w[4] = r.narrow_prev; w[5] = r.narrow_nc; w[6] = r.npw;
+      w[7] = r.wide_mask; w[8] = r.col_begin;
+      for (uint32_t k = 0; k <= r.hi - r.lo; k++) w[9 + k] = r.ncols[k];
+    }
+    *n_launches = n;
+  });
+}
+int32_t cm_merkle_layer_npw(uint32_t log_size, uint32_t has_prev, uint32_t n_cols, uint32_t* npw) {
+  return guard([&] {
+    CM_CHECK(npw, "cm_merkle_layer_npw: null output");
+    CM_CHECK(log_size < 32, "cm_merkle_layer_npw: log size out of range");
+    *npw = merkle_narrow_npw(log_size, has_prev != 0, n_cols);
+  });
+}
 int32_t cm_grind(const uint8_t digest[32], uint32_t pow_bits, uint64_t* nonce_out, cm_stream_t s) {
   return guard([&] { *nonce_out = grind_gpu(digest, pow_bits, S(s)); });
 }

@@ -202,12 +202,9 @@ void merkle_layer(uint32_t log_size, const uint32_t* d_prev, const uint32_t* con
   KProfExt kp("k_merkle_layer", (4.0 * ncols + (d_prev ? 64.0 : 0.0) + 32.0) * (double)n, st,
               /* Blake2s compressions */ (double)n * ((d_prev ? 1.0 : 0.0) + (double)((ncols + 15) / 16)));
   // narrow layers (no columns or one SecureColumn): a wave walks several 64-node chunks with the next chunk's loads in flight
-  // (k_merkle_narrow).  Chunks per wave: as many as still leave >= 2 waves per wave slot of the chip (256 CUs x 32 slots).
-  // A/B: CM_MERKLE_NPW=0 restores k_merkle_layer for these layers, 1 / 2 / 4 / 8 force a chunk count.
-  const int npw_env = tune(T_MERKLE_NPW);
-  if (npw_env != 0 && (ncols == 0 || ncols == 4) && (d_prev || ncols) && log_size >= 14) {
-    uint32_t npw = npw_env > 0 ? (uint32_t)npw_env : std::min(8u, std::max(1u, n >> 20));
-    while (npw > 1 && (n % (256u * npw)) != 0) npw >>= 1;
+  // (k_merkle_narrow).  Whether, and with how many chunks per wave: merkle_narrow_npw (merkle_plan.hpp), the predicate the
+  // commitment plan reports.
+  if (const uint32_t npw = merkle_narrow_npw(log_size, d_prev != nullptr, ncols)) {
     const dim3 grid(n / (256u * npw));
     const bool rfc = framing().hash_node_rfc;
 #define CM_NARROW(R, P, C) CM_KPROF_LAUNCH(kp, (k_merkle_narrow<R, P, C>), grid, dim3(256), 0, st, d_prev, d_cols, d_out, npw)

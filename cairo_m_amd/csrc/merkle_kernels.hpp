@@ -3,6 +3,7 @@
 #pragma once
 #include "blake2s_dev.hpp"
 #include "engine.hpp"
+#include "merkle_plan.hpp"
 #include "device_common.hpp"
 
 namespace cm {
@@ -225,17 +226,12 @@ __device__ __forceinline__ void merkle_node_quad(const uint32_t* children, const
 // (~1.4 us per block, twice the hashing).  Here the whole BLOCK streams the layer's columns through LDS, one group of NT x R words
 // ahead of the hashing quads: the column pointers are copied to LDS once, group g + 1 is loaded into registers before the quads
 // hash group g and written to the other half of a double buffer afterwards, so no memory latency is left on the chain.
-constexpr uint32_t WIDE_PTR_CAP = 2048;   // columns whose pointers fit the LDS table (16 KiB)
-constexpr uint32_t WIDE_MIN_COLS = 48;    // below this a layer pays its one or two loads directly
+// (WIDE_PTR_CAP, WIDE_MIN_COLS, wide_layer_ok and the per-kernel predicates built on it: merkle_plan.hpp, shared with the host plan)
 template <int NT, int R>
 struct WideLds {
   unsigned long long ptrs[WIDE_PTR_CAP];
   uint32_t buf[2][NT * R];   // group-local column-major: word (c, node) of a group at (c << log_n) + node
 };
-template <int NT, int R>
-__device__ __forceinline__ bool wide_layer_ok(uint32_t ncols, uint32_t log_n) {
-  return ncols >= WIDE_MIN_COLS && ncols <= WIDE_PTR_CAP && (16u << log_n) <= (uint32_t)(NT * R) && (4u << log_n) <= (uint32_t)NT;
-}
 // Every thread of the block calls this (barriers inside); the quad of lanes (node_local, q) of an `active` thread owns node
 // node0 + node_local of the layer and returns its hash words h[q], h[4 + q].  `children` = the node's 16 child words or null.
 template <bool RFC, int NT, int R>
@@ -364,7 +360,7 @@ __global__ void __launch_bounds__(1024) k_merkle_tail(MerkleTailArgs a) {
     const bool from_global = (l == (int)a.top_log);
     const uint32_t* ch = (!from_global || a.prev) ? (from_global ? a.prev + (size_t)node * 16 : buf[cur ^ 1] + node * 16) : nullptr;
     uint32_t h0, h1;
-    const bool is_wide = wide_layer_ok<1024, 4>(a.col_end[l] - a.col_begin[l], (uint32_t)l);   // block-uniform
+    const bool is_wide = merkle_tail_wide(a.col_end[l] - a.col_begin[l], (uint32_t)l);   // block-uniform
     if (is_wide) merkle_wide_quad<RFC, 1024, 4>(wide, ch, node < n, a.cols, a.col_begin[l], a.col_end[l], 0u, (uint32_t)l, node, q, threadIdx.x, h0, h1);
     if (node < n) {
       if (!is_wide) merkle_node_quad<RFC>(ch, a.cols, a.col_begin[l], a.col_end[l], node, q, h0, h1);
@@ -467,7 +463,7 @@ __global__ void __launch_bounds__(256) k_merkle_top(MerkleTopArgs a) {
   for (int l = base_log - 1; l >= 0; l--) {
     const uint32_t n = 1u << l;
     const bool from_global = (l == base_log - 1);
-    if (wide_layer_ok<256, 16>(a.col_end[l] - a.col_begin[l], (uint32_t)l)) {   // block-uniform; n <= 64 here
+    if (merkle_top_wide(a.col_end[l] - a.col_begin[l], (uint32_t)l)) {   // block-uniform; n <= 64 here
       const uint32_t* ch = from_global ? a.layers[base_log] + (size_t)node * 16 : buf[cur ^ 1] + node * 16;
       uint32_t h0, h1;
       merkle_wide_quad<RFC, 256, 16>(wide, ch, node < n, a.cols, a.col_begin[l], a.col_end[l], 0u, (uint32_t)l, node, q, tid, h0, h1);
@@ -505,7 +501,7 @@ __global__ void __launch_bounds__(256) k_merkle_layer_quad(uint32_t log_size, co
   const uint32_t i = t >> 2, q = t & 3u;
   const uint32_t n = 1u << log_size;
   uint32_t h0, h1;
-  if (log_size >= 6 && wide_layer_ok<256, 16>(n_cols, 6u)) {   // full blocks of 64 nodes: the block streams its columns through LDS
+  if (merkle_quad_wide(log_size, n_cols)) {   // full blocks of 64 nodes: the block streams its columns through LDS
     merkle_wide_quad<RFC, 256, 16>(wide, prev ? prev + (size_t)i * 16 : nullptr, true, cols, 0u, n_cols, blockIdx.x * 64u, 6u, threadIdx.x >> 2, q,
                                    threadIdx.x, h0, h1);
   } else {

@@ -8,6 +8,7 @@
 // commitment_scheme.prove_values -> tree.decommit inside stwo `prove` (prover.rs:131).
 #pragma once
 #include "engine.hpp"
+#include "merkle_plan.hpp"
 #include <algorithm>
 #include <functional>
 #include <map>
@@ -137,12 +138,9 @@ struct MerkleTree {
   // them with the transforms that produce the columns (Prover::commit_enqueue: launch k only needs the columns of >= 2^lo rows).
   std::vector<CommitLaunch> plan_commit() {
     std::vector<CommitLaunch> plan;
-    uint32_t max_log = cols.empty() ? 0 : col_logs[0];
+    const uint32_t max_log = cols.empty() ? 0 : col_logs[0];
     layers.clear();
     layers.resize(max_log + 1);
-    size_t ci = 0;
-    const int tail_top = (int)std::min<uint32_t>(max_log, MERKLE_TAIL_LOG);
-    static const bool use_top = getenv("CM_NO_MERKLE_TOP") == nullptr;   // A/B switch
     pace_recorded = false;
     top_launch_has_extras = top_launch_has_fold = false;
     bool pace_planned = false;
@@ -151,102 +149,85 @@ struct MerkleTree {
       if (pace) pace_planned = true;
       plan.push_back(CommitLaunch{hi, lo, pace, std::move(f)});
     };
-    for (int log = (int)max_log; log > tail_top;) {
-      // the whole top of the tree in one launch once no wide layer is left among the per-lane levels
-      if (use_top && log <= (int)MERKLE_TOP_MAX_LOG && log >= 9) {
-        bool wide_inside = false;
-        size_t cj = ci;
-        for (int l = log; l >= log - 8; l--) {
-          size_t cnt = 0;
-          while (cj + cnt < cols.size() && col_logs[cj + cnt] == (uint32_t)l) cnt++;
-          if (cnt >= MERKLE_QUAD_MIN_COLS) wide_inside = true;
-          cj += cnt;
+    // which kernel takes which layers is decided by merkle_plan() (merkle_plan.hpp: host code, also behind cm_merkle_plan); here
+    // the records get their buffers and argument structs
+    MerkleLaunchPlan recs[MERKLE_PLAN_MAX_LAUNCHES];
+    const uint32_t n_recs = merkle_plan(col_logs.data(), cols.size(), recs);
+    for (uint32_t ri = 0; ri < n_recs; ri++) {
+      const MerkleLaunchPlan& r = recs[ri];
+      const int hi = (int)r.hi, lo = (int)r.lo;
+      const uint32_t* prev = r.has_prev ? layers[hi + 1].u32() : nullptr;
+      switch (r.kind) {
+        case MP_LAYER:
+        case MP_NARROW:
+        case MP_QUAD: {
+          if (hi == (int)max_log && leaf_prealloc.p && leaf_prealloc.bytes >= ((size_t)32 << hi)) layers[hi] = std::move(leaf_prealloc);
+          else layers[hi].alloc((size_t)32 << hi);
+          const uint32_t* const* dc = dcols() + r.col_begin;
+          const uint32_t nc = r.ncols[0];
+          uint32_t* outp = layers[hi].u32();
+          // (merkle_layer chooses k_merkle_narrow or k_merkle_layer itself, at launch, by the predicate the record was made with)
+          if (r.kind == MP_QUAD) push(hi, hi, [=](hipStream_t st) { merkle_layer_quad((uint32_t)hi, prev, dc, nc, outp, st); });
+          else push(hi, hi, [=](hipStream_t st) { merkle_layer((uint32_t)hi, prev, dc, nc, outp, st); });
+          break;
         }
-        if (!wide_inside) {
-          MerkleTopArgs a;
-          a.top_log = (uint32_t)log;
-          a.prev = (log < (int)max_log) ? layers[log + 1].u32() : nullptr;
+        case MP_MULTI: {
+          MerkleMultiArgs a;
+          a.top_log = r.hi;
+          a.n_levels = r.hi - r.lo + 1;
+          a.prev = prev;
           a.cols = dcols();
-          for (int l = log; l >= 0; l--) {
-            a.col_begin[l] = (uint32_t)ci;
-            while (ci < cols.size() && col_logs[ci] == (uint32_t)l) ci++;
-            a.col_end[l] = (uint32_t)ci;
+          double bytes = 0;
+          uint32_t c = r.col_begin;
+          for (int lv = 0; lv <= hi - lo; lv++) {
+            const int l = hi - lv;
+            a.col_begin[lv] = c;
+            c += r.ncols[lv];
+            a.col_end[lv] = c;
+            layers[l].alloc((size_t)32 << l);
+            a.layers[lv] = layers[l].u32();
+            bytes += (4.0 * (a.col_end[lv] - a.col_begin[lv]) + 32.0 + ((lv == 0 && a.prev) ? 64.0 : 0.0)) * (double)((size_t)1 << l);
+          }
+          push(hi, lo, [a, bytes](hipStream_t st) { merkle_multi(a, bytes, st); });
+          break;
+        }
+        case MP_TOP: {
+          MerkleTopArgs a;
+          a.top_log = r.hi;
+          a.prev = prev;
+          a.cols = dcols();
+          uint32_t c = r.col_begin;
+          for (int l = hi; l >= 0; l--) {
+            a.col_begin[l] = c;
+            c += r.ncols[hi - l];
+            a.col_end[l] = c;
             layers[l].alloc((size_t)32 << l);
             a.layers[l] = layers[l].u32();
           }
           a.x = top_extra;
-          if (log != (int)max_log) a.x.fold_mode = 0;   // the fold makes the leaf level: only a launch that starts there may carry it
+          if (hi != (int)max_log) a.x.fold_mode = 0;   // the fold makes the leaf level: only a launch that starts there may carry it
           top_launch_has_extras = a.x.chan != nullptr;
           top_launch_has_fold = a.x.fold_mode != 0;
-          push(log, 0, [a](hipStream_t st) mutable { merkle_top(a, st); });
-          return plan;
+          push(hi, 0, [a](hipStream_t st) mutable { merkle_top(a, st); });
+          break;
+        }
+        default: {   // MP_TAIL: layers 2^hi .. 2^0 in one fused launch
+          MerkleTailArgs a;
+          a.top_log = r.hi;
+          a.prev = prev;
+          a.cols = dcols();
+          uint32_t c = r.col_begin;
+          for (int l = hi; l >= 0; l--) {
+            a.col_begin[l] = c;
+            c += r.ncols[hi - l];
+            a.col_end[l] = c;
+            layers[l].alloc((size_t)32 << l);
+            a.layers[l] = layers[l].u32();
+          }
+          push(hi, 0, [a](hipStream_t st) { merkle_tail(a, st); });
+          break;
         }
       }
-      // group of up to MERKLE_MULTI_LEVELS layers per launch (the top layer of a group needs >= 256 nodes)
-      int levels = std::min<int>((int)MERKLE_MULTI_LEVELS, log - tail_top);
-      if (log < 8) levels = 1;
-      // big layers are throughput-bound: one node per thread with every lane busy beats the fused kernel
-      // (whose parent levels run on half / quarter of the block); fusion pays only once launches are latency-bound
-      if (log >= tune(T_MERKLE_MULTI_TOP)) levels = 1;   // (default MERKLE_MULTI_MAX_TOP = 19; A/B: "merkle_multi_top")
-      // a mid-size layer carrying many columns is one long compression chain per node: quad-lane kernel
-      size_t n_here = 0;
-      while (ci + n_here < cols.size() && col_logs[ci + n_here] == (uint32_t)log) n_here++;
-      const bool wide = log <= (int)MERKLE_QUAD_MAX_LOG && n_here >= MERKLE_QUAD_MIN_COLS;
-      if (!wide && levels > 1) {  // a fused group must stop in front of a wide layer further down
-        size_t cj = ci + n_here;
-        for (int lv = 1; lv < levels; lv++) {
-          size_t cnt = 0;
-          while (cj + cnt < cols.size() && col_logs[cj + cnt] == (uint32_t)(log - lv)) cnt++;
-          if (log - lv <= (int)MERKLE_QUAD_MAX_LOG && cnt >= MERKLE_QUAD_MIN_COLS) { levels = lv; break; }
-          cj += cnt;
-        }
-      }
-      if (levels == 1 || wide) {
-        size_t c0 = ci;
-        ci += n_here;
-        if (log == (int)max_log && leaf_prealloc.p && leaf_prealloc.bytes >= ((size_t)32 << log)) layers[log] = std::move(leaf_prealloc);
-        else layers[log].alloc((size_t)32 << log);
-        const uint32_t* prev = (log < (int)max_log) ? layers[log + 1].u32() : nullptr;
-        const uint32_t* const* dc = dcols() + c0;
-        const uint32_t nc = (uint32_t)(ci - c0);
-        uint32_t* outp = layers[log].u32();
-        if (wide) push(log, log, [=](hipStream_t st) { merkle_layer_quad((uint32_t)log, prev, dc, nc, outp, st); });
-        else push(log, log, [=](hipStream_t st) { merkle_layer((uint32_t)log, prev, dc, nc, outp, st); });
-        log--;
-        continue;
-      }
-      MerkleMultiArgs a;
-      a.top_log = (uint32_t)log;
-      a.n_levels = (uint32_t)levels;
-      a.prev = (log < (int)max_log) ? layers[log + 1].u32() : nullptr;
-      a.cols = dcols();
-      double bytes = 0;
-      for (int lv = 0; lv < levels; lv++) {
-        int l = log - lv;
-        a.col_begin[lv] = (uint32_t)ci;
-        while (ci < cols.size() && col_logs[ci] == (uint32_t)l) ci++;
-        a.col_end[lv] = (uint32_t)ci;
-        layers[l].alloc((size_t)32 << l);
-        a.layers[lv] = layers[l].u32();
-        bytes += (4.0 * (a.col_end[lv] - a.col_begin[lv]) + 32.0 + ((lv == 0 && a.prev) ? 64.0 : 0.0)) * (double)((size_t)1 << l);
-      }
-      push(log, log - levels + 1, [a, bytes](hipStream_t st) { merkle_multi(a, bytes, st); });
-      log -= levels;
-    }
-    {
-      // layers 2^tail_top .. 2^0: one fused launch
-      MerkleTailArgs a;
-      a.top_log = (uint32_t)tail_top;
-      a.prev = (tail_top < (int)max_log) ? layers[tail_top + 1].u32() : nullptr;
-      a.cols = dcols();
-      for (int log = tail_top; log >= 0; log--) {
-        a.col_begin[log] = (uint32_t)ci;
-        while (ci < cols.size() && col_logs[ci] == (uint32_t)log) ci++;
-        a.col_end[log] = (uint32_t)ci;
-        layers[log].alloc((size_t)32 << log);
-        a.layers[log] = layers[log].u32();
-      }
-      push(tail_top, 0, [a](hipStream_t st) { merkle_tail(a, st); });
     }
     return plan;
   }

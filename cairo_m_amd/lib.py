@@ -51,6 +51,44 @@ def fft_extend_fused(log_n, lib=None):
     return bool(f.value)
 
 
+MERKLE_PLAN_WORDS = 26
+MERKLE_KINDS = ("layer", "narrow", "quad", "multi", "top", "tail")
+
+
+def merkle_plan(col_logs, lib=None):
+    """cm_merkle_plan: the launches of cm_merkle_commit for columns of these log sizes (commitment order), in launch order.  One
+    dict per launch: kind (a MERKLE_KINDS name), hi, lo, has_prev, ncols (columns of layer hi, hi - 1, .., lo), wide (the layers
+    that stream their columns through LDS, descending), first_col, and for "narrow" prev / nc / npw.  Host code: needs no GPU."""
+    L = lib or load_library()
+    logs = np.ascontiguousarray(col_logs, dtype=np.uint32)
+    out = ((C.c_uint32 * MERKLE_PLAN_WORDS) * 33)()
+    n = C.c_uint32(0)
+    rc = L.cm_merkle_plan(_p(logs), C.c_uint32(logs.size), out, C.c_uint32(33), C.byref(n))
+    if rc != 0:
+        raise _lib_error(L, rc)
+    plan = []
+    for i in range(n.value):
+        w = list(out[i])
+        hi, lo = w[1], w[2]
+        rec = {"kind": MERKLE_KINDS[w[0]], "hi": hi, "lo": lo, "has_prev": bool(w[3]), "ncols": w[9:9 + hi - lo + 1],
+               "wide": [l for l in range(hi, -1, -1) if w[7] >> l & 1], "first_col": w[8]}
+        if rec["kind"] == "narrow":
+            rec.update(prev=bool(w[4]), nc=w[5], npw=w[6])
+        plan.append(rec)
+    return plan
+
+
+def merkle_layer_npw(log_size, has_prev, n_cols, lib=None):
+    """cm_merkle_layer_npw: what cm_merkle_commit_layer launches for such a layer: 0 = k_merkle_layer, else the chunks per wave
+    of k_merkle_narrow.  Host code: needs no GPU."""
+    L = lib or load_library()
+    npw = C.c_uint32(0)
+    rc = L.cm_merkle_layer_npw(C.c_uint32(log_size), C.c_uint32(1 if has_prev else 0), C.c_uint32(n_cols), C.byref(npw))
+    if rc != 0:
+        raise _lib_error(L, rc)
+    return npw.value
+
+
 class Backend:
     """Host-side handle on the HIP backend.  One instance per process / GPU."""
 
@@ -139,6 +177,16 @@ class Backend:
         root = (C.c_uint8 * 32)()
         self._ck(self.L.cm_merkle_commit(self._harr(cols), _p(logs), C.c_uint32(len(cols)), root, C.c_uint64(0)))
         return bytes(root)
+
+    def merkle_commit_layers(self, cols, col_logs):
+        """cm_merkle_commit_layers: (root, layers) with every stored layer largest first, 8 words per node — the layout of the
+        oracle's merkle_commit."""
+        logs = np.ascontiguousarray(col_logs, dtype=np.uint32)
+        root = (C.c_uint8 * 32)()
+        layers = np.zeros(((2 << (int(logs.max()) if logs.size else 0)) - 1) * 8, dtype=np.uint32)
+        self._ck(self.L.cm_merkle_commit_layers(self._harr(cols), _p(logs), C.c_uint32(len(cols)), root, _p(layers),
+                                                C.c_uint64(layers.size), C.c_uint64(0)))
+        return bytes(root), layers
 
     def merkle_commit_layer(self, log_size, prev, cols, out):
         self._ck(self.L.cm_merkle_commit_layer(C.c_uint32(log_size), C.c_uint64(prev), self._harr(cols),

@@ -38,7 +38,8 @@
  *    cm_check_run.
  *    Still 10 (additive: four new functions and one struct, nothing moved): cm_mem_opening, cm_input_open_memory, cm_run_open_memory,
  *    cm_verify_memory_openings, cm_verify_memory_opening.
- *    Still 10 (additive: two host-only queries): cm_fft_plan, cm_fft_extend_fused. */
+ *    Still 10 (additive: two host-only queries): cm_fft_plan, cm_fft_extend_fused.
+ *    Still 10 (additive: two host-only queries, one op): cm_merkle_plan, cm_merkle_layer_npw, cm_merkle_commit_layers. */
 #define CM_ABI_REVISION 10
 
 #ifdef __cplusplus
@@ -151,6 +152,29 @@ int32_t cm_merkle_commit_layer(uint32_t log_size, cm_handle prev_layer, const cm
  * log sizes; writes the 32-byte root. */
 int32_t cm_merkle_commit(const cm_handle* cols, const uint32_t* col_logs, uint32_t n_cols, uint8_t root[32],
                          cm_stream_t s);
+/* cm_merkle_commit, and every stored layer copied out: layers_out (host, cap_words u32) receives the layers largest first, 8 u32
+ * per node, ((2 << max_log) - 1) * 8 words in all (max_log = the largest column log).  The words are read back from the
+ * tree's own layer buffers, the ones a decommitment gathers its hash witnesses from; nothing is recomputed. */
+int32_t cm_merkle_commit_layers(const cm_handle* cols, const uint32_t* col_logs, uint32_t n_cols, uint8_t root[32],
+                                uint32_t* layers_out, uint64_t cap_words, cm_stream_t s);
+/* The launches of cm_merkle_commit for columns of these log sizes (commitment order), in launch order: host code only, no GPU
+ * is touched or initialised.  The commitment consumes the same records, and the flags below come from the predicates the
+ * kernels and the launch code evaluate, so this is what runs.  out[i] = one launch:
+ *   [0] kind: 0 k_merkle_layer, 1 k_merkle_narrow, 2 k_merkle_layer_quad, 3 k_merkle_multi, 4 k_merkle_top, 5 k_merkle_tail
+ *   [1] hi, [2] lo: the launch produces the layers 2^hi .. 2^lo      [3] 1 when layer hi + 1 exists (the launch reads children)
+ *   [4] PREV, [5] NC, [6] chunks per wave of a k_merkle_narrow launch (0 otherwise)
+ *   [7] bit l set: layer 2^l streams its columns through LDS (the quad kernel's layer, phase 2 of the top kernel, the tail)
+ *   [8] index of the launch's first column among the columns sorted by size, descending
+ *   [9 + k] columns of layer hi - k, k = 0 .. hi - lo
+ * Depends on the tuning keys "merkle_npw" and "merkle_multi_top" and on CM_NO_MERKLE_TOP in the environment (read once).
+ * At most 33 launches; cap_launches = the rows of `out`. */
+#define CM_MERKLE_PLAN_WORDS 26
+int32_t cm_merkle_plan(const uint32_t* col_logs, uint32_t n_cols, uint32_t out[][CM_MERKLE_PLAN_WORDS], uint32_t cap_launches,
+                       uint32_t* n_launches);
+/* What cm_merkle_commit_layer launches for a layer of 2^log_size nodes with n_cols columns, with (has_prev != 0) or without
+ * children: *npw = 0 for k_merkle_layer, else the chunks per wave of k_merkle_narrow.  The predicate the launch itself and
+ * cm_merkle_plan evaluate, under the current "merkle_npw".  Host code only. */
+int32_t cm_merkle_layer_npw(uint32_t log_size, uint32_t has_prev, uint32_t n_cols, uint32_t* npw);
 
 /* ---- GrindOps<Blake2sChannel>::grind (reference: prover.rs:90) ------------------------------- */
 int32_t cm_grind(const uint8_t digest[32], uint32_t pow_bits, uint64_t* nonce_out, cm_stream_t s);

@@ -233,6 +233,8 @@ pub struct cm_comm {
     pub abort: Option<unsafe extern "C" fn(ctx: *mut c_void)>,
 }
 pub const CM_COMM_STREAM_ORDERED: u32 = 1;
+/// u32 words of one launch record of `cm_merkle_plan`
+pub const CM_MERKLE_PLAN_WORDS: usize = 26;
 #[repr(C)]
 pub struct cm_rccl_comm {
     _private: [u8; 0],
@@ -364,6 +366,9 @@ unsafe extern "C" {
     pub fn cm_eval_at_point(coeffs: *const cm_handle, n_cols: u32, log_n: u32, pt_xy: *const u32, out: *mut u32, s: cm_stream_t) -> i32;
     pub fn cm_merkle_commit_layer(log_size: u32, prev_layer: cm_handle, cols: *const cm_handle, n_cols: u32, out_hashes: cm_handle, s: cm_stream_t) -> i32;
     pub fn cm_merkle_commit(cols: *const cm_handle, col_logs: *const u32, n_cols: u32, root: *mut u8, s: cm_stream_t) -> i32;
+    pub fn cm_merkle_commit_layers(cols: *const cm_handle, col_logs: *const u32, n_cols: u32, root: *mut u8, layers_out: *mut u32, cap_words: u64, s: cm_stream_t) -> i32;
+    pub fn cm_merkle_plan(col_logs: *const u32, n_cols: u32, out: *mut [u32; CM_MERKLE_PLAN_WORDS], cap_launches: u32, n_launches: *mut u32) -> i32;
+    pub fn cm_merkle_layer_npw(log_size: u32, has_prev: u32, n_cols: u32, npw: *mut u32) -> i32;
     pub fn cm_grind(digest: *const u8, pow_bits: u32, nonce_out: *mut u64, s: cm_stream_t) -> i32;
     pub fn cm_batch_inverse_m31(src: cm_handle, out: cm_handle, n: u64, s: cm_stream_t) -> i32;
     pub fn cm_batch_inverse_qm31(src: *const cm_handle, out: *const cm_handle, n: u64, s: cm_stream_t) -> i32;

@@ -441,6 +441,46 @@ pub fn fft_extend_fused(log_n: u32) -> Result<bool, String> {
     Ok(fused != 0)
 }
 
+/// The launches of a Merkle commitment of columns with these log sizes (`cm_merkle_plan`), in launch order: per launch
+/// `[kind, hi, lo, has_prev, PREV, NC, npw, wide_mask, first_column, columns of layer hi, hi - 1, ..]` (include/cairom_hip.h).
+/// Host code: touches no GPU.
+pub fn merkle_plan(col_logs: &[u32]) -> Result<Vec<[u32; CM_MERKLE_PLAN_WORDS]>, String> {
+    let mut out = [[0u32; CM_MERKLE_PLAN_WORDS]; 33];
+    let mut n: u32 = 0;
+    let rc = unsafe { cm_merkle_plan(col_logs.as_ptr(), col_logs.len() as u32, out.as_mut_ptr(), 33, &mut n) };
+    if rc != 0 {
+        return Err(last_error());
+    }
+    Ok(out[..n as usize].to_vec())
+}
+
+/// What `cm_merkle_commit_layer` launches for such a layer (`cm_merkle_layer_npw`): 0 = `k_merkle_layer`, else the chunks per
+/// wave of `k_merkle_narrow`.  Host code: touches no GPU.
+pub fn merkle_layer_npw(log_size: u32, has_prev: bool, n_cols: u32) -> Result<u32, String> {
+    let mut npw: u32 = 0;
+    let rc = unsafe { cm_merkle_layer_npw(log_size, has_prev as u32, n_cols, &mut npw) };
+    if rc != 0 {
+        return Err(last_error());
+    }
+    Ok(npw)
+}
+
+/// `cm_merkle_commit_layers`: the root of the mixed-degree tree over `cols` and every stored layer, largest first, 8 words per node.
+pub fn merkle_commit_layers(cols: &[cm_handle], col_logs: &[u32]) -> Result<([u8; 32], Vec<u32>), String> {
+    ensure_init();
+    assert_eq!(cols.len(), col_logs.len());
+    let max_log = col_logs.iter().copied().max().unwrap_or(0);
+    let mut layers = vec![0u32; ((2usize << max_log) - 1) * 8];
+    let mut root = [0u8; 32];
+    let rc = unsafe {
+        cm_merkle_commit_layers(cols.as_ptr(), col_logs.as_ptr(), cols.len() as u32, root.as_mut_ptr(), layers.as_mut_ptr(), layers.len() as u64, 0)
+    };
+    if rc != 0 {
+        return Err(last_error());
+    }
+    Ok((root, layers))
+}
+
 /// Twin of `debug_tools::relation_tracker::track_and_summarize_relations` (relation_tracker.rs:21-31, the `.cleaned()` summary) on
 /// the GPU: relation name -> the tuples (values without trailing zeros) whose multiplicities do not sum to zero, with their net
 /// multiplicity.  Only the relations whose sums do not cancel are tracked, so a valid input returns an empty map at the cost of

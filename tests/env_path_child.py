@@ -4,6 +4,8 @@ environment; this module only does the work and prints one JSON line.
 
   prove  OUT_DIR NAME[,NAME...]   proves each named input twice on GPU 0 and writes the words to OUT_DIR/NAME.K.npy
   verify WORDS.npy FLIPS.json     host code only: cm_verify_proof_words of the words and of each one-bit tampering
+  merkle_layers                   commits NO_TOP_SHAPES (tests/merkle_op_shapes.py) on GPU 0 and compares every stored layer
+                                  with the oracle; reports the launch kinds cm_merkle_plan names in this environment
 """
 import json
 import os
@@ -54,7 +56,27 @@ def verify(words_path, flips_path):
     return {"verdicts": out}
 
 
+def merkle_layers():
+    from cairo_m_amd import Backend
+    from cairo_m_amd.lib import merkle_plan
+    from tests.merkle_layers_util import assert_all_layers_equal_oracle
+    from tests.merkle_op_shapes import NO_TOP_SHAPES
+    from tests.oracle_binding import Oracle
+    t0 = time.time()
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    orc = Oracle(os.path.join(root, "oracle", "liboracle.so"))
+    be = Backend(0)
+    plans = []
+    for k, logs in enumerate(NO_TOP_SHAPES):
+        assert_all_layers_equal_oracle(be, orc, logs, seed=8200 + k)   # (an AssertionError ends the child with status 1)
+        plans.append([[r["kind"], r["hi"], r["lo"], r["has_prev"]] for r in merkle_plan(logs)])
+    return {"plans": plans, "wall_s": round(time.time() - t0, 3)}
+
+
 if __name__ == "__main__":
     mode = sys.argv[1]
-    res = prove(sys.argv[2], sys.argv[3].split(",")) if mode == "prove" else verify(sys.argv[2], sys.argv[3])
+    if mode == "merkle_layers":
+        res = merkle_layers()
+    else:
+        res = prove(sys.argv[2], sys.argv[3].split(",")) if mode == "prove" else verify(sys.argv[2], sys.argv[3])
     print(json.dumps(res), flush=True)

@@ -117,6 +117,31 @@ def test_env_selected_path_keeps_the_proof_bytes(expected, tmp_path, env, big):
             assert diff.size == 0, (env, name, k, "first differing word", int(diff[0]), "of", got.size)
 
 
+@pytest.mark.gpu
+def test_no_merkle_top_stores_every_layer(backend):
+    """CM_NO_MERKLE_TOP=1 in one fresh process: the shapes NO_TOP_SHAPES of tests/merkle_op_shapes.py become k_merkle_multi groups
+    of 4 + 4, 3 and 2 levels, each above a k_merkle_tail with a previous layer, and the child compares the root and every node of
+    every stored layer with the oracle (the proof-parity case above touches some 80 query paths per tree).  Same limit and the
+    same rule as the other children: a child that ends badly stops every later case."""
+    if _gpu_lost:
+        pytest.fail("not started: " + _gpu_lost[0])
+    env = {"CM_NO_MERKLE_TOP": "1"}
+    cmd = [sys.executable, "-m", "tests.env_path_child", "merkle_layers"]
+    try:
+        r = subprocess.run(cmd, cwd=ROOT, env=_child_env(env), capture_output=True, text=True, timeout=CHILD_LIMIT_S)
+    except subprocess.TimeoutExpired:
+        _gpu_lost.append(f"the merkle_layers child with {env} did not end within {CHILD_LIMIT_S} s")
+        pytest.fail(_gpu_lost[0])
+    if r.returncode != 0 and "AssertionError" not in r.stderr:   # a comparison that fails is a finding, not a lost GPU
+        _gpu_lost.append(f"the merkle_layers child with {env} ended with status {r.returncode}: {r.stderr[-400:]}")
+    assert r.returncode == 0, (env, r.returncode, r.stderr[-2000:])
+    out = json.loads(r.stdout.strip().splitlines()[-1])
+    print(f"merkle_layers child {env}: {out['wall_s']} s")
+    M, T = "multi", "tail"
+    assert out["plans"] == [[[M, 16, 13, False], [M, 12, 9, True], [T, 8, 0, True]], [[M, 11, 9, False], [T, 8, 0, True]],
+                            [[M, 10, 9, False], [T, 8, 0, True]]]
+
+
 def test_host_blake2s_without_avx512_gives_the_same_verdicts(oracle, tmp_path):
     from cairo_m_amd.lib import load_library, synth_fibonacci
     from tests.verify_many_util import hand_flips, host_verify_words

@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 
 from tests.fft_op_sizes import EVALUATE_EXTEND_LOGS, EVALUATE_PADDED, EXTEND_LOGS, INTERPOLATE_LOGS
+from tests.merkle_layers_util import first_difference
+from tests.merkle_op_shapes import COMMIT_PARITY_SHAPES
 
 P = 2**31 - 1
 pytestmark = pytest.mark.gpu
@@ -170,23 +172,25 @@ def test_eval_at_point_parity(backend, oracle, log_n):
         backend.col_free(h)
 
 
-@pytest.mark.parametrize("logs", [[6, 6, 6], [8] * 17 + [5] * 3 + [3], [10] * 40 + [9] * 16 + [4] * 5, [1], [12, 3],
-                                  # k_merkle_top: multi-block ticket (2^16 = 256 blocks), columns entering at phase-1 and
-                                  # phase-2 levels, single-layer kernels above; a wide layer (70 columns) forces the old path
-                                  [17] * 3 + [16] * 2 + [13] * 5 + [9] * 2 + [7] * 20 + [5] * 3 + [2], [16] * 4, [9] * 33,
-                                  [15] * 2 + [11] * 70 + [6] * 3,
-                                  # layers of 2^19 nodes and more go through k_merkle_layer (one node per lane, the dominant
-                                  # kernel of the bench): leaf layer without children, 18- and 4-column layers with children
-                                  [20] * 3 + [19] * 18 + [12] * 2, [19] * 4, [21] + [20] * 42 + [19]])
+# k_merkle_top: multi-block ticket (2^16 = 256 blocks), columns entering at phase-1 and phase-2 levels, single-layer kernels above;
+# a wide layer (70 columns) forces the old path.  Layers of 2^19 nodes and more go through k_merkle_layer (one node per lane, the
+# dominant kernel of the bench): leaf layer without children, 18- and 4-column layers with children.  (The lists live in
+# tests/merkle_op_shapes.py, where tests/test_merkle_plan_cpu.py pins their plans.)
+@pytest.mark.parametrize("logs", COMMIT_PARITY_SHAPES)
 def test_merkle_commit_parity(backend, oracle, logs):
+    """cm_merkle_commit's root equals the oracle's, and so does every node of every stored layer (cm_merkle_commit_layers)."""
     rng = np.random.default_rng(len(logs))
     cols = [rng.integers(0, P, size=1 << l, dtype=np.uint32) for l in logs]
     hs = [backend.upload(c) for c in cols]
     root = backend.merkle_commit(hs, logs)
-    want, _ = oracle.merkle_commit(cols)
-    assert root == want
+    root2, layers = backend.merkle_commit_layers(hs, logs)
     for h in hs:
         backend.col_free(h)
+    want, want_layers = oracle.merkle_commit(cols)
+    assert root == want
+    diff = first_difference(layers, want_layers, logs)
+    assert diff is None, diff
+    assert root2 == want
 
 
 @pytest.mark.parametrize("n_cols", [0, 4, 16, 17, 42])
