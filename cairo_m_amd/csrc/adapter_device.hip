@@ -4,7 +4,8 @@
 // The reference walks the memory log sequentially through a HashMap<address, (value, clock, multiplicity)>
 // to find, for every access, the previous access of the same cell.  Here:
 //   1. per step: opcode from the (immutable) program words at `pc`, entry / operand counts  -> exclusive scans
-//      give every step its slice of the memory log (checked against the log: first entry address == pc);
+//      give every step its slice of the memory log (checked against the log: first entry address == pc, and the opcode it
+//      logs is the one those words hold: a segment that stores over code it fetches later is refused);
 //   2. all log entries are sorted by (address, entry index) with one 64-bit radix sort (hipCUB): the
 //      predecessor in the sorted order IS the previous access of the cell (or the segment's initial memory);
 //   3. clock-update rows (gaps > 2^20 - 1) are counted per entry, scanned and scattered in log order;
@@ -71,12 +72,17 @@ __global__ void k_step_counts(const uint32_t* __restrict__ trace, uint32_t n_ste
 // bounds the sort's bit range
 __global__ void k_entry_keys(const uint32_t* __restrict__ trace, uint32_t n_steps, const unsigned long long* __restrict__ off,
                              const uint32_t* __restrict__ info, const uint32_t* __restrict__ mem /*5 words each*/, uint32_t n_mem,
-                             uint32_t* __restrict__ addr_key, uint32_t* __restrict__ entry_id, uint32_t* __restrict__ entry_clock,
-                             uint32_t* __restrict__ err /*[0] flags, [1] largest address*/) {
+                             const uint32_t* __restrict__ init_mem, uint32_t* __restrict__ addr_key, uint32_t* __restrict__ entry_id,
+                             uint32_t* __restrict__ entry_clock, uint32_t* __restrict__ err /*[0] flags, [1] largest address*/) {
   uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   uint32_t amax = 0;
   if (t < n_steps) {
     uint32_t e0 = (uint32_t)off[t], n = info_ne(info[t]);
+    // The offsets come from the opcodes of the memory at segment start (k_step_counts); the log is what the bundles are built
+    // from.  A fetch that logs another opcode than that memory holds (code stored over earlier in the segment) would be sized by
+    // the old one: refused by name.  (n != 0: the opcode at pc was valid, so pc is inside init_mem.)
+    if (n && e0 < n_mem && mem[5 * (size_t)e0] == trace[2 * t] && mem[5 * (size_t)e0 + 1] != init_mem[4 * (size_t)trace[2 * t]])
+      atomicOr(err, 8u);
     if (e0 + n > n_mem) { atomicOr(err, 2u); n = 0; }
     if (n && mem[5 * (size_t)e0] != trace[2 * t]) atomicOr(err, 4u);  // first entry of a step is the fetch at pc
     for (uint32_t k = 0; k < n; k++) {
@@ -368,7 +374,7 @@ static DeviceInput* adapt_impl(const cm_runner_segment& seg, Run* run, uint64_t 
   DevBuf d_addr((size_t)n_mem * 4 + 4), d_eid((size_t)n_mem * 4 + 4), d_saddr((size_t)n_mem * 4 + 4), d_se((size_t)n_mem * 4 + 4),
       d_eclk((size_t)n_mem * 4 + 4);
   hipLaunchKernelGGL(k_entry_keys, grid1(n_steps), dim3(256), 0, st, d_trace.u32(), n_steps, d_off.as<unsigned long long>(), d_info.u32(),
-                     d_mem.u32(), n_mem, d_addr.u32(), d_eid.u32(), d_eclk.u32(), d_err.u32());
+                     d_mem.u32(), n_mem, init.lo, d_addr.u32(), d_eid.u32(), d_eclk.u32(), d_err.u32());
   {
     // totals, error flags and the largest address are needed on the host before the sort sizes are trusted
     CM_HIP(hipMemcpyAsync(pin + 2, d_off.as<unsigned long long>() + (n_steps - 1), 8, hipMemcpyDeviceToHost, st));
@@ -376,6 +382,8 @@ static DeviceInput* adapt_impl(const cm_runner_segment& seg, Run* run, uint64_t 
     CM_HIP(hipStreamSynchronize(st));
     const uint32_t err = pin[4], amax = pin[5];
     CM_CHECK(!(err & 1u), "adapter: invalid opcode (or an opcode without a prover component)");
+    CM_CHECK(!(err & 8u), "adapter: a step's logged opcode differs from the memory at segment start (code rewritten inside a segment: "
+                          "the device adapter sizes the log by the memory at segment start)");
     CM_CHECK(!(err & 2u) && pin[0] + pin[2] == n_mem, "adapter: memory trace length does not match the instructions executed");
     CM_CHECK(!(err & 4u), "adapter: a step's first memory entry is not the instruction fetch at pc");
     n_acc = pin[1] + pin[3];

@@ -1,6 +1,7 @@
 // Host-only part of the C ABI: synthetic VM + adapter (cm_vm_run, cm_synth_fibonacci, ...).
 #include "../../include/cairom_hip.h"
 #include "host_adapter.hpp"
+#include <memory>
 #include <string>
 #include <string.h>
 
@@ -158,6 +159,59 @@ int32_t cm_host_segment_set_initial_heap(cm_host_segment* h, const uint32_t* ini
   h->view.initial_heap = h->heap.data(); h->view.n_initial_heap = n_initial_heap;
   h->seg.end_heap = n_initial_heap;
   return 0;
+}
+// The host adapter over a caller-supplied segment: host::import_segment, the log defines every opcode.  What import_segment does
+// not look at is checked here with the device adapter's messages: a step's first entry is the fetch at pc, and the log ends with
+// the last step.
+int32_t cm_adapt_segment_host(const cm_runner_segment* s, cm_host_input** out) {
+  try {
+    if (!s || !out) return cm_set_last_error("cm_adapt_segment_host: null argument");
+    if (s->n_trace < 2 || !s->trace) return cm_set_last_error("adapter: empty trace");
+    if (s->n_memory_trace < 1 || !s->memory_trace) return cm_set_last_error("adapter: empty memory trace");
+    if (s->n_trace >= (1ull << 32) || s->n_memory_trace >= (1ull << 32)) return cm_set_last_error("adapter: segment too large");
+    if ((s->n_initial_memory && !s->initial_memory) || (s->n_initial_heap && !s->initial_heap))
+      return cm_set_last_error("cm_adapt_segment_host: null memory");
+    const uint64_t SPACE = (uint64_t)cm::host::MAX_ADDRESS + 1;
+    if (s->n_initial_memory > SPACE || s->n_initial_heap > SPACE || s->n_initial_memory + s->n_initial_heap > SPACE)
+      return cm_set_last_error("adapter: locals and heap overlap");
+    // one walk over the log by its own opcodes: the shape import_segment relies on
+    uint64_t e = 0;
+    for (uint64_t t = 0; t + 1 < s->n_trace; t++) {
+      if (e >= s->n_memory_trace) return cm_set_last_error("adapter: memory trace length does not match the instructions executed");
+      if (s->memory_trace[5 * e] != s->trace[2 * t]) return cm_set_last_error("adapter: a step's first memory entry is not the instruction fetch at pc");
+      cm::host::OpInfo oi;
+      const uint32_t op = s->memory_trace[5 * e + 1];
+      if (!cm::host::op_info(op, oi) || air::component_of_opcode(op) < 0)
+        return cm_set_last_error("adapter: invalid opcode (or an opcode without a prover component)");
+      e += 1u + (oi.size_m31 > 4 ? 1u : 0u) + (uint32_t)oi.accesses;
+    }
+    if (e != s->n_memory_trace) return cm_set_last_error("adapter: memory trace length does not match the instructions executed");
+    cm::host::Segment seg;
+    seg.trace.resize(s->n_trace);
+    for (uint64_t i = 0; i < s->n_trace; i++) seg.trace[i] = {s->trace[2 * i], s->trace[2 * i + 1]};
+    seg.memory_trace.resize(s->n_memory_trace);
+    for (uint64_t i = 0; i < s->n_memory_trace; i++) {
+      const uint32_t* w = s->memory_trace + 5 * i;
+      seg.memory_trace[i] = cm::host::MemEntry{w[0], cm::host::Cell{w[1], w[2], w[3], w[4]}};
+    }
+    seg.initial_memory.resize(s->n_initial_memory);
+    for (uint64_t i = 0; i < s->n_initial_memory; i++) {
+      const uint32_t* w = s->initial_memory + 4 * i;
+      seg.initial_memory[i] = cm::host::Cell{w[0], w[1], w[2], w[3]};
+    }
+    seg.initial_heap.resize(s->n_initial_heap);
+    for (uint64_t i = 0; i < s->n_initial_heap; i++) {
+      const uint32_t* w = s->initial_heap + 4 * i;
+      seg.initial_heap[i] = cm::host::Cell{w[0], w[1], w[2], w[3]};
+    }
+    std::unique_ptr<cm_host_input> h(new cm_host_input());
+    h->owned = cm::host::import_segment(seg, s->program_range, s->input_range, s->output_range);
+    h->view = h->owned.view();
+    *out = h.release();
+    return 0;
+  } catch (const std::exception& e) {
+    return cm_set_last_error(e.what());
+  }
 }
 const cm_prover_input* cm_host_input_view(const cm_host_input* h) { return &h->view; }
 uint64_t cm_host_input_steps(const cm_host_input* h) { return h->owned.n_steps; }

@@ -1881,16 +1881,25 @@ int32_t cm_proof_public_data(const cm_proof* p, cm_public_data* out) {
     memcpy(out, &o, sizeof(o));
   });
 }
+static void public_entries_out(const cm::PublicData& d, uint32_t which, uint32_t* out, uint64_t cap_entries, uint64_t* n_entries, const char* too_small) {
+  const std::vector<cm::PublicEntry>& v = which == 0 ? d.program : which == 1 ? d.input : d.output;
+  *n_entries = v.size();
+  if (!out) return;
+  CM_CHECK(cap_entries >= v.size(), too_small);
+  static_assert(sizeof(cm::PublicEntry) == 28, "seven words per public entry");
+  if (!v.empty()) memcpy(out, v.data(), v.size() * sizeof(cm::PublicEntry));
+}
 int32_t cm_proof_public_entries(const cm_proof* p, uint32_t which, uint32_t* out, uint64_t cap_entries, uint64_t* n_entries) {
   return pguard([&] {
     CM_CHECK(p && p->d && n_entries && which <= 2, "cm_proof_public_entries: null argument, or `which` is not 0 (program), 1 (input) or 2 (output)");
-    const cm::PublicData& d = p->d->public_data;
-    const std::vector<cm::PublicEntry>& v = which == 0 ? d.program : which == 1 ? d.input : d.output;
-    *n_entries = v.size();
-    if (!out) return;
-    CM_CHECK(cap_entries >= v.size(), "cm_proof_public_entries: the output array is too small (the count is reported)");
-    static_assert(sizeof(cm::PublicEntry) == 28, "seven words per public entry");
-    if (!v.empty()) memcpy(out, v.data(), v.size() * sizeof(cm::PublicEntry));
+    public_entries_out(p->d->public_data, which, out, cap_entries, n_entries, "cm_proof_public_entries: the output array is too small (the count is reported)");
+  });
+}
+// the public data a device input already holds (host memory: no GPU work)
+int32_t cm_device_input_public_entries(const cm_device_input* in, uint32_t which, uint32_t* out, uint64_t cap_entries, uint64_t* n_entries) {
+  return pguard([&] {
+    CM_CHECK(in && in->d && n_entries && which <= 2, "cm_device_input_public_entries: null argument, or `which` is not 0 (program), 1 (input) or 2 (output)");
+    public_entries_out(in->d->public_data, which, out, cap_entries, n_entries, "cm_device_input_public_entries: the output array is too small (the count is reported)");
   });
 }
 // host code: every proof verifies, and each segment starts where its predecessor stopped (crates/prover/tests/prover.rs:198-243;

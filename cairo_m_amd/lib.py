@@ -601,6 +601,56 @@ def vm_segment(program, entry_pc=0, args=(), n_returns=0, max_steps=1 << 30, seg
     return hs
 
 
+class ArraySegment:
+    """A cm_runner_segment over caller-supplied arrays (hand-built segments: tests/adapter_segments.py): the `.view` / `.free()`
+    surface of HostSegment.  trace (n + 1, 2) (pc, fp); memory_trace (m, 5); initial_memory (k, 4); initial_heap (h, 4), index i =
+    the cell at 2^28 - 1 - i; ranges = program, input, output [start, end)."""
+
+    def __init__(self, trace, memory_trace, initial_memory, initial_heap=(), ranges=(0, 0, 0, 0, 0, 0)):
+        f = lambda a, w: np.ascontiguousarray(np.asarray(a, dtype=np.uint32).reshape(-1, w))
+        self.trace, self.memory_trace = f(trace, 2), f(memory_trace, 5)
+        self.initial_memory, self.initial_heap = f(initial_memory, 4), f(initial_heap, 4)
+        self.ranges = [int(x) for x in ranges]
+        ptr = lambda a: a.ctypes.data if a.shape[0] else None
+        self._v = RunnerSegmentView(ptr(self.trace), self.trace.shape[0], ptr(self.memory_trace), self.memory_trace.shape[0],
+                                    ptr(self.initial_memory), self.initial_memory.shape[0], (C.c_uint32 * 6)(*self.ranges),
+                                    ptr(self.initial_heap), self.initial_heap.shape[0])
+
+    @property
+    def view(self):
+        return C.cast(C.pointer(self._v), C.c_void_p)
+
+    def run_segment(self, n_memory_end, n_heap_end):
+        """the cm_run_segment of this segment's trace and log (this object must outlive it)"""
+        return RunSegmentC(self._v.trace, self._v.n_trace, self._v.memory_trace, self._v.n_memory_trace, int(n_memory_end), int(n_heap_end))
+
+    def free(self):
+        pass
+
+
+def adapt_segment_host(segment, lib=None):
+    """cm_adapt_segment_host: the host adapter (import_segment, what cm_vm_run runs) over a HostSegment / ArraySegment.  No GPU."""
+    L = lib or load_library()
+    h = C.c_void_p()
+    rc = L.cm_adapt_segment_host(segment.view, C.byref(h))
+    if rc:
+        raise _lib_error(L, rc)
+    return HostInput(L, h)
+
+
+def _backend_public_entries(self, dev_input):
+    """cm_device_input_public_entries: {"program" | "input" | "output": (n, 7) present, address, value[4], clock} as the device
+    input holds them (what its proof will carry)."""
+    out = {}
+    for which, name in enumerate(("program", "input", "output")):
+        n = C.c_uint64(0)
+        self._ck(self.L.cm_device_input_public_entries(dev_input, C.c_uint32(which), None, C.c_uint64(0), C.byref(n)))
+        a = np.zeros((n.value, 7), dtype=np.uint32)
+        self._ck(self.L.cm_device_input_public_entries(dev_input, C.c_uint32(which), _p(a), C.c_uint64(n.value), C.byref(n)))
+        out[name] = a
+    return out
+
+
 def _backend_adapt_segment(self, host_segment):
     """import_from_runner_output on the GPU: runner segment -> device-resident ProverInput."""
     h = C.c_void_p()
@@ -616,6 +666,7 @@ def _backend_download_input(self, dev_input):
 
 Backend.adapt_segment = _backend_adapt_segment
 Backend.download_input = _backend_download_input
+Backend.public_entries = _backend_public_entries
 
 
 def _backend_prove_many(self, dev_inputs, inflight=3, cfg=None):

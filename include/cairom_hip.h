@@ -39,7 +39,8 @@
  *    Still 10 (additive: four new functions and one struct, nothing moved): cm_mem_opening, cm_input_open_memory, cm_run_open_memory,
  *    cm_verify_memory_openings, cm_verify_memory_opening.
  *    Still 10 (additive: two host-only queries): cm_fft_plan, cm_fft_extend_fused.
- *    Still 10 (additive: two host-only queries, one op): cm_merkle_plan, cm_merkle_layer_npw, cm_merkle_commit_layers. */
+ *    Still 10 (additive: two host-only queries, one op): cm_merkle_plan, cm_merkle_layer_npw, cm_merkle_commit_layers.
+ *    Still 10 (additive: two host-side entry points): cm_adapt_segment_host, cm_device_input_public_entries. */
 #define CM_ABI_REVISION 10
 
 #ifdef __cplusplus
@@ -538,7 +539,9 @@ int32_t cm_set_memory_budget(uint64_t bytes);
  * segment start (crates/runner/src/vm/mod.rs:306-375, crates/common/src/execution.rs:28-66).
  * cm_adapt_segment_device = import_from_runner_output (crates/prover/src/adapter/mod.rs:97-193) with the
  * per-step work (previous-access tracking, clock updates, opcode bucketing) on the GPU; the result is the
- * device-resident ProverInput cm_prove_device consumes.  Same row order as the host adapter (cm_vm_run). */
+ * device-resident ProverInput cm_prove_device consumes.  Same row order as the host adapter (cm_vm_run).
+ * Every step's slice of the log is sized by the opcode the memory at segment start holds at its pc: a segment whose log shows
+ * another opcode at a fetch (code stored over inside the segment) is refused by name (status 1), here and in a run. */
 typedef struct {
   const uint32_t* trace;           /* (pc, fp) pairs: n_trace = steps + 1 entries */
   uint64_t n_trace;
@@ -554,6 +557,11 @@ typedef struct {
   uint64_t n_initial_heap;
 } cm_runner_segment;
 int32_t cm_adapt_segment_device(const cm_runner_segment* seg, cm_device_input** out);
+/* The host adapter (the sequential restatement of adapter/mod.rs:97-193 behind cm_vm_run) over a caller-supplied segment: the same
+ * cm_host_input cm_vm_run returns, no GPU.  The log defines every step's opcode.  Status 1 for the input errors of
+ * cm_adapt_segment_device, with its messages (empty trace, invalid opcode, a memory trace whose length does not match the
+ * instructions executed, a step whose first entry is not the fetch at pc, overlapping regions). */
+int32_t cm_adapt_segment_host(const cm_runner_segment* seg, cm_host_input** out);
 /* streaming ingest from runner segments: see cm_prove_many_host */
 int32_t cm_prove_many_segments(const cm_runner_segment* const* segments, uint32_t n, const cm_pcs_config* config, uint32_t inflight,
                                cm_proof** outs);
@@ -606,6 +614,9 @@ int32_t cm_proof_public_data(const cm_proof* p, cm_public_data* out);
 /* which: 0 program, 1 input, 2 output.  *n_entries always receives the count; out (NULL = count only) receives seven words per
  * entry: present, address, value[4], clock (all zero where the boundary memory has no such cell). */
 int32_t cm_proof_public_entries(const cm_proof* p, uint32_t which, uint32_t* out, uint64_t cap_entries, uint64_t* n_entries);
+/* The same entries, read from a device input (they are what its proof will carry): contract of cm_proof_public_entries.  The data
+ * is held in host memory: no GPU work. */
+int32_t cm_device_input_public_entries(const cm_device_input* in, uint32_t which, uint32_t* out, uint64_t cap_entries, uint64_t* n_entries);
 /* Host code, no GPU: every proof passes cm_verify_proof, and for every i > 0 the initial pc, fp and memory root of proof i equal
  * the final ones of proof i - 1.  Status 11; the message names the link and the field, e.g.
  * "run: segment 3 initial_root != segment 2 final_root", or "run: segment 3: verification failed: ...". */

@@ -408,6 +408,7 @@ unsafe extern "C" {
     pub fn cm_prove_run(r: *mut cm_run, segs: *const *const cm_run_segment, n: u32, config: *const cm_pcs_config, inflight: u32, outs: *mut *mut cm_proof) -> i32;
     pub fn cm_proof_public_data(p: *const cm_proof, out: *mut cm_public_data) -> i32;
     pub fn cm_proof_public_entries(p: *const cm_proof, which: u32, out: *mut u32, cap_entries: u64, n_entries: *mut u64) -> i32;
+    pub fn cm_device_input_public_entries(input: *const cm_device_input, which: u32, out: *mut u32, cap_entries: u64, n_entries: *mut u64) -> i32;
     pub fn cm_verify_run(proofs: *const *const cm_proof, n: u32, expected: *const cm_pcs_config) -> i32;
     pub fn cm_verify_many(proofs: *const *const cm_proof, n: u32, expected: *const cm_pcs_config, results: *mut cm_verify_result, s: cm_stream_t) -> i32;
     pub fn cm_verify_run_device(proofs: *const *const cm_proof, n: u32, expected: *const cm_pcs_config) -> i32;
@@ -424,6 +425,7 @@ unsafe extern "C" {
     pub fn cm_proof_transcript(p: *const cm_proof, json_out: *mut *const c_char, len_out: *mut usize) -> i32;
     pub fn cm_proof_commitments(p: *const cm_proof, roots: *mut [u8; 32]) -> i32;
     pub fn cm_adapt_segment_device(seg: *const cm_runner_segment, out: *mut *mut cm_device_input) -> i32;
+    pub fn cm_adapt_segment_host(seg: *const cm_runner_segment, out: *mut *mut cm_host_input) -> i32;
     pub fn cm_device_input_download(src: *const cm_device_input, out: *mut *mut cm_host_input) -> i32;
     pub fn cm_vm_segment(instr_words: *const u32, instr_lens: *const u32, n_instr: u32, entry_pc: u32, args: *const u32, n_args: u32, n_returns: u32, max_steps: u64, segment_index: u32, out: *mut *mut cm_host_segment, n_segments_out: *mut u32) -> i32;
     pub fn cm_synth_fibonacci_segment(n: u32, max_steps: u64, segment_index: u32, out: *mut *mut cm_host_segment) -> i32;

@@ -465,6 +465,33 @@ pub fn merkle_layer_npw(log_size: u32, has_prev: bool, n_cols: u32) -> Result<u3
     Ok(npw)
 }
 
+/// The host adapter over a caller-supplied runner segment (`cm_adapt_segment_host`): the `cm_host_input` that `cm_vm_run`
+/// returns, built without a GPU; the log defines every step's opcode.  The caller frees it with `cm_host_input_free`.
+pub fn adapt_segment_host(seg: &cm_runner_segment) -> Result<*mut cm_host_input, String> {
+    let mut out: *mut cm_host_input = std::ptr::null_mut();
+    let rc = unsafe { cm_adapt_segment_host(seg, &mut out) };
+    if rc != 0 {
+        return Err(last_error());
+    }
+    Ok(out)
+}
+
+/// The public entries a device input holds (`cm_device_input_public_entries`; `which`: 0 program, 1 input, 2 output): per
+/// address of the range `[present, address, value[4], clock]`, as its proof will carry them.  Host memory: touches no GPU.
+pub fn device_input_public_entries(input: *const cm_device_input, which: u32) -> Result<Vec<[u32; 7]>, String> {
+    let mut n: u64 = 0;
+    let rc = unsafe { cm_device_input_public_entries(input, which, std::ptr::null_mut(), 0, &mut n) };
+    if rc != 0 {
+        return Err(last_error());
+    }
+    let mut out = vec![[0u32; 7]; n as usize];
+    let rc = unsafe { cm_device_input_public_entries(input, which, out.as_mut_ptr() as *mut u32, n, &mut n) };
+    if rc != 0 {
+        return Err(last_error());
+    }
+    Ok(out)
+}
+
 /// `cm_merkle_commit_layers`: the root of the mixed-degree tree over `cols` and every stored layer, largest first, 8 words per node.
 pub fn merkle_commit_layers(cols: &[cm_handle], col_logs: &[u32]) -> Result<([u8; 32], Vec<u32>), String> {
     ensure_init();
