@@ -19,6 +19,7 @@
 #include "engine.hpp"
 #include "host_adapter.hpp"
 #include "mem_open.hpp"
+#include "mem_range.hpp"
 #include "proof.hpp"
 #include <hipcub/hipcub.hpp>
 #include <stdlib.h>

@@ -379,11 +379,9 @@ void run_memory(Run& r, uint32_t* locals, uint64_t cap_l, uint64_t* n_l, uint32_
 // Openings under the root of the image as it is now (mem_open.hip): the leaves of every image cell (k_image_leaves) through the
 // device tree builder on first use — one round trip for the tree's size and root, one wait behind its copy into a right-sized
 // block — then one round trip per call for the records.
-void run_open_memory(Run& r, const uint32_t* addresses, uint64_t n, cm_mem_opening* out, uint32_t* root) {
-  bind_thread_to_library_device();
-  hipStream_t st = thread_main_stream();
+static void run_image_tree(Run& r, const char* who, hipStream_t st) {
   const uint64_t cells = (uint64_t)r.n_lo + r.n_hi;
-  CM_CHECK(cells > 0, "cm_run_open_memory: the image is empty: there is no tree to open");
+  CM_CHECK(cells > 0, std::string(who) + ": the image is empty: there is no tree to open");
   if (!r.img_tree.p) {
     r.wait_on(st);   // the last advance may have been enqueued from another thread's stream
     const uint32_t cap = (uint32_t)(4 * cells);
@@ -405,8 +403,21 @@ void run_open_memory(Run& r, const uint32_t* addresses, uint64_t n, cm_mem_openi
     CM_HIP(hipStreamSynchronize(st));
     r.img_tree = std::move(exact); r.n_img_tree = n_nodes; r.img_root = img_root;
   }
+}
+void run_open_memory(Run& r, const uint32_t* addresses, uint64_t n, cm_mem_opening* out, uint32_t* root) {
+  bind_thread_to_library_device();
+  hipStream_t st = thread_main_stream();
+  run_image_tree(r, "cm_run_open_memory", st);
   *root = r.img_root;
   open_paths(r.img_tree.as<cm_merkle_node>(), r.n_img_tree, addresses, n, out, st);
+}
+// The same cached tree, opened over a range (mem_range.hip): one round trip per call once the tree exists.
+void run_open_memory_range(Run& r, uint32_t start, uint32_t n_cells, uint32_t* values, cm_mem_range_opening* out, uint32_t* root) {
+  bind_thread_to_library_device();
+  hipStream_t st = thread_main_stream();
+  run_image_tree(r, "cm_run_open_memory_range", st);
+  open_range(r.img_tree.as<cm_merkle_node>(), r.n_img_tree, start, n_cells, values, out, st);
+  *root = r.img_root;
 }
 // an upper bound of the boundary-memory rows of the next segment, for the memory budget: the image and every logged access
 uint64_t run_rows_bound(const Run& r, uint64_t n_memory_trace) {

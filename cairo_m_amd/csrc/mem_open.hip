@@ -158,6 +158,12 @@ void open_check_addresses(const char* who, const uint32_t* addresses, uint64_t n
                                                ") is beyond the address space of 2^28 cells");
 }
 
+void open_depth_offsets_enqueue(const cm_merkle_node* nodes, uint64_t n_nodes, uint32_t* off, hipStream_t st) {
+  CM_CHECK(n_nodes < (1ull << 32), "memory openings: the tree is too large");
+  hipLaunchKernelGGL(k_open_depth_offsets, dim3(1), dim3(64), 0, st, reinterpret_cast<const uint32_t*>(nodes), (uint32_t)n_nodes, off);
+  CM_HIP(hipGetLastError());
+}
+
 void image_leaves_enqueue(const uint32_t* lo, uint32_t n_lo, const uint32_t* hi, uint32_t n_hi, uint32_t* idx, uint32_t* val, uint32_t* mult,
                           hipStream_t st) {
   const uint64_t cells = (uint64_t)n_lo + n_hi;

@@ -167,6 +167,8 @@ std::mutex& run_mutex(Run& r);
 void run_open_memory(Run& r, const uint32_t* addresses, uint64_t n, cm_mem_opening* out, uint32_t* root);
 void open_require_device(const char* who);   // mem_open.hip
 void open_check_addresses(const char* who, const uint32_t* addresses, uint64_t n, const cm_mem_opening* out);
+void run_open_memory_range(Run& r, uint32_t start, uint32_t n_cells, uint32_t* values, cm_mem_range_opening* out, uint32_t* root);
+void open_range_check(const char* who, uint32_t start, uint32_t n_cells, const uint32_t* values, const cm_mem_range_opening* out);   // mem_range.hip
 void run_free(Run* r);
 // copy a device-resident input back to the host (tests)
 void download_input(const DeviceInput& d, host::ProverInputOwned& o) {
@@ -1828,6 +1830,16 @@ int32_t cm_run_open_memory(cm_run* r, const uint32_t* addresses, uint64_t n, cm_
     cm::open_check_addresses("cm_run_open_memory", addresses, n, out);
     std::lock_guard<std::mutex> lk(cm::run_mutex(*r->r));
     cm::run_open_memory(*r->r, addresses, n, out, root);
+  });
+}
+// a range under the same root (mem_range.hip); every refusal comes before the first write
+int32_t cm_run_open_memory_range(cm_run* r, uint32_t start, uint32_t n_cells, uint32_t* values, cm_mem_range_opening* out, uint32_t* root) {
+  return pguard([&] {
+    cm::open_require_device("cm_run_open_memory_range");
+    CM_CHECK(r && r->r && root, "cm_run_open_memory_range: null argument");
+    cm::open_range_check("cm_run_open_memory_range", start, n_cells, values, out);
+    std::lock_guard<std::mutex> lk(cm::run_mutex(*r->r));
+    cm::run_open_memory_range(*r->r, start, n_cells, values, out, root);
   });
 }
 int32_t cm_run_free(cm_run* r) { delete r; return 0; }

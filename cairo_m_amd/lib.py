@@ -1590,3 +1590,121 @@ def verify_opening(root, opening, lib=None):
 Backend.open_memory = _backend_open_memory
 Backend.verify_openings = lambda self, root, openings, stream=0: verify_openings(root, openings, self.L, stream)
 Run.open = _run_open
+
+
+# ---- range openings (include/cairom_hip.h, additive to revision 10) -------------------------------------------------
+RANGE_MAX_CELLS = 1 << 24
+RANGE_KERNELS = ("cells", "level", "tail")
+
+
+class MemRangeOpening(C.Structure):
+    """cm_mem_range_opening: a contiguous run of cells under a memory root.  left[k] / right[k] = the node left / right of the
+    interval the range covers at depth 28 - k, where hashing it up needs one, else 0.  The values travel beside the record."""
+    _fields_ = [("start", C.c_uint32), ("n_cells", C.c_uint32), ("left", C.c_uint32 * 28), ("right", C.c_uint32 * 28)]
+
+    def words(self):
+        return [self.start, self.n_cells] + list(self.left) + list(self.right)
+
+    @classmethod
+    def from_words(cls, words):
+        w = [int(x) for x in words]
+        return cls(w[0], w[1], (C.c_uint32 * 28)(*w[2:30]), (C.c_uint32 * 28)(*w[30:58]))
+
+    def __repr__(self):
+        return f"MemRangeOpening(start={self.start}, n_cells={self.n_cells})"
+
+
+class MemRangeStep(C.Structure):
+    """cm_mem_range_step: one hashing step of a range's verification (cm_mem_range_plan)."""
+    _fields_ = [("depth", C.c_uint32), ("lo", C.c_uint32), ("hi", C.c_uint32), ("kernel", C.c_uint32), ("uses_left", C.c_uint32),
+                ("uses_right", C.c_uint32)]
+
+
+def _range_call(L, fn, head, start, n):
+    start, n = int(start), int(n)
+    if not (0 <= start < 1 << 32 and 0 <= n < 1 << 32):
+        raise ValueError("start or n does not fit 32 bits")
+    # (a refused call writes nothing: the array only has to exist)
+    values = np.zeros((n if 0 < n <= RANGE_MAX_CELLS else 1, 4), dtype=np.uint32)
+    out, root = MemRangeOpening(), C.c_uint32(0)
+    rc = fn(*head, C.c_uint32(start), C.c_uint32(n), _p(values), C.byref(out), C.byref(root))
+    if rc:
+        raise _lib_error(L, rc)
+    return out, values, root.value
+
+
+def _backend_open_memory_range(self, dev_input, which, start, n):
+    """cm_input_open_memory_range: the cells [start, start + n) under the input's initial (which = 0) or final (1) tree, built on
+    the GPU -> (MemRangeOpening, values (n, 4), root)."""
+    return _range_call(self.L, self.L.cm_input_open_memory_range, (dev_input, C.c_uint32(which)), start, n)
+
+
+def _run_open_range(self, start, n):
+    """cm_run_open_memory_range: a range under the root of the image as it is now -> (MemRangeOpening, values (n, 4), root).
+    Shares the cached image tree of Run.open."""
+    return _range_call(self.L, self.L.cm_run_open_memory_range, (self.h,), start, n)
+
+
+def _run_open_image(self):
+    """The whole image under its one root: the locals [0, n_l) and the heap [2^28 - n_h, 2^28), each omitted when empty ->
+    ([(MemRangeOpening, values)], root).  Every other cell is zero exactly when both ranges verify under a root that commits to
+    nothing else: the sibling words of the two records are what stands next to the image."""
+    n_l, n_h = self.lengths()
+    spans = [(s, n) for s, n in ((0, n_l), (ADDRESS_SPACE - n_h, n_h)) if n]
+    if not spans:
+        raise CmError("open_image: the image is empty: there is no tree to open")
+    out, root = [], None
+    for s, n in spans:
+        for off in range(0, n, RANGE_MAX_CELLS):                                  # (one call takes 2^24 cells)
+            rec, values, root = self.open_range(s + off, min(RANGE_MAX_CELLS, n - off))
+            out.append((rec, values))
+    return out, root
+
+
+def _range_values(opening, values):
+    v = np.ascontiguousarray(values, dtype=np.uint32).reshape(-1)
+    if v.size != 4 * opening.n_cells and opening.n_cells <= RANGE_MAX_CELLS:
+        raise ValueError(f"{v.size} value words for a range of {opening.n_cells} cells")
+    return v if v.size else np.zeros(4, dtype=np.uint32)
+
+
+def verify_range(root, opening, values, lib=None, stream=0):
+    """cm_verify_memory_range (GPU) -> bool: record and values are well formed and hash to `root`."""
+    L = lib or load_library()
+    v = _range_values(opening, values)
+    ok = C.c_uint8(0)
+    rc = L.cm_verify_memory_range(C.c_uint32(root), C.byref(opening), _p(v), C.byref(ok), C.c_uint64(stream))
+    if rc:
+        raise _lib_error(L, rc)
+    return bool(ok.value)
+
+
+def verify_range_host(root, opening, values, lib=None):
+    """cm_verify_memory_range_host (host code, no GPU) -> (status, message): (0, "") accepted, (11, why) rejected."""
+    L = lib or load_library()
+    v = _range_values(opening, values)
+    rc = L.cm_verify_memory_range_host(C.c_uint32(root), C.byref(opening), _p(v))
+    if not rc:
+        return 0, ""
+    buf = C.create_string_buffer(512)
+    L.cm_last_error(buf, C.c_size_t(512))
+    return rc, buf.value.decode(errors="replace")
+
+
+def mem_range_plan(start, n, lib=None):
+    """cm_mem_range_plan: the hashing steps of a range's verification, one dict per step: depth, lo, hi (the nodes the step
+    produces), kernel (a RANGE_KERNELS name), uses_left, uses_right.  Host code: needs no GPU."""
+    L = lib or load_library()
+    steps = (MemRangeStep * 29)()
+    k = C.c_uint32(0)
+    rc = L.cm_mem_range_plan(C.c_uint32(start), C.c_uint32(n), steps, C.c_uint32(29), C.byref(k))
+    if rc:
+        raise _lib_error(L, rc)
+    return [{"depth": s.depth, "lo": s.lo, "hi": s.hi, "kernel": RANGE_KERNELS[s.kernel], "uses_left": bool(s.uses_left),
+             "uses_right": bool(s.uses_right)} for s in steps[:k.value]]
+
+
+Backend.open_memory_range = _backend_open_memory_range
+Backend.verify_range = lambda self, root, opening, values, stream=0: verify_range(root, opening, values, self.L, stream)
+Run.open_range = _run_open_range
+Run.open_image = _run_open_image

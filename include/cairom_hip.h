@@ -40,6 +40,8 @@
  *    cm_verify_memory_openings, cm_verify_memory_opening.
  *    Still 10 (additive: two host-only queries): cm_fft_plan, cm_fft_extend_fused.
  *    Still 10 (additive: two host-only queries, one op): cm_merkle_plan, cm_merkle_layer_npw, cm_merkle_commit_layers.
+ *    Still 10 (additive: five new functions and two structs, nothing moved): cm_mem_range_opening, cm_mem_range_step,
+ *    cm_input_open_memory_range, cm_run_open_memory_range, cm_verify_memory_range, cm_verify_memory_range_host, cm_mem_range_plan.
  *    Still 10 (additive: two host-side entry points): cm_adapt_segment_host, cm_device_input_public_entries. */
 #define CM_ABI_REVISION 10
 
@@ -897,6 +899,60 @@ int32_t cm_verify_memory_openings(uint32_t root, const cm_mem_opening* openings,
  * the field that makes the record malformed with its depth (a value word: depth 30; "the sibling at depth <d>"), or, for a
  * well-formed record, "the path hashes to root <x>, not <y>". */
 int32_t cm_verify_memory_opening(uint32_t root, const cm_mem_opening* opening);
+/* ---- range openings (additive to revision 10: new symbols and two structs, nothing moved) ---------------------------------------
+ * A contiguous run of cells under one root: a checkpoint image, an array-shaped result.  Neighbouring cells share almost every
+ * node above them, so the statement needs the values (16 bytes per cell), at most two siblings per depth and about 4 hashes per
+ * cell, where cell-by-cell openings cost 136 bytes and 31 hashes each.  The range [start, start + n_cells), with
+ * last = start + n_cells - 1, covers the nodes [start >> k, last >> k] of depth 28 - k, k = 0 .. 27; hashing that interval up one
+ * depth needs the node left of it exactly when start >> k is odd and the node right of it exactly when last >> k is even.
+ * The values travel beside the record: 4 * n_cells words, an absent cell as (0, 0, 0, 0).  There is no `present` flag: a cell
+ * held with zeros hashes like an absent one and a range has no use for the distinction.  A slot the range does not need is 0
+ * and a record with a non-zero unused slot is malformed, so a range has exactly one valid record and the same call gives the
+ * same bytes.  For n_cells = 1 exactly one of left[k] / right[k] is used at every k and equals siblings[k] of the cm_mem_opening
+ * of that address.
+ *
+ * cm_input_open_memory_range / cm_run_open_memory_range build the record and the values on the GPU, on the calling thread's stream
+ * and pool (threading as cm_run_open_memory): one lane per cell half bisects depth 30 of the node list, 56 more lanes bisect the
+ * sibling slots — the lookup rule of the single openings, so the two can never disagree about a tree — and the words come back
+ * in one host round trip (one more per further 2^19 cells).  cm_run_open_memory_range shares the cached image tree of
+ * cm_run_open_memory: built on first use by either call, dropped when the image advances.  *root is written whenever the status
+ * is 0.  Status 1, with nothing written to values or out: n_cells == 0, start + n_cells > 2^28, n_cells > 2^24, which > 1, a
+ * NULL argument, a run whose image is empty.  Without a GPU the status is cm_init's (3).
+ * cm_verify_memory_range uploads the values and the record and recomputes the root on the GPU (stream s; 0 = the calling
+ * thread's own): one lane per cell gives the nodes of depth 28, one launch per depth halves the interval while it is wider than
+ * 128 nodes, one workgroup finishes the remaining depths, checks the record's own words and compares with `root`; one word comes
+ * back.  *ok = 1 when record and values are well formed and hash to `root`; a word >= P, a non-zero unused slot, n_cells == 0 or
+ * start + n_cells > 2^28 give *ok = 0 and do not fail the call.  Status 1: a NULL argument or n_cells > 2^24 (read before
+ * anything is allocated).  The call keeps nothing.
+ * cm_verify_memory_range_host is the same check in host code, for a light client: it needs no GPU.
+ * cm_mem_range_plan lists the hashing steps of the verification, host code only: steps[0] = the cells (depth 28, lo = start,
+ * hi = last), steps[k + 1] = the step that hashes the interval of depth 28 - k into the nodes [lo, hi] of `depth` = 27 - k and
+ * reads left[k] / right[k] where uses_left / uses_right are 1; `kernel` = 0 the per-cell kernel, 1 the per-level kernel, 2 the
+ * single-workgroup tail (consecutive tail steps are one launch).  Always 29 steps; the device verifier launches from the same
+ * records, so this is what runs.  Status 1: a bad range, a NULL argument, cap < 29. */
+typedef struct {
+  uint32_t start, n_cells;      /* n_cells >= 1, start + n_cells <= 2^28 */
+  uint32_t left[28];            /* left[k]  = node (depth 28-k, index (start>>k) - 1) when (start>>k) is odd,  else 0 */
+  uint32_t right[28];           /* right[k] = node (depth 28-k, index (last>>k) + 1)  when (last>>k) is even, else 0 */
+} cm_mem_range_opening;         /* sizeof = 232 */
+typedef struct {
+  uint32_t depth, lo, hi;       /* the step produces the nodes lo .. hi of this depth */
+  uint32_t kernel;              /* 0 k_range_cells, 1 k_range_level, 2 k_range_tail */
+  uint32_t uses_left, uses_right;
+} cm_mem_range_step;            /* sizeof = 24 */
+/* which: 0 = the input's initial tree, 1 = its final tree.  values: 4 * n_cells words.  *root receives that tree's root. */
+int32_t cm_input_open_memory_range(const cm_device_input* in, uint32_t which, uint32_t start, uint32_t n_cells, uint32_t* values,
+                                   cm_mem_range_opening* out, uint32_t* root);
+/* Under the root of the run's image as it is now.  Serialised with the other calls on the run. */
+int32_t cm_run_open_memory_range(cm_run* r, uint32_t start, uint32_t n_cells, uint32_t* values, cm_mem_range_opening* out, uint32_t* root);
+/* GPU: *ok in {0, 1}; returns 0 when it ran. */
+int32_t cm_verify_memory_range(uint32_t root, const cm_mem_range_opening* opening, const uint32_t* values, uint8_t* ok, cm_stream_t s);
+/* Host code, no GPU: 0 accepted, 11 rejected (1: a NULL argument or n_cells > 2^24).  cm_last_error() then reads
+ * "memory range [<start>, <end>): " and what is wrong: "value word <i> of cell <a> is not below P", "the left sibling at depth
+ * <d> is not below P" / "the right sibling ...", "unused left slot at depth <d> is not zero" / "unused right slot ...", a bad
+ * start or n_cells, or, for a well-formed record, "the range hashes to root <x>, not <y>". */
+int32_t cm_verify_memory_range_host(uint32_t root, const cm_mem_range_opening* opening, const uint32_t* values);
+int32_t cm_mem_range_plan(uint32_t start, uint32_t n_cells, cm_mem_range_step* steps, uint32_t cap, uint32_t* n_steps);
 /* AccumulationOps::accumulate: dst[k][i] += src[k][i] (4 coordinate columns of n words); generate_secure_powers:
  * out[i] = felt^i for i < n (host array of 4 * n words).  Column::zeros = cm_col_alloc + cm_col_zero. */
 int32_t cm_accumulate(const cm_handle dst[4], const cm_handle src[4], uint64_t n, cm_stream_t s);

@@ -333,6 +333,31 @@ pub struct cm_mem_opening {
     pub siblings: [u32; 28],
 }
 pub type CmMemOpening = cm_mem_opening;
+/// A contiguous run of cells under a 31-bit memory root (`cm_input_open_memory_range`, `cm_run_open_memory_range`): with
+/// last = start + n_cells - 1, `left[k]` is the node of depth 28 - k left of the interval [start >> k, last >> k] when
+/// start >> k is odd and `right[k]` the node right of it when last >> k is even; a slot the range does not need is 0.  The values
+/// travel beside the record, four words per cell
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct cm_mem_range_opening {
+    pub start: u32,
+    pub n_cells: u32,
+    pub left: [u32; 28],
+    pub right: [u32; 28],
+}
+pub type CmMemRangeOpening = cm_mem_range_opening;
+/// One hashing step of a range's verification (`cm_mem_range_plan`): the nodes `lo ..= hi` of `depth` it produces, the kernel
+/// that runs it (0 per cell, 1 per level, 2 the single-workgroup tail) and which sibling words it reads
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct cm_mem_range_step {
+    pub depth: u32,
+    pub lo: u32,
+    pub hi: u32,
+    pub kernel: u32,
+    pub uses_left: u32,
+    pub uses_right: u32,
+}
 
 unsafe extern "C" {
     pub fn cm_init(device: i32) -> i32;
@@ -453,6 +478,11 @@ unsafe extern "C" {
     pub fn cm_run_open_memory(r: *mut cm_run, addresses: *const u32, n: u64, out: *mut cm_mem_opening, root: *mut u32) -> i32;
     pub fn cm_verify_memory_openings(root: u32, openings: *const cm_mem_opening, n: u64, ok: *mut u8, s: cm_stream_t) -> i32;
     pub fn cm_verify_memory_opening(root: u32, opening: *const cm_mem_opening) -> i32;
+    pub fn cm_input_open_memory_range(input: *const cm_device_input, which: u32, start: u32, n_cells: u32, values: *mut u32, out: *mut cm_mem_range_opening, root: *mut u32) -> i32;
+    pub fn cm_run_open_memory_range(r: *mut cm_run, start: u32, n_cells: u32, values: *mut u32, out: *mut cm_mem_range_opening, root: *mut u32) -> i32;
+    pub fn cm_verify_memory_range(root: u32, opening: *const cm_mem_range_opening, values: *const u32, ok: *mut u8, s: cm_stream_t) -> i32;
+    pub fn cm_verify_memory_range_host(root: u32, opening: *const cm_mem_range_opening, values: *const u32) -> i32;
+    pub fn cm_mem_range_plan(start: u32, n_cells: u32, steps: *mut cm_mem_range_step, cap: u32, n_steps: *mut u32) -> i32;
     pub fn cm_relation_sums(component: i32, trace_cols: *const cm_handle, preprocessed: *const cm_handle, log_size: u32, relations: *const cm_relations, sums: *mut [u32; 4], s: cm_stream_t) -> i32;
     pub fn cm_accumulate(dst: *const cm_handle, src: *const cm_handle, n: u64, s: cm_stream_t) -> i32;
     pub fn cm_generate_secure_powers(felt: *const u32, n: u64, out: *mut u32) -> i32;

@@ -419,6 +419,37 @@ pub fn verify_memory_openings(root: u32, openings: &[CmMemOpening]) -> Result<Ve
     Ok(ok.iter().map(|v| *v != 0).collect())
 }
 
+/// The cells `start .. start + n_cells` under the initial (`which` = 0) or final (1) memory root of a device-resident input
+/// (`cm_input_open_memory_range`), built on the GPU: the record, the values (four words per cell, an absent cell as zeros) and
+/// that root.  At most 2^24 cells per call.  Checked without the memory by `verify_memory_range` (GPU) or by
+/// `ffi::cm_verify_memory_range_host` (host code).
+pub fn open_memory_range(input: *const cm_device_input, which: u32, start: u32, n_cells: u32) -> Result<(CmMemRangeOpening, Vec<u32>, u32), String> {
+    ensure_init();
+    let mut out: CmMemRangeOpening = unsafe { std::mem::zeroed() };
+    let mut values: Vec<u32> = vec![0; 4 * (n_cells.min(1 << 24).max(1) as usize)];
+    let mut root: u32 = 0;
+    let rc = unsafe { cm_input_open_memory_range(input, which, start, n_cells, values.as_mut_ptr(), &mut out, &mut root) };
+    if rc != 0 {
+        return Err(last_error());
+    }
+    Ok((out, values, root))
+}
+
+/// A range checked against `root` on the GPU (`cm_verify_memory_range`): `values` holds four words per cell of the record; a
+/// malformed record or value is a `false`, not an error.
+pub fn verify_memory_range(root: u32, opening: &CmMemRangeOpening, values: &[u32]) -> Result<bool, String> {
+    ensure_init();
+    if opening.n_cells <= 1 << 24 && values.len() != 4 * opening.n_cells as usize {
+        return Err(format!("{} value words for a range of {} cells", values.len(), opening.n_cells));
+    }
+    let mut ok: u8 = 0;
+    let rc = unsafe { cm_verify_memory_range(root, opening, values.as_ptr(), &mut ok, 0) };
+    if rc != 0 {
+        return Err(last_error());
+    }
+    Ok(ok != 0)
+}
+
 /// The passes of a 2^`log_n` transform as the library runs it (`cm_fft_plan`), in layer order: `[lo, hi, tile_log, M]` per pass,
 /// `tile_log` 0 = the generic kernel.  Host code: touches no GPU.
 pub fn fft_plan(log_n: u32) -> Result<Vec<[u32; 4]>, String> {

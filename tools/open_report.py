@@ -10,7 +10,13 @@ One process, one GPU session.  Recorded, wall ms:
   open_cached  the same call again with the tree cached: upload of the addresses, two launches, download of the records;
   verify_gpu   cm_verify_memory_openings over the records (upload, one launch, download);
   verify_host  a loop of the host cm_verify_memory_opening over the same records in the same process (one ctypes call each).
-No threshold: these are first measurements."""
+No threshold: these are first measurements.
+
+    python tools/open_report.py --range --out profiles/<set>_open_range_report.json
+
+The `range` section: on the same image, --queries CONSECUTIVE cells opened and checked as one range (cm_run_open_memory_range with
+the image's tree cached, cm_verify_memory_range) against the same cells through cm_run_open_memory + cm_verify_memory_openings,
+timed in alternating blocks in one process; medians and the bytes each side returns (16 n + 232 against 136 n)."""
 import argparse
 import ctypes as C
 import json
@@ -29,6 +35,59 @@ def stats(v):
     return {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4), "n": len(v)}
 
 
+def range_section(a, be, lo, hp):
+    from cairo_m_amd.lib import MemOpening, MemRangeOpening
+    L = be.L
+    n = a.queries
+    start = (lo.shape[0] - n) // 2 | 1                                            # odd: the range needs a left sibling at once
+    assert start > 0 and start + n <= lo.shape[0], "the range has to lie inside the locals"
+    run = be.run_begin(lo, hp, [0, 1, 1, 1, 1, 1])
+    addrs = np.arange(start, start + n, dtype=np.uint32)
+    ap_, singles, ok_n = addrs.ctypes.data_as(C.c_void_p), (MemOpening * n)(), (C.c_uint8 * n)()
+    values = np.zeros((n, 4), dtype=np.uint32)
+    vp = values.ctypes.data_as(C.c_void_p)
+    rec, ok1, root, root2 = MemRangeOpening(), C.c_uint8(0), C.c_uint32(0), C.c_uint32(0)
+
+    def timed(fn, *args):
+        t0 = time.perf_counter()
+        rc = fn(*args)
+        dt = (time.perf_counter() - t0) * 1e3
+        assert rc == 0, rc
+        return dt
+
+    sides = {"range": {"open": lambda: timed(L.cm_run_open_memory_range, run.h, C.c_uint32(start), C.c_uint32(n), vp, C.byref(rec), C.byref(root)),
+                       "verify": lambda: timed(L.cm_verify_memory_range, root, C.byref(rec), vp, C.byref(ok1), C.c_uint64(0))},
+             "single": {"open": lambda: timed(L.cm_run_open_memory, run.h, ap_, C.c_uint64(n), singles, C.byref(root2)),
+                        "verify": lambda: timed(L.cm_verify_memory_openings, root2, singles, C.c_uint64(n), ok_n, C.c_uint64(0))}}
+    for side in sides.values():                                                   # the tree is built, the pool and the code objects are warm
+        for _ in range(2):
+            side["open"](); side["verify"]()
+    assert root.value == root2.value and ok1.value == 1 and all(ok_n)
+    assert np.array_equal(values, lo[start:start + n])
+    assert all(list(singles[i].value) == values[i].tolist() for i in (0, n // 2, n - 1))
+    t = {f"{k}_{what}": [] for k in sides for what in ("open", "verify")}
+    for _ in range(a.blocks):
+        for k, side in sides.items():
+            for _ in range(a.calls):
+                t[f"{k}_open"].append(side["open"]())
+                t[f"{k}_verify"].append(side["verify"]())
+    assert ok1.value == 1 and all(ok_n)
+    run.free()
+    ms = {k: stats(v) for k, v in t.items()}
+    rep = {"cells": a.cells, "heap_cells": a.heap, "range": {
+        "start": int(start), "n_cells": n, "blocks": a.blocks, "calls_per_block": a.calls, "ms": ms,
+        "bytes_returned": {"range": 16 * n + C.sizeof(MemRangeOpening), "single": C.sizeof(MemOpening) * n},
+        "total_ms": {k: round(ms[f"{k}_open"]["median"] + ms[f"{k}_verify"]["median"], 4) for k in sides}}}
+    r = rep["range"]
+    r["single_over_range"] = {what: round(ms[f"single_{what}"]["median"] / ms[f"range_{what}"]["median"], 2) for what in ("open", "verify")}
+    r["single_over_range"]["total"] = round(r["total_ms"]["single"] / r["total_ms"]["range"], 2)
+    text = json.dumps(rep, indent=1)
+    print(text)
+    if a.out:
+        open(a.out, "w").write(text + "\n")
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cells", type=int, default=1 << 18)
@@ -36,6 +95,8 @@ def main():
     ap.add_argument("--queries", type=int, default=1 << 16)
     ap.add_argument("--runs", type=int, default=3, help="fresh runs (each gives one open_first)")
     ap.add_argument("--calls", type=int, default=5, help="timed calls of the cached opening and of the GPU verifier per run")
+    ap.add_argument("--range", action="store_true", help="the range section instead: one range against the same cells one by one")
+    ap.add_argument("--blocks", type=int, default=6, help="alternating blocks per side of the range section")
     ap.add_argument("--out")
     a = ap.parse_args()
     from cairo_m_amd import Backend
@@ -51,6 +112,8 @@ def main():
     inside = np.concatenate([rng.integers(0, lo.shape[0], a.queries // 4), (1 << 28) - 1 - rng.integers(0, a.heap, a.queries // 4)])
     addrs = np.concatenate([inside, rng.integers(0, 1 << 28, a.queries - inside.size)]).astype(np.uint32)
     rng.shuffle(addrs)
+    if a.range:
+        return range_section(a, be, lo, hp)
     t = {"open_first": [], "open_cached": [], "verify_gpu": [], "verify_host": []}
     n_ok = None
     for r in range(a.runs + 1):                                                   # (run 0 warms the pool and the code objects)
