@@ -20,6 +20,7 @@
 #include "host_adapter.hpp"
 #include "mem_open.hpp"
 #include "mem_range.hpp"
+#include "mem_set.hpp"
 #include "proof.hpp"
 #include <hipcub/hipcub.hpp>
 #include <stdlib.h>

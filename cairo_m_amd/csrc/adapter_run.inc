@@ -419,6 +419,14 @@ void run_open_memory_range(Run& r, uint32_t start, uint32_t n_cells, uint32_t* v
   open_range(r.img_tree.as<cm_merkle_node>(), r.n_img_tree, start, n_cells, values, out, st);
   *root = r.img_root;
 }
+// The same cached tree, opened over a set of cells (mem_set.hip).  The set is good and n_siblings is its plan's (the caller checked).
+void run_open_memory_set(Run& r, const uint32_t* addresses, uint32_t n, uint32_t* values, uint32_t* siblings, uint32_t n_siblings, uint32_t* root) {
+  bind_thread_to_library_device();
+  hipStream_t st = thread_main_stream();
+  run_image_tree(r, "cm_run_open_memory_set", st);
+  open_set(r.img_tree.as<cm_merkle_node>(), r.n_img_tree, addresses, n, values, siblings, n_siblings, st);
+  *root = r.img_root;
+}
 // an upper bound of the boundary-memory rows of the next segment, for the memory budget: the image and every logged access
 uint64_t run_rows_bound(const Run& r, uint64_t n_memory_trace) {
   const uint64_t gap = (uint64_t)host::MAX_ADDRESS + 1 - r.n_lo - r.n_hi;

@@ -28,7 +28,7 @@
 namespace cm {
 namespace {
 
-constexpr uint32_t RANGE_BLOCK = 256, NODE_WORDS = 8;
+constexpr uint32_t RANGE_BLOCK = 256;
 constexpr uint32_t RANGE_LAND_CELLS = 1u << 19;   // 8 MB of values per trip through the pinned landing buffer
 // device words behind the record: the malformed flag of k_range_cells, the verdict of k_range_tail
 enum : uint32_t { RW_FLAG = RANGE_WORDS, RW_VERDICT = RANGE_WORDS + 1, RANGE_DEV_WORDS = RANGE_WORDS + 2 };
@@ -38,19 +38,6 @@ static_assert(RANGE_TAIL <= 1024 && RANGE_TAIL >= 2 && 2 * RANGE_SLOTS <= RANGE_
 struct RangeDefaults { uint32_t h[air::TREE_HEIGHT + 1]; };   // h[d] = the hash of an empty subtree whose top is at depth d
 
 // ---- kernels -----------------------------------------------------------------------------------------------------------
-// the record of `depth` that holds the pair `index` (even), or nullptr: bisection over the depth's slice, as k_open_paths
-__device__ __forceinline__ const uint32_t* range_find(const uint32_t* __restrict__ nodes, const uint32_t* __restrict__ off, uint32_t depth,
-                                                      uint32_t index) {
-  const uint32_t end = off[air::TREE_HEIGHT + 1 - depth];
-  uint32_t lo = off[air::TREE_HEIGHT - depth], hi = end;
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (nodes[NODE_WORDS * (size_t)mid] < index) lo = mid + 1; else hi = mid;
-  }
-  const uint32_t* const nd = nodes + NODE_WORDS * (size_t)lo;
-  return lo < end && nd[0] == index ? nd : nullptr;
-}
-
 __global__ void __launch_bounds__(RANGE_BLOCK)
 k_range_open(const uint32_t* __restrict__ nodes, const uint32_t* __restrict__ off, uint32_t start, uint32_t n_cells, RangeDefaults dflt,
              uint32_t* __restrict__ values, uint32_t* __restrict__ slots) {

@@ -54,6 +54,22 @@ CM_HD void range_children(const uint32_t* in, uint32_t lo, uint32_t hi, uint32_t
   r = c + 1 > hi ? right : in[c + 1 - lo];
 }
 
+// ---- the lookup in a tree's node list, device only ------------------------------------------------------------------------------
+constexpr uint32_t RANGE_NODE_WORDS = 8;   // a cm_merkle_node in words: index, depth, left_value, right_value, ...
+// the record of `depth` that holds the pair `index` (even), or nullptr: bisection over the depth's slice, as k_open_paths (shared with
+// the set openings of mem_set.hip, so the three kinds of opening read one tree alike)
+__device__ __forceinline__ const uint32_t* range_find(const uint32_t* __restrict__ nodes, const uint32_t* __restrict__ off, uint32_t depth,
+                                                      uint32_t index) {
+  const uint32_t end = off[air::TREE_HEIGHT + 1 - depth];
+  uint32_t lo = off[air::TREE_HEIGHT - depth], hi = end;
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (nodes[RANGE_NODE_WORDS * (size_t)mid] < index) lo = mid + 1; else hi = mid;
+  }
+  const uint32_t* const nd = nodes + RANGE_NODE_WORDS * (size_t)lo;
+  return lo < end && nd[0] == index ? nd : nullptr;
+}
+
 // ---- the plan: one record per hashing step, consumed by the device verifier and handed out by cm_mem_range_plan -------------
 // steps[0]: the cells -> the nodes [start, last] of depth 28.  steps[k + 1]: the interval of depth 28 - k -> [lo, hi] of depth
 // 27 - k, with left[k] / right[k] where uses_left / uses_right say so; the per-level kernel while the interval it reads is wider

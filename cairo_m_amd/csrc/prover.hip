@@ -169,6 +169,9 @@ void open_require_device(const char* who);   // mem_open.hip
 void open_check_addresses(const char* who, const uint32_t* addresses, uint64_t n, const cm_mem_opening* out);
 void run_open_memory_range(Run& r, uint32_t start, uint32_t n_cells, uint32_t* values, cm_mem_range_opening* out, uint32_t* root);
 void open_range_check(const char* who, uint32_t start, uint32_t n_cells, const uint32_t* values, const cm_mem_range_opening* out);   // mem_range.hip
+void run_open_memory_set(Run& r, const uint32_t* addresses, uint32_t n, uint32_t* values, uint32_t* siblings, uint32_t n_siblings, uint32_t* root);
+void open_set_check(const char* who, const uint32_t* addresses, uint64_t n, const uint32_t* values, const uint32_t* siblings, uint32_t cap_siblings,
+                    uint32_t* n_siblings);   // mem_set.hip
 void run_free(Run* r);
 // copy a device-resident input back to the host (tests)
 void download_input(const DeviceInput& d, host::ProverInputOwned& o) {
@@ -1840,6 +1843,17 @@ int32_t cm_run_open_memory_range(cm_run* r, uint32_t start, uint32_t n_cells, ui
     cm::open_range_check("cm_run_open_memory_range", start, n_cells, values, out);
     std::lock_guard<std::mutex> lk(cm::run_mutex(*r->r));
     cm::run_open_memory_range(*r->r, start, n_cells, values, out, root);
+  });
+}
+// a set of cells under the same root (mem_set.hip); every refusal comes before the first write to values or siblings
+int32_t cm_run_open_memory_set(cm_run* r, const uint32_t* addresses, uint64_t n, uint32_t* values, uint32_t* siblings, uint32_t cap_siblings,
+                               uint32_t* n_siblings, uint32_t* root) {
+  return pguard([&] {
+    cm::open_require_device("cm_run_open_memory_set");
+    CM_CHECK(r && r->r && root, "cm_run_open_memory_set: null argument");
+    cm::open_set_check("cm_run_open_memory_set", addresses, n, values, siblings, cap_siblings, n_siblings);
+    std::lock_guard<std::mutex> lk(cm::run_mutex(*r->r));
+    cm::run_open_memory_set(*r->r, addresses, (uint32_t)n, values, siblings, *n_siblings, root);
   });
 }
 int32_t cm_run_free(cm_run* r) { delete r; return 0; }

@@ -1708,3 +1708,128 @@ Backend.open_memory_range = _backend_open_memory_range
 Backend.verify_range = lambda self, root, opening, values, stream=0: verify_range(root, opening, values, self.L, stream)
 Run.open_range = _run_open_range
 Run.open_image = _run_open_image
+
+
+# ---- set openings (include/cairom_hip.h, additive to revision 10) ---------------------------------------------------
+SET_MAX_CELLS = 1 << 20
+SET_KERNELS = ("cells", "level", "tail")
+
+
+class MemSetStep(C.Structure):
+    """cm_mem_set_step: one hashing step of a set's verification (cm_mem_set_plan)."""
+    _fields_ = [("depth", C.c_uint32), ("n_nodes", C.c_uint32), ("n_siblings", C.c_uint32), ("kernel", C.c_uint32)]
+
+
+class MemSetOpening:
+    """Any set of cells under a memory root: .addresses (strictly ascending), .values (n, 4), .siblings (depth by depth from depth
+    28 up, inside a depth by ascending node: the sibling of every node on a path of the set whose sibling is on none) and
+    .counts (28: the words per depth, a function of the addresses alone).  Built by Backend.open_memory_set / Run.open_set, or
+    from arrays as they are (a verifier's input: nothing is checked here)."""
+
+    def __init__(self, addresses, values, siblings, counts=None):
+        self.addresses = np.ascontiguousarray(addresses, dtype=np.uint32).reshape(-1)
+        self.values = np.ascontiguousarray(values, dtype=np.uint32).reshape(-1, 4)
+        self.siblings = np.ascontiguousarray(siblings, dtype=np.uint32).reshape(-1)
+        self.counts = None if counts is None else [int(c) for c in counts]
+
+    @property
+    def nbytes(self):
+        """what travels: addresses, values and sibling words"""
+        return 20 * self.addresses.size + 4 * self.siblings.size
+
+    def __repr__(self):
+        return f"MemSetOpening(n={self.addresses.size}, n_siblings={self.siblings.size})"
+
+
+def _set_addresses(addresses):
+    a = np.array(addresses, dtype=np.uint64).reshape(-1)
+    if a.size and int(a.max()) >= 1 << 32:
+        raise ValueError("an address does not fit 32 bits")
+    return np.ascontiguousarray(a.astype(np.uint32))
+
+
+def mem_set_plan(addresses, lib=None):
+    """cm_mem_set_plan of strictly ascending addresses: ([one dict per hashing step: depth, n_nodes, n_siblings, kernel (a
+    SET_KERNELS name)], the record's sibling words in all).  Host code: needs no GPU."""
+    L = lib or load_library()
+    a = _set_addresses(addresses)
+    steps = (MemSetStep * 29)()
+    k, m = C.c_uint32(0), C.c_uint32(0)
+    rc = L.cm_mem_set_plan(_p(a), C.c_uint64(a.size), steps, C.c_uint32(29), C.byref(k), C.byref(m))
+    if rc:
+        raise _lib_error(L, rc)
+    return [{"depth": s.depth, "n_nodes": s.n_nodes, "n_siblings": s.n_siblings, "kernel": SET_KERNELS[s.kernel]} for s in steps[:k.value]], m.value
+
+
+def _set_call(L, fn, head, addresses):
+    """any order, any repeats: sorted and made unique here (the C ABI takes strictly ascending addresses only)"""
+    a = np.unique(_set_addresses(addresses))
+    plan, m = mem_set_plan(a, L)                                                  # (refuses what the call would refuse)
+    values, siblings = np.zeros((a.size, 4), dtype=np.uint32), np.zeros(max(m, 1), dtype=np.uint32)
+    need, root = C.c_uint32(0), C.c_uint32(0)
+    rc = fn(*head, _p(a), C.c_uint64(a.size), _p(values), _p(siblings), C.c_uint32(m), C.byref(need), C.byref(root))
+    if rc:
+        raise _lib_error(L, rc)
+    return MemSetOpening(a, values, siblings[:need.value], [s["n_siblings"] for s in plan[1:]]), root.value
+
+
+def _backend_open_memory_set(self, dev_input, which, addresses):
+    """cm_input_open_memory_set: the cells `addresses` (any order, repeats allowed) under the input's initial (which = 0) or
+    final (1) tree, built on the GPU -> (MemSetOpening, root)."""
+    return _set_call(self.L, self.L.cm_input_open_memory_set, (dev_input, C.c_uint32(which)), addresses)
+
+
+def _run_open_set(self, addresses):
+    """cm_run_open_memory_set: a set of cells under the root of the image as it is now -> (MemSetOpening, root).  Shares the
+    cached image tree of Run.open and Run.open_range."""
+    return _set_call(self.L, self.L.cm_run_open_memory_set, (self.h,), addresses)
+
+
+def _set_args(opening, values=None):
+    a, s = opening.addresses, opening.siblings
+    v = opening.values if values is None else np.ascontiguousarray(values, dtype=np.uint32)
+    if v.size != 4 * a.size:
+        raise ValueError(f"{v.size} value words for a set of {a.size} cells")
+    pad = lambda x: x if x.size else np.zeros(4, dtype=np.uint32)                 # (an empty array still has to be an address)
+    return (_p(pad(a)), C.c_uint64(a.size), _p(pad(v.reshape(-1))), _p(pad(s)), C.c_uint32(s.size)), (a, v, s)
+
+
+def verify_set(root, opening, lib=None, stream=0, with_root=False):
+    """cm_verify_memory_set (GPU) -> bool: addresses, values and sibling words are well formed and fold to `root`; with_root:
+    (bool, the root they fold to, 0 when malformed)."""
+    L = lib or load_library()
+    args, keep = _set_args(opening)
+    ok, got = C.c_uint8(0), C.c_uint32(0)
+    rc = L.cm_verify_memory_set(C.c_uint32(root), *args, C.byref(ok), C.byref(got), C.c_uint64(stream))
+    if rc:
+        raise _lib_error(L, rc)
+    return (bool(ok.value), got.value) if with_root else bool(ok.value)
+
+
+def verify_set_host(root, opening, lib=None):
+    """cm_verify_memory_set_host (host code, no GPU) -> (status, message): (0, "") accepted, (11, why) rejected."""
+    L = lib or load_library()
+    args, keep = _set_args(opening)
+    rc = L.cm_verify_memory_set_host(C.c_uint32(root), *args)
+    if not rc:
+        return 0, ""
+    buf = C.create_string_buffer(512)
+    L.cm_last_error(buf, C.c_size_t(512))
+    return rc, buf.value.decode(errors="replace")
+
+
+def set_root(opening, values=None, lib=None):
+    """cm_memory_set_root_host (host code, no GPU): the root the record folds to with its own values or with `values` in their
+    place — the root AFTER a write that touched only cells of the set, from the sibling words opened BEFORE it."""
+    L = lib or load_library()
+    args, keep = _set_args(opening, values)
+    got = C.c_uint32(0)
+    rc = L.cm_memory_set_root_host(*args, C.byref(got))
+    if rc:
+        raise _lib_error(L, rc)
+    return got.value
+
+
+Backend.open_memory_set = _backend_open_memory_set
+Backend.verify_set = lambda self, root, opening, stream=0, with_root=False: verify_set(root, opening, self.L, stream, with_root)
+Run.open_set = _run_open_set

@@ -42,7 +42,9 @@
  *    Still 10 (additive: two host-only queries, one op): cm_merkle_plan, cm_merkle_layer_npw, cm_merkle_commit_layers.
  *    Still 10 (additive: five new functions and two structs, nothing moved): cm_mem_range_opening, cm_mem_range_step,
  *    cm_input_open_memory_range, cm_run_open_memory_range, cm_verify_memory_range, cm_verify_memory_range_host, cm_mem_range_plan.
- *    Still 10 (additive: two host-side entry points): cm_adapt_segment_host, cm_device_input_public_entries. */
+ *    Still 10 (additive: two host-side entry points): cm_adapt_segment_host, cm_device_input_public_entries.
+ *    Still 10 (additive: six new functions and one struct, nothing moved): cm_mem_set_step, cm_mem_set_plan,
+ *    cm_input_open_memory_set, cm_run_open_memory_set, cm_verify_memory_set, cm_memory_set_root_host, cm_verify_memory_set_host. */
 #define CM_ABI_REVISION 10
 
 #ifdef __cplusplus
@@ -953,6 +955,82 @@ int32_t cm_verify_memory_range(uint32_t root, const cm_mem_range_opening* openin
  * start or n_cells, or, for a well-formed record, "the range hashes to root <x>, not <y>". */
 int32_t cm_verify_memory_range_host(uint32_t root, const cm_mem_range_opening* opening, const uint32_t* values);
 int32_t cm_mem_range_plan(uint32_t start, uint32_t n_cells, cm_mem_range_step* steps, uint32_t cap, uint32_t* n_steps);
+/* ---- set openings (additive to revision 10: new symbols and one struct, nothing moved) -----------------------------------------
+ * Any set of cells under one root: a few thousand unrelated cells for a bridge, a heap result behind pointers, the cells a segment
+ * wrote, program + input + output + a few heap objects.  The third and general member of the family: a single cell and a
+ * contiguous range are its special cases.  Paths that meet share every node above the meeting point, so the record holds each
+ * sibling word once.
+ *
+ * The statement.  The addresses a[0] < a[1] < ... < a[n-1] < 2^28 are strictly ascending.  For k = 0 .. 27 let S_k be the
+ * ascending list of distinct a[i] >> k: the nodes of depth 28 - k on some path.  A node x of S_k needs a sibling exactly when
+ * x ^ 1 is not in S_k.  The record's sibling words come depth by depth, k = 0 first, inside a depth by ascending node index, and
+ * each word is node(28 - k, x ^ 1).  count[k] is the number of words of depth 28 - k and n_siblings the sum of the counts: both
+ * are functions of the addresses alone.  The values travel beside the record: 4 n words, an absent cell as (0, 0, 0, 0); there is
+ * no `present` flag, as for ranges.
+ * The fold walks S_k in order.  The cells first become nodes of depth 28 (H(H(v0, v1), H(v2, v3)), as for ranges).  An even x
+ * whose successor in S_k is x + 1 hashes with it; any other x takes the next unread sibling word, on the right when x is even and
+ * on the left when x is odd.  The parents form S_{k+1}; after k = 27 one node is left, the root.
+ * A set has exactly one valid record: n_siblings must equal the sum of the counts, every word must be below P, the addresses must
+ * be strictly ascending and below 2^28, and the same call gives the same bytes.  A record of m words travels as 20 n + 4 m bytes
+ * (addresses, values, words) and folds with 3 n + sum_k |S_{k+1}| hashes.  For a contiguous set the words of depth 28 - k are
+ * [left[k] if used] + [right[k] if used] of the cm_mem_range_opening of that range; for n = 1 they are siblings[0 .. 27] of the
+ * cm_mem_opening.  When only cells of the set change between two trees the sibling words under both trees are identical, so
+ * folding them with the new values (cm_memory_set_root_host) gives the root AFTER the write.
+ *
+ * cm_mem_set_plan lists the hashing steps of the verification, host code only, always 29: steps[0] = the cells (depth 28, n
+ * nodes), steps[k + 1] = the step that hashes S_k into the n_nodes = |S_{k+1}| nodes of `depth` = 27 - k and reads
+ * n_siblings = count[k] words; `kernel` = 0 the per-cell kernel, 1 the per-level kernel (while S_k is wider than 128 nodes), 2 the
+ * single-workgroup tail (consecutive tail steps are one launch).  *n_siblings receives the sum of the counts: what a caller
+ * allocates for.  The device verifier launches from these same records, so this is what runs.  Status 1: a NULL argument, n == 0
+ * or n > 2^20, addresses not strictly ascending or not below 2^28, cap < 29.
+ * cm_input_open_memory_set / cm_run_open_memory_set build the values and the words on the GPU, on the calling thread's stream and
+ * pool (threading, stream, pool and image-tree cache as cm_run_open_memory_range): the addresses go up; a flag pass over the
+ * 28 n pairs (depth, address lane), depth-major, applies the one rule the plan and the verifier also use; one exclusive scan turns
+ * the flags into each word's position in the canonical order; a gather has every flagged lane bisect its depth's slice of the node
+ * list — the lookup of the range and the single openings, a missing record being the default hash — while 2 n more lanes store
+ * the value halves.  Every word is written by exactly one lane, without atomics; values, words and the device's count come back
+ * in one host round trip (one more per further 8 MB) and the count is checked against the host plan's.  Temporaries: 448 bytes
+ * per cell (the 28 flags and their scan, two words each).  *n_siblings receives the needed count whenever the addresses are good,
+ * also when cap_siblings is too small.  Status 1, with nothing written to values or siblings: a NULL argument, n == 0 or
+ * n > 2^20 ("split the set"), an address >= 2^28, a[i] <= a[i-1] (the message names the first such i), which > 1, an empty image,
+ * cap_siblings too small (the message states the need).  Without a GPU the status is cm_init's (3).
+ * cm_verify_memory_set uploads addresses, values and words and recomputes the root on the GPU (stream s; 0 = the calling thread's
+ * own), with one hashing lane per PARENT, not per address: the opener's flag pass and one scan over all 28 depths give every
+ * node's rank in S_k and every word's position (one scan for both: fewer launches than a scan per level), a scatter lists the head
+ * lane of every node, one lane per cell gives the nodes of depth 28, one launch per depth hashes S_k into S_{k+1} while S_k is
+ * wider than 128 nodes, and one workgroup finishes the remaining depths in LDS with a barrier between them, checks the count,
+ * compares with `root` and writes the verdict and the computed root; three words come back.  Temporaries: 588 bytes per cell at
+ * the most (flags and scan 448, head lanes up to 112, values 16, address 4, two node buffers 8) plus the words.  *ok = 1 when the
+ * statement is well formed and folds to `root`; *computed_root (may be NULL) receives the root it folds to when well formed, else
+ * 0.  Malformed input — n == 0, addresses not ascending or not below 2^28, a word not below P, a wrong n_siblings — gives
+ * *ok = 0 and does not fail the call.  Status 1 only for a NULL argument or n > 2^20.  The call keeps nothing.
+ * cm_memory_set_root_host and cm_verify_memory_set_host are the same fold in host code, for a light client: no GPU. */
+typedef struct {
+  uint32_t depth;               /* the step produces n_nodes nodes of this depth */
+  uint32_t n_nodes;
+  uint32_t n_siblings;          /* sibling words the step reads: count[27 - depth], 0 for the cells */
+  uint32_t kernel;              /* 0 k_set_cells, 1 k_set_level, 2 k_set_tail */
+} cm_mem_set_step;              /* sizeof = 16 */
+int32_t cm_mem_set_plan(const uint32_t* addresses, uint64_t n, cm_mem_set_step* steps, uint32_t cap, uint32_t* n_steps, uint32_t* n_siblings);
+/* which: 0 = the input's initial tree, 1 = its final tree.  values: 4 * n words.  siblings: cap_siblings words.  *root receives
+ * that tree's root. */
+int32_t cm_input_open_memory_set(const cm_device_input* in, uint32_t which, const uint32_t* addresses, uint64_t n, uint32_t* values,
+                                 uint32_t* siblings, uint32_t cap_siblings, uint32_t* n_siblings, uint32_t* root);
+/* Under the root of the run's image as it is now.  Serialised with the other calls on the run. */
+int32_t cm_run_open_memory_set(cm_run* r, const uint32_t* addresses, uint64_t n, uint32_t* values, uint32_t* siblings, uint32_t cap_siblings,
+                               uint32_t* n_siblings, uint32_t* root);
+/* GPU: *ok in {0, 1}; returns 0 when it ran. */
+int32_t cm_verify_memory_set(uint32_t root, const uint32_t* addresses, uint64_t n, const uint32_t* values, const uint32_t* siblings,
+                             uint32_t n_siblings, uint8_t* ok, uint32_t* computed_root, cm_stream_t s);
+/* Host code, no GPU: 0 = well formed, *root_out = the root it folds to; 11 = malformed (1: a NULL argument or n > 2^20).
+ * cm_last_error() then reads "memory set of <n> cells: " and what is wrong: "address <i> is not above address <i-1>" (or, for
+ * an address alone, "address <i> is beyond the address space of 2^28 cells"), "value word <j> of cell <a> is not below P",
+ * "sibling <q> (depth <d>) is not below P", "<m> sibling words where the addresses need <m'>". */
+int32_t cm_memory_set_root_host(const uint32_t* addresses, uint64_t n, const uint32_t* values, const uint32_t* siblings, uint32_t n_siblings,
+                                uint32_t* root_out);
+/* The same, compared with `root`: 0 accepted, 11 rejected; for a well-formed record "the set hashes to root <x>, not <y>". */
+int32_t cm_verify_memory_set_host(uint32_t root, const uint32_t* addresses, uint64_t n, const uint32_t* values, const uint32_t* siblings,
+                                  uint32_t n_siblings);
 /* AccumulationOps::accumulate: dst[k][i] += src[k][i] (4 coordinate columns of n words); generate_secure_powers:
  * out[i] = felt^i for i < n (host array of 4 * n words).  Column::zeros = cm_col_alloc + cm_col_zero. */
 int32_t cm_accumulate(const cm_handle dst[4], const cm_handle src[4], uint64_t n, cm_stream_t s);

@@ -358,6 +358,16 @@ pub struct cm_mem_range_step {
     pub uses_left: u32,
     pub uses_right: u32,
 }
+/// One hashing step of a set's verification (`cm_mem_set_plan`): the `n_nodes` nodes of `depth` it produces, the sibling words
+/// it reads and the kernel that runs it (0 per cell, 1 per level, 2 the single-workgroup tail)
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct cm_mem_set_step {
+    pub depth: u32,
+    pub n_nodes: u32,
+    pub n_siblings: u32,
+    pub kernel: u32,
+}
 
 unsafe extern "C" {
     pub fn cm_init(device: i32) -> i32;
@@ -483,6 +493,12 @@ unsafe extern "C" {
     pub fn cm_verify_memory_range(root: u32, opening: *const cm_mem_range_opening, values: *const u32, ok: *mut u8, s: cm_stream_t) -> i32;
     pub fn cm_verify_memory_range_host(root: u32, opening: *const cm_mem_range_opening, values: *const u32) -> i32;
     pub fn cm_mem_range_plan(start: u32, n_cells: u32, steps: *mut cm_mem_range_step, cap: u32, n_steps: *mut u32) -> i32;
+    pub fn cm_mem_set_plan(addresses: *const u32, n: u64, steps: *mut cm_mem_set_step, cap: u32, n_steps: *mut u32, n_siblings: *mut u32) -> i32;
+    pub fn cm_input_open_memory_set(input: *const cm_device_input, which: u32, addresses: *const u32, n: u64, values: *mut u32, siblings: *mut u32, cap_siblings: u32, n_siblings: *mut u32, root: *mut u32) -> i32;
+    pub fn cm_run_open_memory_set(r: *mut cm_run, addresses: *const u32, n: u64, values: *mut u32, siblings: *mut u32, cap_siblings: u32, n_siblings: *mut u32, root: *mut u32) -> i32;
+    pub fn cm_verify_memory_set(root: u32, addresses: *const u32, n: u64, values: *const u32, siblings: *const u32, n_siblings: u32, ok: *mut u8, computed_root: *mut u32, s: cm_stream_t) -> i32;
+    pub fn cm_memory_set_root_host(addresses: *const u32, n: u64, values: *const u32, siblings: *const u32, n_siblings: u32, root_out: *mut u32) -> i32;
+    pub fn cm_verify_memory_set_host(root: u32, addresses: *const u32, n: u64, values: *const u32, siblings: *const u32, n_siblings: u32) -> i32;
     pub fn cm_relation_sums(component: i32, trace_cols: *const cm_handle, preprocessed: *const cm_handle, log_size: u32, relations: *const cm_relations, sums: *mut [u32; 4], s: cm_stream_t) -> i32;
     pub fn cm_accumulate(dst: *const cm_handle, src: *const cm_handle, n: u64, s: cm_stream_t) -> i32;
     pub fn cm_generate_secure_powers(felt: *const u32, n: u64, out: *mut u32) -> i32;

@@ -450,6 +450,87 @@ pub fn verify_memory_range(root: u32, opening: &CmMemRangeOpening, values: &[u32
     Ok(ok != 0)
 }
 
+/// A set of cells under one memory root (`cm_input_open_memory_set`): the strictly ascending addresses, four value words per
+/// cell (an absent cell as zeros) and the sibling words, depth by depth from depth 28 up and by ascending node inside a depth: the
+/// sibling of every node on a path of the set whose sibling is on none.
+#[derive(Clone, Debug)]
+pub struct MemSetOpening {
+    pub addresses: Vec<u32>,
+    pub values: Vec<u32>,
+    pub siblings: Vec<u32>,
+}
+
+/// The cells `addresses` (any order, repeats allowed: sorted and made unique here) under the initial (`which` = 0) or final (1)
+/// memory root of a device-resident input, built on the GPU: the record and that root.  At most 2^20 cells per call.  Checked
+/// without the memory by `verify_memory_set` (GPU) or `memory_set_root` (host code).
+pub fn open_memory_set(input: *const cm_device_input, which: u32, addresses: &[u32]) -> Result<(MemSetOpening, u32), String> {
+    ensure_init();
+    let mut a: Vec<u32> = addresses.to_vec();
+    a.sort_unstable();
+    a.dedup();
+    let mut steps: [cm_mem_set_step; 29] = unsafe { std::mem::zeroed() };
+    let (mut n_steps, mut need): (u32, u32) = (0, 0);
+    let rc = unsafe { cm_mem_set_plan(a.as_ptr(), a.len() as u64, steps.as_mut_ptr(), 29, &mut n_steps, &mut need) };
+    if rc != 0 {
+        return Err(last_error());
+    }
+    let mut values: Vec<u32> = vec![0; 4 * a.len()];
+    let mut siblings: Vec<u32> = vec![0; need as usize];
+    let (mut got, mut root): (u32, u32) = (0, 0);
+    let rc = unsafe {
+        cm_input_open_memory_set(input, which, a.as_ptr(), a.len() as u64, values.as_mut_ptr(), siblings.as_mut_ptr(), need, &mut got, &mut root)
+    };
+    if rc != 0 {
+        return Err(last_error());
+    }
+    siblings.truncate(got as usize);
+    Ok((MemSetOpening { addresses: a, values, siblings }, root))
+}
+
+/// A set checked against `root` on the GPU (`cm_verify_memory_set`) -> (accepted, the root it folds to; 0 when malformed).  A
+/// malformed record is a `false`, not an error.
+pub fn verify_memory_set(root: u32, opening: &MemSetOpening) -> Result<(bool, u32), String> {
+    ensure_init();
+    if opening.values.len() != 4 * opening.addresses.len() {
+        return Err(format!("{} value words for a set of {} cells", opening.values.len(), opening.addresses.len()));
+    }
+    let (mut ok, mut got): (u8, u32) = (0, 0);
+    let rc = unsafe {
+        cm_verify_memory_set(
+            root,
+            opening.addresses.as_ptr(),
+            opening.addresses.len() as u64,
+            opening.values.as_ptr(),
+            opening.siblings.as_ptr(),
+            opening.siblings.len() as u32,
+            &mut ok,
+            &mut got,
+            0,
+        )
+    };
+    if rc != 0 {
+        return Err(last_error());
+    }
+    Ok((ok != 0, got))
+}
+
+/// The root a set folds to with its own values (`values` = None) or with others in their place (`cm_memory_set_root_host`): the
+/// root AFTER a write that touched only cells of the set, from the sibling words opened BEFORE it.  Host code: touches no GPU.
+pub fn memory_set_root(opening: &MemSetOpening, values: Option<&[u32]>) -> Result<u32, String> {
+    let v: &[u32] = values.unwrap_or(&opening.values);
+    if v.len() != 4 * opening.addresses.len() {
+        return Err(format!("{} value words for a set of {} cells", v.len(), opening.addresses.len()));
+    }
+    let mut root: u32 = 0;
+    let rc = unsafe {
+        cm_memory_set_root_host(opening.addresses.as_ptr(), opening.addresses.len() as u64, v.as_ptr(), opening.siblings.as_ptr(), opening.siblings.len() as u32, &mut root)
+    };
+    if rc != 0 {
+        return Err(last_error());
+    }
+    Ok(root)
+}
+
 /// The passes of a 2^`log_n` transform as the library runs it (`cm_fft_plan`), in layer order: `[lo, hi, tile_log, M]` per pass,
 /// `tile_log` 0 = the generic kernel.  Host code: touches no GPU.
 pub fn fft_plan(log_n: u32) -> Result<Vec<[u32; 4]>, String> {

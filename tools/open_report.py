@@ -16,7 +16,15 @@ No threshold: these are first measurements.
 
 The `range` section: on the same image, --queries CONSECUTIVE cells opened and checked as one range (cm_run_open_memory_range with
 the image's tree cached, cm_verify_memory_range) against the same cells through cm_run_open_memory + cm_verify_memory_openings,
-timed in alternating blocks in one process; medians and the bytes each side returns (16 n + 232 against 136 n)."""
+timed in alternating blocks in one process; medians and the bytes each side returns (16 n + 232 against 136 n).
+
+    python tools/open_report.py --set --out profiles/<set>_open_set_report.json
+
+The `set` section: --queries seeded random cells of the image (repeats dropped) opened and checked as ONE set
+(cm_run_open_memory_set with the image's tree cached, cm_verify_memory_set) against the same cells through cm_run_open_memory +
+cm_verify_memory_openings, timed in alternating blocks in one process.  It asserts that the set verifies, that a sample of its
+sibling words equals the single openings', and that bytes (20 n + 4 m) and hashes (3 n + sum |S_k+1|) are the plan's; it records
+open / verify / total medians, bytes returned and hash counts of both sides.  No threshold on the times."""
 import argparse
 import ctypes as C
 import json
@@ -88,6 +96,77 @@ def range_section(a, be, lo, hp):
     return 0
 
 
+def set_section(a, be, lo, hp):
+    from cairo_m_amd.lib import MemOpening, mem_set_plan
+    L = be.L
+    n_lo, space = lo.shape[0], 1 << 28
+    j = np.unique(np.random.default_rng(2).integers(0, a.cells, a.queries))
+    addrs = np.ascontiguousarray(np.where(j < n_lo, j, space - a.heap + (j - n_lo)).astype(np.uint32))   # ascending: the heap lies on top
+    n = addrs.shape[0]
+    steps, m = mem_set_plan(addrs, L)
+    run = be.run_begin(lo, hp, [0, 1, 1, 1, 1, 1])
+    ap_, singles, ok_n = addrs.ctypes.data_as(C.c_void_p), (MemOpening * n)(), (C.c_uint8 * n)()
+    values, words = np.zeros((n, 4), dtype=np.uint32), np.zeros(m, dtype=np.uint32)
+    vp, wp = values.ctypes.data_as(C.c_void_p), words.ctypes.data_as(C.c_void_p)
+    need, ok1, got, root, root2 = C.c_uint32(0), C.c_uint8(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+
+    def timed(fn, *args):
+        t0 = time.perf_counter()
+        rc = fn(*args)
+        dt = (time.perf_counter() - t0) * 1e3
+        assert rc == 0, rc
+        return dt
+
+    sides = {"set": {"open": lambda: timed(L.cm_run_open_memory_set, run.h, ap_, C.c_uint64(n), vp, wp, C.c_uint32(m), C.byref(need), C.byref(root)),
+                     "verify": lambda: timed(L.cm_verify_memory_set, root, ap_, C.c_uint64(n), vp, wp, C.c_uint32(m), C.byref(ok1), C.byref(got),
+                                             C.c_uint64(0))},
+             "single": {"open": lambda: timed(L.cm_run_open_memory, run.h, ap_, C.c_uint64(n), singles, C.byref(root2)),
+                        "verify": lambda: timed(L.cm_verify_memory_openings, root2, singles, C.c_uint64(n), ok_n, C.c_uint64(0))}}
+    for side in sides.values():                                                   # the tree is built, the pool and the code objects are warm
+        for _ in range(2):
+            side["open"](); side["verify"]()
+    assert root.value == root2.value == got.value and ok1.value == 1 and all(ok_n) and need.value == m
+    assert all(list(singles[i].value) == values[i].tolist() for i in (0, n // 2, n - 1))
+    # a sample of sibling words against the single openings: word q of depth 28 - k belongs to a node x = addrs[i] >> k
+    a_list, q, checked = addrs.tolist(), 0, 0
+    for k in range(28):
+        x = np.unique(addrs >> k)
+        lone = x[~np.isin(x ^ 1, x)]
+        assert lone.size == steps[k + 1]["n_siblings"]
+        for pos in sorted({0, lone.size // 2, lone.size - 1}) if lone.size else ():
+            i = int(np.searchsorted(addrs, int(lone[pos]) << k))
+            assert a_list[i] >> k == int(lone[pos]) and int(words[q + pos]) == singles[i].siblings[k], (k, pos)
+            checked += 1
+        q += lone.size
+    assert q == m
+    hashes = {"set": 3 * n + sum(s["n_nodes"] for s in steps[1:]), "single": 31 * n}
+    bytes_returned = {"set": 20 * n + 4 * m, "single": C.sizeof(MemOpening) * n}
+    assert bytes_returned["set"] == addrs.nbytes + values.nbytes + words.nbytes
+    t = {f"{k}_{what}": [] for k in sides for what in ("open", "verify")}
+    for _ in range(a.blocks):
+        for k, side in sides.items():
+            for _ in range(a.calls):
+                t[f"{k}_open"].append(side["open"]())
+                t[f"{k}_verify"].append(side["verify"]())
+    assert ok1.value == 1 and all(ok_n)
+    run.free()
+    ms = {k: stats(v) for k, v in t.items()}
+    rep = {"cells": a.cells, "heap_cells": a.heap, "set": {
+        "drawn": a.queries, "n_cells": n, "n_siblings": m, "sibling_words_checked": checked, "blocks": a.blocks, "calls_per_block": a.calls,
+        "level_launches": sum(1 for s in steps if s["kernel"] == "level"), "ms": ms, "bytes_returned": bytes_returned, "hashes": hashes,
+        "total_ms": {k: round(ms[f"{k}_open"]["median"] + ms[f"{k}_verify"]["median"], 4) for k in sides}}}
+    r = rep["set"]
+    r["single_over_set"] = {what: round(ms[f"single_{what}"]["median"] / ms[f"set_{what}"]["median"], 2) for what in ("open", "verify")}
+    r["single_over_set"]["total"] = round(r["total_ms"]["single"] / r["total_ms"]["set"], 2)
+    r["single_over_set"]["bytes"] = round(bytes_returned["single"] / bytes_returned["set"], 2)
+    r["single_over_set"]["hashes"] = round(hashes["single"] / hashes["set"], 2)
+    text = json.dumps(rep, indent=1)
+    print(text)
+    if a.out:
+        open(a.out, "w").write(text + "\n")
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cells", type=int, default=1 << 18)
@@ -96,7 +175,8 @@ def main():
     ap.add_argument("--runs", type=int, default=3, help="fresh runs (each gives one open_first)")
     ap.add_argument("--calls", type=int, default=5, help="timed calls of the cached opening and of the GPU verifier per run")
     ap.add_argument("--range", action="store_true", help="the range section instead: one range against the same cells one by one")
-    ap.add_argument("--blocks", type=int, default=6, help="alternating blocks per side of the range section")
+    ap.add_argument("--set", action="store_true", help="the set section instead: one set of random cells against the same cells one by one")
+    ap.add_argument("--blocks", type=int, default=6, help="alternating blocks per side of the range and the set section")
     ap.add_argument("--out")
     a = ap.parse_args()
     from cairo_m_amd import Backend
@@ -114,6 +194,8 @@ def main():
     rng.shuffle(addrs)
     if a.range:
         return range_section(a, be, lo, hp)
+    if a.set:
+        return set_section(a, be, lo, hp)
     t = {"open_first": [], "open_cached": [], "verify_gpu": [], "verify_host": []}
     n_ok = None
     for r in range(a.runs + 1):                                                   # (run 0 warms the pool and the code objects)
