@@ -1833,3 +1833,101 @@ def set_root(opening, values=None, lib=None):
 Backend.open_memory_set = _backend_open_memory_set
 Backend.verify_set = lambda self, root, opening, stream=0, with_root=False: verify_set(root, opening, self.L, stream, with_root)
 Run.open_set = _run_open_set
+
+
+# ---- program identity and the statement of a run (include/cairom_hip.h: cm_program_id_entries .. cm_run_statement_of) ----------
+class RunStatementC(C.Structure):
+    """cm_run_statement"""
+    _fields_ = [(n, C.c_uint32) for n in ("struct_size", "n_segments", "program_id", "program_start", "n_program", "initial_pc",
+                                          "initial_fp", "final_pc", "final_fp", "initial_root", "final_root", "n_input", "n_output",
+                                          "reserved0")]
+
+
+def program_entries(start, values):
+    """The (n, 7) entry array (present, address, value[4], clock) of a program whose cells start, start + 1, .. hold `values`
+    (n x 4 words, or n shorter rows padded with zeros); clocks 0."""
+    rows = [list(v) + [0] * (4 - len(v)) for v in values]
+    v = np.array(rows, dtype=np.uint32).reshape(-1, 4)
+    e = np.zeros((v.shape[0], 7), dtype=np.uint32)
+    e[:, 0] = 1
+    e[:, 1] = (int(start) + np.arange(v.shape[0], dtype=np.uint64)).astype(np.uint32)
+    e[:, 2:6] = v
+    return e
+
+
+def _entries(entries):
+    e = np.ascontiguousarray(entries, dtype=np.uint32)
+    if e.size % 7:
+        raise ValueError(f"{e.size} words are not seven-word entries")
+    return e.reshape(-1, 7)
+
+
+def program_id(entries, lib=None):
+    """cm_program_id_entries (host code, no GPU): the id of the program whose public entries these are — the root of the partial
+    memory tree that holds only these cells (Proof::program_id of the reference).  Raises CmError where the reference panics (an
+    absent entry, no entries) and for entries that are no dense range of field words."""
+    L = lib or load_library()
+    e = _entries(entries)
+    got = C.c_uint32(0)
+    pad = e if e.size else np.zeros((1, 7), dtype=np.uint32)                     # (an empty array still has to be an address)
+    rc = L.cm_program_id_entries(_p(pad), C.c_uint64(e.shape[0]), C.byref(got))
+    if rc:
+        raise _lib_error(L, rc)
+    return got.value
+
+
+def _proof_program_id(self):
+    """cm_proof_program_id (host code, no GPU): which program this proof is about."""
+    got = C.c_uint32(0)
+    rc = self.L.cm_proof_program_id(self.h, C.byref(got))
+    if rc:
+        raise _lib_error(self.L, rc)
+    return got.value
+
+
+def _backend_program_ids(self, items, stream=0, with_status=False):
+    """cm_program_ids / cm_proofs_program_ids (GPU): the ids of a batch of programs in one call.  items: Proofs, or entry arrays
+    (n, 7).  Returns the ids; a bad item raises CmError naming the lowest one — with_status: (ids, status list, message) instead."""
+    items = list(items)
+    n = len(items)
+    ids = np.zeros(max(n, 1), dtype=np.uint32)
+    status = np.zeros(max(n, 1), dtype=np.int32)
+    st = status.ctypes.data_as(C.POINTER(C.c_int32))
+    if n and all(isinstance(x, Proof) for x in items):
+        rc = self.L.cm_proofs_program_ids(_proof_handles(items), C.c_uint32(n), _p(ids), st, C.c_uint64(stream))
+    else:
+        keep = [_entries(x) for x in items]
+        ptrs = (C.c_void_p * max(n, 1))(*[k.ctypes.data if k.size else None for k in keep])
+        counts = (C.c_uint64 * max(n, 1))(*[k.shape[0] for k in keep])
+        rc = self.L.cm_program_ids(ptrs, counts, C.c_uint32(n), _p(ids), st, C.c_uint64(stream))
+    buf = C.create_string_buffer(1024)
+    self.L.cm_last_error(buf, C.c_size_t(1024))
+    msg = buf.value.decode(errors="replace") if rc else ""
+    if rc and (rc != 1 or not msg.startswith("item ") or not with_status):
+        raise CmError(f"libcairom_hip status {rc}: {msg}")
+    return (ids[:n].copy(), status[:n].tolist(), msg) if with_status else ids[:n].copy()
+
+
+def run_statement(proofs, cfg=None, program_id=None, device=False, lib=None):
+    """cm_run_statement_of -> (status, message, dict): the chain check of verify_run (device=True: on the GPU), then one program in
+    every segment, then its id (hashed on the GPU when device=True) against `program_id` when that is given.  The dict (None
+    unless status 0) holds the fields of cm_run_statement plus the run's `input` (proof 0's) and `output` (the last proof's) entry
+    arrays."""
+    L = lib or proofs[0].L
+    out = RunStatementC()
+    out.struct_size = C.sizeof(RunStatementC)
+    want = C.byref(C.c_uint32(int(program_id))) if program_id is not None else None
+    rc = L.cm_run_statement_of(_proof_handles(proofs), C.c_uint32(len(proofs)), _cfg(cfg), want, C.c_uint32(1 if device else 0), C.byref(out))
+    if rc:
+        buf = C.create_string_buffer(1024)
+        L.cm_last_error(buf, C.c_size_t(1024))
+        return rc, buf.value.decode(errors="replace"), None
+    d = {n: getattr(out, n) for n, _ in RunStatementC._fields_ if n not in ("struct_size", "reserved0")}
+    d["input"] = proofs[0].public_data()["input"]
+    d["output"] = proofs[-1].public_data()["output"]
+    return 0, "", d
+
+
+Proof.program_id = _proof_program_id
+Backend.program_ids = _backend_program_ids
+Backend.run_statement = lambda self, proofs, cfg=None, program_id=None, device=False: run_statement(proofs, cfg, program_id, device, self.L)

@@ -44,7 +44,9 @@
  *    cm_input_open_memory_range, cm_run_open_memory_range, cm_verify_memory_range, cm_verify_memory_range_host, cm_mem_range_plan.
  *    Still 10 (additive: two host-side entry points): cm_adapt_segment_host, cm_device_input_public_entries.
  *    Still 10 (additive: six new functions and one struct, nothing moved): cm_mem_set_step, cm_mem_set_plan,
- *    cm_input_open_memory_set, cm_run_open_memory_set, cm_verify_memory_set, cm_memory_set_root_host, cm_verify_memory_set_host. */
+ *    cm_input_open_memory_set, cm_run_open_memory_set, cm_verify_memory_set, cm_memory_set_root_host, cm_verify_memory_set_host.
+ *    Still 10 (additive: five new functions and one struct, nothing moved): cm_run_statement, cm_program_id_entries,
+ *    cm_proof_program_id, cm_program_ids, cm_proofs_program_ids, cm_run_statement_of. */
 #define CM_ABI_REVISION 10
 
 #ifdef __cplusplus
@@ -1031,6 +1033,65 @@ int32_t cm_memory_set_root_host(const uint32_t* addresses, uint64_t n, const uin
 /* The same, compared with `root`: 0 accepted, 11 rejected; for a well-formed record "the set hashes to root <x>, not <y>". */
 int32_t cm_verify_memory_set_host(uint32_t root, const uint32_t* addresses, uint64_t n, const uint32_t* values, const uint32_t* siblings,
                                   uint32_t n_siblings);
+/* ---- program identity and the statement of a run (additive to revision 10) ---------------------------------------------------
+ * Which program a proof is about, as one 31-bit word: Proof::program_id() of the reference (crates/prover/src/lib.rs:75-97), the
+ * Poseidon2 root of the partial memory tree that holds only the proof's public program cells.  An "entry" is the seven-word record
+ * of cm_proof_public_entries: present, address, value[4], clock.
+ *
+ * The statement.  The entries are present and their addresses are first, first + 1, .., first + n - 1 (first = entry 0's address).
+ * Every cell becomes its node of depth 28, H(H(v0, v1), H(v2, v3)), as for ranges; the interval [first >> k, last >> k] of depth
+ * 28 - k is hashed into the interval of depth 27 - k, a child outside the interval being the default hash of depth 28 - k (the
+ * range fold of cm_mem_range_opening with every left[k] / right[k] the default); once the interval is one node the same step chains
+ * it to depth 0.  About 4 n + 28 hashes.  Clocks do not enter.  A present cell whose value is (0, 0, 0, 0) hashes to the default
+ * of depth 28, so it leaves no trace in the id: a property of the tree, as for the link diff's `zero only` cells.
+ * cm_program_id_entries is host code, no device call.  Status 1, nothing written, cm_last_error() naming the entry and address:
+ * NULL pointers; n == 0 (the reference returns None and unwraps it); more than 2^24 entries; an entry with present == 0 (the
+ * reference's res.unwrap() panics there); "entry <i> has address <a>, not <first + i>"; "value word <j> of entry <i> (address <a>)
+ * is not below P"; a range that ends beyond the address space of 2^28 cells.
+ * cm_proof_program_id: the same computation over the proof's program entries.
+ * cm_program_ids / cm_proofs_program_ids compute the ids of n programs on the GPU in one batch (stream s; 0 = the calling thread's
+ * own): the host walks each item once, checking present flags and addresses and gathering the value words; one upload of all
+ * values behind a table of offsets; two launches whatever n is — one lane per cell of the whole batch range-checks the four words
+ * and writes the node of depth 28, then one workgroup of 1024 lanes per item folds its interval, through two global buffers while
+ * it is wider than 1024 nodes and in LDS from there on; one download of ids and flags.  Every word is written by exactly one lane,
+ * without atomics: the same call gives the same bytes.  status[i] is 0 or 1 by the rules of cm_program_id_entries, ids[i] the id
+ * or 0; a bad item does not disturb its neighbours' ids.  Returns 0 when every status is 0, else 1 with cm_last_error() reading
+ * "item <i>: ..." for the lowest bad i.  n == 0 (or more than 2^20 items, or more than 2^26 cells in all) or a NULL array:
+ * status 1; a NULL entries[i] or proofs[i] is a bad item.  Without a GPU the status is cm_init's (3), returned before any argument
+ * is looked at.  The call keeps nothing: its device buffers come from the calling thread's pool and are back there when it returns. */
+int32_t cm_program_id_entries(const uint32_t* entries, uint64_t n, uint32_t* id);
+int32_t cm_proof_program_id(const cm_proof* p, uint32_t* id);
+int32_t cm_program_ids(const uint32_t* const* entries, const uint64_t* n_entries, uint32_t n, uint32_t* ids, int32_t* status, cm_stream_t s);
+int32_t cm_proofs_program_ids(const cm_proof* const* proofs, uint32_t n, uint32_t* ids, int32_t* status, cm_stream_t s);
+/* What a chain of proofs states: which program, from which registers and memory root to which.  Set struct_size =
+ * sizeof(cm_run_statement) before the call (a NULL or short `out`, or device > 1: status 1).  In this order:
+ * 1. cm_verify_run (device == 0) or cm_verify_run_device (device == 1); its status and message pass through unchanged.
+ * 2. For every segment i > 0 the program entries equal segment 0's in present, address and value (clocks are not compared); else
+ *    status 11 with "run: segment <i> program differs from segment 0 at address <a>" or "run: segment <i> has <k> program entries,
+ *    segment 0 has <m>".
+ * 3. The id is hashed once: through the batch path on the GPU when device == 1, in host code otherwise (a program that has no id
+ *    is status 1 with cm_program_id_entries' words behind "run: program id: ").
+ * 4. expected_program_id, when not NULL, must equal it: else status 11 with "run: program_id 0x%08x != expected 0x%08x".
+ * On success the registers, initial_root and n_input are proof 0's, the final registers, final_root and n_output those of proof
+ * n - 1; the entries themselves stay reachable through cm_proof_public_entries. */
+typedef struct {
+  uint32_t struct_size;
+  uint32_t n_segments;
+  uint32_t program_id;
+  uint32_t program_start;
+  uint32_t n_program;
+  uint32_t initial_pc;
+  uint32_t initial_fp;
+  uint32_t final_pc;
+  uint32_t final_fp;
+  uint32_t initial_root;
+  uint32_t final_root;
+  uint32_t n_input;
+  uint32_t n_output;
+  uint32_t reserved0;
+} cm_run_statement;             /* sizeof = 56 */
+int32_t cm_run_statement_of(const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected, const uint32_t* expected_program_id,
+                            uint32_t device, cm_run_statement* out);
 /* AccumulationOps::accumulate: dst[k][i] += src[k][i] (4 coordinate columns of n words); generate_secure_powers:
  * out[i] = felt^i for i < n (host array of 4 * n words).  Column::zeros = cm_col_alloc + cm_col_zero. */
 int32_t cm_accumulate(const cm_handle dst[4], const cm_handle src[4], uint64_t n, cm_stream_t s);

@@ -279,6 +279,26 @@ pub struct cm_public_data {
     pub n_input: u32,
     pub n_output: u32,
 }
+/// What a chain of proofs states (`cm_run_statement_of`): the program's id and range, the registers and memory roots the run
+/// starts from and ends at, the counts of its input and output entries; set `struct_size` before the call
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug, PartialEq, Eq)]
+pub struct cm_run_statement {
+    pub struct_size: u32,
+    pub n_segments: u32,
+    pub program_id: u32,
+    pub program_start: u32,
+    pub n_program: u32,
+    pub initial_pc: u32,
+    pub initial_fp: u32,
+    pub final_pc: u32,
+    pub final_fp: u32,
+    pub initial_root: u32,
+    pub final_root: u32,
+    pub n_input: u32,
+    pub n_output: u32,
+    pub reserved0: u32,
+}
 /// One cell that makes a link's roots differ (`cm_link_diff`): kind 1 present on both sides with different values, 2 present only
 /// in the later segment's initial memory, 3 only in the earlier segment's final memory
 #[repr(C)]
@@ -499,6 +519,11 @@ unsafe extern "C" {
     pub fn cm_verify_memory_set(root: u32, addresses: *const u32, n: u64, values: *const u32, siblings: *const u32, n_siblings: u32, ok: *mut u8, computed_root: *mut u32, s: cm_stream_t) -> i32;
     pub fn cm_memory_set_root_host(addresses: *const u32, n: u64, values: *const u32, siblings: *const u32, n_siblings: u32, root_out: *mut u32) -> i32;
     pub fn cm_verify_memory_set_host(root: u32, addresses: *const u32, n: u64, values: *const u32, siblings: *const u32, n_siblings: u32) -> i32;
+    pub fn cm_program_id_entries(entries: *const u32, n: u64, id: *mut u32) -> i32;
+    pub fn cm_proof_program_id(p: *const cm_proof, id: *mut u32) -> i32;
+    pub fn cm_program_ids(entries: *const *const u32, n_entries: *const u64, n: u32, ids: *mut u32, status: *mut i32, s: cm_stream_t) -> i32;
+    pub fn cm_proofs_program_ids(proofs: *const *const cm_proof, n: u32, ids: *mut u32, status: *mut i32, s: cm_stream_t) -> i32;
+    pub fn cm_run_statement_of(proofs: *const *const cm_proof, n: u32, expected: *const cm_pcs_config, expected_program_id: *const u32, device: u32, out: *mut cm_run_statement) -> i32;
     pub fn cm_relation_sums(component: i32, trace_cols: *const cm_handle, preprocessed: *const cm_handle, log_size: u32, relations: *const cm_relations, sums: *mut [u32; 4], s: cm_stream_t) -> i32;
     pub fn cm_accumulate(dst: *const cm_handle, src: *const cm_handle, n: u64, s: cm_stream_t) -> i32;
     pub fn cm_generate_secure_powers(felt: *const u32, n: u64, out: *mut u32) -> i32;

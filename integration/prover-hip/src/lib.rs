@@ -265,6 +265,67 @@ pub fn verify_cairo_m_many(proofs: &[ProofHandleRef], pcs_config: Option<PcsConf
 }
 /// Borrowed library proof object (e.g. kept by a caller that proves many segments and verifies them later).
 pub struct ProofHandleRef(pub *const cm_proof);
+impl ProofHandleRef {
+    /// `Proof::program_id()` of the reference for a library proof (`cm_proof_program_id`, host code, no GPU): the Poseidon2 root of
+    /// the partial memory tree that holds only the proof's public program cells.  Where the reference panics (an absent program
+    /// entry, no program at all) this returns the library's words instead.
+    pub fn program_id(&self) -> Result<u32, String> {
+        let mut id = 0u32;
+        let rc = unsafe { cm_proof_program_id(self.0, &mut id) };
+        if rc == 0 {
+            Ok(id)
+        } else {
+            Err(last_error())
+        }
+    }
+}
+/// `cm_proofs_program_ids`: the ids of a whole batch of library proofs, hashed on the GPU in one call (one upload, two launches,
+/// one download).  One entry per proof, in order; `Err` for a proof whose program has no id.  Panics when the batch cannot be run
+/// at all (no GPU, no proofs).
+pub fn program_ids(proofs: &[ProofHandleRef]) -> Vec<Result<u32, String>> {
+    ensure_init();
+    let raw: Vec<*const cm_proof> = proofs.iter().map(|p| p.0).collect();
+    let mut ids = vec![0u32; raw.len()];
+    let mut status = vec![0i32; raw.len()];
+    let rc = unsafe { cm_proofs_program_ids(raw.as_ptr(), raw.len() as u32, ids.as_mut_ptr(), status.as_mut_ptr(), 0) };
+    let words = last_error();
+    assert!(rc == 0 || (rc == 1 && words.starts_with("item ")), "cm_proofs_program_ids: status {rc}: {words}");
+    ids.iter()
+        .zip(status.iter())
+        .enumerate()
+        .map(|(i, (id, st))| {
+            if *st == 0 {
+                Ok(*id)
+            } else {
+                Err(format!("item {i}: the program has no id ({words})"))
+            }
+        })
+        .collect()
+}
+/// `cm_run_statement_of`: what a chain of library proofs states.  The chain check of `cm_verify_run` (`device`: of
+/// `cm_verify_run_device`) comes first, then every segment must carry segment 0's program, then the program's id is hashed once
+/// (on the GPU when `device`) and compared with `expected_program_id` when that is given.  `Err` carries the library's status and
+/// words: 11 for a chain that does not verify, does not link, changes its program or is about another program.
+pub fn run_statement(
+    proofs: &[ProofHandleRef],
+    pcs_config: Option<PcsConfig>,
+    expected_program_id: Option<u32>,
+    device: bool,
+) -> Result<cm_run_statement, (i32, String)> {
+    if device {
+        ensure_init();
+    }
+    let cfg = pcs(&pcs_config.unwrap_or(REGULAR_96_BITS));
+    let raw: Vec<*const cm_proof> = proofs.iter().map(|p| p.0).collect();
+    let mut out = cm_run_statement { struct_size: std::mem::size_of::<cm_run_statement>() as u32, ..Default::default() };
+    let want = expected_program_id.as_ref().map_or(std::ptr::null(), |x| x as *const u32);
+    let rc = unsafe { cm_run_statement_of(raw.as_ptr(), raw.len() as u32, &cfg, want, device as u32, &mut out) };
+    if rc == 0 {
+        Ok(out)
+    } else {
+        Err((rc, last_error()))
+    }
+}
 
 /// Why `assert_constraints` rejected an input: the library's whole report (per-component failing rows, lowest failing
 /// (row, constraint), claimed sums, per-relation sums, the relations used) and its one-line verdict.
