@@ -17,6 +17,11 @@
 //   scan             exclusive sum of the listed flags over the merged order (hipCUB, as the run tail's gap scan)
 //   k_link_compact   one thread per merged slot: a listed slot below `cap` gathers its two rows into one cm_link_cell
 // The four totals are integer sums (one atomic per wave and kind): their value does not depend on the order of the adds.
+//
+// The classification and the scan are link_merge_enqueue, for any two row arrays: a segment's write set (mem_transition.hip) runs
+// them over one input's initial and final boundary memory and compacts with
+//   k_link_addresses the listed slots' addresses alone, ascending, or asks with
+//   k_link_missing   for the lowest listed address that a given ascending set does not hold (a minimum).
 #include "../../include/cairom_hip.h"
 #include "segment_input.hpp"
 #include <hipcub/hipcub.hpp>
@@ -29,8 +34,6 @@ namespace {
 
 constexpr uint32_t LINK_BLOCK = 256, ROW_WORDS = 7;
 constexpr uint32_t NO_ROW = 0xffffffffu, SIDE_NEXT = 0x80000000u;
-// device words of one diff: totals per kind, the zero-only count, flags (1: a row array is not in ascending address order)
-enum : uint32_t { LS_CHANGED = 0, LS_ONLY_NEXT = 1, LS_ONLY_PREV = 2, LS_ZERO_ONLY = 3, LS_ERR = 4, LS_WORDS = 8 };
 // cells that travel with the totals; a caller that asked for more and has more gets the rest in a second copy
 constexpr uint64_t LINK_FIRST_TRIP = 4096;
 
@@ -114,6 +117,35 @@ k_link_compact(const uint32_t* __restrict__ prev, uint32_t n_prev, const uint32_
   o[10] = a ? a[5] : 0u;
 }
 
+// the address of the listed merged slot whose source is s
+__device__ __forceinline__ uint32_t slot_address(const uint32_t* __restrict__ prev, const uint32_t* __restrict__ next, uint2 s) {
+  return ((s.x & SIDE_NEXT) ? next : prev)[ROW_WORDS * (size_t)(s.x & ~SIDE_NEXT)];
+}
+// the write set's form of the compaction: a listed slot below `cap` stores its address alone
+__global__ void __launch_bounds__(LINK_BLOCK)
+k_link_addresses(const uint32_t* __restrict__ prev, const uint32_t* __restrict__ next, const uint32_t* __restrict__ flag, const uint32_t* __restrict__ pos,
+                 const uint2* __restrict__ src, uint32_t n_slots, uint32_t cap, uint32_t* __restrict__ out) {
+  const uint32_t r = blockIdx.x * LINK_BLOCK + threadIdx.x;
+  if (r >= n_slots || !flag[r]) return;
+  const uint32_t p = pos[r];
+  if (p < cap) out[p] = slot_address(prev, next, src[r]);
+}
+// a listed slot bisects the ascending `set` (n_set addresses) for its address: *missing = the lowest one that is not there
+// (a minimum: the order of the atomics does not decide it); the caller stored NO_ROW
+__global__ void __launch_bounds__(LINK_BLOCK)
+k_link_missing(const uint32_t* __restrict__ prev, const uint32_t* __restrict__ next, const uint32_t* __restrict__ flag, const uint2* __restrict__ src,
+               uint32_t n_slots, const uint32_t* __restrict__ set, uint32_t n_set, uint32_t* __restrict__ missing) {
+  const uint32_t r = blockIdx.x * LINK_BLOCK + threadIdx.x;
+  if (r >= n_slots || !flag[r]) return;
+  const uint32_t a = slot_address(prev, next, src[r]);
+  uint32_t lo = 0, hi = n_set;
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (set[mid] < a) lo = mid + 1; else hi = mid;
+  }
+  if (lo >= n_set || set[lo] != a) atomicMin(missing, a);
+}
+
 inline dim3 blocks_for(uint64_t n) { return dim3((uint32_t)((n + LINK_BLOCK - 1) / LINK_BLOCK)); }
 
 void set_message(cm_link_report& rep, const std::string& m) {
@@ -130,6 +162,34 @@ void require_device(const char* who) {
 
 }  // namespace
 
+void link_merge_enqueue(const uint32_t* a, uint64_t n_a, const uint32_t* b, uint64_t n_b, bool with_scan, LinkMerge& m, hipStream_t st) {
+  const uint64_t n_slots = n_a + n_b;
+  CM_CHECK(n_slots > 0 && n_slots < (1ull << 31), "link diff: boundary memories too large");
+  m.prev = a; m.next = b; m.n_prev = (uint32_t)n_a; m.n_next = (uint32_t)n_b; m.n_slots = (uint32_t)n_slots;
+  m.state.alloc(LS_WORDS * 4); m.flag.alloc(n_slots * 4); m.src.alloc(n_slots * 8);
+  CM_HIP(hipMemsetAsync(m.state.p, 0, LS_WORDS * 4, st));
+  CM_HIP(hipMemsetAsync(m.flag.p, 0, n_slots * 4, st));
+  const dim3 ga = blocks_for(n_a), gb = blocks_for(n_b);
+  const int vec16 = (((uintptr_t)a | (uintptr_t)b) & 15u) == 0;
+  hipLaunchKernelGGL(k_link_classify, dim3(ga.x + gb.x), dim3(LINK_BLOCK), 0, st, a, (uint32_t)n_a, b, (uint32_t)n_b, ga.x, vec16, m.flag.u32(),
+                     m.src.as<uint2>(), m.state.u32());
+  if (!with_scan) return;
+  m.pos.alloc(n_slots * 4);
+  size_t tmp_bytes = 0;
+  CM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, m.flag.u32(), m.pos.u32(), (int)n_slots, st));
+  m.tmp.alloc(tmp_bytes ? tmp_bytes : 4);
+  CM_HIP(hipcub::DeviceScan::ExclusiveSum(m.tmp.p, tmp_bytes, m.flag.u32(), m.pos.u32(), (int)n_slots, st));
+}
+void link_addresses_enqueue(const LinkMerge& m, uint32_t* out, uint32_t cap, hipStream_t st) {
+  hipLaunchKernelGGL(k_link_addresses, blocks_for(m.n_slots), dim3(LINK_BLOCK), 0, st, m.prev, m.next, (const uint32_t*)m.flag.u32(),
+                     (const uint32_t*)m.pos.u32(), (const uint2*)m.src.as<uint2>(), m.n_slots, cap, out);
+}
+void link_missing_enqueue(const LinkMerge& m, const uint32_t* set, uint32_t n_set, uint32_t* missing, hipStream_t st) {
+  CM_HIP(hipMemsetAsync(missing, 0xff, 4, st));
+  hipLaunchKernelGGL(k_link_missing, blocks_for(m.n_slots), dim3(LINK_BLOCK), 0, st, m.prev, m.next, (const uint32_t*)m.flag.u32(),
+                     (const uint2*)m.src.as<uint2>(), m.n_slots, set, n_set, missing);
+}
+
 void link_diff(const DeviceInput& prev, const DeviceInput& next, uint32_t seg_index, cm_link_report& rep, cm_link_cell* cells, uint64_t cap,
                uint64_t& n_total) {
   bind_thread_to_library_device();
@@ -141,17 +201,10 @@ void link_diff(const DeviceInput& prev, const DeviceInput& next, uint32_t seg_in
     const uint64_t cap_dev = std::min<uint64_t>(cap, n_slots), first = std::min<uint64_t>(cap_dev, LINK_FIRST_TRIP);
     const uint32_t* const a = prev.fin_mem.u32();
     const uint32_t* const b = next.init_mem.u32();
-    DevBuf state(LS_WORDS * 4), flag(n_slots * 4), pos(n_slots * 4), src(n_slots * 8), recs(cap_dev * sizeof(cm_link_cell) + 4);
-    CM_HIP(hipMemsetAsync(state.p, 0, LS_WORDS * 4, st));
-    CM_HIP(hipMemsetAsync(flag.p, 0, n_slots * 4, st));
-    const dim3 ga = blocks_for(n_prev), gb = blocks_for(n_next);
-    const int vec16 = (((uintptr_t)a | (uintptr_t)b) & 15u) == 0;
-    hipLaunchKernelGGL(k_link_classify, dim3(ga.x + gb.x), dim3(LINK_BLOCK), 0, st, a, (uint32_t)n_prev, b, (uint32_t)n_next, ga.x, vec16, flag.u32(),
-                       src.as<uint2>(), state.u32());
-    size_t tmp_bytes = 0;
-    CM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, flag.u32(), pos.u32(), (int)n_slots, st));
-    DevBuf tmp(tmp_bytes ? tmp_bytes : 4);
-    CM_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, tmp_bytes, flag.u32(), pos.u32(), (int)n_slots, st));
+    LinkMerge m;
+    DevBuf recs(cap_dev * sizeof(cm_link_cell) + 4);
+    link_merge_enqueue(a, n_prev, b, n_next, true, m, st);
+    DevBuf &state = m.state, &flag = m.flag, &pos = m.pos, &src = m.src;
     if (cap_dev)
       hipLaunchKernelGGL(k_link_compact, blocks_for(n_slots), dim3(LINK_BLOCK), 0, st, a, (uint32_t)n_prev, b, (uint32_t)n_next, flag.u32(), pos.u32(),
                          src.as<uint2>(), (uint32_t)n_slots, (uint32_t)cap_dev, recs.u32());

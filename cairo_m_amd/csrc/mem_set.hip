@@ -40,16 +40,11 @@
 namespace cm {
 namespace {
 
-constexpr uint32_t SET_BLOCK = 256;
-constexpr size_t SET_LAND_BYTES = (size_t)8 << 20;   // per trip through the pinned landing buffer
 // device words of the verifier: the malformed flag of the hashing kernels, the verdict and the root of k_set_tail
 enum : uint32_t { SW_FLAG = 0, SW_VERDICT = 1, SW_ROOT = 2, SET_DEV_WORDS = 3 };
 
 static_assert(SET_TAIL <= 1024 && SET_TAIL >= 2, "one workgroup holds a level");
 static_assert((uint64_t)SET_DEPTHS * SET_MAX_CELLS + 2ull * SET_MAX_CELLS < (1ull << 32), "the lanes of a launch fit 32 bits");
-
-struct SetDefaults { uint32_t h[air::TREE_HEIGHT + 1]; };   // h[d] = the hash of an empty subtree whose top is at depth d
-struct SetWidths { uint32_t w[SET_STEPS]; };                  // w[k] = |S_k|, k = 0 .. 28 (the plan's)
 
 // ---- kernels -----------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(SET_BLOCK)
@@ -68,18 +63,13 @@ k_set_gather(const uint32_t* __restrict__ nodes, const uint32_t* __restrict__ of
   if (t >= n_pairs) {
     const uint32_t u = t - n_pairs;
     if (u >= 2u * n) return;
-    const uint32_t* const nd = range_find(nodes, off, air::TREE_HEIGHT, 4u * a[u >> 1] + 2u * (u & 1u));
-    values[2 * (size_t)u] = nd ? nd[2] : 0u;
-    values[2 * (size_t)u + 1] = nd ? nd[3] : 0u;
+    set_gather_half(nodes, off, a, u, values);
     return;
   }
   const uint32_t needs = (uint32_t)flag[t] & 1u, pos = (uint32_t)scan[t];
   if (t == n_pairs - 1) *count = pos + needs;
   if (!needs || pos >= cap_words) return;   // (the host compares *count with its plan before it reads a word)
-  const uint32_t k = t / n, depth = SET_DEPTHS - k, x = a[t % n] >> k;
-  // the sibling x ^ 1 is the other half of the pair x & ~1: the left half when x is odd
-  const uint32_t* const nd = range_find(nodes, off, depth, x & ~1u);
-  words[pos] = nd ? ((x & 1u) ? nd[2] : nd[3]) : dflt.h[depth];
+  words[pos] = set_gather_word(nodes, off, a, n, t, dflt);
 }
 
 __global__ void __launch_bounds__(SET_BLOCK)
@@ -101,27 +91,13 @@ k_set_cells(const uint4* __restrict__ values, uint32_t n, uint32_t* __restrict__
   out[t] = range_cell_node(v);
 }
 
-// what the hashing lanes read: the addresses, the flags and their scan, the head lanes, the record
-struct SetView {
-  const uint32_t* a;
-  const unsigned long long* flag;
-  const unsigned long long* scan;
-  const uint32_t* heads;
-  const uint32_t* words;
-  uint32_t n, n_words;
-};
 // the children of parent r of S_{k+1}, where in[c] = node c of S_k; false when the sibling word it needs is missing or not below P
 __device__ __forceinline__ bool set_children(const SetView& s, const uint32_t* in, uint32_t k, uint32_t r, uint32_t& l, uint32_t& rr) {
-  // the parent's head lane is the head lane of its first child: a lane that starts a node at shift k + 1 starts one at shift k
-  const uint32_t i = k + 1 < SET_DEPTHS ? s.heads[(uint32_t)(s.scan[(size_t)(k + 1) * s.n] >> 32) + r] : 0u;
-  const size_t t = (size_t)k * s.n + i;
-  const uint32_t c = (uint32_t)(s.scan[t] >> 32) - (uint32_t)(s.scan[(size_t)k * s.n] >> 32);
-  const uint32_t me = in[c];
-  if (!((uint32_t)s.flag[t] & 1u)) { l = me; rr = in[c + 1]; return true; }   // an even node whose successor in S_k is x + 1
-  const uint32_t q = (uint32_t)s.scan[t], w = q < s.n_words ? s.words[q] : P;
-  const bool odd = (s.a[i] >> k) & 1u;
-  l = odd ? w : me; rr = odd ? me : w;
-  return w < P;
+  const SetParent p = set_parent(s, k, r);
+  const uint32_t me = in[p.c];
+  if (p.paired) { l = me; rr = in[p.c + 1]; return true; }
+  l = p.odd ? p.w : me; rr = p.odd ? me : p.w;
+  return p.w < P;
 }
 
 // in = S_k, out = S_{k+1} (n_out nodes)
@@ -168,6 +144,8 @@ k_set_tail(SetView s, const uint32_t* __restrict__ in, SetWidths w, uint32_t k0,
 inline dim3 blocks_for(uint64_t n, uint32_t block) { return dim3((uint32_t)((n + block - 1) / block)); }
 inline hipStream_t stream_or_own(cm_stream_t s) { return s ? (hipStream_t)(uintptr_t)s : thread_main_stream(); }
 
+}  // namespace
+
 // flag[t] and scan[t] of the 28 n pairs, enqueued on st (the scan's temporary lives in `tmp` until the stream has run)
 void set_flags_and_scan(const uint32_t* d_addr, uint32_t n, DevBuf& flag, DevBuf& scan, DevBuf& tmp, hipStream_t st) {
   const uint32_t n_pairs = SET_DEPTHS * n;
@@ -179,11 +157,13 @@ void set_flags_and_scan(const uint32_t* d_addr, uint32_t n, DevBuf& flag, DevBuf
   tmp.alloc(tmp_bytes ? tmp_bytes : 4);
   CM_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, tmp_bytes, flag.as<unsigned long long>(), scan.as<unsigned long long>(), (int)n_pairs, st));
 }
-
-}  // namespace
+void set_heads_enqueue(const DevBuf& flag, const DevBuf& scan, uint32_t n, uint32_t n_heads, uint32_t* heads, hipStream_t st) {
+  hipLaunchKernelGGL(k_set_heads, blocks_for((uint64_t)SET_DEPTHS * n, SET_BLOCK), dim3(SET_BLOCK), 0, st, (const unsigned long long*)flag.as<unsigned long long>(),
+                     (const unsigned long long*)scan.as<unsigned long long>(), n, n_heads, heads);
+}
 
 // what is wrong with address `bad` = set_first_bad_address(a, n) < n
-static std::string set_address_complaint(const uint32_t* a, uint64_t bad) {
+std::string set_address_complaint(const uint32_t* a, uint64_t bad) {
   if (a[bad] >= RANGE_SPACE) return "address " + std::to_string(bad) + " is beyond the address space of 2^28 cells";
   return "address " + std::to_string(bad) + " is not above address " + std::to_string(bad - 1);
 }
@@ -260,8 +240,7 @@ void verify_set_device(uint32_t root, const uint32_t* addresses, uint32_t n, con
   stage_upload(d_vals.p, values, (size_t)n * 16, st);
   stage_upload(d_words.p, siblings, (size_t)n_siblings * 4, st);
   set_flags_and_scan(d_addr.u32(), n, flag, scan, tmp, st);
-  hipLaunchKernelGGL(k_set_heads, blocks_for((uint64_t)SET_DEPTHS * n, SET_BLOCK), dim3(SET_BLOCK), 0, st, (const unsigned long long*)flag.as<unsigned long long>(),
-                     (const unsigned long long*)scan.as<unsigned long long>(), n, (uint32_t)n_heads, d_heads.u32());
+  set_heads_enqueue(flag, scan, n, (uint32_t)n_heads, d_heads.u32(), st);
   uint32_t* in = d_a.u32();
   uint32_t* out = d_b.u32();
   hipLaunchKernelGGL(k_set_cells, blocks_for(n, SET_BLOCK), dim3(SET_BLOCK), 0, st, (const uint4*)d_vals.as<uint4>(), n, in, d_dev.u32() + SW_FLAG);
@@ -280,9 +259,6 @@ void verify_set_device(uint32_t root, const uint32_t* addresses, uint32_t n, con
   *ok = land[SW_VERDICT] == 1 ? 1 : 0;
   if (computed_root) *computed_root = land[SW_ROOT];
 }
-
-// the host fold: 0 and *root_out, or 11 and the message
-int32_t set_root_host(const char* who, const uint32_t* a, uint64_t n64, const uint32_t* values, const uint32_t* words, uint32_t n_words, uint32_t* root_out);
 }  // namespace
 
 }  // namespace cm
@@ -299,18 +275,18 @@ int32_t set_guard(F&& f) {
 }  // namespace
 
 namespace cm {
-namespace {
-int32_t set_root_host(const char* who, const uint32_t* a, uint64_t n64, const uint32_t* values, const uint32_t* words, uint32_t n_words, uint32_t* root_out) {
+int32_t set_root_host(const char* who, const uint32_t* a, uint64_t n64, const uint32_t* values, const uint32_t* words, uint32_t n_words, uint32_t* root_out,
+                      const char* noun, const char* value_word) {
   if (!a || !values || !words || !root_out) return cm_set_last_error((std::string(who) + ": null argument").c_str());
   if (n64 > SET_MAX_CELLS) return cm_set_last_error((std::string(who) + ": more than 2^20 cells in one call: split the set").c_str());
   const uint32_t n = (uint32_t)n64;
-  const std::string head = "memory set of " + std::to_string(n) + " cells: ";
+  const std::string head = std::string(noun) + " of " + std::to_string(n) + " cells: ";
   auto reject = [&](const std::string& why) { cm_set_last_error((head + why).c_str()); return 11; };
   if (n == 0) return reject("no cells");
   const uint64_t bad = set_first_bad_address(a, n);
   if (bad < n) return reject(set_address_complaint(a, bad));
   for (uint64_t i = 0; i < 4ull * n; i++)
-    if (values[i] >= P) return reject("value word " + std::to_string(i % 4) + " of cell " + std::to_string(a[i / 4]) + " is not below P");
+    if (values[i] >= P) return reject(std::string(value_word) + " " + std::to_string(i % 4) + " of cell " + std::to_string(a[i / 4]) + " is not below P");
   cm_mem_set_step steps[SET_STEPS];
   const uint32_t need = mem_set_plan(a, n, steps);
   if (need != n_words) return reject(std::to_string(n_words) + " sibling words where the addresses need " + std::to_string(need));
@@ -339,7 +315,6 @@ int32_t set_root_host(const char* who, const uint32_t* a, uint64_t n64, const ui
   *root_out = h[0];
   return 0;
 }
-}  // namespace
 }  // namespace cm
 
 extern "C" {

@@ -8,6 +8,7 @@
 #include "engine.hpp"
 #include "host_adapter.hpp"
 #include "mem_range.hpp"
+#include <string>
 #include <vector>
 
 namespace cm {
@@ -83,6 +84,67 @@ inline uint32_t mem_set_plan(const uint32_t* a, uint32_t n, cm_mem_set_step step
   }
   return total;
 }
+
+// ---- what the kernels of the set openings and of the transitions (mem_transition.hip) share, device only ---------------------
+constexpr uint32_t SET_BLOCK = 256;
+constexpr size_t SET_LAND_BYTES = (size_t)8 << 20;   // per trip through the pinned landing buffer
+struct SetDefaults { uint32_t h[air::TREE_HEIGHT + 1]; };   // h[d] = the hash of an empty subtree whose top is at depth d
+struct SetWidths { uint32_t w[SET_STEPS]; };                  // w[k] = |S_k|, k = 0 .. 28 (the plan's)
+// the sibling word of lane t = k * n + i, which has the needs flag: the other half of the pair x & ~1, x = a[i] >> k (the left half
+// when x is odd), from depth 28 - k's slice of the node list, or that depth's default hash
+__device__ __forceinline__ uint32_t set_gather_word(const uint32_t* __restrict__ nodes, const uint32_t* __restrict__ off, const uint32_t* __restrict__ a,
+                                                    uint32_t n, uint32_t t, const SetDefaults& dflt) {
+  const uint32_t k = t / n, depth = SET_DEPTHS - k, x = a[t % n] >> k;
+  const uint32_t* const nd = range_find(nodes, off, depth, x & ~1u);
+  return nd ? ((x & 1u) ? nd[2] : nd[3]) : dflt.h[depth];
+}
+// half u & 1 of the value of cell a[u / 2] into values[2 u], values[2 u + 1]: the pair 4a + 2 * (u & 1) of depth 30, zeros when missing
+__device__ __forceinline__ void set_gather_half(const uint32_t* __restrict__ nodes, const uint32_t* __restrict__ off, const uint32_t* __restrict__ a,
+                                                uint32_t u, uint32_t* __restrict__ values) {
+  const uint32_t* const nd = range_find(nodes, off, air::TREE_HEIGHT, 4u * a[u >> 1] + 2u * (u & 1u));
+  values[2 * (size_t)u] = nd ? nd[2] : 0u;
+  values[2 * (size_t)u + 1] = nd ? nd[3] : 0u;
+}
+// what the hashing lanes read: the addresses, the flags and their scan, the head lanes, the record
+struct SetView {
+  const uint32_t* a;
+  const unsigned long long* flag;
+  const unsigned long long* scan;
+  const uint32_t* heads;
+  const uint32_t* words;
+  uint32_t n, n_words;
+};
+// Parent r of S_{k+1}: its first child is node c of S_k.  paired: an even node whose successor in S_k is x + 1, the children are
+// nodes c and c + 1.  Else the other child is the sibling word w, on the left when the node is odd; w = P when the record has no
+// such word.  Index arithmetic only: the same for every plane of values folded over the addresses.
+struct SetParent { uint32_t c, w; bool paired, odd; };
+__device__ __forceinline__ SetParent set_parent(const SetView& s, uint32_t k, uint32_t r) {
+  // the parent's head lane is the head lane of its first child: a lane that starts a node at shift k + 1 starts one at shift k
+  const uint32_t i = k + 1 < SET_DEPTHS ? s.heads[(uint32_t)(s.scan[(size_t)(k + 1) * s.n] >> 32) + r] : 0u;
+  const size_t t = (size_t)k * s.n + i;
+  SetParent p;
+  p.c = (uint32_t)(s.scan[t] >> 32) - (uint32_t)(s.scan[(size_t)k * s.n] >> 32);
+  p.paired = !((uint32_t)s.flag[t] & 1u);
+  p.w = 0u;
+  p.odd = false;
+  if (p.paired) return p;
+  const uint32_t q = (uint32_t)s.scan[t];
+  p.w = q < s.n_words ? s.words[q] : P;
+  p.odd = (s.a[i] >> k) & 1u;
+  return p;
+}
+
+// ---- the host pieces both verifiers and both openers run (mem_set.hip) ---------------------------------------------------------
+// flag[t] and scan[t] of the 28 n pairs, enqueued on st (the scan's temporary lives in `tmp` until the stream has run)
+void set_flags_and_scan(const uint32_t* d_addr, uint32_t n, DevBuf& flag, DevBuf& scan, DevBuf& tmp, hipStream_t st);
+// heads[rank] = the head lane of every node of S_0 .. S_27, depth-major (k_set_heads), n_heads of them
+void set_heads_enqueue(const DevBuf& flag, const DevBuf& scan, uint32_t n, uint32_t n_heads, uint32_t* heads, hipStream_t st);
+// what is wrong with address `bad` = set_first_bad_address(a, n) < n
+std::string set_address_complaint(const uint32_t* a, uint64_t bad);
+// the host fold: 0 and *root_out, or 11 and the message "<noun> of <n> cells: ...", a bad value named "<value_word> <j> of cell <a>"
+// (1: a NULL argument or n > 2^20, behind `who`)
+int32_t set_root_host(const char* who, const uint32_t* a, uint64_t n64, const uint32_t* values, const uint32_t* words, uint32_t n_words, uint32_t* root_out,
+                      const char* noun = "memory set", const char* value_word = "value word");
 
 // ---- what the run adapter (adapter_run.inc) and the C ABI need --------------------------------------------------------------
 // values[4 * n] and siblings[n_siblings] = the opening of the set under the tree whose node list is `nodes`: four launches, one

@@ -172,6 +172,7 @@ void open_range_check(const char* who, uint32_t start, uint32_t n_cells, const u
 void run_open_memory_set(Run& r, const uint32_t* addresses, uint32_t n, uint32_t* values, uint32_t* siblings, uint32_t n_siblings, uint32_t* root);
 void open_set_check(const char* who, const uint32_t* addresses, uint64_t n, const uint32_t* values, const uint32_t* siblings, uint32_t cap_siblings,
                     uint32_t* n_siblings);   // mem_set.hip
+cm_mem_transition* open_transition(const DeviceInput& d, const uint32_t* addresses, uint64_t n);   // mem_transition.hip
 void run_free(Run* r);
 // copy a device-resident input back to the host (tests)
 void download_input(const DeviceInput& d, host::ProverInputOwned& o) {
@@ -1857,21 +1858,41 @@ int32_t cm_run_open_memory_set(cm_run* r, const uint32_t* addresses, uint64_t n,
   });
 }
 int32_t cm_run_free(cm_run* r) { delete r; return 0; }
-int32_t cm_prove_run(cm_run* r, const cm_run_segment* const* segs, uint32_t n, const cm_pcs_config* config, uint32_t inflight, cm_proof** outs) {
-  if (!r || !r->r || (n && (!segs || !outs))) return cm_set_last_error("cm_prove_run: null argument");
+// The ingest loop of cm_prove_run and cm_prove_run_transitions.  adapted (optional; null for cm_prove_run): called on the adapting
+// thread with segment i's input right after the adapter, before the input is handed to a worker; when it throws the segment counts
+// as one that could not be made.
+extern "C++" {
+template <class Adapted>
+static int32_t prove_run_ingest(const char* who, cm_run* r, const cm_run_segment* const* segs, uint32_t n, const cm_pcs_config* config, uint32_t inflight,
+                                cm_proof** outs, Adapted adapted) {
   // the image is serial: ONE producer (the calling thread) adapts the segments in order, the workers prove behind it
   std::lock_guard<std::mutex> lk(cm::run_mutex(*r->r));
   return prove_streamed(n, [&](uint32_t i) {
-    check_run_segment(segs[i], "cm_prove_run");
-    return cm::run_adapt_next(*r->r, *segs[i]);
+    check_run_segment(segs[i], who);
+    std::unique_ptr<cm::DeviceInput> d(cm::run_adapt_next(*r->r, *segs[i]));
+    if constexpr (!std::is_same<Adapted, std::nullptr_t>::value) adapted(i, *d);
+    return d.release();
   }, [&](uint32_t i, const cm_pcs_config&, bool& known) {
-    check_run_segment(segs[i], "cm_prove_run");
+    check_run_segment(segs[i], who);
     known = false;   // as for cm_prove_many_segments: the component sizes exist once the adapter has run
     const cm_run_segment& g = *segs[i];
     const uint64_t cells = cm::run_rows_bound(*r->r, g.n_memory_trace);   // (the image as it is now: this thread is its only writer)
     return cm::ItemBytes{g.n_trace * sizeof(cm_bundle) + g.n_memory_trace * (sizeof(cm_data_access) + sizeof(cm_clock_update)) +
                              2 * cells * sizeof(cm_memory_cell), 0};
   }, config, inflight, outs, /*n_producers=*/1);
+}
+}  // extern "C++"
+int32_t cm_prove_run(cm_run* r, const cm_run_segment* const* segs, uint32_t n, const cm_pcs_config* config, uint32_t inflight, cm_proof** outs) {
+  if (!r || !r->r || (n && (!segs || !outs))) return cm_set_last_error("cm_prove_run: null argument");
+  return prove_run_ingest("cm_prove_run", r, segs, n, config, inflight, outs, nullptr);
+}
+// the same with every adapted segment's write-set transition (mem_transition.hip) opened on this thread before a worker takes the input
+int32_t cm_prove_run_transitions(cm_run* r, const cm_run_segment* const* segs, uint32_t n, const cm_pcs_config* config, uint32_t inflight,
+                                 cm_proof** outs, cm_mem_transition** transitions) {
+  if (!r || !r->r || (n && (!segs || !outs || !transitions))) return cm_set_last_error("cm_prove_run_transitions: null argument");
+  for (uint32_t i = 0; i < n; i++) transitions[i] = nullptr;
+  return prove_run_ingest("cm_prove_run_transitions", r, segs, n, config, inflight, outs,
+                          [&](uint32_t i, const cm::DeviceInput& d) { transitions[i] = cm::open_transition(d, nullptr, 0); });
 }
 // The same walk with the PCS-free check (check.hip) and the link diff (link.hip) in the place of the proof: every verdict is
 // collected, only a segment that cannot be adapted ends the call.  Segment i - 1's input lives until link i has been looked at.

@@ -74,6 +74,22 @@ void check_segment(const DeviceInput& din, const cm_relations* relations, cm_che
 // index of `next` in its run (the report's first sentence names it).  cells: room for `cap` records; n_total: all there are.
 void link_diff(const DeviceInput& prev, const DeviceInput& next, uint32_t seg_index, cm_link_report& rep, cm_link_cell* cells, uint64_t cap,
                uint64_t& n_total);
+// The diff's first half for any two row arrays in ascending address order (device pointers; `a` in the role of prev, `b` of next,
+// n_a + n_b > 0): the classification of every row into its slot of the merged order, and with_scan the exclusive sum of the listed
+// flags.  state[LS_*] = the totals.  Enqueued on st; the buffers live in `m`.  The segment write set (mem_transition.hip) runs it
+// over one input's initial and final boundary memory.
+enum : uint32_t { LS_CHANGED = 0, LS_ONLY_NEXT = 1, LS_ONLY_PREV = 2, LS_ZERO_ONLY = 3, LS_ERR = 4, LS_WORDS = 8 };
+struct LinkMerge {
+  DevBuf state, flag, pos, src, tmp;
+  const uint32_t* prev = nullptr;
+  const uint32_t* next = nullptr;
+  uint32_t n_prev = 0, n_next = 0, n_slots = 0;
+};
+void link_merge_enqueue(const uint32_t* a, uint64_t n_a, const uint32_t* b, uint64_t n_b, bool with_scan, LinkMerge& m, hipStream_t st);
+// out[p] = the address of the p-th listed cell, p < cap (ascending: the merged order is); needs the scan
+void link_addresses_enqueue(const LinkMerge& m, uint32_t* out, uint32_t cap, hipStream_t st);
+// *missing (device) = the lowest listed address that is not in the ascending device array set[0 .. n_set), or 0xffffffff
+void link_missing_enqueue(const LinkMerge& m, const uint32_t* set, uint32_t n_set, uint32_t* missing, hipStream_t st);
 // link i of a checked run into its record: cells + i * cap_per_link receive the cells
 void check_link_into(const DeviceInput& prev, const DeviceInput& next, uint32_t i, cm_run_check& rec, cm_link_cell* cells, uint64_t cap_per_link);
 // the line cm_check_run / cm_check_chain leave for cm_last_error(): the first bad link or segment, or empty

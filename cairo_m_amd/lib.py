@@ -811,21 +811,28 @@ class Run:
         self.B._ck(self.L.cm_run_memory(self.h, _p(lo), C.c_uint64(nl.value), C.byref(nl), _p(hi), C.c_uint64(nh.value), C.byref(nh)))
         return lo, hi
 
-    def prove(self, segs, inflight=3, cfg=None):
-        """cm_prove_run: the next segments of this run (RunSegmentC or HostSegment each), proved in order of `segs`."""
+    def prove(self, segs, inflight=3, cfg=None, transitions=False):
+        """cm_prove_run: the next segments of this run (RunSegmentC or HostSegment each), proved in order of `segs`.
+        transitions=True: cm_prove_run_transitions -> (proofs, [MemTransition]), every segment's write set between its two roots."""
         segs = [s if isinstance(s, RunSegmentC) else run_segment(s) for s in segs]
         n = len(segs)
         ins = (C.c_void_p * n)(*[C.addressof(s) for s in segs])
         outs = (C.c_void_p * n)()
-        rc = self.L.cm_prove_run(self.h, ins, C.c_uint32(n), _cfg(cfg), C.c_uint32(inflight), outs)
+        if transitions:
+            ts = (C.c_void_p * n)()
+            rc = self.L.cm_prove_run_transitions(self.h, ins, C.c_uint32(n), _cfg(cfg), C.c_uint32(inflight), outs, ts)
+            moves = [_take_transition(self.L, C.c_void_p(ts[i])) if ts[i] else None for i in range(n)]
+        else:
+            rc = self.L.cm_prove_run(self.h, ins, C.c_uint32(n), _cfg(cfg), C.c_uint32(inflight), outs)
         proofs = [Proof(self.L, C.c_void_p(outs[i])) if outs[i] else None for i in range(n)]
         if rc != 0:
             try:
                 self.B._ck(rc)
             except CmError as e:
                 e.partial = proofs
+                e.partial_transitions = moves if transitions else None
                 raise
-        return proofs
+        return (proofs, moves) if transitions else proofs
 
     def free(self):
         if self.h:
@@ -1833,6 +1840,143 @@ def set_root(opening, values=None, lib=None):
 Backend.open_memory_set = _backend_open_memory_set
 Backend.verify_set = lambda self, root, opening, stream=0, with_root=False: verify_set(root, opening, self.L, stream, with_root)
 Run.open_set = _run_open_set
+
+
+# ---- memory transitions (include/cairom_hip.h: cm_input_write_set .. cm_prove_run_transitions) ----------------------------------
+class MemTransitionViewC(C.Structure):
+    """cm_mem_transition_view"""
+    _fields_ = [(n, C.c_uint32) for n in ("struct_size", "root_before", "root_after", "n", "n_siblings", "n_zero_only")] + \
+               [(n, _u32p) for n in ("addresses", "old_values", "new_values", "siblings")]
+
+
+class MemTransition:
+    """A set of cells with their values under two roots and one list of sibling words (a set opening's): `old_values` fold to
+    `root_before`, `new_values` to `root_after`, so the two memories agree outside `addresses`."""
+
+    def __init__(self, addresses, old_values, new_values, siblings, root_before, root_after, n_zero_only=0):
+        self.addresses = np.ascontiguousarray(addresses, dtype=np.uint32).reshape(-1)
+        self.old_values = np.ascontiguousarray(old_values, dtype=np.uint32).reshape(-1, 4)
+        self.new_values = np.ascontiguousarray(new_values, dtype=np.uint32).reshape(-1, 4)
+        self.siblings = np.ascontiguousarray(siblings, dtype=np.uint32).reshape(-1)
+        self.root_before, self.root_after, self.n_zero_only = int(root_before), int(root_after), int(n_zero_only)
+
+    @property
+    def nbytes(self):
+        """what travels: addresses, old and new values, sibling words"""
+        return 36 * self.addresses.size + 4 * self.siblings.size
+
+    def updates(self):
+        """[(address, (v0, v1, v2, v3))]: what a follower writes into its copy of the memory"""
+        return [(int(a), tuple(int(x) for x in v)) for a, v in zip(self.addresses, self.new_values)]
+
+    def __repr__(self):
+        return f"MemTransition(n={self.addresses.size}, n_siblings={self.siblings.size}, {self.root_before} -> {self.root_after})"
+
+
+def _take_transition(L, h):
+    """the arrays of a cm_mem_transition, copied; the handle is freed"""
+    v = MemTransitionViewC()
+    v.struct_size = C.sizeof(MemTransitionViewC)
+    try:
+        rc = L.cm_mem_transition_get(h, C.byref(v))
+        if rc:
+            raise _lib_error(L, rc)
+        take = lambda p, k: np.ctypeslib.as_array(p, shape=(k,)).copy() if k else np.zeros(0, dtype=np.uint32)
+        return MemTransition(take(v.addresses, v.n), take(v.old_values, 4 * v.n), take(v.new_values, 4 * v.n), take(v.siblings, v.n_siblings),
+                             v.root_before, v.root_after, v.n_zero_only)
+    finally:
+        L.cm_mem_transition_free(h)
+
+
+def _backend_write_set(self, dev_input, cap=None, with_counts=False):
+    """cm_input_write_set (GPU): the ascending addresses of the cells whose value differs between the input's initial and final
+    boundary memory; with_counts: (addresses, n_total, n_zero_only).  cap: room for that many (the rest is counted, not listed)."""
+    n, z = C.c_uint64(0), C.c_uint64(0)
+    if cap is None:
+        self._ck(self.L.cm_input_write_set(dev_input, None, C.c_uint64(0), C.byref(n), C.byref(z)))
+        cap = n.value
+    a = np.zeros(max(cap, 1), dtype=np.uint32)
+    self._ck(self.L.cm_input_write_set(dev_input, _p(a), C.c_uint64(cap), C.byref(n), C.byref(z)))
+    a = a[:min(cap, n.value)].copy()
+    return (a, n.value, z.value) if with_counts else a
+
+
+def _backend_open_transition(self, dev_input, addresses=None):
+    """cm_input_open_transition (GPU) -> MemTransition of the input from its initial to its final tree: over the segment's write
+    set, or over `addresses` (any order, repeats allowed), which must hold every cell the segment changes."""
+    h = C.c_void_p()
+    if addresses is None:
+        self._ck(self.L.cm_input_open_transition(dev_input, None, C.c_uint64(0), C.byref(h)))
+    else:
+        a = np.unique(_set_addresses(addresses))
+        pad = a if a.size else np.zeros(1, dtype=np.uint32)
+        self._ck(self.L.cm_input_open_transition(dev_input, _p(pad), C.c_uint64(a.size), C.byref(h)))
+    return _take_transition(self.L, h)
+
+
+def _transition_args(t):
+    a, s = t.addresses, t.siblings
+    old, new = t.old_values.reshape(-1), t.new_values.reshape(-1)
+    if old.size != 4 * a.size or new.size != 4 * a.size:
+        raise ValueError(f"{old.size} old and {new.size} new value words for a transition of {a.size} cells")
+    pad = lambda x: x if x.size else np.zeros(4, dtype=np.uint32)                 # (an empty array still has to be an address)
+    keep = (pad(a), pad(old), pad(new), pad(s))
+    return (C.c_uint32(t.root_before), C.c_uint32(t.root_after), _p(keep[0]), C.c_uint64(a.size), _p(keep[1]), _p(keep[2]), _p(keep[3]),
+            C.c_uint32(s.size)), keep
+
+
+def verify_transition(t, lib=None, stream=0, with_roots=False):
+    """cm_verify_memory_transition (GPU) -> bool: the transition is well formed, its old values fold to root_before and its new
+    values to root_after; with_roots: (bool, (the two roots they fold to, zeros when malformed))."""
+    L = lib or load_library()
+    args, keep = _transition_args(t)
+    ok, got = C.c_uint8(0), (C.c_uint32 * 2)()
+    rc = L.cm_verify_memory_transition(*args, C.byref(ok), got, C.c_uint64(stream))
+    if rc:
+        raise _lib_error(L, rc)
+    return (bool(ok.value), (got[0], got[1])) if with_roots else bool(ok.value)
+
+
+def verify_transition_host(t, lib=None):
+    """cm_verify_memory_transition_host (host code, no GPU) -> (status, message): (0, "") accepted, (11, why) rejected."""
+    L = lib or load_library()
+    args, keep = _transition_args(t)
+    rc = L.cm_verify_memory_transition_host(*args)
+    if not rc:
+        return 0, ""
+    buf = C.create_string_buffer(512)
+    L.cm_last_error(buf, C.c_size_t(512))
+    return rc, buf.value.decode(errors="replace")
+
+
+def follow_run(proofs, transitions, lib=None, device=True):
+    """What a client that holds only the proofs' roots does with a run's transitions: transition i must go from proof i's public
+    initial_root to its final_root and must verify (device=True: on the GPU, else in host code).  Returns the updates
+    [(address, new value)] in run order; raises CmError naming the first segment whose transition does not fit."""
+    L = lib or proofs[0].L
+    if len(proofs) != len(transitions):
+        raise CmError(f"follow_run: {len(transitions)} transitions for {len(proofs)} proofs")
+    out = []
+    for i, (p, t) in enumerate(zip(proofs, transitions)):
+        d = p.public_data()
+        for side, want in (("before", d["initial_root"]), ("after", d["final_root"])):
+            got = getattr(t, "root_" + side)
+            if got != want:
+                raise CmError(f"follow_run: segment {i}: the transition's root {side} is {got}, the proof's is {want}")
+        if device:
+            ok, why = verify_transition(t, L), "the transition does not verify on the GPU"
+        else:
+            rc, why = verify_transition_host(t, L)
+            ok = rc == 0
+        if not ok:
+            raise CmError(f"follow_run: segment {i}: {why}")
+        out += t.updates()
+    return out
+
+
+Backend.write_set = _backend_write_set
+Backend.open_transition = _backend_open_transition
+Backend.verify_transition = lambda self, t, stream=0, with_roots=False: verify_transition(t, self.L, stream, with_roots)
 
 
 # ---- program identity and the statement of a run (include/cairom_hip.h: cm_program_id_entries .. cm_run_statement_of) ----------

@@ -46,7 +46,10 @@
  *    Still 10 (additive: six new functions and one struct, nothing moved): cm_mem_set_step, cm_mem_set_plan,
  *    cm_input_open_memory_set, cm_run_open_memory_set, cm_verify_memory_set, cm_memory_set_root_host, cm_verify_memory_set_host.
  *    Still 10 (additive: five new functions and one struct, nothing moved): cm_run_statement, cm_program_id_entries,
- *    cm_proof_program_id, cm_program_ids, cm_proofs_program_ids, cm_run_statement_of. */
+ *    cm_proof_program_id, cm_program_ids, cm_proofs_program_ids, cm_run_statement_of.
+ *    Still 10 (additive: seven new functions, one view struct and one opaque handle, nothing moved): cm_mem_transition,
+ *    cm_mem_transition_view, cm_input_write_set, cm_input_open_transition, cm_mem_transition_get, cm_mem_transition_free,
+ *    cm_verify_memory_transition, cm_verify_memory_transition_host, cm_prove_run_transitions. */
 #define CM_ABI_REVISION 10
 
 #ifdef __cplusplus
@@ -1033,6 +1036,79 @@ int32_t cm_memory_set_root_host(const uint32_t* addresses, uint64_t n, const uin
 /* The same, compared with `root`: 0 accepted, 11 rejected; for a well-formed record "the set hashes to root <x>, not <y>". */
 int32_t cm_verify_memory_set_host(uint32_t root, const uint32_t* addresses, uint64_t n, const uint32_t* values, const uint32_t* siblings,
                                   uint32_t n_siblings);
+/* ---- memory transitions (additive to revision 10: new symbols and structs, nothing moved) --------------------------------------
+ * A proof states initial_root -> final_root.  A transition says which cells changed, and to what, in a form a holder of only the
+ * two roots can check: the state diff a client following a run applies to its own copy of the memory.
+ *
+ * The statement.  A transition from root R0 to root R1 is: strictly ascending addresses a[0 .. n) < 2^28, old_values (4 n words),
+ * new_values (4 n words) and ONE list of sibling words, exactly the record of a set opening of `a`: same order, same count[k],
+ * same n_siblings.  It is valid when the set fold of (a, old_values, words) is R0 and the fold of (a, new_values, words) is R1,
+ * and then says that the two memories agree in every cell outside `a` (the words ARE every subtree beside the set's paths).  An
+ * absent cell is (0, 0, 0, 0) on either side, as for sets; there is no `present` flag.  A superset of the write set is allowed
+ * (cells with old == new).  n == 0 is well formed only with n_siblings == 0 and is accepted exactly when R0 == R1, a read-only
+ * segment; nothing is launched for it.  n <= 2^20, as for sets.  A transition travels as 36 n + 4 m bytes.
+ *
+ * cm_input_write_set lists, ascending, the cells whose four value words differ between the input's initial and final boundary
+ * memory.  Built on the GPU, on the calling thread's stream and pool, by the classification and the scan of cm_link_diff with the
+ * roles (initial, final) and a compaction to addresses: no atomic decides an order, the same call gives the same bytes.  A cell
+ * present on one side only with an all-zero value does not change the root: it is counted in *n_zero_only and not listed
+ * (cm_link_diff's rule).  *n_total = all there are; *n_total > cap means truncated and is not an error.  An input without
+ * boundary memory (trees alone) has an empty write set.  Status 1: a NULL argument, NULL addresses with a capacity, rows not in
+ * ascending address order.
+ * cm_input_open_transition opens the transition of the input from its initial to its final tree over `addresses`; addresses ==
+ * NULL means the write set (n is ignored), which then stays on the device between the diff and the opening.  The result is an
+ * opaque handle because the sizes are not known before the call; cm_mem_transition_get fills a view (set struct_size =
+ * sizeof(cm_mem_transition_view) first) whose pointers stay valid until cm_mem_transition_free.  On the GPU: the set opener's flag
+ * pass and scan, then one gather launch of 28 n + 2 n + 2 n lanes — the sibling words and the old value halves from the INITIAL
+ * tree exactly as cm_input_open_memory_set takes them, and 2 n more lanes that bisect depth 30 of the FINAL tree for the new
+ * halves.  For a supplied set a membership launch over the diff's listed cells finds the lowest one the set misses: status 1,
+ * "cell <a> changes in this segment and is not in the set".  One host round trip carries the data (one more per further 8 MB;
+ * with addresses == NULL the write set's size comes back in a small one of its own); the device's word count is checked against
+ * cm_mem_set_plan's.  n_zero_only is the write set's.  Refusals are otherwise those of cm_input_open_memory_set: a NULL `in` or
+ * `out`, n == 0 with addresses given, n > 2^20, addresses not strictly ascending or not below 2^28.  With addresses == NULL a
+ * segment that changes nothing gives n == 0 and no words, and one that changes more than 2^20 cells is refused.  Without a GPU
+ * the status is cm_init's (3).
+ * cm_verify_memory_transition checks both roots on the GPU in ONE fold over two value planes (stream s; 0 = the calling thread's
+ * own).  The set verifier's flag pass, scan and head scatter run once; k_trans_cells, one lane per cell, range-checks all eight
+ * words and writes two nodes of depth 28; k_trans_level, one lane per parent while S_k is wider than 128 nodes, does the index
+ * arithmetic and loads the sibling word once and compresses twice; k_trans_tail, one workgroup, finishes the remaining depths of
+ * both planes in LDS, checks the count, compares both roots and writes the verdict and the roots; four words come back.  The
+ * launches come from cm_mem_set_plan's records.  *ok = 1 when the statement is well formed and both folds match; computed (may be
+ * NULL) receives the two roots it folds to when well formed (n == 0: root_before twice), else zeros.  Malformed input is a verdict
+ * (*ok = 0), never a failed call; status 1 only for a NULL argument or n > 2^20.  The call keeps nothing.  Temporaries: the set
+ * verifier's plus 24 bytes per cell.
+ * cm_verify_memory_transition_host is the same check in host code, two runs of the set fold: 0 accepted, 11 rejected, 1 for a
+ * NULL argument or n > 2^20.  cm_last_error() then reads "memory transition of <n> cells: " and the set verifier's own words for a
+ * malformed record, with "old value word <j> of cell <a>" / "new value word ..." where a value is bad; for a well-formed record
+ * "the old values hash to root <x>, not <y>", or, when that side passes, "the new values hash to root <x>, not <y>"; for n == 0
+ * "no cell changes, and root <x> is not root <y>".
+ * cm_prove_run_transitions is cm_prove_run with each segment's write-set transition opened on the adapting thread right after the
+ * segment is adapted and before a worker proves it: the proofs are cm_prove_run's, byte for byte.  Error contract: cm_prove_run's;
+ * transitions[i] is NULL for every segment that was not adapted, and the caller frees the others. */
+typedef struct cm_mem_transition cm_mem_transition;
+typedef struct {
+  uint32_t struct_size;
+  uint32_t root_before;
+  uint32_t root_after;
+  uint32_t n;
+  uint32_t n_siblings;
+  uint32_t n_zero_only;
+  const uint32_t* addresses;    /* n */
+  const uint32_t* old_values;   /* 4 n */
+  const uint32_t* new_values;   /* 4 n */
+  const uint32_t* siblings;     /* n_siblings */
+} cm_mem_transition_view;       /* sizeof = 56 */
+int32_t cm_input_write_set(const cm_device_input* in, uint32_t* addresses, uint64_t cap, uint64_t* n_total, uint64_t* n_zero_only);
+int32_t cm_input_open_transition(const cm_device_input* in, const uint32_t* addresses, uint64_t n, cm_mem_transition** out);
+int32_t cm_mem_transition_get(const cm_mem_transition* t, cm_mem_transition_view* out);
+int32_t cm_mem_transition_free(cm_mem_transition* t);
+int32_t cm_verify_memory_transition(uint32_t root_before, uint32_t root_after, const uint32_t* addresses, uint64_t n, const uint32_t* old_values,
+                                    const uint32_t* new_values, const uint32_t* siblings, uint32_t n_siblings, uint8_t* ok, uint32_t computed[2],
+                                    cm_stream_t s);
+int32_t cm_verify_memory_transition_host(uint32_t root_before, uint32_t root_after, const uint32_t* addresses, uint64_t n, const uint32_t* old_values,
+                                         const uint32_t* new_values, const uint32_t* siblings, uint32_t n_siblings);
+int32_t cm_prove_run_transitions(cm_run* r, const cm_run_segment* const* segs, uint32_t n, const cm_pcs_config* config, uint32_t inflight,
+                                 cm_proof** outs, cm_mem_transition** transitions);
 /* ---- program identity and the statement of a run (additive to revision 10) ---------------------------------------------------
  * Which program a proof is about, as one 31-bit word: Proof::program_id() of the reference (crates/prover/src/lib.rs:75-97), the
  * Poseidon2 root of the partial memory tree that holds only the proof's public program cells.  An "entry" is the seven-word record

@@ -279,6 +279,26 @@ pub struct cm_public_data {
     pub n_input: u32,
     pub n_output: u32,
 }
+/// A memory transition as the library hands it out (`cm_input_open_transition`); read through `cm_mem_transition_get`
+#[repr(C)]
+pub struct cm_mem_transition {
+    _private: [u8; 0],
+}
+/// The arrays of a `cm_mem_transition`, valid until `cm_mem_transition_free`; set `struct_size` before `cm_mem_transition_get`
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct cm_mem_transition_view {
+    pub struct_size: u32,
+    pub root_before: u32,
+    pub root_after: u32,
+    pub n: u32,
+    pub n_siblings: u32,
+    pub n_zero_only: u32,
+    pub addresses: *const u32,
+    pub old_values: *const u32,
+    pub new_values: *const u32,
+    pub siblings: *const u32,
+}
 /// What a chain of proofs states (`cm_run_statement_of`): the program's id and range, the registers and memory roots the run
 /// starts from and ends at, the counts of its input and output entries; set `struct_size` before the call
 #[repr(C)]
@@ -519,6 +539,13 @@ unsafe extern "C" {
     pub fn cm_verify_memory_set(root: u32, addresses: *const u32, n: u64, values: *const u32, siblings: *const u32, n_siblings: u32, ok: *mut u8, computed_root: *mut u32, s: cm_stream_t) -> i32;
     pub fn cm_memory_set_root_host(addresses: *const u32, n: u64, values: *const u32, siblings: *const u32, n_siblings: u32, root_out: *mut u32) -> i32;
     pub fn cm_verify_memory_set_host(root: u32, addresses: *const u32, n: u64, values: *const u32, siblings: *const u32, n_siblings: u32) -> i32;
+    pub fn cm_input_write_set(input: *const cm_device_input, addresses: *mut u32, cap: u64, n_total: *mut u64, n_zero_only: *mut u64) -> i32;
+    pub fn cm_input_open_transition(input: *const cm_device_input, addresses: *const u32, n: u64, out: *mut *mut cm_mem_transition) -> i32;
+    pub fn cm_mem_transition_get(t: *const cm_mem_transition, out: *mut cm_mem_transition_view) -> i32;
+    pub fn cm_mem_transition_free(t: *mut cm_mem_transition) -> i32;
+    pub fn cm_verify_memory_transition(root_before: u32, root_after: u32, addresses: *const u32, n: u64, old_values: *const u32, new_values: *const u32, siblings: *const u32, n_siblings: u32, ok: *mut u8, computed: *mut u32, s: cm_stream_t) -> i32;
+    pub fn cm_verify_memory_transition_host(root_before: u32, root_after: u32, addresses: *const u32, n: u64, old_values: *const u32, new_values: *const u32, siblings: *const u32, n_siblings: u32) -> i32;
+    pub fn cm_prove_run_transitions(r: *mut cm_run, segs: *const *const cm_run_segment, n: u32, config: *const cm_pcs_config, inflight: u32, outs: *mut *mut cm_proof, transitions: *mut *mut cm_mem_transition) -> i32;
     pub fn cm_program_id_entries(entries: *const u32, n: u64, id: *mut u32) -> i32;
     pub fn cm_proof_program_id(p: *const cm_proof, id: *mut u32) -> i32;
     pub fn cm_program_ids(entries: *const *const u32, n_entries: *const u64, n: u32, ids: *mut u32, status: *mut i32, s: cm_stream_t) -> i32;

@@ -592,6 +592,112 @@ pub fn memory_set_root(opening: &MemSetOpening, values: Option<&[u32]>) -> Resul
     Ok(root)
 }
 
+/// A memory transition (`cm_input_open_transition`): strictly ascending addresses, their values under the root before and under
+/// the root after, and ONE list of sibling words, a set opening's.  The old values fold to `root_before`, the new ones to
+/// `root_after`: the two memories agree in every cell outside the set.
+#[derive(Clone, Debug)]
+pub struct MemTransition {
+    pub addresses: Vec<u32>,
+    pub old_values: Vec<u32>,
+    pub new_values: Vec<u32>,
+    pub siblings: Vec<u32>,
+    pub root_before: u32,
+    pub root_after: u32,
+    pub n_zero_only: u32,
+}
+
+/// The cells a segment changes (`cm_input_write_set`), ascending: those whose value differs between the input's initial and final
+/// boundary memory, and the count of cells present on one side only with an all-zero value, which are not listed.
+pub fn write_set(input: *const cm_device_input) -> Result<(Vec<u32>, u64), String> {
+    ensure_init();
+    let (mut n, mut zero_only): (u64, u64) = (0, 0);
+    let rc = unsafe { cm_input_write_set(input, std::ptr::null_mut(), 0, &mut n, &mut zero_only) };
+    if rc != 0 {
+        return Err(last_error());
+    }
+    let mut a: Vec<u32> = vec![0; n as usize];
+    let rc = unsafe { cm_input_write_set(input, a.as_mut_ptr(), a.len() as u64, &mut n, &mut zero_only) };
+    if rc != 0 {
+        return Err(last_error());
+    }
+    a.truncate(n as usize);
+    Ok((a, zero_only))
+}
+
+/// The transition of a device-resident input from its initial to its final memory root, built on the GPU: over the segment's
+/// write set (`addresses` = None) or over the given cells (any order, repeats allowed), which must hold every cell that changes.
+pub fn open_transition(input: *const cm_device_input, addresses: Option<&[u32]>) -> Result<MemTransition, String> {
+    ensure_init();
+    let mut h: *mut cm_mem_transition = std::ptr::null_mut();
+    let rc = match addresses {
+        None => unsafe { cm_input_open_transition(input, std::ptr::null(), 0, &mut h) },
+        Some(list) => {
+            let mut a: Vec<u32> = list.to_vec();
+            a.sort_unstable();
+            a.dedup();
+            unsafe { cm_input_open_transition(input, a.as_ptr(), a.len() as u64, &mut h) }
+        }
+    };
+    if rc != 0 {
+        return Err(last_error());
+    }
+    let mut v: cm_mem_transition_view = unsafe { std::mem::zeroed() };
+    v.struct_size = std::mem::size_of::<cm_mem_transition_view>() as u32;
+    let rc = unsafe { cm_mem_transition_get(h, &mut v) };
+    let copy = |p: *const u32, k: usize| -> Vec<u32> {
+        if k == 0 {
+            Vec::new()
+        } else {
+            unsafe { std::slice::from_raw_parts(p, k) }.to_vec()
+        }
+    };
+    let out = if rc == 0 {
+        Ok(MemTransition {
+            addresses: copy(v.addresses, v.n as usize),
+            old_values: copy(v.old_values, 4 * v.n as usize),
+            new_values: copy(v.new_values, 4 * v.n as usize),
+            siblings: copy(v.siblings, v.n_siblings as usize),
+            root_before: v.root_before,
+            root_after: v.root_after,
+            n_zero_only: v.n_zero_only,
+        })
+    } else {
+        Err(last_error())
+    };
+    unsafe { cm_mem_transition_free(h) };
+    out
+}
+
+/// A transition checked against its two roots on the GPU in one fold (`cm_verify_memory_transition`) -> (accepted, the two roots
+/// it folds to; zeros when malformed).  A malformed record is a `false`, not an error.
+pub fn verify_memory_transition(t: &MemTransition) -> Result<(bool, [u32; 2]), String> {
+    ensure_init();
+    if t.old_values.len() != 4 * t.addresses.len() || t.new_values.len() != 4 * t.addresses.len() {
+        return Err(format!("{} old and {} new value words for a transition of {} cells", t.old_values.len(), t.new_values.len(), t.addresses.len()));
+    }
+    let mut ok: u8 = 0;
+    let mut got = [0u32; 2];
+    let rc = unsafe {
+        cm_verify_memory_transition(
+            t.root_before,
+            t.root_after,
+            t.addresses.as_ptr(),
+            t.addresses.len() as u64,
+            t.old_values.as_ptr(),
+            t.new_values.as_ptr(),
+            t.siblings.as_ptr(),
+            t.siblings.len() as u32,
+            &mut ok,
+            got.as_mut_ptr(),
+            0,
+        )
+    };
+    if rc != 0 {
+        return Err(last_error());
+    }
+    Ok((ok != 0, got))
+}
+
 /// The passes of a 2^`log_n` transform as the library runs it (`cm_fft_plan`), in layer order: `[lo, hi, tile_log, M]` per pass,
 /// `tile_log` 0 = the generic kernel.  Host code: touches no GPU.
 pub fn fft_plan(log_n: u32) -> Result<Vec<[u32; 4]>, String> {
