@@ -1969,7 +1969,8 @@ int32_t cm_verify_run(const cm_proof* const* proofs, uint32_t n, const cm_pcs_co
 }
 // The same verdicts from the GPU, for a whole batch (verify_device.hip): results[i] = what cm_verify_proof says about proofs[i]
 static int32_t verify_many_impl(const char* who, const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected,
-                                std::vector<cm::VerifyOutcome>& out, cm_stream_t s) {
+                                std::vector<cm::VerifyOutcome>& out, cm_stream_t s,
+                                std::vector<std::vector<cm::VerifySlotDetail>>* detail = nullptr) {
   return pguard([&] {
     CM_CHECK(n >= 1 && proofs, std::string(who) + ": no proofs");
     std::vector<const cm::ProofData*> pd(n);
@@ -1977,13 +1978,11 @@ static int32_t verify_many_impl(const char* who, const cm_proof* const* proofs, 
       CM_CHECK(proofs[i] && proofs[i]->d, std::string(who) + ": null proof");
       pd[i] = proofs[i]->d;
     }
-    cm::verify_many_device(pd.data(), n, expected ? *expected : default_cfg(), out, (hipStream_t)(uintptr_t)s);
+    cm::verify_many_device(pd.data(), n, expected ? *expected : default_cfg(), out, (hipStream_t)(uintptr_t)s, detail);
   });
 }
-int32_t cm_verify_many(const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected, cm_verify_result* results, cm_stream_t s) {
-  std::vector<cm::VerifyOutcome> out;
-  const int32_t rc = verify_many_impl("cm_verify_many", proofs, n, expected, out, s);
-  if (rc) return rc;
+// the verdicts of a batch as cm_verify_many reports them: results, the call's status and cm_last_error()
+static int32_t verify_many_report(const std::vector<cm::VerifyOutcome>& out, uint32_t n, cm_verify_result* results) {
   int64_t first = -1;
   for (uint32_t i = 0; i < n; i++) {
     const bool ok = out[i].message.empty();
@@ -1998,6 +1997,46 @@ int32_t cm_verify_many(const cm_proof* const* proofs, uint32_t n, const cm_pcs_c
   if (first < 0) return 0;
   cm_set_last_error(("proof " + std::to_string(first) + ": verification failed: " + out[first].message).c_str());
   return 11;
+}
+int32_t cm_verify_many(const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected, cm_verify_result* results, cm_stream_t s) {
+  std::vector<cm::VerifyOutcome> out;
+  const int32_t rc = verify_many_impl("cm_verify_many", proofs, n, expected, out, s);
+  return rc ? rc : verify_many_report(out, n, results);
+}
+int32_t cm_verify_many_detail(const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected, cm_verify_result* results,
+                              cm_verify_slot* slots, uint32_t cap_slots, uint32_t* slot_first, cm_stream_t s) {
+  if (!slot_first || (!slots && cap_slots)) return cm_set_last_error("cm_verify_many_detail: null output");
+  std::vector<cm::VerifyOutcome> out;
+  std::vector<std::vector<cm::VerifySlotDetail>> detail;
+  const int32_t rc = verify_many_impl("cm_verify_many_detail", proofs, n, expected, out, s, &detail);
+  if (rc) return rc;
+  slot_first[0] = 0;
+  for (uint32_t i = 0; i < n; i++) slot_first[i + 1] = slot_first[i] + (uint32_t)detail[i].size();
+  if (slot_first[n] > cap_slots) return cm_set_last_error("cm_verify_many_detail: the slot array is too small (the count is in slot_first[n])");
+  for (uint32_t i = 0; i < n; i++)
+    for (size_t k = 0; k < detail[i].size(); k++) {
+      cm_verify_slot& o = slots[slot_first[i] + k];
+      memset(&o, 0, sizeof(o));
+      o.check = detail[i][k].check;
+      o.on_device = detail[i][k].on_device ? 1u : 0u;
+      o.raised = detail[i][k].raised ? 1u : 0u;
+      snprintf(o.message, sizeof(o.message), "%s", detail[i][k].message.c_str());
+    }
+  return verify_many_report(out, n, results);
+}
+int32_t cm_verify_plan_stats(const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected, cm_verify_stats* out) {
+  return pguard([&] {
+    CM_CHECK(n >= 1 && proofs && out, "cm_verify_plan_stats: no proofs, or null output");
+    std::vector<const cm::ProofData*> pd(n);
+    for (uint32_t i = 0; i < n; i++) {
+      CM_CHECK(proofs[i] && proofs[i]->d, "cm_verify_plan_stats: null proof");
+      CM_CHECK(out[i].struct_size >= sizeof(cm_verify_stats), "cm_verify_plan_stats: struct_size does not cover cm_verify_stats (set it to sizeof(cm_verify_stats))");
+      pd[i] = proofs[i]->d;
+    }
+    std::vector<cm_verify_stats> st(n);
+    cm::verify_plan_stats(pd.data(), n, expected ? *expected : default_cfg(), st.data());
+    for (uint32_t i = 0; i < n; i++) { const uint32_t keep = out[i].struct_size; out[i] = st[i]; out[i].struct_size = keep; }
+  });
 }
 int32_t cm_verify_run_device(const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected) {
   std::vector<cm::VerifyOutcome> out;

@@ -1,6 +1,7 @@
 // cm_verify_many: the query phase of verify_cairo_m for a whole batch of proofs on the GPU (plan format: verify_device.hpp).
 // Host: verify_prelude + a symbolic walk of merkle_verify / rebuild_evals per proof.  Device: k_verify_answers (DEEP quotients),
 // k_verify_fri (pairs, folds, last layer), k_verify_merkle (every tree of every proof), k_verify_reduce (lowest failed check).
+// cm_verify_plan_stats and cm_verify_many_detail read what the same Planner built (shapes; every slot's own flag) for the tests.
 #include "../../include/cairom_hip.h"
 #include "engine.hpp"
 #include "blake2s_dev.hpp"
@@ -524,7 +525,47 @@ Timing& timing() {
 
 void verify_many_timing(double ms[4]) { for (int i = 0; i < 4; i++) ms[i] = timing().ms[i]; }
 
-void verify_many_device(const ProofData* const* proofs, uint32_t n, const cm_pcs_config& cfg, std::vector<VerifyOutcome>& out, hipStream_t st) {
+// What the kernels would walk for this planner's proofs, read back from its tables (verify_device.hpp: the plan format)
+static void read_plan_stats(const Planner& pl, cm_verify_stats& s) {
+  const uint32_t* B = pl.blob.data();
+  s.n_answer_jobs = (uint32_t)(pl.ans_jobs.size() / 8);
+  for (size_t j = 0; j < pl.ans_jobs.size(); j += 8) {
+    const uint32_t* G = B + pl.ans_jobs[j];
+    for (uint32_t b = 0; b < G[0]; b++) s.max_batch_entries = std::max(s.max_batch_entries, G[5 + 10 * b + 8]);
+  }
+  for (uint32_t off : pl.fri_jobs) {
+    const uint32_t* F = B + off;
+    for (uint32_t g = 0; g < F[VF_N_GROUPS]; g++) s.max_first_pairs = std::max(s.max_first_pairs, B[F[VF_GROUPS] + VF_GROUP_WORDS * g + 1]);
+    for (uint32_t li = 0; li < F[VF_N_LAYERS]; li++) s.max_inner_pairs = std::max(s.max_inner_pairs, B[F[VF_LAYERS] + VF_LAYER_WORDS * li + 1]);
+  }
+  s.n_tree_jobs = (uint32_t)(pl.tree_jobs.size() / 8);
+  for (size_t j = 0; j < pl.tree_jobs.size(); j += 8)
+    for (uint32_t lv = 0; lv < pl.tree_jobs[j]; lv++) s.max_level_nodes = std::max(s.max_level_nodes, B[pl.tree_jobs[j + 1] + 4 * lv]);
+  s.merkle_lds_bytes = s.n_tree_jobs ? (uint32_t)verify_merkle_lds_bytes(s.max_level_nodes) : 0u;
+  s.blob_words = pl.blob.size();
+  s.scratch_words = pl.scr_words;
+}
+
+void verify_plan_stats(const ProofData* const* proofs, uint32_t n, const cm_pcs_config& cfg, cm_verify_stats* out) {
+  FramingUse framing_use;
+  for (uint32_t i = 0; i < n; i++) {
+    Planner pl;
+    ProofPlan pp;
+    pl.plan_proof(*proofs[i], cfg, pp);
+    cm_verify_stats s;
+    memset(&s, 0, sizeof(s));
+    s.struct_size = sizeof(s);
+    if (pp.decided_early) s.early_check = pp.early.check;
+    else {
+      read_plan_stats(pl, s);
+      s.n_slots = (uint32_t)pp.slots.size();
+    }
+    out[i] = s;
+  }
+}
+
+void verify_many_device(const ProofData* const* proofs, uint32_t n, const cm_pcs_config& cfg, std::vector<VerifyOutcome>& out, hipStream_t st,
+                        std::vector<std::vector<VerifySlotDetail>>* detail) {
   {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
@@ -562,7 +603,7 @@ void verify_many_device(const ProofData* const* proofs, uint32_t n, const cm_pcs
   if (n_fri) hipLaunchKernelGGL(k_verify_fri, dim3(n_fri), dim3(FRI_THREADS), 0, st, blob, d_scr.u32(), d_flags.u32(), blob + fri_off);
   if (n_tree) {
     const uint32_t cap = pl.max_level_nodes;
-    const size_t lds = 2 * (size_t)cap * 32;
+    const size_t lds = verify_merkle_lds_bytes(cap);
     if (framing().hash_node_rfc)
       hipLaunchKernelGGL(k_verify_merkle<true>, dim3(n_tree), dim3(MERKLE_THREADS), lds, st, blob, (const uint32_t*)d_scr.u32(), d_flags.u32(), blob + tree_off, cap);
     else
@@ -571,7 +612,9 @@ void verify_many_device(const ProofData* const* proofs, uint32_t n, const cm_pcs
   hipLaunchKernelGGL(k_verify_reduce, dim3((n + 63) / 64), dim3(64), 0, st, (const uint32_t*)d_flags.u32(), blob + red_off, n, d_out);
   CM_HIP(hipGetLastError());
   CM_HIP(hipEventRecord(tm.ev[2], st));
-  const uint32_t* res = (const uint32_t*)stage_download_async(d_out, 4 * (size_t)n, st);
+  // (detail: the flag words sit in front of the verdicts in one buffer, and come down with them)
+  const uint32_t* flags = detail ? (const uint32_t*)stage_download_async(d_flags.p, 4 * ((size_t)pl.n_flags + n), st) : nullptr;
+  const uint32_t* res = detail ? flags + pl.n_flags : (const uint32_t*)stage_download_async(d_out, 4 * (size_t)n, st);
   CM_HIP(hipEventRecord(tm.ev[3], st));
   CM_HIP(hipStreamSynchronize(st));
   for (int k = 0; k < 3; k++) {
@@ -586,6 +629,15 @@ void verify_many_device(const ProofData* const* proofs, uint32_t n, const cm_pcs
     int slot = pp.fail_slot;
     if (res[i] != 0xffffffffu) slot = (int)res[i];   // a raised flag is always in front of the slot that failed while planning
     if (slot >= 0) { out[i].check = pp.slots[slot].check; out[i].message = pp.slots[slot].message; }
+  }
+  if (!detail) return;
+  detail->assign(n, std::vector<VerifySlotDetail>());
+  for (uint32_t i = 0; i < n; i++) {
+    const ProofPlan& pp = plans[i];
+    for (size_t k = 0; k < pp.slots.size(); k++) {
+      const bool planned = (int)k == pp.fail_slot;
+      (*detail)[i].push_back(VerifySlotDetail{pp.slots[k].check, pp.slots[k].message, !planned, planned || flags[pp.flag_base + k] != 0});
+    }
   }
 }
 

@@ -23,7 +23,7 @@
 //                  absorbed per node, has children]; a node is [left, right, values]: a child is an index into the level below or
 //                  (bit 31) the blob offset of a hash witness, values point at queried values, column witness or (bit 31) scratch
 //   reduce jobs    per proof: [first flag, n_flags]
-// One download: per proof the lowest raised flag, or 0xffffffff.
+// One download: per proof the lowest raised flag, or 0xffffffff (cm_verify_many_detail: the flag words in front of them as well).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -37,11 +37,24 @@ struct VerifyOutcome {
   int32_t check = 0;     // CM_VERIFY_* of the failed check, 0 = accepted
   std::string message;   // the host verifier's string, "" = accepted
 };
-// out[i] = the verdict on proofs[i]; throws CmError for everything that is not a verdict (no device: code 3)
-void verify_many_device(const ProofData* const* proofs, uint32_t n, const cm_pcs_config& cfg, std::vector<VerifyOutcome>& out, hipStream_t st);
+// one slot of a proof's plan as the batch left it (cm_verify_many_detail)
+struct VerifySlotDetail {
+  int32_t check = 0;       // CM_VERIFY_* id
+  std::string message;     // what the host verifier says when this check fails
+  bool on_device = false;  // decided by a kernel (owns a flag word); false: failed while planning
+  bool raised = false;     // the flag word was set (or the slot failed while planning)
+};
+// out[i] = the verdict on proofs[i]; throws CmError for everything that is not a verdict (no device: code 3).
+// detail (optional): every proof's slots in the host verifier's order, read from the flag words of the same launches.
+void verify_many_device(const ProofData* const* proofs, uint32_t n, const cm_pcs_config& cfg, std::vector<VerifyOutcome>& out, hipStream_t st,
+                        std::vector<std::vector<VerifySlotDetail>>* detail = nullptr);
 // the calling thread's last verify_many_device: plan, upload, kernels, download (ms)
 void verify_many_timing(double ms[4]);
+// Host code, no GPU: the shapes of the plan verify_many_device would launch for each proof ALONE (read back from the tables the
+// planner built, so they are what the kernels would walk).  out[i].struct_size is kept.
+void verify_plan_stats(const ProofData* const* proofs, uint32_t n, const cm_pcs_config& cfg, cm_verify_stats* out);
 
 constexpr uint32_t VERIFY_MAX_LEVEL_NODES = 1024;   // two levels of a tree in 64 KB of LDS
+constexpr size_t verify_merkle_lds_bytes(uint32_t cap) { return 2 * (size_t)cap * 32; }   // k_verify_merkle: 2 levels x cap nodes x 8 words
 
 }  // namespace cm

@@ -872,6 +872,54 @@ def verify_many(proofs, cfg=None, lib=None, stream=0, checks=False):
     return out
 
 
+class VerifyStatsC(C.Structure):
+    """cm_verify_stats: the shapes of one proof's device-verifier plan"""
+    _fields_ = [("struct_size", C.c_uint32), ("early_check", C.c_int32), ("n_answer_jobs", C.c_uint32), ("max_batch_entries", C.c_uint32),
+                ("max_first_pairs", C.c_uint32), ("max_inner_pairs", C.c_uint32), ("max_level_nodes", C.c_uint32),
+                ("merkle_lds_bytes", C.c_uint32), ("n_tree_jobs", C.c_uint32), ("n_slots", C.c_uint32),
+                ("blob_words", C.c_uint64), ("scratch_words", C.c_uint64)]
+
+
+class VerifySlotC(C.Structure):
+    """cm_verify_slot: one check of one proof as cm_verify_many_detail left it"""
+    _fields_ = [("check", C.c_int32), ("on_device", C.c_uint32), ("raised", C.c_uint32), ("message", C.c_char * 116)]
+
+
+def verify_plan_stats(proofs, cfg=None, lib=None):
+    """cm_verify_plan_stats (host code, no GPU): per proof a dict of the shapes cm_verify_many's plan has for it alone"""
+    L = lib or proofs[0].L
+    n = len(proofs)
+    out = (VerifyStatsC * max(n, 1))()
+    for s in out:
+        s.struct_size = C.sizeof(VerifyStatsC)
+    rc = L.cm_verify_plan_stats(_proof_handles(proofs), C.c_uint32(n), _cfg(cfg), out)
+    if rc:
+        raise _lib_error(L, rc)
+    return [{name: getattr(s, name) for name, _ in VerifyStatsC._fields_[1:]} for s in out[:n]]
+
+
+def verify_many_detail(proofs, cfg=None, lib=None, stream=0):
+    """cm_verify_many_detail (GPU): per proof ((status, message, check), [(check, message, on_device, raised)]) — cm_verify_many's
+    verdict and every slot of the proof in the host verifier's order, from the same launches."""
+    L = lib or proofs[0].L
+    n = len(proofs)
+    res = (VerifyResultC * max(n, 1))()
+    first = (C.c_uint32 * (n + 1))()
+    cap = 64 * max(n, 1)
+    while True:
+        slots = (VerifySlotC * cap)()
+        rc = L.cm_verify_many_detail(_proof_handles(proofs), C.c_uint32(n), _cfg(cfg), res, slots, C.c_uint32(cap), first, C.c_uint64(stream))
+        if rc == 1 and first[n] > cap:
+            cap = first[n]
+            continue
+        break
+    if rc not in (0, 11):
+        raise _lib_error(L, rc)
+    return [((r.status, r.message.decode(errors="replace"), r.check),
+             [(s.check, s.message.decode(errors="replace"), bool(s.on_device), bool(s.raised)) for s in slots[first[i]:first[i + 1]]])
+            for i, r in enumerate(res[:n])]
+
+
 def verify_many_timing(lib=None):
     """cm_verify_many_timing: where the calling thread's last cm_verify_many spent its time (ms)"""
     L = lib or load_library()
@@ -896,6 +944,8 @@ Backend.run_begin = lambda self, initial_memory, initial_heap, ranges: Run(self,
 Backend.prove_run = lambda self, host_segments, inflight=3, cfg=None: prove_run(self, host_segments, inflight, cfg)
 Backend.verify_run = lambda self, proofs, cfg=None, device=False: verify_run(proofs, cfg, self.L, device)
 Backend.verify_many = lambda self, proofs, cfg=None: verify_many(proofs, cfg, self.L)
+Backend.verify_many_detail = lambda self, proofs, cfg=None: verify_many_detail(proofs, cfg, self.L)
+Backend.verify_plan_stats = lambda self, proofs, cfg=None: verify_plan_stats(proofs, cfg, self.L)
 
 
 # ---- device-memory accounting, estimate and budget (include/cairom_hip.h, revision 9) --------------------------

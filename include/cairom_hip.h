@@ -49,7 +49,9 @@
  *    cm_proof_program_id, cm_program_ids, cm_proofs_program_ids, cm_run_statement_of.
  *    Still 10 (additive: seven new functions, one view struct and one opaque handle, nothing moved): cm_mem_transition,
  *    cm_mem_transition_view, cm_input_write_set, cm_input_open_transition, cm_mem_transition_get, cm_mem_transition_free,
- *    cm_verify_memory_transition, cm_verify_memory_transition_host, cm_prove_run_transitions. */
+ *    cm_verify_memory_transition, cm_verify_memory_transition_host, cm_prove_run_transitions.
+ *    Still 10 (additive: one host-only query, one entry point, two structs): cm_verify_stats, cm_verify_plan_stats, cm_verify_slot,
+ *    cm_verify_many_detail. */
 #define CM_ABI_REVISION 10
 
 #ifdef __cplusplus
@@ -666,6 +668,38 @@ int32_t cm_verify_run_device(const cm_proof* const* proofs, uint32_t n, const cm
 /* Where the calling thread's last cm_verify_many / cm_verify_run_device spent its time, in milliseconds: 0 host planning,
  * 1 upload, 2 kernels, 3 download of the result words (1-3 from events on the stream). */
 int32_t cm_verify_many_timing(double ms[4]);
+/* The shapes of the plan cm_verify_many would launch for each proof ALONE, read back from the tables its planner built (host
+ * code, works without a GPU; the tests read it to prove that a config reaches a kernel's second stride trip or the LDS limit).
+ * Set out[i].struct_size = sizeof(cm_verify_stats) before the call.  A proof decided in front of the queries reports its
+ * CM_VERIFY_* id in early_check and zeros elsewhere.  A proof wider than the device limit still gets its stats: the refusal
+ * stays with cm_verify_many. */
+typedef struct cm_verify_stats {
+  uint32_t struct_size;
+  int32_t  early_check;        /* 0, or the CM_VERIFY_* id of the check that failed in front of the queries */
+  uint32_t n_answer_jobs;      /* workgroups of the answers kernel: one per (size group, query row) */
+  uint32_t max_batch_entries;  /* the largest number of entries in one sample batch */
+  uint32_t max_first_pairs;    /* the largest pair count of a first-layer size group */
+  uint32_t max_inner_pairs;    /* the largest pair count of an inner FRI layer */
+  uint32_t max_level_nodes;    /* the widest level of any tree, in nodes */
+  uint32_t merkle_lds_bytes;   /* dynamic LDS the Merkle launch would ask for: 2 * max_level_nodes * 32 */
+  uint32_t n_tree_jobs;        /* workgroups of the Merkle kernel: one per tree */
+  uint32_t n_slots;            /* checks of the query phase, planned ones included */
+  uint64_t blob_words, scratch_words;
+} cm_verify_stats;
+int32_t cm_verify_plan_stats(const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected, cm_verify_stats* out);
+/* cm_verify_many — the same plan, the same launches, the same verdicts in results (may be NULL) — that also hands back every
+ * proof's slots in the host verifier's order: the slots of proof i are slots[slot_first[i] .. slot_first[i + 1]) (slot_first
+ * has n + 1 entries and is filled whenever the batch ran; a proof decided in front of the queries has none).  When
+ * slot_first[n] > cap_slots nothing is written to slots and the status is 1: call again with that many.  One more download than cm_verify_many: the flag words next to the verdicts.
+ * The call's status and cm_last_error() are cm_verify_many's. */
+typedef struct cm_verify_slot {
+  int32_t  check;        /* CM_VERIFY_* id of this slot's check */
+  uint32_t on_device;    /* 1: a kernel decides it (a tree's root, the last layer's evaluations); 0: it failed while planning */
+  uint32_t raised;       /* 1: this check failed — on its own, whatever the slots in front of it say */
+  char     message[116]; /* what the host verifier says when this check is the first to fail, NUL-terminated */
+} cm_verify_slot;
+int32_t cm_verify_many_detail(const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected, cm_verify_result* results,
+                              cm_verify_slot* slots, uint32_t cap_slots, uint32_t* slot_first, cm_stream_t s);
 /* (Checking a whole run BEFORE proving it — cm_link_diff, cm_check_chain, cm_check_run — is declared behind the relation tracker
  * below: its records embed cm_check_report.) */
 /* Copy a device-resident ProverInput back (tests: device adapter vs host adapter). */

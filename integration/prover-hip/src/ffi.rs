@@ -263,6 +263,32 @@ pub struct cm_verify_result {
     pub check: i32,
     pub message: [c_char; 160],
 }
+/// The shapes of the plan `cm_verify_many` would launch for one proof (`cm_verify_plan_stats`); set `struct_size` before the call
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct cm_verify_stats {
+    pub struct_size: u32,
+    pub early_check: i32,
+    pub n_answer_jobs: u32,
+    pub max_batch_entries: u32,
+    pub max_first_pairs: u32,
+    pub max_inner_pairs: u32,
+    pub max_level_nodes: u32,
+    pub merkle_lds_bytes: u32,
+    pub n_tree_jobs: u32,
+    pub n_slots: u32,
+    pub blob_words: u64,
+    pub scratch_words: u64,
+}
+/// One check of one proof as `cm_verify_many_detail` left it
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct cm_verify_slot {
+    pub check: i32,
+    pub on_device: u32,
+    pub raised: u32,
+    pub message: [c_char; 116],
+}
 /// A proof's public data (public_data.rs:192-227); set `struct_size` before the call
 #[repr(C)]
 pub struct cm_public_data {
@@ -488,6 +514,9 @@ unsafe extern "C" {
     pub fn cm_verify_many(proofs: *const *const cm_proof, n: u32, expected: *const cm_pcs_config, results: *mut cm_verify_result, s: cm_stream_t) -> i32;
     pub fn cm_verify_run_device(proofs: *const *const cm_proof, n: u32, expected: *const cm_pcs_config) -> i32;
     pub fn cm_verify_many_timing(ms: *mut f64) -> i32;
+    pub fn cm_verify_plan_stats(proofs: *const *const cm_proof, n: u32, expected: *const cm_pcs_config, out: *mut cm_verify_stats) -> i32;
+    pub fn cm_verify_many_detail(proofs: *const *const cm_proof, n: u32, expected: *const cm_pcs_config, results: *mut cm_verify_result,
+                                 slots: *mut cm_verify_slot, cap_slots: u32, slot_first: *mut u32, s: cm_stream_t) -> i32;
     pub fn cm_host_segment_end_lengths(h: *const cm_host_segment, n_memory_end: *mut u64, n_heap_end: *mut u64) -> i32;
     pub fn cm_set_preprocessed_cache(on: i32) -> i32;
     pub fn cm_set_twiddle_cache(on: i32) -> i32;

@@ -14,7 +14,7 @@ from tests.verify_many_util import hand_flips, host_verify_words, proof_from_wor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HDR = open(os.path.join(ROOT, "include", "cairom_hip.h")).read()
-NEW = ["cm_verify_many", "cm_verify_run_device", "cm_verify_many_timing"]
+NEW = ["cm_verify_many", "cm_verify_run_device", "cm_verify_many_timing", "cm_verify_plan_stats", "cm_verify_many_detail"]
 # the host verifier's order (cairo_m_amd/csrc/verifier_common.hpp verify_prelude, then verifier.hip verify_proof)
 ORDER = ["STRUCTURE", "POW_INTERACTION", "LOGUP_SUM", "OODS", "FRI_STRUCTURE", "POW", "MERKLE", "QUERIED_VALUES", "FRI_FIRST_EVALS",
          "FRI_FIRST_COMMITMENT", "FRI_INNER_EVALS", "FRI_INNER_COMMITMENT", "FRI_LAST_EVALS"]
