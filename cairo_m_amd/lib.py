@@ -2024,9 +2024,70 @@ def follow_run(proofs, transitions, lib=None, device=True):
     return out
 
 
+def _transition_view(t):
+    """(a filled cm_mem_transition_view over t's arrays, the arrays to keep alive)"""
+    a, s = t.addresses, t.siblings
+    old, new = t.old_values.reshape(-1), t.new_values.reshape(-1)
+    if old.size != 4 * a.size or new.size != 4 * a.size:
+        raise ValueError(f"{old.size} old and {new.size} new value words for a transition of {a.size} cells")
+    v = MemTransitionViewC()
+    v.struct_size = C.sizeof(MemTransitionViewC)
+    v.root_before, v.root_after, v.n, v.n_siblings, v.n_zero_only = t.root_before, t.root_after, a.size, s.size, t.n_zero_only
+    for name, x in (("addresses", a), ("old_values", old), ("new_values", new), ("siblings", s)):
+        if x.size:
+            setattr(v, name, _p(x))
+    return v, (a, old, new, s)
+
+
+def compose_transitions(transitions, lib=None, device=True):
+    """cm_compose_transitions -> MemTransition: the chain transitions[0] -> ... -> transitions[-1] as ONE transition from the first
+    root before to the last root after over the union of their cells, from the records alone (device=True: on the GPU, else in
+    host code; the same bytes).  Nothing is hashed: the result is valid if every part is and the roots chain.  Raises CmError
+    (with .status and .message) for input that is detectably broken."""
+    L = lib or load_library()
+    transitions = list(transitions)
+    views = (MemTransitionViewC * max(len(transitions), 1))()
+    keep = []
+    for i, t in enumerate(transitions):
+        views[i], k = _transition_view(t)
+        keep.append(k)
+    h = C.c_void_p()
+    rc = L.cm_compose_transitions(views, C.c_uint32(len(transitions)), C.c_uint32(1 if device else 0), C.byref(h))
+    if rc:
+        err = _lib_error(L, rc)
+        err.status, err.message = rc, str(err).split(": ", 1)[1]
+        raise err
+    return _take_transition(L, h)
+
+
+def run_transition(proofs, transitions, lib=None, device=True):
+    """What a client that wants only the run's first and last memory does with a run's transitions: compose them into one, require
+    its roots to be proof 0's initial_root and the last proof's final_root, and verify it (device=True: composed and verified on
+    the GPU, else in host code).  Returns the composed MemTransition; raises CmError saying which of the three failed."""
+    L = lib or proofs[0].L
+    try:
+        t = compose_transitions(transitions, L, device)
+    except CmError as e:
+        raise CmError(f"run_transition: the transitions do not compose: {e}") from e
+    for side, want in (("before", proofs[0].public_data()["initial_root"]), ("after", proofs[-1].public_data()["final_root"])):
+        got = getattr(t, "root_" + side)
+        if got != want:
+            which = "first proof's initial_root" if side == "before" else "last proof's final_root"
+            raise CmError(f"run_transition: the composed transition's root {side} is {got}, the {which} is {want}")
+    if device:
+        ok, why = verify_transition(t, L), "the composed transition does not verify on the GPU"
+    else:
+        rc, why = verify_transition_host(t, L)
+        ok = rc == 0
+    if not ok:
+        raise CmError(f"run_transition: {why}")
+    return t
+
+
 Backend.write_set = _backend_write_set
 Backend.open_transition = _backend_open_transition
 Backend.verify_transition = lambda self, t, stream=0, with_roots=False: verify_transition(t, self.L, stream, with_roots)
+Backend.compose_transitions = lambda self, transitions, device=True: compose_transitions(transitions, self.L, device)
 
 
 # ---- program identity and the statement of a run (include/cairom_hip.h: cm_program_id_entries .. cm_run_statement_of) ----------

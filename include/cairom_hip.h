@@ -51,7 +51,8 @@
  *    cm_mem_transition_view, cm_input_write_set, cm_input_open_transition, cm_mem_transition_get, cm_mem_transition_free,
  *    cm_verify_memory_transition, cm_verify_memory_transition_host, cm_prove_run_transitions.
  *    Still 10 (additive: one host-only query, one entry point, two structs): cm_verify_stats, cm_verify_plan_stats, cm_verify_slot,
- *    cm_verify_many_detail. */
+ *    cm_verify_many_detail.
+ *    Still 10 (additive: one new function, no struct): cm_compose_transitions. */
 #define CM_ABI_REVISION 10
 
 #ifdef __cplusplus
@@ -1143,6 +1144,46 @@ int32_t cm_verify_memory_transition_host(uint32_t root_before, uint32_t root_aft
                                          const uint32_t* new_values, const uint32_t* siblings, uint32_t n_siblings);
 int32_t cm_prove_run_transitions(cm_run* r, const cm_run_segment* const* segs, uint32_t n, const cm_pcs_config* config, uint32_t inflight,
                                  cm_proof** outs, cm_mem_transition** transitions);
+/* Composed transitions (additive to revision 10: one new function, no new struct).  cm_compose_transitions makes a chain of
+ * transitions R0 -> R1 -> ... -> Rk into the ONE transition R0 -> Rk over the union U of their cells, from the records alone: no
+ * memory image, no tree and no hash is needed, so a relay that holds only the records can do it.  parts[i] is a filled
+ * cm_mem_transition_view (from cm_mem_transition_get, or built over bytes that arrived over a wire; struct_size set).  The result
+ * is an ordinary transition: read it with cm_mem_transition_get, free it with cm_mem_transition_free, check it with
+ * cm_verify_memory_transition or cm_verify_memory_transition_host; its wire format is the existing one.
+ * The statement.  addresses = the strictly ascending union U of all parts' addresses; old_values[u] = the old value of u in the
+ * first part that holds u; new_values[u] = the new value of u in the last part that holds u (a cell some part writes and a later
+ * part writes back stays in U with old == new: a superset of the write set is valid, and dropping the cell would need hashes no
+ * record holds); siblings = the canonical record of U (cm_mem_set_plan's order and counts); root_before = parts[0].root_before,
+ * root_after = parts[n_parts - 1].root_after; n_zero_only = the sum of the parts'.  Parts with n == 0 take part in the chain and
+ * add nothing; when every part is empty the result has n == 0 and no words; one part composes to itself, byte for byte.
+ * Why the records suffice.  S_k(U) = the distinct u >> k.  The record of U needs node(28 - k, x ^ 1) exactly when x is in S_k(U)
+ * and x ^ 1 is not.  Then no cell of U lies under x ^ 1, and since every part is valid the memories of the chain agree outside each
+ * part's set: that subtree has the same hash under every root of the chain.  The first part r that holds the lowest address of U
+ * under x has x in S_k(a_r) and not x ^ 1 (S_k(a_r) is a subset of S_k(U)), so its record holds that very word, and the word is
+ * copied from there.  A word that a part holds for a subtree containing a cell of U may be stale; such a word is never needed.
+ * The guarantee.  The call hashes nothing.  IF every part is a valid transition and the roots chain, the result is a valid
+ * transition from parts[0].root_before to parts[n_parts - 1].root_after.  A caller that does not trust its source verifies the
+ * result, or the parts.  The same call gives the same bytes, and device 0 and device 1 give the same bytes.
+ * device == 0 composes in host code and needs no GPU: a stable merge of the sorted lists, then cm_mem_set_plan's walk over every
+ * part and over U.  device == 1 composes on the GPU on the calling thread's stream and pool, which the call waits for: one upload
+ * of the concatenated parts; a stable 28-bit radix sort of the N addresses (equal addresses stay in chain order); k_compose_heads
+ * (head flags and the seam check), one scan for the ranks, one small round trip for |U|; k_compose_cells (U, the values, the source
+ * part of every cell); the set opener's flag pass and scan over U, ONE segmented flag pass and ONE scan over the 28 N pairs of all
+ * parts; k_compose_gather, one lane per pair of U, every word written by exactly one lane without atomics; one download (one more
+ * trip per further 8 MB); the device's word count is checked against cm_mem_set_plan(U).  The number of launches and round trips
+ * does not depend on n_parts.  Temporaries: flags and scans, 448 bytes per cell of N plus of |U|, dominate; with the sort's
+ * buffers, the uploaded parts and the result the cap of 2^20 cells bounds a call near 1 GB (derived, not measured).  Every
+ * device buffer is back in the pool when the call returns.
+ * Refusals, the same status and message on both paths; *out is NULL on every failure.  device == 1 without a GPU: cm_init's
+ * status (3), returned before any argument is looked at.  Status 1, cm_last_error() naming the cause: device > 1; a NULL `parts`
+ * or `out`; n_parts == 0 or n_parts > 2^16; a part with a short struct_size; a part with a NULL array where n > 0 or n_siblings
+ * > 0; the parts' n summing to more than 2^20 ("compose in groups": the operation is associative, so a caller can always split)
+ * — all before any address is read.  Status 11 (rejected), parts in ascending order: "part <i>: " and the set verifier's own
+ * words for addresses that are not strictly ascending or not below 2^28; "part <i>: <m> sibling words where the addresses need
+ * <m'>" (established before any word of the part is read); "part <i> starts at root <x>, part <i-1> ended at root <y>"; then the
+ * seam check: where a cell occurs in part j and next in part i > j, old_i must equal new_j, else "cell <a>: part <i> reads a value
+ * part <j> did not leave" for the lowest such address and, for it, the lowest i. */
+int32_t cm_compose_transitions(const cm_mem_transition_view* parts, uint32_t n_parts, uint32_t device, cm_mem_transition** out);
 /* ---- program identity and the statement of a run (additive to revision 10) ---------------------------------------------------
  * Which program a proof is about, as one 31-bit word: Proof::program_id() of the reference (crates/prover/src/lib.rs:75-97), the
  * Poseidon2 root of the partial memory tree that holds only the proof's public program cells.  An "entry" is the seven-word record

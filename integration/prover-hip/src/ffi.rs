@@ -575,6 +575,7 @@ unsafe extern "C" {
     pub fn cm_verify_memory_transition(root_before: u32, root_after: u32, addresses: *const u32, n: u64, old_values: *const u32, new_values: *const u32, siblings: *const u32, n_siblings: u32, ok: *mut u8, computed: *mut u32, s: cm_stream_t) -> i32;
     pub fn cm_verify_memory_transition_host(root_before: u32, root_after: u32, addresses: *const u32, n: u64, old_values: *const u32, new_values: *const u32, siblings: *const u32, n_siblings: u32) -> i32;
     pub fn cm_prove_run_transitions(r: *mut cm_run, segs: *const *const cm_run_segment, n: u32, config: *const cm_pcs_config, inflight: u32, outs: *mut *mut cm_proof, transitions: *mut *mut cm_mem_transition) -> i32;
+    pub fn cm_compose_transitions(parts: *const cm_mem_transition_view, n_parts: u32, device: u32, out: *mut *mut cm_mem_transition) -> i32;
     pub fn cm_program_id_entries(entries: *const u32, n: u64, id: *mut u32) -> i32;
     pub fn cm_proof_program_id(p: *const cm_proof, id: *mut u32) -> i32;
     pub fn cm_program_ids(entries: *const *const u32, n_entries: *const u64, n: u32, ids: *mut u32, status: *mut i32, s: cm_stream_t) -> i32;

@@ -641,6 +641,11 @@ pub fn open_transition(input: *const cm_device_input, addresses: Option<&[u32]>)
     if rc != 0 {
         return Err(last_error());
     }
+    take_transition(h)
+}
+
+/// The arrays of a `cm_mem_transition` handle, copied; the handle is freed.
+fn take_transition(h: *mut cm_mem_transition) -> Result<MemTransition, String> {
     let mut v: cm_mem_transition_view = unsafe { std::mem::zeroed() };
     v.struct_size = std::mem::size_of::<cm_mem_transition_view>() as u32;
     let rc = unsafe { cm_mem_transition_get(h, &mut v) };
@@ -666,6 +671,41 @@ pub fn open_transition(input: *const cm_device_input, addresses: Option<&[u32]>)
     };
     unsafe { cm_mem_transition_free(h) };
     out
+}
+
+/// A chain of transitions `parts[0] -> ... -> parts[k-1]` composed into ONE transition from the first root before to the last root
+/// after over the union of their cells (`cm_compose_transitions`), from the records alone: `device` = false in host code (no GPU
+/// needed), true on the GPU; the same bytes.  Nothing is hashed: the result is valid if every part is and the roots chain, so a
+/// caller that does not trust its source verifies the result.  Input that is detectably broken (roots that do not chain, a seam
+/// whose old value is not the previous new value, bad addresses or word counts) is an `Err` naming the cause.
+pub fn compose_transitions(parts: &[MemTransition], device: bool) -> Result<MemTransition, String> {
+    if device {
+        ensure_init();
+    }
+    let mut views: Vec<cm_mem_transition_view> = Vec::with_capacity(parts.len());
+    for t in parts {
+        if t.old_values.len() != 4 * t.addresses.len() || t.new_values.len() != 4 * t.addresses.len() {
+            return Err(format!("{} old and {} new value words for a transition of {} cells", t.old_values.len(), t.new_values.len(), t.addresses.len()));
+        }
+        let mut v: cm_mem_transition_view = unsafe { std::mem::zeroed() };
+        v.struct_size = std::mem::size_of::<cm_mem_transition_view>() as u32;
+        v.root_before = t.root_before;
+        v.root_after = t.root_after;
+        v.n = t.addresses.len() as u32;
+        v.n_siblings = t.siblings.len() as u32;
+        v.n_zero_only = t.n_zero_only;
+        v.addresses = t.addresses.as_ptr();
+        v.old_values = t.old_values.as_ptr();
+        v.new_values = t.new_values.as_ptr();
+        v.siblings = t.siblings.as_ptr();
+        views.push(v);
+    }
+    let mut h: *mut cm_mem_transition = std::ptr::null_mut();
+    let rc = unsafe { cm_compose_transitions(views.as_ptr(), views.len() as u32, if device { 1 } else { 0 }, &mut h) };
+    if rc != 0 {
+        return Err(last_error());
+    }
+    take_transition(h)
 }
 
 /// A transition checked against its two roots on the GPU in one fold (`cm_verify_memory_transition`) -> (accepted, the two roots
