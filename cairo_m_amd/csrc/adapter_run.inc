@@ -376,6 +376,31 @@ void run_memory(Run& r, uint32_t* locals, uint64_t cap_l, uint64_t* n_l, uint32_
   if (want_h) CM_HIP(hipMemcpyAsync(heap, r.hi.p, (size_t)r.n_hi * 16, hipMemcpyDeviceToHost, st));
   CM_HIP(hipStreamSynchronize(st));
 }
+// The tree over the four leaves of each of `cells` cells, which `fill(idx, val, mult)` enqueues on st in ascending index order:
+// the device tree builder, one round trip for the tree's size and root, one wait behind its copy into a right-sized block (the
+// builder's is sized for 30 nodes per leaf: see run_tail).  For the image tree of a run and for cm_mem_image_create.
+void leaves_tree_build(uint64_t cells, const std::function<void(uint32_t*, uint32_t*, uint32_t*)>& fill, DevBuf& nodes_out, uint64_t& n_nodes_out,
+                       uint32_t& root_out, hipStream_t st) {
+  CM_CHECK(cells > 0 && cells <= (uint64_t)host::MAX_ADDRESS + 1, "image tree: no cells, or more than the address space");
+  const uint32_t cap = (uint32_t)(4 * cells);
+  TreeJob j;
+  for (int k = 0; k < 3; k++) j.a[k].alloc((size_t)cap * 4);
+  j.state.alloc(sizeof(TreeState));
+  const TreeState s0{cap, 0};
+  stage_upload(j.state.p, &s0, sizeof(s0), st);
+  fill(j.a[0].u32(), j.a[1].u32(), j.a[2].u32());
+  DevBuf nodes;
+  uint32_t* const pin3 = pinned_words() + PIN_LAST_LAYER + 56;
+  partial_merkle_tree_enqueue(j, cap, nodes, pin3, st);
+  CM_HIP(hipStreamSynchronize(st));
+  CM_CHECK(pin3[0] == 1, "partial merkle tree: did not converge to one root");
+  const uint64_t n_nodes = pin3[1];
+  const uint32_t root = pin3[2];
+  DevBuf exact(n_nodes * sizeof(cm_merkle_node) + 4);
+  CM_HIP(hipMemcpyAsync(exact.p, nodes.p, n_nodes * sizeof(cm_merkle_node), hipMemcpyDeviceToDevice, st));
+  CM_HIP(hipStreamSynchronize(st));
+  nodes_out = std::move(exact); n_nodes_out = n_nodes; root_out = root;
+}
 // Openings under the root of the image as it is now (mem_open.hip): the leaves of every image cell (k_image_leaves) through the
 // device tree builder on first use — one round trip for the tree's size and root, one wait behind its copy into a right-sized
 // block — then one round trip per call for the records.
@@ -384,24 +409,8 @@ static void run_image_tree(Run& r, const char* who, hipStream_t st) {
   CM_CHECK(cells > 0, std::string(who) + ": the image is empty: there is no tree to open");
   if (!r.img_tree.p) {
     r.wait_on(st);   // the last advance may have been enqueued from another thread's stream
-    const uint32_t cap = (uint32_t)(4 * cells);
-    TreeJob j;
-    for (int k = 0; k < 3; k++) j.a[k].alloc((size_t)cap * 4);
-    j.state.alloc(sizeof(TreeState));
-    const TreeState s0{cap, 0};
-    stage_upload(j.state.p, &s0, sizeof(s0), st);
-    image_leaves_enqueue(r.lo.u32(), r.n_lo, r.hi.u32(), r.n_hi, j.a[0].u32(), j.a[1].u32(), j.a[2].u32(), st);
-    DevBuf nodes;
-    uint32_t* const pin3 = pinned_words() + PIN_LAST_LAYER + 56;
-    partial_merkle_tree_enqueue(j, cap, nodes, pin3, st);
-    CM_HIP(hipStreamSynchronize(st));
-    CM_CHECK(pin3[0] == 1, "partial merkle tree: did not converge to one root");
-    const uint64_t n_nodes = pin3[1];
-    const uint32_t img_root = pin3[2];
-    DevBuf exact(n_nodes * sizeof(cm_merkle_node) + 4);   // (the builder's block is sized for 30 nodes per leaf: see run_tail)
-    CM_HIP(hipMemcpyAsync(exact.p, nodes.p, n_nodes * sizeof(cm_merkle_node), hipMemcpyDeviceToDevice, st));
-    CM_HIP(hipStreamSynchronize(st));
-    r.img_tree = std::move(exact); r.n_img_tree = n_nodes; r.img_root = img_root;
+    leaves_tree_build(cells, [&](uint32_t* idx, uint32_t* val, uint32_t* mult) { image_leaves_enqueue(r.lo.u32(), r.n_lo, r.hi.u32(), r.n_hi, idx, val, mult, st); },
+                      r.img_tree, r.n_img_tree, r.img_root, st);
   }
 }
 void run_open_memory(Run& r, const uint32_t* addresses, uint64_t n, cm_mem_opening* out, uint32_t* root) {

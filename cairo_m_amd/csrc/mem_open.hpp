@@ -9,6 +9,10 @@ namespace cm {
 // order, 4 * (n_lo + n_hi) of them, for partial_merkle_tree_enqueue's device-pointer form.  Enqueued; waits for nothing.
 void image_leaves_enqueue(const uint32_t* lo, uint32_t n_lo, const uint32_t* hi, uint32_t n_hi, uint32_t* idx, uint32_t* val, uint32_t* mult,
                           hipStream_t st);
+// nodes_out (exact size), n_nodes_out and root_out = the tree over 4 * cells leaves that `fill(idx, val, mult)` enqueues on st in
+// ascending index order, through the device tree builder (adapter_run.inc); two waits on `st`
+void leaves_tree_build(uint64_t cells, const std::function<void(uint32_t*, uint32_t*, uint32_t*)>& fill, DevBuf& nodes_out, uint64_t& n_nodes_out,
+                       uint32_t& root_out, hipStream_t st);
 // out[i] = the opening of addresses[i] under the tree whose node list (depth 30..1, ascending index inside a depth) is `nodes`:
 // one upload, two launches, one download on `st`, which is waited for.  The addresses are below 2^28 (the caller checked).
 void open_paths(const cm_merkle_node* nodes, uint64_t n_nodes, const uint32_t* addresses, uint64_t n, cm_mem_opening* out, hipStream_t st);

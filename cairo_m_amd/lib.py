@@ -2090,6 +2090,175 @@ Backend.verify_transition = lambda self, t, stream=0, with_roots=False: verify_t
 Backend.compose_transitions = lambda self, transitions, device=True: compose_transitions(transitions, self.L, device)
 
 
+# ---- followed memory (include/cairom_hip.h: cm_mem_image_create .. cm_mem_image_open_memory_set) --------------------------------
+class MemImageStatsC(C.Structure):
+    """cm_mem_image_stats"""
+    _fields_ = [("struct_size", C.c_uint32), ("device", C.c_uint32), ("n_cells", C.c_uint64), ("n_nodes", C.c_uint64), ("bytes", C.c_uint64)]
+
+
+def _raise_status(L, rc):
+    """CmError with .status and .message (the text behind "libcairom_hip status <rc>: ")"""
+    err = _lib_error(L, rc)
+    err.status, err.message = rc, str(err).split(": ", 1)[1]
+    raise err
+
+
+def _cell_values(values, n):
+    v = np.ascontiguousarray(values, dtype=np.uint32).reshape(-1)
+    if v.size != 4 * n:
+        raise ValueError(f"{v.size} value words for {n} cells")
+    return v if v.size else np.zeros(4, dtype=np.uint32)
+
+
+def _bare(self):
+    """A copy without sibling words: addresses, both value planes and the two roots, all a holder of the tree needs
+    (MemImage.apply_transition never reads the words)."""
+    return MemTransition(self.addresses.copy(), self.old_values.copy(), self.new_values.copy(), np.zeros(0, dtype=np.uint32), self.root_before,
+                         self.root_after, self.n_zero_only)
+
+
+MemTransition.bare = _bare
+MemTransition.nbytes_bare = property(lambda self: 20 * self.addresses.size, doc="what a follower needs: addresses and new values")
+
+
+class MemImage:
+    """cm_mem_image: a memory image with its partial Merkle tree, on the GPU (device=True) or in host memory, independent of any
+    prover handle.  It absorbs updates by re-hashing only the dirty paths, checks itself against the roots it is given and opens
+    cells under its current root.  A refused update raises CmError (.status, .message) and leaves the image as it was."""
+
+    def __init__(self, lib, handle, device):
+        self.L, self.h, self.device = lib, handle, bool(device)
+
+    @classmethod
+    def from_cells(cls, cells, lib=None, device=True):
+        """cells: [(address, v0, v1, v2, v3)] in any order, addresses distinct"""
+        L = lib or load_library()
+        c = np.array(sorted(tuple(int(x) for x in r) for r in cells), dtype=np.uint64).reshape(-1, 5)
+        if c.size and int(c.max()) >= 1 << 32:
+            raise ValueError("a word does not fit 32 bits")
+        a = np.ascontiguousarray(c[:, 0].astype(np.uint32))
+        v = np.ascontiguousarray(c[:, 1:].astype(np.uint32)).reshape(-1)
+        pad = lambda x: x if x.size else np.zeros(4, dtype=np.uint32)
+        h = C.c_void_p()
+        rc = L.cm_mem_image_create(_p(pad(a)), _p(pad(v)), C.c_uint64(a.size), C.c_uint32(1 if device else 0), C.byref(h))
+        if rc:
+            _raise_status(L, rc)
+        return cls(L, h, device)
+
+    @classmethod
+    def from_run(cls, run, device=True):
+        """the image of a Run as it is now (Run.memory()): locals dense from 0, heap cell i at 2^28 - 1 - i"""
+        lo, hi = run.memory()
+        cells = [(a,) + tuple(int(x) for x in lo[a]) for a in range(lo.shape[0])]
+        cells += [(ADDRESS_SPACE - 1 - i,) + tuple(int(x) for x in hi[i]) for i in range(hi.shape[0])]
+        return cls.from_cells(cells, run.L, device)
+
+    def _ck(self, rc):
+        if rc:
+            _raise_status(self.L, rc)
+
+    @property
+    def root(self):
+        r = C.c_uint32(0)
+        self._ck(self.L.cm_mem_image_root(self.h, C.byref(r)))
+        return r.value
+
+    def stats(self):
+        """{"device", "n_cells", "n_nodes", "bytes"}"""
+        s = MemImageStatsC()
+        s.struct_size = C.sizeof(MemImageStatsC)
+        self._ck(self.L.cm_mem_image_stats_get(self.h, C.byref(s)))
+        return {"device": bool(s.device), "n_cells": s.n_cells, "n_nodes": s.n_nodes, "bytes": s.bytes}
+
+    @property
+    def n_cells(self):
+        return self.stats()["n_cells"]
+
+    def read(self, addresses):
+        """values (n, 4) of `addresses`, any order, repeats allowed; an absent cell reads as zeros"""
+        a = _set_addresses(addresses)
+        v = np.zeros((a.size, 4), dtype=np.uint32)
+        if a.size:
+            self._ck(self.L.cm_mem_image_read(self.h, _p(a), C.c_uint64(a.size), _p(v)))
+        return v
+
+    def cells(self):
+        """(addresses ascending, values (n, 4)) of every cell the image holds"""
+        n = self.n_cells
+        a, v, total = np.zeros(max(n, 1), dtype=np.uint32), np.zeros((max(n, 1), 4), dtype=np.uint32), C.c_uint64(0)
+        self._ck(self.L.cm_mem_image_cells(self.h, _p(a), _p(v), C.c_uint64(n), C.byref(total)))
+        return a[:n].copy(), v[:n].copy()
+
+    def nodes(self):
+        """the node list (n, 8): index, depth, left, right, parent and three multiplicity words that enter no hash"""
+        n = self.stats()["n_nodes"]
+        out, total = np.zeros((max(n, 1), 8), dtype=np.uint32), C.c_uint64(0)
+        self._ck(self.L.cm_mem_image_nodes(self.h, out.ctypes.data_as(C.c_void_p), C.c_uint64(n), C.byref(total)))
+        return out[:n].copy()
+
+    def apply(self, addresses, new_values, old_values=None, root_before=None, root_after=None, record=False):
+        """cm_mem_image_apply: write new_values (n, 4) to the strictly ascending `addresses`.  old_values, root_before and
+        root_after are checked when given.  Returns the new root, or (root, MemTransition) with record=True: the full transition
+        over the addresses, its old values and sibling words read from the tree before the update."""
+        a = _set_addresses(addresses)
+        nv = _cell_values(new_values, a.size)
+        ov = None if old_values is None else _cell_values(old_values, a.size)
+        word = lambda x: None if x is None else C.byref(C.c_uint32(int(x)))
+        root, h = C.c_uint32(0), C.c_void_p()
+        pad = a if a.size else np.zeros(1, dtype=np.uint32)
+        self._ck(self.L.cm_mem_image_apply(self.h, _p(pad), _p(nv), C.c_uint64(a.size), None if ov is None else _p(ov), word(root_before),
+                                           word(root_after), C.byref(root), C.byref(h) if record else None))
+        return (root.value, _take_transition(self.L, h)) if record else root.value
+
+    def apply_transition(self, t, record=False):
+        """cm_mem_image_apply_transition: apply with t's addresses, both value planes and both roots; t's sibling words are never
+        read (MemTransition.bare()).  Returns the new root, or (root, the full MemTransition) with record=True."""
+        view, keep = _transition_view(t)
+        h = C.c_void_p()
+        self._ck(self.L.cm_mem_image_apply_transition(self.h, C.byref(view), C.byref(h) if record else None))
+        return (self.root, _take_transition(self.L, h)) if record else self.root
+
+    def open(self, addresses):
+        """cm_mem_image_open_memory -> ([MemOpening], root): under the image's current root (device images)"""
+        return _open_call(self.L, self.L.cm_mem_image_open_memory, (self.h,), addresses)
+
+    def open_range(self, start, n):
+        """cm_mem_image_open_memory_range -> (MemRangeOpening, values (n, 4), root)"""
+        return _range_call(self.L, self.L.cm_mem_image_open_memory_range, (self.h,), start, n)
+
+    def open_set(self, addresses):
+        """cm_mem_image_open_memory_set -> (MemSetOpening, root); any order, repeats allowed"""
+        return _set_call(self.L, self.L.cm_mem_image_open_memory_set, (self.h,), addresses)
+
+    def free(self):
+        if self.h:
+            self.L.cm_mem_image_free(self.h)
+            self.h = None
+
+
+def follow_run_image(proofs, updates, image):
+    """What a follower that keeps its own copy of the memory does with a run: update i — a MemTransition, bare or full, or an
+    (addresses, new_values) pair — is applied to `image` from proof i's public initial_root to its final_root.  Raises CmError
+    naming the first segment that does not fit; the image then stays at the last good segment.  Returns the image's root."""
+    if len(proofs) != len(updates):
+        raise CmError(f"follow_run_image: {len(updates)} updates for {len(proofs)} proofs")
+    for i, (p, u) in enumerate(zip(proofs, updates)):
+        d = p.public_data()
+        try:
+            if isinstance(u, MemTransition):
+                for side, want in (("before", d["initial_root"]), ("after", d["final_root"])):
+                    if getattr(u, "root_" + side) != want:
+                        raise CmError(f"the transition's root {side} is {getattr(u, 'root_' + side)}, the proof's is {want}")
+                image.apply_transition(u)
+            elif len(u[0]):
+                image.apply(u[0], u[1], root_before=d["initial_root"], root_after=d["final_root"])
+            else:
+                image.apply_transition(MemTransition([], [], [], [], d["initial_root"], d["final_root"]))
+        except CmError as e:
+            raise CmError(f"follow_run_image: segment {i}: {getattr(e, 'message', e)}") from e
+    return image.root
+
+
 # ---- program identity and the statement of a run (include/cairom_hip.h: cm_program_id_entries .. cm_run_statement_of) ----------
 class RunStatementC(C.Structure):
     """cm_run_statement"""

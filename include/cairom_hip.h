@@ -1184,6 +1184,87 @@ int32_t cm_prove_run_transitions(cm_run* r, const cm_run_segment* const* segs, u
  * seam check: where a cell occurs in part j and next in part i > j, old_i must equal new_j, else "cell <a>: part <i> reads a value
  * part <j> did not leave" for the lowest such address and, for it, the lowest i. */
 int32_t cm_compose_transitions(const cm_mem_transition_view* parts, uint32_t n_parts, uint32_t device, cm_mem_transition** out);
+/* ---- followed memory (additive to revision 10: new symbols and one struct, nothing moved) --------------------------------------
+ * The party between the prover and the light client: a follower (a bridge, an RPC node, a checkpoint service) that keeps its own
+ * copy of a run's memory and answers openings under the run's latest root.  cm_mem_image is that copy: a memory image with its
+ * partial Merkle tree, resident on the GPU (device == 1) or in host memory (device == 0, host code only, no GPU needed),
+ * independent of any prover handle.  It absorbs a segment's writes by re-hashing only the dirty paths, checks itself against the
+ * proof's roots, serves the three kinds of opening under its current root and re-emits a full transition from a bare update.
+ *
+ * The handle holds one list of cm_merkle_node records in the order every opener reads: depth 30 .. 1, ascending index inside a
+ * depth.  Only the first five words of a record are contract (index, depth, left_value, right_value, parent_value); the three
+ * multiplicity words enter no hash and are unspecified.  The cells are the list's depth-30 slice: a held cell a owns the
+ * records 4a and 4a + 2 there and the record 2a of depth 29, whatever its value, so a cell written to (0, 0, 0, 0) stays held
+ * with zeros, which hashes like an absent one.  Both modes give the same roots and the same node words 0 .. 4.
+ *
+ * cm_mem_image_create makes the image of n cells: addresses strictly ascending and below 2^28, value words below P, n at most
+ * 2^22 (the device tree builder's transient block is 3840 bytes per cell: 15 GiB at the limit; a device image may grow beyond
+ * it by updates).  n == 0 gives the empty image, whose root is default[0].  device == 1 builds the tree with the device tree
+ * builder (the leaves of every cell, then one launch group per depth), on the calling thread's stream and pool; device == 0
+ * folds the cells into the empty image in host code.  Status 1 for a bad argument, naming the first bad address or value word;
+ * device == 1 without a GPU is cm_init's status (3), returned before any argument is looked at.
+ * cm_mem_image_root, cm_mem_image_stats_get (set struct_size first) and cm_mem_image_free read and free the handle.
+ * cm_mem_image_read gathers the values of n addresses in any order, repeats allowed, an absent cell as zeros (at most 2^24 a
+ * call).  cm_mem_image_cells lists the whole image in ascending address order and cm_mem_image_nodes the node list: *n_total =
+ * all there are; *n_total > cap means truncated and is not an error (cm_input_write_set's contract).
+ *
+ * cm_mem_image_apply writes new_values to `addresses` (strictly ascending, below 2^28, 0 < n <= 2^20, as for a set opening).
+ * The checks run in this order, and the image is unchanged — root, nodes and cells byte for byte — unless all of them pass:
+ *   1. bad arguments: status 1 (a NULL img, addresses, new_values or root_out; n == 0; n > 2^20; addresses not ascending);
+ *   2. a new value word not below P: status 11, "memory image: new value word <j> of cell <a> is not below P";
+ *   3. root_before given and not the image's root: 11, "the image is at root <x>, the update starts from <y>";
+ *   4. old_values given and not the image's current values (an absent cell reads as zeros): 11, "cell <a> holds (..), the
+ *      update's old value is (..)" for the lowest such address;
+ *   5. the new root is computed;
+ *   6. root_after given and different: 11, "the image would hash to root <x>, not <y>".
+ * Then the new node list is committed: new addresses are inserted, held ones replaced.  *root_out receives the new root.
+ * record_out (may be NULL) receives an ordinary cm_mem_transition over the addresses: its old values and sibling words are read
+ * from the tree before the update, its new values are the given ones, its roots the ones seen; the transition verifiers accept
+ * it unchanged, so a follower that received 20 n bytes can serve the 36 n + 4 m byte record to light clients.
+ * The rule.  The update is the set fold with each sibling word taken from the image's own tree.  With S_k the distinct
+ * a[i] >> k, the dirty nodes of depth 28 - k are exactly S_k and the dirty pair records of that depth one per node of S_{k+1}:
+ * 3 n + sum_k |S_{k+1}| hashes, the set fold's count, whatever the size of the image.
+ * On the GPU (the calling thread's stream and pool): k_img_check, one lane per cell half, bisects the depth-30 slice for the
+ * current value and reports the lowest differing cell by an atomic minimum; k_img_cells, one lane per cell, writes the two
+ * depth-30 records and the depth-29 record from the new value alone; the set verifier's flag pass, scan and head scatter; then
+ * the steps of cm_mem_set_plan for the same addresses — k_img_level, one lane per parent while S_k is wider than 128 nodes, and
+ * k_img_tail, one workgroup, for the rest — where a child in S_k takes its new hash from the level below and any other child
+ * the old tree's word (the openers' lookup; a missing record is the depth's default hash).  The commit: k_img_rank bisects
+ * every dirty record's place in the old slice of its depth, one exclusive scan counts the inserts, k_img_merge moves old and
+ * dirty records into a new buffer in one launch and k_img_offsets updates the depth offsets.  Everything is enqueued before
+ * the call's one host round trip (one more for a record); the handle swaps buffers only behind check 6.  The number of
+ * launches does not depend on the size of the image.
+ * cm_mem_image_apply_transition is cm_mem_image_apply with t's addresses, both value planes and both roots; t->siblings is
+ * never read and may be NULL with n_siblings 0 (the "bare" transition: 20 n bytes and two roots).  t->n == 0 changes nothing
+ * and still checks the roots: "no cell changes, and root <x> is not root <y>".
+ * cm_mem_image_open_memory, _range and _set follow the contract of their cm_run_open_* twins (argument checks, an empty image
+ * is refused, *root is written) and are thin calls into the same openers over the image's node list.  Device images only: a
+ * host image refuses them with status 1 and says so.
+ * Threading: calls on one image are serialised by a mutex in the handle, as for cm_run; every call waits for its GPU work, so
+ * any thread may make the next one.  cm_mem_stats counts a device image while it lives. */
+typedef struct cm_mem_image cm_mem_image;
+typedef struct {
+  uint32_t struct_size;
+  uint32_t device;              /* 1: on the GPU, 0: in host memory */
+  uint64_t n_cells;
+  uint64_t n_nodes;
+  uint64_t bytes;               /* held by the handle: pool blocks (device) or the node vector's capacity (host) */
+} cm_mem_image_stats;           /* sizeof = 32 */
+int32_t cm_mem_image_create(const uint32_t* addresses, const uint32_t* values, uint64_t n, uint32_t device, cm_mem_image** out);
+int32_t cm_mem_image_free(cm_mem_image* img);
+int32_t cm_mem_image_root(cm_mem_image* img, uint32_t* root);
+int32_t cm_mem_image_stats_get(cm_mem_image* img, cm_mem_image_stats* out);
+int32_t cm_mem_image_read(cm_mem_image* img, const uint32_t* addresses, uint64_t n, uint32_t* values);
+int32_t cm_mem_image_cells(cm_mem_image* img, uint32_t* addresses, uint32_t* values, uint64_t cap, uint64_t* n_total);
+int32_t cm_mem_image_nodes(cm_mem_image* img, cm_merkle_node* nodes, uint64_t cap, uint64_t* n_total);
+int32_t cm_mem_image_apply(cm_mem_image* img, const uint32_t* addresses, const uint32_t* new_values, uint64_t n, const uint32_t* old_values,
+                           const uint32_t* root_before, const uint32_t* root_after, uint32_t* root_out, cm_mem_transition** record_out);
+int32_t cm_mem_image_apply_transition(cm_mem_image* img, const cm_mem_transition_view* t, cm_mem_transition** record_out);
+int32_t cm_mem_image_open_memory(cm_mem_image* img, const uint32_t* addresses, uint64_t n, cm_mem_opening* out, uint32_t* root);
+int32_t cm_mem_image_open_memory_range(cm_mem_image* img, uint32_t start, uint32_t n_cells, uint32_t* values, cm_mem_range_opening* out,
+                                       uint32_t* root);
+int32_t cm_mem_image_open_memory_set(cm_mem_image* img, const uint32_t* addresses, uint64_t n, uint32_t* values, uint32_t* siblings,
+                                     uint32_t cap_siblings, uint32_t* n_siblings, uint32_t* root);
 /* ---- program identity and the statement of a run (additive to revision 10) ---------------------------------------------------
  * Which program a proof is about, as one 31-bit word: Proof::program_id() of the reference (crates/prover/src/lib.rs:75-97), the
  * Poseidon2 root of the partial memory tree that holds only the proof's public program cells.  An "entry" is the seven-word record

@@ -325,6 +325,21 @@ pub struct cm_mem_transition_view {
     pub new_values: *const u32,
     pub siblings: *const u32,
 }
+/// A followed memory image (`cm_mem_image_create`): opaque, freed with `cm_mem_image_free`
+#[repr(C)]
+pub struct cm_mem_image {
+    _private: [u8; 0],
+}
+/// What `cm_mem_image_stats_get` fills; set `struct_size` before the call
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug, PartialEq, Eq)]
+pub struct cm_mem_image_stats {
+    pub struct_size: u32,
+    pub device: u32,
+    pub n_cells: u64,
+    pub n_nodes: u64,
+    pub bytes: u64,
+}
 /// What a chain of proofs states (`cm_run_statement_of`): the program's id and range, the registers and memory roots the run
 /// starts from and ends at, the counts of its input and output entries; set `struct_size` before the call
 #[repr(C)]
@@ -576,6 +591,18 @@ unsafe extern "C" {
     pub fn cm_verify_memory_transition_host(root_before: u32, root_after: u32, addresses: *const u32, n: u64, old_values: *const u32, new_values: *const u32, siblings: *const u32, n_siblings: u32) -> i32;
     pub fn cm_prove_run_transitions(r: *mut cm_run, segs: *const *const cm_run_segment, n: u32, config: *const cm_pcs_config, inflight: u32, outs: *mut *mut cm_proof, transitions: *mut *mut cm_mem_transition) -> i32;
     pub fn cm_compose_transitions(parts: *const cm_mem_transition_view, n_parts: u32, device: u32, out: *mut *mut cm_mem_transition) -> i32;
+    pub fn cm_mem_image_create(addresses: *const u32, values: *const u32, n: u64, device: u32, out: *mut *mut cm_mem_image) -> i32;
+    pub fn cm_mem_image_free(img: *mut cm_mem_image) -> i32;
+    pub fn cm_mem_image_root(img: *mut cm_mem_image, root: *mut u32) -> i32;
+    pub fn cm_mem_image_stats_get(img: *mut cm_mem_image, out: *mut cm_mem_image_stats) -> i32;
+    pub fn cm_mem_image_read(img: *mut cm_mem_image, addresses: *const u32, n: u64, values: *mut u32) -> i32;
+    pub fn cm_mem_image_cells(img: *mut cm_mem_image, addresses: *mut u32, values: *mut u32, cap: u64, n_total: *mut u64) -> i32;
+    pub fn cm_mem_image_nodes(img: *mut cm_mem_image, nodes: *mut cm_merkle_node, cap: u64, n_total: *mut u64) -> i32;
+    pub fn cm_mem_image_apply(img: *mut cm_mem_image, addresses: *const u32, new_values: *const u32, n: u64, old_values: *const u32, root_before: *const u32, root_after: *const u32, root_out: *mut u32, record_out: *mut *mut cm_mem_transition) -> i32;
+    pub fn cm_mem_image_apply_transition(img: *mut cm_mem_image, t: *const cm_mem_transition_view, record_out: *mut *mut cm_mem_transition) -> i32;
+    pub fn cm_mem_image_open_memory(img: *mut cm_mem_image, addresses: *const u32, n: u64, out: *mut cm_mem_opening, root: *mut u32) -> i32;
+    pub fn cm_mem_image_open_memory_range(img: *mut cm_mem_image, start: u32, n_cells: u32, values: *mut u32, out: *mut cm_mem_range_opening, root: *mut u32) -> i32;
+    pub fn cm_mem_image_open_memory_set(img: *mut cm_mem_image, addresses: *const u32, n: u64, values: *mut u32, siblings: *mut u32, cap_siblings: u32, n_siblings: *mut u32, root: *mut u32) -> i32;
     pub fn cm_program_id_entries(entries: *const u32, n: u64, id: *mut u32) -> i32;
     pub fn cm_proof_program_id(p: *const cm_proof, id: *mut u32) -> i32;
     pub fn cm_program_ids(entries: *const *const u32, n_entries: *const u64, n: u32, ids: *mut u32, status: *mut i32, s: cm_stream_t) -> i32;

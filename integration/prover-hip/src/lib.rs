@@ -708,6 +708,96 @@ pub fn compose_transitions(parts: &[MemTransition], device: bool) -> Result<MemT
     take_transition(h)
 }
 
+/// A followed memory image (`cm_mem_image_*`): a copy of a run's memory with its partial Merkle tree, on the GPU (`device` = true)
+/// or in host memory, independent of any prover handle.  It absorbs a segment's writes by re-hashing only the dirty paths, checks
+/// itself against the proof's roots and opens cells under its current root.  A refused update is an `Err` and leaves the image
+/// as it was.  The handle is freed when the value is dropped.
+pub struct MemImage {
+    handle: *mut cm_mem_image,
+}
+
+impl MemImage {
+    /// The image of `addresses` (strictly ascending, below 2^28) with `values` (four words per cell, each below P).
+    pub fn create(addresses: &[u32], values: &[u32], device: bool) -> Result<MemImage, String> {
+        if device {
+            ensure_init();
+        }
+        if values.len() != 4 * addresses.len() {
+            return Err(format!("{} value words for an image of {} cells", values.len(), addresses.len()));
+        }
+        let mut h: *mut cm_mem_image = std::ptr::null_mut();
+        let rc = unsafe { cm_mem_image_create(addresses.as_ptr(), values.as_ptr(), addresses.len() as u64, if device { 1 } else { 0 }, &mut h) };
+        if rc != 0 {
+            return Err(last_error());
+        }
+        Ok(MemImage { handle: h })
+    }
+
+    /// The image's current root.
+    pub fn root(&self) -> Result<u32, String> {
+        let mut root: u32 = 0;
+        let rc = unsafe { cm_mem_image_root(self.handle, &mut root) };
+        if rc != 0 {
+            return Err(last_error());
+        }
+        Ok(root)
+    }
+
+    /// `t`'s new values written to its addresses, from `t.root_before` to `t.root_after`, both checked, as are the old values
+    /// (`cm_mem_image_apply_transition`).  The sibling words are never read: a bare transition (addresses, both value planes, two
+    /// roots) is enough.  Returns the new root.
+    pub fn apply_transition(&mut self, t: &MemTransition) -> Result<u32, String> {
+        if t.old_values.len() != 4 * t.addresses.len() || t.new_values.len() != 4 * t.addresses.len() {
+            return Err(format!("{} old and {} new value words for a transition of {} cells", t.old_values.len(), t.new_values.len(), t.addresses.len()));
+        }
+        let mut v: cm_mem_transition_view = unsafe { std::mem::zeroed() };
+        v.struct_size = std::mem::size_of::<cm_mem_transition_view>() as u32;
+        v.root_before = t.root_before;
+        v.root_after = t.root_after;
+        v.n = t.addresses.len() as u32;
+        v.n_zero_only = t.n_zero_only;
+        v.addresses = t.addresses.as_ptr();
+        v.old_values = t.old_values.as_ptr();
+        v.new_values = t.new_values.as_ptr();
+        let rc = unsafe { cm_mem_image_apply_transition(self.handle, &v, std::ptr::null_mut()) };
+        if rc != 0 {
+            return Err(last_error());
+        }
+        self.root()
+    }
+
+    /// The cells `addresses` (any order, repeats allowed: sorted and made unique here) under the image's current root, built on
+    /// the GPU (`cm_mem_image_open_memory_set`; device images only): the record and that root.
+    pub fn open_set(&self, addresses: &[u32]) -> Result<(MemSetOpening, u32), String> {
+        let mut a: Vec<u32> = addresses.to_vec();
+        a.sort_unstable();
+        a.dedup();
+        let mut steps: [cm_mem_set_step; 29] = unsafe { std::mem::zeroed() };
+        let (mut n_steps, mut need): (u32, u32) = (0, 0);
+        let rc = unsafe { cm_mem_set_plan(a.as_ptr(), a.len() as u64, steps.as_mut_ptr(), 29, &mut n_steps, &mut need) };
+        if rc != 0 {
+            return Err(last_error());
+        }
+        let mut values: Vec<u32> = vec![0; 4 * a.len()];
+        let mut siblings: Vec<u32> = vec![0; need as usize];
+        let (mut got, mut root): (u32, u32) = (0, 0);
+        let rc = unsafe {
+            cm_mem_image_open_memory_set(self.handle, a.as_ptr(), a.len() as u64, values.as_mut_ptr(), siblings.as_mut_ptr(), need, &mut got, &mut root)
+        };
+        if rc != 0 {
+            return Err(last_error());
+        }
+        siblings.truncate(got as usize);
+        Ok((MemSetOpening { addresses: a, values, siblings }, root))
+    }
+}
+
+impl Drop for MemImage {
+    fn drop(&mut self) {
+        unsafe { cm_mem_image_free(self.handle) };
+    }
+}
+
 /// A transition checked against its two roots on the GPU in one fold (`cm_verify_memory_transition`) -> (accepted, the two roots
 /// it folds to; zeros when malformed).  A malformed record is a `false`, not an error.
 pub fn verify_memory_transition(t: &MemTransition) -> Result<(bool, [u32; 2]), String> {
