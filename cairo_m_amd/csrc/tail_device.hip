@@ -305,6 +305,17 @@ __global__ void __launch_bounds__(256) k_tail_gather(const TailDesc* __restrict_
 }
 
 // ================================================================= host wrappers
+void tail_last_twiddles(uint32_t log_n, uint32_t* ninv, uint32_t xinv[TAIL_MAX_LAST]) {
+  CM_CHECK((1u << log_n) <= TAIL_MAX_LAST, "tail_last_twiddles: last layer too large");
+  const uint32_t n = 1u << log_n;
+  *ninv = inv(M31::from_u32(n)).v;
+  for (uint32_t l = 0; l < log_n; l++)
+    for (uint32_t h = 0; h < (n >> (l + 1)); h++) {
+      const uint32_t clog_ = log_n - l;
+      const uint32_t idx = subgroup_gen_index(clog_ + 2) + subgroup_gen_index(clog_) * bit_reverse(h, clog_ - 1);
+      xinv[(n - (n >> l)) + h] = inv(point_at_index(idx).x).v;
+    }
+}
 void tail_last_layer(const TailLastArgs& a, hipStream_t st) {
   CM_CHECK((1u << a.log_n) <= TAIL_MAX_LAST && a.log_keep <= a.log_n, "tail_last_layer: last layer too large");
   KProfScope kp("k_tail_last", 0.0, st);

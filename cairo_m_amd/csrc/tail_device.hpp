@@ -59,6 +59,9 @@ struct TailLastArgs {
   unsigned long long* nonce;     // device: set to ~0
 };
 void tail_last_layer(const TailLastArgs& a, hipStream_t st);
+// a.ninv and a.xinv for a last layer of 2^log_n values (log_n <= 6): level l of the line IFFT runs over the coset
+// half_odds(log_n - l), pair h at its point bit_reverse(h) — the twiddles FriPhase::commit_finish computes for the host replay
+void tail_last_twiddles(uint32_t log_n, uint32_t* ninv, uint32_t xinv[TAIL_MAX_LAST]);
 // smallest nonce in [0, 2^(bits + 4)) whose mix_u64 hash has `bits` trailing zero bits; digest read from `chan`
 void tail_grind(const uint32_t* d_chan, uint32_t bits, unsigned long long* d_nonce, hipStream_t st);
 

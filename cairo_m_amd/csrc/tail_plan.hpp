@@ -113,17 +113,11 @@ struct DeviceTail {
       memset(&a, 0, sizeof(a));
       a.d_ar = fri.d_ar.u32();
       a.n_ar_words = (fri.n_inner_ + 1) * 12;
-      const uint32_t last_log = fri.last_log_, n = 1u << last_log;
+      const uint32_t last_log = fri.last_log_;
       for (int c = 0; c < 4; c++) a.last[c] = fri.last_layer.ptrs[c];
       a.log_n = last_log;
       a.log_keep = cfg.log_last_layer_degree_bound;
-      a.ninv = inv(M31::from_u32(n)).v;
-      for (uint32_t l = 0; l < last_log; l++)
-        for (uint32_t h = 0; h < (n >> (l + 1)); h++) {
-          const uint32_t clog_ = last_log - l;
-          const uint32_t idx = subgroup_gen_index(clog_ + 2) + subgroup_gen_index(clog_) * bit_reverse(h, clog_ - 1);
-          a.xinv[(n - (n >> l)) + h] = inv(point_at_index(idx).x).v;
-        }
+      tail_last_twiddles(last_log, &a.ninv, a.xinv);
       a.chan = fri.d_chan_;
       a.h_ar = pinned_words() + PIN_ALPHAS;
       a.h_last = pinned_words() + PIN_LAST_LAYER;

@@ -89,6 +89,26 @@ def merkle_layer_npw(log_size, has_prev, n_cols, lib=None):
     return npw.value
 
 
+TAIL_HASH_W, TAIL_HASH_F, TAIL_COORDS_W, TAIL_ROWS_U = 0, 1, 2, 3   # cm_tail_piece.kind
+TAIL_HDR_WORDS, TAIL_SHIFTS, TAIL_NO_NONCE = 16, 32, 1
+TAIL_MISS = (1 << 64) - 1                                           # the nonce cell of a proof of work that found nothing
+
+
+class TailPiece(C.Structure):
+    """cm_tail_piece"""
+    _fields_ = [("kind", C.c_uint32), ("k", C.c_uint32), ("width", C.c_uint32), ("reserved", C.c_uint32), ("cols", C.POINTER(C.c_uint64))]
+
+
+class TailTablesOut(C.Structure):
+    """cm_tail_tables_out"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("hdr", _u32p), ("positions", _u32p), ("tab", _u32p),
+                ("offsets", _u32p), ("words", _u32p), ("words_cap", C.c_uint64)]
+
+
+def _digest_words(digest):
+    return np.frombuffer(bytes(digest), dtype="<u4").astype(np.uint32)
+
+
 class Backend:
     """Host-side handle on the HIP backend.  One instance per process / GPU."""
 
@@ -162,6 +182,8 @@ class Backend:
                                               C.c_uint32(log_n), C.c_uint64(tw), C.c_uint64(0)))
 
     def bit_reverse(self, cols, log_n):
+        """ColumnOps::bit_reverse_column in place on every column of `cols` (2^log_n words each).  One launch swaps all columns at
+        once, so the same handle must not appear twice: its swaps would race with each other."""
         self._ck(self.L.cm_bit_reverse(self._harr(cols), C.c_uint32(len(cols)), C.c_uint32(log_n), C.c_uint64(0)))
 
     def eval_at_point(self, coeffs, log_n, pt_xy):
@@ -197,6 +219,61 @@ class Backend:
         nonce = C.c_uint64(0)
         self._ck(self.L.cm_grind(d, C.c_uint32(bits), C.byref(nonce), C.c_uint64(0)))
         return nonce.value
+
+    # -- the device-side proof tail, kernel by kernel (cm_tail_*_op) ---------------------------
+    def tail_grind(self, digest, bits):
+        """cm_tail_grind_op: k_tail_grind on `digest` (32 bytes); the nonce cell afterwards, TAIL_MISS (~0) = no nonce within the
+        search limit (or the "tail_grind_cap" tuning)."""
+        nonce = C.c_uint64(0)
+        self._ck(self.L.cm_tail_grind_op(_p(_digest_words(digest)), C.c_uint32(bits), C.byref(nonce), C.c_uint64(0)))
+        return nonce.value
+
+    def tail_tables(self, digest, nonce, n_queries, nq_pad, log_domain, qmask, pieces=(), n_small=None):
+        """cm_tail_tables_op: k_tail_tables + k_tail_gather.  pieces: (kind, k, handles) in output order (TAIL_HASH_W / TAIL_HASH_F:
+        one handle; TAIL_COORDS_W: four; TAIL_ROWS_U: one per word of a row); n_small defaults to the number of leading pieces that
+        are not row pieces.  Returns a dict: hdr (16 words), positions (the n_unique sorted positions), cnt (3 x 32: U, W, F),
+        U / W / F (one array per shift k <= log_domain), offsets (per piece), words (the gathered stream)."""
+        pieces = list(pieces)
+        if n_small is None:
+            n_small = next((i for i, p in enumerate(pieces) if p[0] == TAIL_ROWS_U), len(pieces))
+        keep, arr = [], (TailPiece * max(len(pieces), 1))()
+        bound = 0
+        for i, (kind, k, handles) in enumerate(pieces):
+            hs = self._harr(list(handles))
+            keep.append(hs)
+            arr[i].kind, arr[i].k, arr[i].width, arr[i].cols = kind, k, len(handles), C.cast(hs, C.POINTER(C.c_uint64))
+            items = min(n_queries, 1 << max(log_domain - k, 0))
+            bound += items * {TAIL_HASH_W: 8, TAIL_HASH_F: 24, TAIL_COORDS_W: 4}.get(kind, len(handles))
+        self.L.cm_tail_tab_words.restype = C.c_uint64
+        hdr = np.zeros(TAIL_HDR_WORDS, dtype=np.uint32)
+        pos = np.zeros(max(nq_pad, 1), dtype=np.uint32)
+        tab = np.zeros(int(self.L.cm_tail_tab_words(C.c_uint32(min(max(nq_pad, 1), 1024)))), dtype=np.uint32)
+        off = np.zeros(max(len(pieces), 1), dtype=np.uint32)
+        words = np.zeros(max(bound, 1), dtype=np.uint32)
+        out = TailTablesOut(C.sizeof(TailTablesOut), 0, _p(hdr), _p(pos), _p(tab), _p(off), _p(words), bound)
+        self._ck(self.L.cm_tail_tables_op(_p(_digest_words(digest)), C.c_uint64(nonce), C.c_uint32(n_queries), C.c_uint32(nq_pad),
+                                          C.c_uint32(log_domain), C.c_uint32(qmask), arr, C.c_uint32(len(pieces)), C.c_uint32(n_small),
+                                          C.byref(out), C.c_uint64(0)))
+        cnt = tab[:3 * TAIL_SHIFTS].reshape(3, TAIL_SHIFTS).copy()
+        base = 3 * TAIL_SHIFTS
+        lists = {}
+        for which, name, per in ((0, "U", 1), (1, "W", 1), (2, "F", 4)):
+            lists[name] = [tab[base + k * per * nq_pad: base + k * per * nq_pad + int(cnt[which][k])].copy() for k in range(log_domain + 1)]
+            base += TAIL_SHIFTS * per * nq_pad
+        return dict(hdr=hdr, positions=pos[:int(hdr[3])].copy() if hdr[0] == 0 else pos[:0], cnt=cnt, offsets=off[:len(pieces)],
+                    words=words[:int(hdr[4])].copy(), **lists)
+
+    def tail_last(self, digest, last4, log_n, log_keep, ar=()):
+        """cm_tail_last_op: k_tail_last on the four coordinate columns last4 (2^log_n words each).  Returns (digest after mix_felts
+        as 32 bytes, degree flag, the 4 x 2^log_n words handed to the host, the copy of `ar`, the nonce cell)."""
+        ar = np.ascontiguousarray(ar, dtype=np.uint32)
+        dig = np.zeros(8, dtype=np.uint32)
+        flag, cell = C.c_uint32(0), C.c_uint64(0)
+        last_out = np.zeros(4 << log_n, dtype=np.uint32)
+        ar_out = np.zeros(max(ar.size, 1), dtype=np.uint32)
+        self._ck(self.L.cm_tail_last_op(_p(_digest_words(digest)), self._harr(last4), C.c_uint32(log_n), C.c_uint32(log_keep), _p(ar),
+                                        C.c_uint32(ar.size), _p(dig), C.byref(flag), _p(last_out), _p(ar_out), C.byref(cell), C.c_uint64(0)))
+        return dig.tobytes(), flag.value, last_out.reshape(4, -1), ar_out[:ar.size], cell.value
 
     # -- FieldOps / FriOps / QuotientOps ----------------------------------------------------
     def batch_inverse_m31(self, src, dst, n):

@@ -52,7 +52,9 @@
  *    cm_verify_memory_transition, cm_verify_memory_transition_host, cm_prove_run_transitions.
  *    Still 10 (additive: one host-only query, one entry point, two structs): cm_verify_stats, cm_verify_plan_stats, cm_verify_slot,
  *    cm_verify_many_detail.
- *    Still 10 (additive: one new function, no struct): cm_compose_transitions. */
+ *    Still 10 (additive: one new function, no struct): cm_compose_transitions.
+ *    Still 10 (additive: four new functions and two structs, nothing moved): cm_tail_piece, cm_tail_tables_out, cm_tail_grind_op,
+ *    cm_tail_tables_op, cm_tail_tab_words, cm_tail_last_op. */
 #define CM_ABI_REVISION 10
 
 #ifdef __cplusplus
@@ -477,6 +479,56 @@ int32_t cm_set_tuning(const char* key, int32_t value);
  * first FRI tree's walk asks for at that layer).  Writes min(*n_out, cap) entries; *n_out = the list's length. */
 int32_t cm_tail_list(const uint32_t* positions, uint32_t n_positions, uint32_t log_domain, uint32_t qmask, uint32_t list, uint32_t k,
                      uint32_t* out, uint32_t cap, uint32_t* n_out);
+/* ---- the device-side tail, kernel by kernel (test surface; cairo_m_amd/csrc/tail_ops.hip) ---------------------------------------
+ * Each entry runs ONE step of the tail the prover enqueues behind the last FRI fold — the same kernels through the same host
+ * wrappers, on the same pinned buffers — on inputs the caller chooses instead of the ones a transcript happens to produce, and
+ * synchronises the stream before it returns.  Every argument is checked before the first device call (status 1 and a message);
+ * what cannot be checked is the height of the caller's columns, stated per piece below.  digest = the channel digest as 8 words.
+ *
+ * cm_tail_grind_op: k_tail_grind on a device channel holding `digest` and a nonce cell armed with ~0, under the "tail_grind_cap"
+ * tuning in force.  *nonce_out = the nonce cell afterwards: the smallest nonce with `bits` trailing zero bits, ~0 = not found within
+ * the search limit (2^max(bits + 4, 8) nonces, or the cap).  bits <= 26. */
+int32_t cm_tail_grind_op(const uint32_t digest[8], uint32_t bits, uint64_t* nonce_out, cm_stream_t s);
+/* One piece of the decommitment, in output order.  kind 0: hashes (8 words per node) of the nodes W[k], cols[0] = a layer of
+ * 2^(log_domain - k) nodes; kind 1: hashes of the nodes F[k] (k >= 1), cols[0] = the layer of 2^(log_domain - k + 1) nodes;
+ * kind 2: 4 words per row W[k], interleaved from the four columns cols[0..3] of 2^(log_domain - k) rows; kind 3: `width` words per
+ * row U[k], word c from cols[c] (2^(log_domain - k) rows; a handle may repeat).  `width` is read for kind 3 only. */
+typedef struct cm_tail_piece {
+  uint32_t kind, k, width, reserved;
+  const cm_handle* cols;
+} cm_tail_piece;
+enum { CM_TAIL_HDR_WORDS = 16, CM_TAIL_SHIFTS = 32, CM_TAIL_NO_NONCE = 1 };
+/* Host buffers cm_tail_tables_op fills.  hdr: CM_TAIL_HDR_WORDS words {status (0 / CM_TAIL_NO_NONCE), nonce lo, nonce hi, n_unique,
+ * total words, -, -, -, tables done}; positions: nq_pad words, the first n_unique are the sorted query positions; tab: the device
+ * tables as they are, cm_tail_tab_words(nq_pad) words = {cntU[32] | cntW[32] | cntF[32] | U[32][nq_pad] | W[32][nq_pad] |
+ * F[32][4 nq_pad]} (a list's entries behind its count are unspecified); offsets: n_pieces words, the first output word of every
+ * piece; words: the gathered words (hdr[4] of them; words_cap must be at least the bound the prover sizes its buffer by: per piece
+ * min(n_queries, 2^(log_domain - k)) items, three times that for kind 1, times the words per item). */
+typedef struct cm_tail_tables_out {
+  uint32_t struct_size, reserved;
+  uint32_t* hdr;
+  uint32_t* positions;
+  uint32_t* tab;
+  uint32_t* offsets;
+  uint32_t* words;
+  uint64_t words_cap;
+} cm_tail_tables_out;
+/* k_tail_tables, then k_tail_gather: mix_u64(nonce) into a device channel holding `digest`, the n_queries raw-word draws of
+ * Queries::generate masked to log_domain bits, sorted and de-duplicated; the U / W / F lists of every shift k <= log_domain under
+ * `qmask` (cm_tail_list's definitions); the offset of every piece; the gathers.  pieces [0, n_small) are of kind 0 - 2, the rest of
+ * kind 3.  1 <= n_queries <= 1024; nq_pad = a power of two in [n_queries, 1024]; log_domain <= 31.  nonce = ~0 (the proof of work
+ * missed) comes back as hdr[0] = CM_TAIL_NO_NONCE. */
+int32_t cm_tail_tables_op(const uint32_t digest[8], uint64_t nonce, uint32_t n_queries, uint32_t nq_pad, uint32_t log_domain,
+                          uint32_t qmask, const cm_tail_piece* pieces, uint32_t n_pieces, uint32_t n_small, cm_tail_tables_out* out,
+                          cm_stream_t s);
+uint64_t cm_tail_tab_words(uint32_t nq_pad);
+/* k_tail_last on the 2^log_n evaluations last[0..3] (bit-reversed order, log_n <= 6) with the prover's own twiddle table:
+ * digest_out = the device channel's digest after mix_felts(the first 2^log_keep coefficients in LinePoly order), *degree_flag = 1
+ * if a coefficient above the bound is non-zero, last_out = the 4 * 2^log_n words handed to the host (coordinate-major), ar_out =
+ * the copy of the n_ar_words (<= 384) words `ar` (the commit phase's challenges and roots), *nonce_cell = the armed nonce cell (~0). */
+int32_t cm_tail_last_op(const uint32_t digest[8], const cm_handle last[4], uint32_t log_n, uint32_t log_keep, const uint32_t* ar,
+                        uint32_t n_ar_words, uint32_t digest_out[8], uint32_t* degree_flag, uint32_t* last_out, uint32_t* ar_out,
+                        uint64_t* nonce_cell, cm_stream_t s);
 /* Proof object from its flat word stream (host code, no GPU): re-serialise with cm_proof_json / verify with cm_verify_proof. */
 int32_t cm_proof_from_words(const uint32_t* words, uint64_t n_words, cm_proof** out);
 /* Flat u32 serialisation of the proof (format: cairo_m_amd/csrc/proof.hpp), used by the parity tests. */

@@ -450,6 +450,29 @@ pub struct cm_mem_set_step {
     pub kernel: u32,
 }
 
+/// One piece of the decommitment for `cm_tail_tables_op` (test surface of the device-side proof tail).
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct cm_tail_piece {
+    pub kind: u32,
+    pub k: u32,
+    pub width: u32,
+    pub reserved: u32,
+    pub cols: *const cm_handle,
+}
+/// Host buffers `cm_tail_tables_op` fills.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct cm_tail_tables_out {
+    pub struct_size: u32,
+    pub reserved: u32,
+    pub hdr: *mut u32,
+    pub positions: *mut u32,
+    pub tab: *mut u32,
+    pub offsets: *mut u32,
+    pub words: *mut u32,
+    pub words_cap: u64,
+}
 unsafe extern "C" {
     pub fn cm_init(device: i32) -> i32;
     pub fn cm_shutdown() -> i32;
@@ -538,6 +561,10 @@ unsafe extern "C" {
     pub fn cm_set_device_tail(on: i32) -> i32;
     pub fn cm_set_tuning(key: *const c_char, value: i32) -> i32;
     pub fn cm_tail_list(positions: *const u32, n_positions: u32, log_domain: u32, qmask: u32, list: u32, k: u32, out: *mut u32, cap: u32, n_out: *mut u32) -> i32;
+    pub fn cm_tail_grind_op(digest: *const u32, bits: u32, nonce_out: *mut u64, s: cm_stream_t) -> i32;
+    pub fn cm_tail_tables_op(digest: *const u32, nonce: u64, n_queries: u32, nq_pad: u32, log_domain: u32, qmask: u32, pieces: *const cm_tail_piece, n_pieces: u32, n_small: u32, out: *mut cm_tail_tables_out, s: cm_stream_t) -> i32;
+    pub fn cm_tail_tab_words(nq_pad: u32) -> u64;
+    pub fn cm_tail_last_op(digest: *const u32, last: *const cm_handle, log_n: u32, log_keep: u32, ar: *const u32, n_ar_words: u32, digest_out: *mut u32, degree_flag: *mut u32, last_out: *mut u32, ar_out: *mut u32, nonce_cell: *mut u64, s: cm_stream_t) -> i32;
     pub fn cm_proof_from_words(words: *const u32, n_words: u64, out: *mut *mut cm_proof) -> i32;
     pub fn cm_proof_words(p: *const cm_proof, words_out: *mut *const u32, n_out: *mut u64) -> i32;
     pub fn cm_proof_json(p: *const cm_proof, json_out: *mut *const c_char, len_out: *mut usize) -> i32;

@@ -83,6 +83,7 @@ void orc_merkle_commit(const uint32_t* data, const uint32_t* col_logs, size_t n_
 }
 // Channel scripted test: ops encoded as a tiny bytecode; returns final digest + drawn felts.
 // op 0: mix_u64(v)  op 1: mix_u32s(words...)  op 2: draw_felt -> out  op 3: mix_root(32B as 8 words)
+// op 4: start from a given digest (8 words; counters reset)  op 5: draw_random_bytes -> out (8 raw words: what Queries::generate masks)
 void orc_channel_script(const uint64_t* ops, size_t n_ops, uint8_t* digest_out, uint32_t* felts_out) {
   Channel ch;
   size_t i = 0, fo = 0;
@@ -101,6 +102,13 @@ void orc_channel_script(const uint64_t* ops, size_t n_ops, uint8_t* digest_out, 
       Hash32 r;
       for (int k = 0; k < 8; k++) { uint32_t w = (uint32_t)ops[i++]; memcpy(r.data() + 4 * k, &w, 4); }
       ch.mix_root(r);
+    } else if (op == 4) {
+      ch = Channel();
+      for (int k = 0; k < 8; k++) { uint32_t w = (uint32_t)ops[i++]; memcpy(ch.digest.data() + 4 * k, &w, 4); }
+    } else if (op == 5) {
+      Hash32 b = ch.draw_random_bytes();
+      memcpy(felts_out + fo, b.data(), 32);
+      fo += 8;
     }
   }
   memcpy(digest_out, ch.digest.data(), 32);

@@ -65,6 +65,21 @@ class Oracle:
         d = (C.c_uint8 * 32)(*digest)
         return int(self.L.orc_grind(d, C.c_uint32(bits)))
 
+    def channel_script(self, ops, n_out_words=0):
+        """orc_channel_script: a flat list of integers (op 0 v = mix_u64, 1 n w.. = mix_u32s, 2 = draw_felt, 3 w[8] = mix_root,
+        4 w[8] = start from this digest, 5 = draw_random_bytes) -> (final digest, the words drawn)."""
+        o = np.ascontiguousarray(ops, dtype=np.uint64)
+        dig = (C.c_uint8 * 32)()
+        out = np.zeros(max(n_out_words, 1), dtype=np.uint32)
+        self.L.orc_channel_script(o.ctypes.data_as(C.POINTER(C.c_uint64)), C.c_size_t(o.size), dig, _p(out))
+        return bytes(dig), out[:n_out_words]
+
+    def query_draws(self, digest, nonce, n_queries):
+        """The raw words Queries::generate reads behind mix_u64(nonce) on a channel at `digest`: n_queries of them, unmasked."""
+        ndraw = (n_queries + 7) // 8
+        ops = [4] + [int.from_bytes(digest[4 * i:4 * i + 4], "little") for i in range(8)] + [0, nonce] + [5] * ndraw
+        return self.channel_script(ops, 8 * ndraw)[1][:n_queries]
+
     def m31_mul(self, a, b):
         a = np.ascontiguousarray(a, dtype=np.uint32); b = np.ascontiguousarray(b, dtype=np.uint32)
         o = np.empty_like(a)

@@ -20,6 +20,7 @@ def test_all_declared_symbols_exported():
     L = load_library()
     syms = declared_symbols()
     assert len(syms) >= 40
+    assert {"cm_tail_grind_op", "cm_tail_tables_op", "cm_tail_tab_words", "cm_tail_last_op", "cm_bit_reverse"} <= set(syms)
     missing = [s for s in syms if not hasattr(L, s)]
     assert not missing, missing
 

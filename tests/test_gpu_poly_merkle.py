@@ -238,6 +238,15 @@ def test_grind_parity(backend, oracle):
         assert backend.grind(digest, bits) == oracle.grind(digest, bits)
 
 
+def test_grind_parity_second_batch(backend, oracle):
+    """grind_gpu hashes 2^12 nonces in its first launch at 9 bits: a digest (found by searching with oracle.grind, a one-in-e^8
+    event) whose smallest nonce, 4437, lies behind them makes the loop run its second batch"""
+    digest = bytes.fromhex("2fc67ef39569cb009e868b27f7ef5594c6a9c446d6e85113f62f05f967c6cb9b")
+    want = oracle.grind(digest, 9)
+    assert want >= 4096, "the case: the nonce is not in the first batch"
+    assert backend.grind(digest, 9) == want
+
+
 def test_column_element_access_and_copy(backend):
     """Column::at / Column::set / Column::clone of a Rust-side backend (integration/prover-hip/src/backend.rs): cm_col_read,
     cm_col_write, cm_col_copy."""

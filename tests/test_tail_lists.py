@@ -10,56 +10,7 @@ import random
 import numpy as np
 
 from cairo_m_amd.lib import load_library
-
-
-def fold(positions, n=1):
-    out = []
-    for p in positions:
-        if not out or out[-1] != p >> n:
-            out.append(p >> n)
-    return out
-
-
-def pairs(positions):
-    out = []
-    for parent in fold(positions):
-        out += [2 * parent, 2 * parent + 1]
-    return out
-
-
-def generic_walk(n_layers, col_layers, by_log):
-    """MerkleProver::decommit: layers n_layers - 1 .. 0; `col_layers` = set of layers carrying columns; by_log[l] = sorted queried
-    nodes of layer l.  Returns (hash witness [(layer, node)], column rows [(layer, node, is_query)]) in emission order."""
-    hashes, rows = [], []
-    last = []
-    for layer in range(n_layers - 1, -1, -1):
-        colq = by_log.get(layer, [])
-        has_prev = layer + 1 < n_layers
-        total, pi, qi = [], 0, 0
-        while pi < len(last) or qi < len(colq):
-            cands = []
-            if pi < len(last):
-                cands.append(last[pi] // 2)
-            if qi < len(colq):
-                cands.append(colq[qi])
-            node = min(cands)
-            if has_prev:
-                if pi < len(last) and last[pi] == 2 * node:
-                    pi += 1
-                else:
-                    hashes.append((layer + 1, 2 * node))
-                if pi < len(last) and last[pi] == 2 * node + 1:
-                    pi += 1
-                else:
-                    hashes.append((layer + 1, 2 * node + 1))
-            isq = qi < len(colq) and colq[qi] == node
-            if isq:
-                qi += 1
-            if layer in col_layers:
-                rows.append((layer, node, isq))
-            total.append(node)
-        last = total
-    return hashes, rows
+from tests.tail_lists_ref import fold, generic_walk, pairs, ref_lists
 
 
 def tail_list(L, S, log_domain, qmask, which, k):
@@ -150,3 +101,17 @@ def test_tail_list_refuses_bad_arguments():
     assert call([1, 5, 9], null_pos=True) != 0
     assert call([1, 5, 9], out_p=None) != 0
     assert call([1, 5, 9], n_p=C.c_void_p(0)) != 0
+
+
+def test_reference_lists_equal_the_host_mirror_under_every_mask_shape():
+    """ref_lists (tests/tail_lists_ref.py: the walk restated for any set of pair-opening layers) against cm_tail_list, at the mask
+    shapes the GPU tests use: none, every layer (bit 0 included: the root has no sibling), the top layer only, alternating."""
+    L = load_library()
+    rng = random.Random(14)
+    for L0, S in _cases(rng, 60):
+        for qmask in (0, (2 << L0) - 1, 1 << L0, 0x55555555 & ((2 << L0) - 1), 0xAAAAAAAA & ((2 << L0) - 1)):
+            U, W, F = ref_lists(S, L0, qmask)
+            for k in range(L0 + 1):
+                assert tail_list(L, S, L0, qmask, 0, k) == U[k], (L0, qmask, k, S)
+                assert tail_list(L, S, L0, qmask, 1, k) == W[k], (L0, qmask, k, S)
+                assert tail_list(L, S, L0, qmask, 2, k) == F[k], (L0, qmask, k, S)
