@@ -32,6 +32,48 @@ namespace cm {
 // slower: it needs a v_xor per access, and the pass is VALU-bound — tools/fft_lab.hip, tools/lds_lab.hip.)
 __device__ __forceinline__ constexpr uint32_t phys(uint32_t i) { return i + (i >> 5); }
 
+// Wave-uniform index work of the STRIDED passes and of the fused sweep in scalar code (default; measured in DESIGN.md §6.0,
+// profiles/r07f_*).  The twiddle index of a wave-uniform round is built from the wave number,
+// the tile number and compile-time shifts — no per-lane shift, add or v_readfirstlane per butterfly — and the consecutive
+// entries of a layer come with one wide scalar load; the fused sweep takes its column pointers once, before its first store
+// (a pointer loaded behind a store lands in vector registers, and every buffer access through it is then wrapped in a
+// readfirstlane / 64-bit compare loop); the inverse scaling by 2^-n is a 31-bit rotation.
+// CM_FFT_UNIFORM_TW=0: the previous form (per-lane index collapsed with readfirstlane, pointers loaded where used, multiply).
+#ifndef CM_FFT_UNIFORM_TW
+#define CM_FFT_UNIFORM_TW 1
+#endif
+
+// wave number of the thread as a scalar: threadIdx.x >> 6 is the same in every lane, which the compiler cannot see
+__device__ __forceinline__ uint32_t wave_number() { return (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
+// a pointer that is the same in every lane, in scalar registers whatever the load that produced it
+template <class T>
+__device__ __forceinline__ T* uniform_ptr(T* p) {
+  const uint64_t x = (uint64_t)p;
+  const uint32_t l = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)x), h = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(x >> 32));
+  return (T*)(((uint64_t)h << 32) | l);
+}
+// cnt = 1, 2, 4 or 8 consecutive table entries at a wave-uniform address that is a multiple of cnt words: ONE scalar load.
+// The tables are read through the constant address space — no kernel of this file writes them — because a load from global
+// memory that follows a store (the forward halves of the fused sweep) is never selected as a scalar load, uniform or not.
+typedef uint32_t tw_x1 __attribute__((ext_vector_type(1)));
+typedef uint32_t tw_x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t tw_x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t tw_x8 __attribute__((ext_vector_type(8)));
+template <class V, uint32_t N>
+__device__ __forceinline__ void tw_fetch_as(const uint32_t* p, uint32_t* out) {
+  const V q = *(const __attribute__((address_space(4))) V*)(p);
+#pragma clang loop unroll(full)
+  for (uint32_t i = 0; i < N; i++) out[i] = q[i];
+}
+__device__ __forceinline__ void tw_fetch(const uint32_t* p, const uint32_t cnt, uint32_t* out) {
+  if (cnt == 8) tw_fetch_as<tw_x8, 8>(p, out);   // (a strided round has at most E = 4 layers: 8 entries in its lowest)
+  else if (cnt == 4) tw_fetch_as<tw_x4, 4>(p, out);
+  else if (cnt == 2) tw_fetch_as<tw_x2, 2>(p, out);
+  else tw_fetch_as<tw_x1, 1>(p, out);
+}
+// x * 2^sh in M31 (1 <= sh <= 30): a rotation of the 31-bit word; canonical in, canonical out (all ones only from all ones)
+__device__ __forceinline__ M31 m31_rotl(M31 x, uint32_t sh) { return M31(((x.v << sh) & P) | (x.v >> (31u - sh))); }
+
 template <int W, int TL, int E>
 struct PassGeom {
   static constexpr uint32_t M = (W == TL) ? 0u : (uint32_t)(TL - W);
@@ -55,12 +97,14 @@ struct PassGeom {
 // last round stored (non-staged stores only).
 template <bool INVERSE, int W, int TL, int E, bool PRELOADED>
 __device__ __forceinline__ void fft_pass_rb_body(const FftPassArgs& a, const uint32_t* __restrict__ src, uint32_t* __restrict__ dst,
-                                                 const uint32_t bx, M31 (&v)[1 << E], uint32_t* tile) {
+                                                 const uint32_t bx, const uint32_t wave, M31 (&v)[1 << E], uint32_t* tile) {
   using G = PassGeom<W, TL, E>;
   constexpr uint32_t M = G::M;
   constexpr uint32_t NE = 1u << E;            // elements per thread
   constexpr uint32_t NT = 1u << (TL - E);     // threads per block
   static_assert(!PRELOADED || M > 0, "only strided passes take their input in registers");
+  constexpr bool UNIFORM = CM_FFT_UNIFORM_TW && M > 0;   // scalar twiddle indices, launch-wide scaling choice: strided passes
+  static_assert(!UNIFORM || E <= 4, "tw_fetch loads at most 8 entries");
   // raw buffer resources over the two columns (stride 0, no bounds: offsets stay below 2^(n+2) <= 2^30 bytes)
   const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)src, 0, 0xffffffffu, 0x00020000);
   const __amdgpu_buffer_rsrc_t rdst = __builtin_amdgcn_make_buffer_rsrc((void*)dst, 0, 0xffffffffu, 0x00020000);
@@ -101,6 +145,26 @@ __device__ __forceinline__ void fft_pass_rb_body(const FftPassArgs& a, const uin
     auto cgl = [&](uint32_t e) -> uint32_t { return ((c[e] >> M) << lo) | (c[e] & ((1u << M) - 1)); };
     auto gel = [&](uint32_t e) -> uint32_t { return gi0 + cgl(e); };
     const uint32_t gb0 = gi0 << 2;   // byte offset of the lane inside the column
+    // The 64 lanes of a wave differ in 6 consecutive bits of rho = (t << (E-k)) | g, i.e. local index bits below E - k + 6; a
+    // round on bits [b, b+k) with E - k + 6 <= b therefore pairs elements whose twiddle index is the same in every lane.
+    // Above bit b the local index of such a round is (rho >> b) << (b+k) with rho >> b = wave >> (b - (E-k) - 6), and the
+    // tile number adds (high << hi) to the global one, so layer s reads h = (hq << (k-s-1)) + (j >> (s+1)) with
+    // hq = (high << (TL-b-k)) | (wave >> (b-E+k-6)): scalar, the shifts compile-time constants, the 2^(k-s-1) entries of a
+    // layer consecutive and aligned (a layer's table starts at a multiple of twice its length).  All of a round's twiddles
+    // are fetched here, ahead of the round's loads and butterflies, into scalar registers.  Strided passes only: the
+    // contiguous ones have one such round, which the compiler already collapses to one readfirstlane per layer, and measured
+    // 1-2 % slower in this form: they compile to the text they had.
+    const bool uni_tw = UNIFORM && (E - k + 6 <= b);
+    uint32_t utw[E][NE / 2];
+    if (uni_tw) {
+      const uint32_t hq = (high << (TL - b - k)) | (wave >> (b + k - E - 6));
+#pragma clang loop unroll(full)
+      for (uint32_t s = 0; s < k; s++) {
+        const uint32_t L = a.R - a.n + lo + (b - M) + s - 1;   // (a uniform round never holds layer 0: no y twiddles)
+        const uint32_t* __restrict__ twp = a.xtw + ((1u << (a.R - 1)) - (1u << (a.R - 1 - L)));
+        tw_fetch(twp + (hq << (k - s - 1)), 1u << (k - s - 1), utw[s]);
+      }
+    }
     const bool staged_in = (rr == 0) && INVERSE && M == 0;
     if (rr == 0 && PRELOADED) {
       // (the caller's registers)
@@ -171,6 +235,13 @@ __device__ __forceinline__ void fft_pass_rb_body(const FftPassArgs& a, const uin
         const uint32_t e1 = e | (1u << s);
         const uint32_t g0 = e & ~((1u << k) - 1);  // j = 0 element of this group
         const uint32_t j = e & ((1u << k) - 1);
+        if (uni_tw) {   // the round's twiddles are in scalar registers already
+          const uint32_t w = utw[s][j >> (s + 1)];
+          M31 x = v[e], y = v[e1];
+          if (INVERSE) { v[e] = x + y; v[e1] = mul_tw2(x - y, w); }
+          else { M31 yt = mul_tw2(y, w); v[e] = x + yt; v[e1] = x - yt; }
+          continue;
+        }
         uint32_t h = (gel(g0) >> (layer + 1)) + (j >> (s + 1));
         __builtin_assume(h < (1u << 29));  // byte offset fits 32 bits: saddr + 32-bit voffset addressing
         // The 64 lanes of a wave differ in 6 consecutive bits of rho = (t << (E-k)) | g, i.e. local index bits below
@@ -190,12 +261,30 @@ __device__ __forceinline__ void fft_pass_rb_body(const FftPassArgs& a, const uin
     const bool staged_out = (rr + 1 == G::NR) && !INVERSE && M == 0;
     if (rr + 1 == G::NR && !staged_out) {
       const M31 sc(a.scale);
+      if (UNIFORM) {
+        // the scaling is decided once per launch, around the whole element loop.  Every caller passes 1 or 2^-n = 2^(31-n)
+        // (kernels_poly.hip: launch_pass, interpolate_extend): a power of two multiplies as a rotation of the 31-bit word
+        // (3 shift / mask instructions against the 64-bit multiply-add and its fold); any other value keeps the multiply.
+        if (INVERSE && a.scale != 1u) {
+          if (__builtin_popcount(a.scale) == 1) {   // 2^sh with 1 <= sh <= 30: a.scale is canonical and not 1
+            const uint32_t sh = (uint32_t)__builtin_ctz(a.scale);
 #pragma clang loop unroll(full)
-      for (uint32_t e = 0; e < NE; e++) {
-        M31 o = v[e];
-        if (INVERSE && a.scale != 1u) o = sc * o;   // the doubled operand of M31 operator* is the loop-invariant one
-        v[e] = o;
-        __builtin_amdgcn_raw_buffer_store_b32((int)o.v, rdst, (int)gb0, (int)(cgl(e) << 2), 0);
+            for (uint32_t e = 0; e < NE; e++) v[e] = m31_rotl(v[e], sh);
+          } else {
+#pragma clang loop unroll(full)
+            for (uint32_t e = 0; e < NE; e++) v[e] = sc * v[e];
+          }
+        }
+#pragma clang loop unroll(full)
+        for (uint32_t e = 0; e < NE; e++) __builtin_amdgcn_raw_buffer_store_b32((int)v[e].v, rdst, (int)gb0, (int)(cgl(e) << 2), 0);
+      } else {
+#pragma clang loop unroll(full)
+        for (uint32_t e = 0; e < NE; e++) {
+          M31 o = v[e];
+          if (INVERSE && a.scale != 1u) o = sc * o;   // the doubled operand of M31 operator* is the loop-invariant one
+          v[e] = o;
+          __builtin_amdgcn_raw_buffer_store_b32((int)o.v, rdst, (int)gb0, (int)(cgl(e) << 2), 0);
+        }
       }
     } else {
 #ifndef CM_FFT_ABL_NO_LDS  /* tools/fft_lab: cost of the LDS exchanges (results are wrong) */
@@ -221,7 +310,7 @@ template <bool INVERSE, int W, int TL, int E>
 __global__ void __launch_bounds__(1 << (TL - E)) k_fft_pass_rb(FftPassArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint32_t tile[];   // 2^TL + 2^(TL-5) words
   M31 v[1 << E];
-  fft_pass_rb_body<INVERSE, W, TL, E, false>(a, a.src[blockIdx.y], a.dst[blockIdx.y], blockIdx.x, v, tile);
+  fft_pass_rb_body<INVERSE, W, TL, E, false>(a, a.src[blockIdx.y], a.dst[blockIdx.y], blockIdx.x, (CM_FFT_UNIFORM_TW && W != TL) ? wave_number() : 0u, v, tile);
 }
 
 // ---- the last pass of an interpolation and the first pass of the extension by two that follows it, in ONE sweep ------------
@@ -240,15 +329,27 @@ __global__ void __launch_bounds__(1 << (14 - E)) k_fft_fused_rb(FftFusedArgs a) 
   constexpr int TL = 14;
   extern __shared__ __attribute__((aligned(16))) uint32_t tile[];
   M31 v[1 << E], cf[1 << E];
-  fft_pass_rb_body<true, W, TL, E, false>(a.inv, a.inv.src[blockIdx.y], a.inv.dst[blockIdx.y], blockIdx.x, v, tile);
+#if CM_FFT_UNIFORM_TW
+  // all three column pointers before the first store, and marked uniform: the buffer resources built on them stay scalar
+  const uint32_t wave = wave_number();
+  const uint32_t* __restrict__ src = uniform_ptr(a.inv.src[blockIdx.y]);
+  uint32_t* __restrict__ coef = uniform_ptr(a.inv.dst[blockIdx.y]);
+  uint32_t* __restrict__ lde = uniform_ptr(a.fwd.dst[blockIdx.y]);
+  fft_pass_rb_body<true, W, TL, E, false>(a.inv, src, coef, blockIdx.x, wave, v, tile);
+#else
+  const uint32_t wave = 0u;
+  fft_pass_rb_body<true, W, TL, E, false>(a.inv, a.inv.src[blockIdx.y], a.inv.dst[blockIdx.y], blockIdx.x, wave, v, tile);
+#endif
 #pragma clang loop unroll(full)
   for (uint32_t e = 0; e < (1u << E); e++) cf[e] = v[e];
   const uint32_t half_shift = a.fwd.lo - PassGeom<W, TL, E>::M;   // tiles per half = 2^(lo - M)
+#if !CM_FFT_UNIFORM_TW
   uint32_t* __restrict__ lde = a.fwd.dst[blockIdx.y];
-  fft_pass_rb_body<false, W, TL, E, true>(a.fwd, nullptr, lde, blockIdx.x, v, tile);
+#endif
+  fft_pass_rb_body<false, W, TL, E, true>(a.fwd, nullptr, lde, blockIdx.x, wave, v, tile);
 #pragma clang loop unroll(full)
   for (uint32_t e = 0; e < (1u << E); e++) v[e] = cf[e];
-  fft_pass_rb_body<false, W, TL, E, true>(a.fwd, nullptr, lde, (1u << half_shift) | blockIdx.x, v, tile);
+  fft_pass_rb_body<false, W, TL, E, true>(a.fwd, nullptr, lde, (1u << half_shift) | blockIdx.x, wave, v, tile);
 }
 template <int W, int E = 4>
 static void launch_fused_one(const FftFusedArgs& a, uint32_t ntiles, uint32_t ncols, hipStream_t st) {

@@ -6,13 +6,15 @@ ap = argparse.ArgumentParser()
 ap.add_argument("libs", nargs="+")
 ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--pipelined", type=int, default=4)
+ap.add_argument("--steps", type=int, default=16, help="timed lone proofs per process (more = less run-to-run noise)")
+ap.add_argument("--warmup", type=int, default=4)
 a = ap.parse_args()
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 res = {l: {"lone": [], "pipe": [], "phases": []} for l in a.libs}
 for r in range(a.rounds):
     for l in (a.libs if r % 2 == 0 else a.libs[::-1]):
         env = dict(os.environ, CAIROM_HIP_LIB=os.path.abspath(l))
-        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "16", "--warmup", "4", "--no-cpu-baseline", "--no-end-to-end",
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", str(a.steps), "--warmup", str(a.warmup), "--no-cpu-baseline", "--no-end-to-end",
                               "--alt-fib-n", "0", "--big-fib-n", "0", "--cached-setup-steps", "0", "--sharded-one-rank-blocks", "0", "--no-kprof", "--pipelined", str(a.pipelined)], env=env, capture_output=True, text=True, cwd=root)
         try:
             d = json.loads(out.stdout.strip().splitlines()[-1])
