@@ -236,4 +236,69 @@ int32_t cm_accumulate_quotients(uint32_t log_size, const cm_handle* cols, uint32
     CM_HIP(hipStreamSynchronize(S(s)));
   });
 }
+
+// The provers' out-of-domain sampling on inputs the caller chooses: eval_at_point_multi as prover.hip and prover_sharded.inc
+// call it (host-point form, or the device-point form from an uploaded felt), the landing buffer armed as the prover arms its own.
+// In a whole proof the transcript picks the felt and the components pick the sizes; here the tests pick them.
+int32_t cm_eval_at_points_op(const cm_eval_job* jobs, uint32_t n_jobs, const uint32_t* t4, uint32_t want_landing, uint32_t* out,
+                             uint32_t* landing, cm_stream_t s) {
+  return guard([&] {
+    CM_CHECK(jobs && out && (landing || !want_landing), "cm_eval_at_points_op: null argument");
+    CM_CHECK(n_jobs >= 1, "cm_eval_at_points_op: n_jobs is 0");
+    CM_CHECK(n_jobs <= CM_EVAL_MAX_JOBS, "cm_eval_at_points_op: more than 64 jobs");
+    if (t4)
+      for (int w = 0; w < 4; w++) CM_CHECK(t4[w] < P, "cm_eval_at_points_op: a felt word is not below P");
+    size_t n_ptrs = 0;
+    for (uint32_t k = 0; k < n_jobs; k++) {
+      const cm_eval_job& j = jobs[k];
+      CM_CHECK(j.n_cols >= 1, "cm_eval_at_points_op: a job with n_cols 0");
+      CM_CHECK(j.n_cols <= (1u << 16), "cm_eval_at_points_op: a job with more than 65536 columns");
+      CM_CHECK(j.log_n <= 26, "cm_eval_at_points_op: log_n above 26 (columns are limited to 2^26 rows)");
+      CM_CHECK(j.coeffs, "cm_eval_at_points_op: a job without column handles");
+      for (uint32_t c = 0; c < j.n_cols; c++) CM_CHECK(j.coeffs[c], "cm_eval_at_points_op: null column handle");
+      CM_CHECK(j.shift_x < P && j.shift_y < P, "cm_eval_at_points_op: a shift word is not below P");
+      if (!t4)
+        for (int w = 0; w < 8; w++) CM_CHECK(j.point[w] < P, "cm_eval_at_points_op: a point word is not below P");
+      n_ptrs += j.n_cols;
+    }
+
+    hipStream_t st = S(s);
+    // every job's column pointers in one device table (the prover's d_oods_table)
+    std::vector<const uint32_t*> col_ptrs;
+    col_ptrs.reserve(n_ptrs);
+    for (uint32_t k = 0; k < n_jobs; k++)
+      for (uint32_t c = 0; c < jobs[k].n_cols; c++) col_ptrs.push_back(P32(jobs[k].coeffs[c]));
+    DevBuf d_cols = upload(col_ptrs, st);
+    // {4 words per column | guard} per job, on the device and, if asked for, in the pinned landing buffer (a guard of four
+    // words keeps every slice 16-byte aligned, which the kernel's uint4 store into the landing buffer needs)
+    static_assert(CM_EVAL_GUARD_WORDS % 4 == 0, "job slices stay 16-byte aligned");
+    const size_t words = 4 * n_ptrs + (size_t)CM_EVAL_GUARD_WORDS * n_jobs;
+    DevBuf d_out(words * 4);
+    static_assert((CM_EVAL_GUARD & 0xFFu) * 0x01010101u == CM_EVAL_GUARD, "the guard word is one byte repeated: a memset fills it");
+    CM_HIP(hipMemsetAsync(d_out.p, (int)(CM_EVAL_GUARD & 0xFFu), words * 4, st));
+    uint32_t* land = nullptr;
+    if (want_landing) {
+      land = (uint32_t*)stage_landing(words * 4, st);
+      memset(land, 0xFF, words * 4);
+    }
+    DevBuf d_t;
+    if (t4) d_t = upload(std::vector<uint32_t>(t4, t4 + 4), st);
+    std::vector<EapJob> ej;
+    ej.reserve(n_jobs);
+    size_t col0 = 0, off = 0;
+    for (uint32_t k = 0; k < n_jobs; k++) {
+      const cm_eval_job& j = jobs[k];
+      EapJob e{j.log_n, j.n_cols, d_cols.as<const uint32_t*>() + col0, QM31::from_u32(j.point), QM31::from_u32(j.point + 4), d_out.u32() + off};
+      e.has_shift = j.has_shift != 0; e.shift_x = j.shift_x; e.shift_y = j.shift_y;
+      if (land) e.h_out = land + off;
+      ej.push_back(e);
+      col0 += j.n_cols;
+      off += 4 * (size_t)j.n_cols + CM_EVAL_GUARD_WORDS;
+    }
+    eval_at_point_multi(ej, st, t4 ? d_t.u32() : nullptr);
+    CM_HIP(hipMemcpyAsync(out, d_out.p, words * 4, hipMemcpyDeviceToHost, st));
+    CM_HIP(hipStreamSynchronize(st));
+    if (land) memcpy(landing, land, words * 4);
+  });
+}
 }

@@ -105,6 +105,15 @@ class TailTablesOut(C.Structure):
                 ("offsets", _u32p), ("words", _u32p), ("words_cap", C.c_uint64)]
 
 
+EVAL_MAX_JOBS, EVAL_GUARD_WORDS, EVAL_GUARD = 64, 4, 0xA5A5A5A5     # cm_eval_at_points_op
+
+
+class EvalJob(C.Structure):
+    """cm_eval_job"""
+    _fields_ = [("log_n", C.c_uint32), ("n_cols", C.c_uint32), ("coeffs", C.POINTER(C.c_uint64)), ("point", C.c_uint32 * 8),
+                ("has_shift", C.c_uint32), ("shift_x", C.c_uint32), ("shift_y", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 def _digest_words(digest):
     return np.frombuffer(bytes(digest), dtype="<u4").astype(np.uint32)
 
@@ -274,6 +283,42 @@ class Backend:
         self._ck(self.L.cm_tail_last_op(_p(_digest_words(digest)), self._harr(last4), C.c_uint32(log_n), C.c_uint32(log_keep), _p(ar),
                                         C.c_uint32(ar.size), _p(dig), C.byref(flag), _p(last_out), _p(ar_out), C.byref(cell), C.c_uint64(0)))
         return dig.tobytes(), flag.value, last_out.reshape(4, -1), ar_out[:ar.size], cell.value
+
+    # -- the provers' out-of-domain sampling on chosen inputs (cm_eval_at_points_op) ------------
+    def eval_at_points(self, jobs, t=None, landing=False):
+        """cm_eval_at_points_op: eval_at_point_multi on `jobs`, each a dict with log_n, coeffs (handles) and either point (8 words, x
+        then y: the host-point form, t None) or optionally shift (the M31 point (x, y) added to the point of the felt `t`: the
+        device-point form).  Returns a dict: values (per job, n_cols x 4 words from device memory), guards (per job, the
+        EVAL_GUARD_WORDS words behind its slice), and with landing=True land_values / land_guards (the pinned landing buffer, laid
+        out the same way)."""
+        jobs = list(jobs)
+        arr, keep = (EvalJob * max(len(jobs), 1))(), []
+        for i, j in enumerate(jobs):
+            hs = self._harr(list(j["coeffs"]))
+            keep.append(hs)
+            arr[i].log_n, arr[i].n_cols, arr[i].coeffs = j["log_n"], len(j["coeffs"]), C.cast(hs, C.POINTER(C.c_uint64))
+            arr[i].point = (C.c_uint32 * 8)(*[int(w) for w in j.get("point", (0,) * 8)])
+            if j.get("shift") is not None:
+                arr[i].has_shift, arr[i].shift_x, arr[i].shift_y = 1, int(j["shift"][0]), int(j["shift"][1])
+        words = sum(4 * len(j["coeffs"]) + EVAL_GUARD_WORDS for j in jobs)
+        out = np.zeros(max(words, 1), dtype=np.uint32)
+        land = np.zeros(max(words, 1), dtype=np.uint32)
+        t4 = None if t is None else np.ascontiguousarray(t, dtype=np.uint32)
+        self._ck(self.L.cm_eval_at_points_op(arr, C.c_uint32(len(jobs)), None if t4 is None else _p(t4), C.c_uint32(1 if landing else 0),
+                                             _p(out), _p(land) if landing else None, C.c_uint64(0)))
+
+        def split(buf):
+            vals, guards, off = [], [], 0
+            for j in jobs:
+                n = 4 * len(j["coeffs"])
+                vals.append(buf[off:off + n].reshape(-1, 4).copy())
+                guards.append(buf[off + n:off + n + EVAL_GUARD_WORDS].copy())
+                off += n + EVAL_GUARD_WORDS
+            return vals, guards
+        res = dict(zip(("values", "guards"), split(out)))
+        if landing:
+            res.update(zip(("land_values", "land_guards"), split(land)))
+        return res
 
     # -- FieldOps / FriOps / QuotientOps ----------------------------------------------------
     def batch_inverse_m31(self, src, dst, n):

@@ -54,7 +54,8 @@
  *    cm_verify_many_detail.
  *    Still 10 (additive: one new function, no struct): cm_compose_transitions.
  *    Still 10 (additive: four new functions and two structs, nothing moved): cm_tail_piece, cm_tail_tables_out, cm_tail_grind_op,
- *    cm_tail_tables_op, cm_tail_tab_words, cm_tail_last_op. */
+ *    cm_tail_tables_op, cm_tail_tab_words, cm_tail_last_op.
+ *    Still 10 (additive: one new function and one struct, nothing moved): cm_eval_job, cm_eval_at_points_op. */
 #define CM_ABI_REVISION 10
 
 #ifdef __cplusplus
@@ -529,6 +530,36 @@ uint64_t cm_tail_tab_words(uint32_t nq_pad);
 int32_t cm_tail_last_op(const uint32_t digest[8], const cm_handle last[4], uint32_t log_n, uint32_t log_keep, const uint32_t* ar,
                         uint32_t n_ar_words, uint32_t digest_out[8], uint32_t* degree_flag, uint32_t* last_out, uint32_t* ar_out,
                         uint64_t* nonce_cell, cm_stream_t s);
+/* ---- the prover's out-of-domain sampling, on inputs the caller chooses (test surface; cairo_m_amd/csrc/capi_ops.hip) -----------
+ * One sampling group: n_cols coefficient columns of 2^log_n words (log_n <= 26, n_cols >= 1; a handle may repeat) evaluated at one
+ * QM31 circle point.  point = x[4] then y[4], read in the host-point form only.  has_shift / shift_x / shift_y (canonical M31
+ * words, refused otherwise even when has_shift is 0): read in the device-point form only, where the job samples at the point of
+ * the felt plus the M31 point (shift_x, shift_y) in the circle group — the previous-row mask of the prover. */
+typedef struct cm_eval_job {
+  uint32_t log_n, n_cols;
+  const cm_handle* coeffs;
+  uint32_t point[8];
+  uint32_t has_shift, shift_x, shift_y, reserved;
+} cm_eval_job;
+enum { CM_EVAL_MAX_JOBS = 64, CM_EVAL_GUARD_WORDS = 4 };
+#define CM_EVAL_GUARD 0xA5A5A5A5u
+/* All n_jobs groups (1 <= n_jobs <= CM_EVAL_MAX_JOBS; n_jobs == 0 is refused) through the host wrapper the provers call for their
+ * sampling, eval_at_point_multi: k_point_tables_multi, k_eval_partial_multi, k_reduce_partials_multi and, when t4 is not NULL,
+ * k_oods_maps in front of them.  t4 == NULL: the host-point form, every job samples at its own `point`.  t4 != NULL (four canonical
+ * words): the felt is uploaded and every job's point is derived on the device as CirclePoint::get_random_point does from a drawn
+ * felt, ((1 - t^2) / (1 + t^2), 2t / (1 + t^2)), plus the job's shift; a felt with 1 + t^2 = 0 has no point and is the caller's
+ * to avoid.
+ * out: 4 * sum(n_cols) + CM_EVAL_GUARD_WORDS * n_jobs words, the device output buffer as it is after the kernels: per job, in job
+ * order, 4 words per column and then CM_EVAL_GUARD_WORDS words that the entry set to CM_EVAL_GUARD before the launch and no kernel
+ * may touch (the entry fills the whole buffer with that word, which no M31 takes: a value left unwritten shows too).
+ * want_landing != 0: every job's h_out points into a pinned landing buffer of the same layout, filled with 0xFF bytes before the
+ * launch as the prover fills its own; `landing` receives it whole (same size as out), guards and all.  want_landing == 0: landing
+ * is not read and the kernels store to device memory only.
+ * Every argument is checked before the first device call (status 1 and a message): NULL jobs / out / coeffs / handle / landing
+ * with want_landing, n_jobs outside 1..64, n_cols == 0 or above 65536, log_n above 26, a shift, felt or point word >= P.  The
+ * heights of the caller's columns cannot be checked.  The stream is synchronised before the call returns. */
+int32_t cm_eval_at_points_op(const cm_eval_job* jobs, uint32_t n_jobs, const uint32_t* t4, uint32_t want_landing, uint32_t* out,
+                             uint32_t* landing, cm_stream_t s);
 /* Proof object from its flat word stream (host code, no GPU): re-serialise with cm_proof_json / verify with cm_verify_proof. */
 int32_t cm_proof_from_words(const uint32_t* words, uint64_t n_words, cm_proof** out);
 /* Flat u32 serialisation of the proof (format: cairo_m_amd/csrc/proof.hpp), used by the parity tests. */

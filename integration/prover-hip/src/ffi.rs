@@ -473,6 +473,19 @@ pub struct cm_tail_tables_out {
     pub words: *mut u32,
     pub words_cap: u64,
 }
+/// One sampling group for `cm_eval_at_points_op` (test surface of the provers' out-of-domain sampling).
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct cm_eval_job {
+    pub log_n: u32,
+    pub n_cols: u32,
+    pub coeffs: *const cm_handle,
+    pub point: [u32; 8],
+    pub has_shift: u32,
+    pub shift_x: u32,
+    pub shift_y: u32,
+    pub reserved: u32,
+}
 unsafe extern "C" {
     pub fn cm_init(device: i32) -> i32;
     pub fn cm_shutdown() -> i32;
@@ -565,6 +578,7 @@ unsafe extern "C" {
     pub fn cm_tail_tables_op(digest: *const u32, nonce: u64, n_queries: u32, nq_pad: u32, log_domain: u32, qmask: u32, pieces: *const cm_tail_piece, n_pieces: u32, n_small: u32, out: *mut cm_tail_tables_out, s: cm_stream_t) -> i32;
     pub fn cm_tail_tab_words(nq_pad: u32) -> u64;
     pub fn cm_tail_last_op(digest: *const u32, last: *const cm_handle, log_n: u32, log_keep: u32, ar: *const u32, n_ar_words: u32, digest_out: *mut u32, degree_flag: *mut u32, last_out: *mut u32, ar_out: *mut u32, nonce_cell: *mut u64, s: cm_stream_t) -> i32;
+    pub fn cm_eval_at_points_op(jobs: *const cm_eval_job, n_jobs: u32, t4: *const u32, want_landing: u32, out: *mut u32, landing: *mut u32, s: cm_stream_t) -> i32;
     pub fn cm_proof_from_words(words: *const u32, n_words: u64, out: *mut *mut cm_proof) -> i32;
     pub fn cm_proof_words(p: *const cm_proof, words_out: *mut *const u32, n_out: *mut u64) -> i32;
     pub fn cm_proof_json(p: *const cm_proof, json_out: *mut *const c_char, len_out: *mut usize) -> i32;

@@ -103,12 +103,14 @@ def test_transforms_edges(backend, oracle, log_n):
 
 
 # ---- 4. eval_at_point ----------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("log_n", [3, 11, 15])
+@pytest.mark.parametrize("log_n", [3, 11, 12, 13, 15])
 def test_eval_at_point_edges(backend, oracle, log_n):
-    """k_eval_partial_multi (raw products of coefficient * high-table word, a fold every four chunks) and the QM31 products of the
-    point tables.  EAP2_LOW_BITS = 10 and EAP2_GROUP = 32: 2^15 is one full group of 32 chunks (the unrolled branch, eight
-    folds), 2^11 is a group of 2 chunks — a chunk count that is no multiple of four, the bounds-tested branch — and 2^3 has fewer
-    low indices than a block (the bounds-tested branch with idle lanes); no further size is needed."""
+    """cm_eval_at_point, which runs eval_at_point_batch: k_point_table (the QM31 products of the point tables),
+    k_eval_at_point_partial (one block per chunk of 2^EAP_LOW_BITS = 2^12 coefficients, a QM31 * M31 product per coefficient, the
+    block's sum times the chunk's high-table entry) and k_reduce_partials.  2^3 and 2^11 are less than a chunk, 2^12 is exactly
+    one, 2^13 is two — the path's own chunk boundary — and 2^15 is eight.  The provers do not sample through this path: their
+    kernels (k_eval_partial_multi and the rest of eval_at_point_multi) get the same columns and points, from the same seeds, in
+    test_worst_case_columns_on_both_paths of tests/test_gpu_eval_points.py, the file that steers those kernels further."""
     n = 1 << log_n
     rng = np.random.default_rng(500 + log_n)
     cols = [fe.const(P - 1, n), fe.near_p(rng, n), fe.edge_mix(rng, n), fe.alt(n)]
