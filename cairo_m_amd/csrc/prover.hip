@@ -1970,15 +1970,16 @@ int32_t cm_verify_run(const cm_proof* const* proofs, uint32_t n, const cm_pcs_co
 // The same verdicts from the GPU, for a whole batch (verify_device.hip): results[i] = what cm_verify_proof says about proofs[i]
 static int32_t verify_many_impl(const char* who, const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected,
                                 std::vector<cm::VerifyOutcome>& out, cm_stream_t s,
-                                std::vector<std::vector<cm::VerifySlotDetail>>* detail = nullptr) {
+                                std::vector<std::vector<cm::VerifySlotDetail>>* detail = nullptr, uint32_t flags = 0) {
   return pguard([&] {
+    CM_CHECK((flags & ~CM_VERIFY_ARITH_ON_DEVICE) == 0, std::string(who) + ": unknown flag bit");
     CM_CHECK(n >= 1 && proofs, std::string(who) + ": no proofs");
     std::vector<const cm::ProofData*> pd(n);
     for (uint32_t i = 0; i < n; i++) {
       CM_CHECK(proofs[i] && proofs[i]->d, std::string(who) + ": null proof");
       pd[i] = proofs[i]->d;
     }
-    cm::verify_many_device(pd.data(), n, expected ? *expected : default_cfg(), out, (hipStream_t)(uintptr_t)s, detail);
+    cm::verify_many_device(pd.data(), n, expected ? *expected : default_cfg(), out, (hipStream_t)(uintptr_t)s, detail, flags);
   });
 }
 // the verdicts of a batch as cm_verify_many reports them: results, the call's status and cm_last_error()
@@ -1998,17 +1999,25 @@ static int32_t verify_many_report(const std::vector<cm::VerifyOutcome>& out, uin
   cm_set_last_error(("proof " + std::to_string(first) + ": verification failed: " + out[first].message).c_str());
   return 11;
 }
-int32_t cm_verify_many(const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected, cm_verify_result* results, cm_stream_t s) {
+int32_t cm_verify_many_ex(const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected, uint32_t flags, cm_verify_result* results,
+                          cm_stream_t s) {
   std::vector<cm::VerifyOutcome> out;
-  const int32_t rc = verify_many_impl("cm_verify_many", proofs, n, expected, out, s);
+  const int32_t rc = verify_many_impl("cm_verify_many", proofs, n, expected, out, s, nullptr, flags);
   return rc ? rc : verify_many_report(out, n, results);
+}
+int32_t cm_verify_many(const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected, cm_verify_result* results, cm_stream_t s) {
+  return cm_verify_many_ex(proofs, n, expected, 0, results, s);
 }
 int32_t cm_verify_many_detail(const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected, cm_verify_result* results,
                               cm_verify_slot* slots, uint32_t cap_slots, uint32_t* slot_first, cm_stream_t s) {
+  return cm_verify_many_detail_ex(proofs, n, expected, 0, results, slots, cap_slots, slot_first, s);
+}
+int32_t cm_verify_many_detail_ex(const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected, uint32_t flags, cm_verify_result* results,
+                                 cm_verify_slot* slots, uint32_t cap_slots, uint32_t* slot_first, cm_stream_t s) {
   if (!slot_first || (!slots && cap_slots)) return cm_set_last_error("cm_verify_many_detail: null output");
   std::vector<cm::VerifyOutcome> out;
   std::vector<std::vector<cm::VerifySlotDetail>> detail;
-  const int32_t rc = verify_many_impl("cm_verify_many_detail", proofs, n, expected, out, s, &detail);
+  const int32_t rc = verify_many_impl("cm_verify_many_detail", proofs, n, expected, out, s, &detail, flags);
   if (rc) return rc;
   slot_first[0] = 0;
   for (uint32_t i = 0; i < n; i++) slot_first[i + 1] = slot_first[i] + (uint32_t)detail[i].size();
@@ -2039,8 +2048,11 @@ int32_t cm_verify_plan_stats(const cm_proof* const* proofs, uint32_t n, const cm
   });
 }
 int32_t cm_verify_run_device(const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected) {
+  return cm_verify_run_device_ex(proofs, n, expected, 0);
+}
+int32_t cm_verify_run_device_ex(const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected, uint32_t flags) {
   std::vector<cm::VerifyOutcome> out;
-  const int32_t rc = verify_many_impl("cm_verify_run_device", proofs, n, expected, out, 0);
+  const int32_t rc = verify_many_impl("cm_verify_run_device", proofs, n, expected, out, 0, nullptr, flags);
   if (rc) return rc;
   return pguard([&] {
     for (uint32_t i = 0; i < n; i++)

@@ -10,6 +10,7 @@
 #include "framing.hpp"
 #include "air/components.hpp"
 #include <algorithm>
+#include <chrono>
 #include <functional>
 #include <map>
 #include <set>
@@ -227,10 +228,34 @@ struct VerifyPrelude {
   std::map<uint32_t, std::vector<uint32_t>> qpos;                 // log -> sorted unique positions
 };
 
+// What verify_prelude records when its two pure-arithmetic checks are deferred (verify_device.hip decides them on the GPU):
+// `stage` says how far the record goes when the prelude fails behind a deferred check.
+struct DeferredArith {
+  int stage = 0;           // 0: nothing yet; 1: rel (the LogUp sum can be checked); 2: all of it (and the sampled values have their shape)
+  HostRelations rel;       // the relation challenges
+  QM31 random_coeff;
+  CPoint<QM31> oods;
+  std::vector<size_t> tr0, it0;   // per component: its first column in trees 1 and 2
+};
+
+// Where verify_prelude spends its time: filled when the caller hands one in (only cm_verify_plan_stats under
+// CM_VERIFY_PLAN_MARKS does: tools/verify_bench.py --plan-split)
+struct PreludeMarks { double total_ms = 0, logup_ms = 0, oods_ms = 0; };
+struct MarkTimer {
+  double* into;
+  std::chrono::steady_clock::time_point t0;
+  explicit MarkTimer(double* d) : into(d) { if (into) t0 = std::chrono::steady_clock::now(); }
+  ~MarkTimer() { if (into) *into += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+};
+
 // Every check of verify_cairo_m in front of the queries, in its order.  "" = passed (`o` is filled); otherwise the name of the
 // failed check, with its CM_VERIFY_* id in *check.  `cfg` is the verifier's own PcsConfig.  The caller holds a FramingUse.
-inline std::string verify_prelude(const ProofData& pf, const cm_pcs_config& cfg, VerifyPrelude& o, int32_t* check = nullptr) {
+// defer != nullptr: InvalidLogupSum and OodsNotMatching are not decided here (the transcript does not depend on them) and
+// *defer records what deciding them needs; every other check stays, in its place.
+inline std::string verify_prelude(const ProofData& pf, const cm_pcs_config& cfg, VerifyPrelude& o, int32_t* check = nullptr,
+                                  DeferredArith* defer = nullptr, PreludeMarks* marks = nullptr) {
   auto fail = [&](int32_t id, const char* msg) { if (check) *check = id; return std::string(msg); };
+  MarkTimer whole(marks ? &marks->total_ms : nullptr);
   if (pf.config.pow_bits != cfg.pow_bits || pf.config.log_blowup_factor != cfg.log_blowup_factor ||
       pf.config.n_queries != cfg.n_queries || pf.config.log_last_layer_degree_bound != cfg.log_last_layer_degree_bound)
     return fail(CM_VERIFY_STRUCTURE, "InvalidStructure(config): the proof was made under a different PcsConfig than the verifier's");
@@ -270,7 +295,9 @@ inline std::string verify_prelude(const ProofData& pf, const cm_pcs_config& cfg,
     QM31 cur(M31(1));
     for (int i = 0; i < air::MAX_REL_SIZE; i++) { rel.alpha_pow[r][i] = cur; cur = cur * alpha; }
   }
-  {
+  if (defer) { defer->rel = rel; defer->stage = 1; }
+  else {
+    MarkTimer t(marks ? &marks->logup_ms : nullptr);
     QM31 s = initial_logup_sum(pf.public_data, rel);  // verifier.rs:69-77
     for (auto& c : pf.claimed_sums) s += c;
     if (!s.is_zero()) return fail(CM_VERIFY_LOGUP_SUM, "InvalidLogupSum");
@@ -304,7 +331,9 @@ inline std::string verify_prelude(const ProofData& pf, const cm_pcs_config& cfg,
     if (pf.sampled_values[t].size() != logs[t].size()) return fail(CM_VERIFY_STRUCTURE, "InvalidStructure(sampled columns)");
     for (size_t c = 0; c < logs[t].size(); c++) if (pf.sampled_values[t][c].size() != pts[t][c].size()) return fail(CM_VERIFY_STRUCTURE, "InvalidStructure(samples)");
   }
-  {  // composition OODS value == sum_c constraints_c(mask) / vanishing_c(oods)
+  if (defer) { defer->random_coeff = random_coeff; defer->oods = oods; defer->tr0 = tr0; defer->it0 = it0; defer->stage = 2; }
+  else {  // composition OODS value == sum_c constraints_c(mask) / vanishing_c(oods)
+    MarkTimer t(marks ? &marks->oods_ms : nullptr);
     size_t total = 0;
     for (int c = 0; c < air::N_COMPONENTS; c++) total += air::component_info(c).n_constraints;
     std::vector<QM31> powers(total);

@@ -1,13 +1,16 @@
 // cm_verify_many: the query phase of verify_cairo_m for a whole batch of proofs on the GPU (plan format: verify_device.hpp).
 // Host: verify_prelude + a symbolic walk of merkle_verify / rebuild_evals per proof.  Device: k_verify_answers (DEEP quotients),
 // k_verify_fri (pairs, folds, last layer), k_verify_merkle (every tree of every proof), k_verify_reduce (lowest failed check).
+// With CM_VERIFY_ARITH_ON_DEVICE the prelude's LogUp sum and OODS check are deferred into the first two slots (verify_prelude.hpp).
 // cm_verify_plan_stats and cm_verify_many_detail read what the same Planner built (shapes; every slot's own flag) for the tests.
 #include "../../include/cairom_hip.h"
 #include "engine.hpp"
 #include "blake2s_dev.hpp"
 #include "verifier_common.hpp"
 #include "verify_device.hpp"
+#include "verify_prelude.hpp"
 #include <chrono>
+#include <memory>
 
 namespace cm {
 
@@ -232,6 +235,8 @@ struct Planner {
   uint64_t scr_words = 0;
   uint32_t n_flags = 0, max_level_nodes = 1;
   std::vector<uint32_t> ans_jobs, fri_jobs, tree_jobs;
+  PreludeMarks* marks = nullptr;   // cm_verify_plan_stats under CM_VERIFY_PLAN_MARKS; null everywhere else
+  std::vector<uint32_t> sum_jobs, fin_jobs, oods_jobs[air::N_COMPONENTS];   // the deferred arithmetic; oods jobs are sent component-major
 
   uint32_t put(const uint32_t* p, size_t n) {
     const size_t off = blob.size();
@@ -341,13 +346,57 @@ struct Planner {
     return true;
   }
 
-  void plan_proof(const ProofData& pf, const cm_pcs_config& cfg, ProofPlan& pp) {
-    VerifyPrelude pre;
-    {
-      int32_t check = 0;
-      const std::string err = verify_prelude(pf, cfg, pre, &check);
-      if (!err.empty()) { pp.decided_early = true; pp.early.check = check; pp.early.message = err; return; }
+  // The OODS composition check as one job per component (verify_prelude.hpp) and the OODS half of the proof's fin job.  The
+  // coefficient powers are the host's table, built as verify_prelude builds it; the sampled values have their shape (stage 2).
+  void plan_oods(const ProofData& pf, const DeferredArith& da, uint32_t rel_off, uint32_t flag, uint32_t* fin) {
+    size_t total = 0;
+    for (int c = 0; c < air::N_COMPONENTS; c++) total += air::component_info(c).n_constraints;
+    std::vector<QM31> powers(total), flat;
+    QM31 cur(M31(1));
+    for (size_t g = total; g-- > 0;) { powers[g] = cur; cur = cur * da.random_coeff; }
+    const uint32_t coeff_off = put_q(powers.data(), powers.size());
+    for (int i = 0; i < air::N_PREPROC; i++) flat.push_back(pf.sampled_values[0][i][0]);
+    const uint32_t pp_off = put_q(flat.data(), flat.size());
+    flat.clear();
+    for (auto& col : pf.sampled_values[1]) flat.push_back(col[0]);
+    const uint32_t tr_off = put_q(flat.data(), flat.size());
+    flat.clear();
+    std::vector<uint32_t> it_first(pf.sampled_values[2].size());   // a column's first sample in the flat list
+    for (size_t k = 0; k < pf.sampled_values[2].size(); k++) {
+      it_first[k] = (uint32_t)flat.size();
+      for (auto& v : pf.sampled_values[2][k]) flat.push_back(v);
     }
+    const uint32_t it_off = put_q(flat.data(), flat.size());
+    flat.clear();
+    for (int c = 0; c < air::N_COMPONENTS; c++) flat.push_back(pf.claimed_sums[c] * inv(M31::from_u32(1u << pf.claim_log_sizes[c])));
+    const uint32_t shift_off = put_q(flat.data(), flat.size());
+    const uint32_t oods_off = put_q(&da.oods.x, 1);
+    const QM31 c4[4] = {pf.sampled_values[3][0][0], pf.sampled_values[3][1][0], pf.sampled_values[3][2][0], pf.sampled_values[3][3][0]};
+    const uint32_t quot = scratch(4 * air::N_COMPONENTS);
+    size_t g = 0;
+    for (int c = 0; c < air::N_COMPONENTS; c++) {
+      const air::ComponentInfo& info = air::component_info(c);
+      const uint32_t job[VP_OODS_JOB_WORDS] = {(uint32_t)c, (uint32_t)info.n_base_constraints, tr_off + 4 * (uint32_t)da.tr0[c],
+                                               it_off + 4 * it_first[da.it0[c]], pp_off, rel_off, coeff_off + 4 * (uint32_t)g,
+                                               shift_off + 4 * (uint32_t)c, pf.claim_log_sizes[c], oods_off, quot + 4 * (uint32_t)c, 0};
+      oods_jobs[c].insert(oods_jobs[c].end(), job, job + VP_OODS_JOB_WORDS);
+      g += info.n_constraints;
+    }
+    fin[VPF_DO_OODS] = 1;
+    fin[VPF_QUOT] = quot;
+    fin[VPF_N_QUOT] = air::N_COMPONENTS;
+    fin[VPF_COMPOSITION] = put_q(c4, 4);
+    fin[VPF_OODS_FLAG] = flag;
+  }
+
+  // arith_on_device: the LogUp sum and the OODS check are the proof's first two slots, decided by the prelude kernels
+  void plan_proof(const ProofData& pf, const cm_pcs_config& cfg, ProofPlan& pp, bool arith_on_device = false) {
+    VerifyPrelude pre;
+    std::unique_ptr<DeferredArith> deferred(arith_on_device ? new DeferredArith() : nullptr);   // the default mode builds none
+    int32_t check = 0;
+    const std::string err = verify_prelude(pf, cfg, pre, &check, deferred.get(), marks);
+    const int stage = deferred ? deferred->stage : 0;
+    if (!err.empty() && stage == 0) { pp.decided_early = true; pp.early.check = check; pp.early.message = err; return; }
     const auto& logs = pre.logs;
     const auto& pts = pre.pts;
     const auto& q_logs = pre.q_logs;
@@ -355,6 +404,20 @@ struct Planner {
     pp.flag_base = n_flags;
     auto device_slot = [&](int32_t check, const std::string& msg) { pp.slots.push_back(Slot{check, msg}); return n_flags++; };
     auto host_fail = [&](int32_t check, const std::string& msg) { pp.fail_slot = (int)pp.slots.size(); pp.slots.push_back(Slot{check, msg}); n_flags++; };
+    if (stage >= 1) {
+      const DeferredArith& da = *deferred;
+      uint32_t fin[VP_FIN_JOB_WORDS] = {0};
+      uint32_t rel_words[VP_REL_WORDS];
+      relations_words(da.rel, rel_words);
+      const uint32_t rel_off = put(rel_words, VP_REL_WORDS);
+      plan_public_sum(*this, pf.public_data, rel_off, sum_jobs, fin);
+      fin[VPF_CLAIMED] = put_q(pf.claimed_sums.data(), pf.claimed_sums.size());
+      fin[VPF_N_CLAIMED] = (uint32_t)pf.claimed_sums.size();
+      fin[VPF_LOGUP_FLAG] = device_slot(CM_VERIFY_LOGUP_SUM, "InvalidLogupSum");
+      if (da.stage >= 2) plan_oods(pf, da, rel_off, device_slot(CM_VERIFY_OODS, "OodsNotMatching"), fin);
+      fin_jobs.insert(fin_jobs.end(), fin, fin + VP_FIN_JOB_WORDS);
+      if (!err.empty()) return host_fail(check, err);   // a host check behind a deferred one: nothing more is sent
+    }
 
     // ---- the four commitment trees
     uint32_t qv_off[4];
@@ -548,10 +611,21 @@ static void read_plan_stats(const Planner& pl, cm_verify_stats& s) {
 
 void verify_plan_stats(const ProofData* const* proofs, uint32_t n, const cm_pcs_config& cfg, cm_verify_stats* out) {
   FramingUse framing_use;
+  // CM_VERIFY_PLAN_MARKS=1 (tools/verify_bench.py --plan-split): where planning a proof spends its time, on stderr
+  const char* want_marks = getenv("CM_VERIFY_PLAN_MARKS");
   for (uint32_t i = 0; i < n; i++) {
     Planner pl;
     ProofPlan pp;
-    pl.plan_proof(*proofs[i], cfg, pp);
+    PreludeMarks marks;
+    double plan_ms = 0;
+    if (want_marks && want_marks[0] == '1') pl.marks = &marks;
+    {
+      MarkTimer t(&plan_ms);
+      pl.plan_proof(*proofs[i], cfg, pp);
+    }
+    if (want_marks && want_marks[0] == '1')
+      fprintf(stderr, "cm_verify_plan_stats: proof %u: plan %.4f ms = replay and host checks %.4f + public LogUp sum %.4f + OODS evaluation %.4f + tables %.4f\n",
+              i, plan_ms, marks.total_ms - marks.logup_ms - marks.oods_ms, marks.logup_ms, marks.oods_ms, plan_ms - marks.total_ms);
     cm_verify_stats s;
     memset(&s, 0, sizeof(s));
     s.struct_size = sizeof(s);
@@ -565,7 +639,9 @@ void verify_plan_stats(const ProofData* const* proofs, uint32_t n, const cm_pcs_
 }
 
 void verify_many_device(const ProofData* const* proofs, uint32_t n, const cm_pcs_config& cfg, std::vector<VerifyOutcome>& out, hipStream_t st,
-                        std::vector<std::vector<VerifySlotDetail>>* detail) {
+                        std::vector<std::vector<VerifySlotDetail>>* detail, uint32_t flags_in) {
+  CM_CHECK((flags_in & ~CM_VERIFY_ARITH_ON_DEVICE) == 0, "cm_verify_many: unknown flag bit");
+  const bool arith_on_device = (flags_in & CM_VERIFY_ARITH_ON_DEVICE) != 0;
   {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
@@ -578,7 +654,7 @@ void verify_many_device(const ProofData* const* proofs, uint32_t n, const cm_pcs
   Planner pl;
   std::vector<ProofPlan> plans(n);
   for (uint32_t i = 0; i < n; i++) {
-    pl.plan_proof(*proofs[i], cfg, plans[i]);
+    pl.plan_proof(*proofs[i], cfg, plans[i], arith_on_device);
     CM_CHECK(pl.blob.size() < (1u << 30) && pl.scr_words < (1u << 30), "cm_verify_many: the batch is too large for one call (2^30 plan words): split it");
   }
   CM_CHECK(pl.max_level_nodes <= VERIFY_MAX_LEVEL_NODES, "cm_verify_many: more than 1024 nodes in one level of a tree (n_queries above 512) is not supported on the device");
@@ -589,6 +665,16 @@ void verify_many_device(const ProofData* const* proofs, uint32_t n, const cm_pcs
   }
   const uint32_t n_ans = (uint32_t)(pl.ans_jobs.size() / 8), n_fri = (uint32_t)pl.fri_jobs.size(), n_tree = (uint32_t)(pl.tree_jobs.size() / 8);
   const uint32_t ans_off = pl.put(pl.ans_jobs), fri_off = pl.put(pl.fri_jobs), tree_off = pl.put(pl.tree_jobs), red_off = pl.put(reduce_jobs);
+  std::vector<uint32_t> oods_jobs;
+  for (auto& v : pl.oods_jobs) {   // component-major, every component's jobs padded to whole waves: a wave runs ONE arm of the evaluator's switch
+    oods_jobs.insert(oods_jobs.end(), v.begin(), v.end());
+    const size_t n_jobs = v.size() / VP_OODS_JOB_WORDS;
+    oods_jobs.insert(oods_jobs.end(), ((n_jobs + 63) / 64 * 64 - n_jobs) * VP_OODS_JOB_WORDS, VP_NONE);
+  }
+  const uint32_t n_sum = (uint32_t)(pl.sum_jobs.size() / VP_SUM_JOB_WORDS), n_oods = (uint32_t)(oods_jobs.size() / VP_OODS_JOB_WORDS),
+                 n_fin = (uint32_t)(pl.fin_jobs.size() / VP_FIN_JOB_WORDS);
+  const uint32_t sum_off = pl.put(pl.sum_jobs), oods_off = pl.put(oods_jobs), fin_off = pl.put(pl.fin_jobs);
+  CM_CHECK(pl.blob.size() < (1u << 30), "cm_verify_many: the batch is too large for one call (2^30 plan words): split it");
   tm.ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 
   for (auto& e : tm.ev) if (!e) CM_HIP(hipEventCreate(&e));
@@ -609,6 +695,9 @@ void verify_many_device(const ProofData* const* proofs, uint32_t n, const cm_pcs
     else
       hipLaunchKernelGGL(k_verify_merkle<false>, dim3(n_tree), dim3(MERKLE_THREADS), lds, st, blob, (const uint32_t*)d_scr.u32(), d_flags.u32(), blob + tree_off, cap);
   }
+  launch_verify_public_sum(blob, d_scr.u32(), blob + sum_off, n_sum, st);
+  launch_verify_oods(blob, d_scr.u32(), blob + oods_off, n_oods, st);
+  launch_verify_prelude_fin(blob, d_scr.u32(), d_flags.u32(), blob + fin_off, n_fin, st);
   hipLaunchKernelGGL(k_verify_reduce, dim3((n + 63) / 64), dim3(64), 0, st, (const uint32_t*)d_flags.u32(), blob + red_off, n, d_out);
   CM_HIP(hipGetLastError());
   CM_HIP(hipEventRecord(tm.ev[2], st));
@@ -627,7 +716,7 @@ void verify_many_device(const ProofData* const* proofs, uint32_t n, const cm_pcs
     const ProofPlan& pp = plans[i];
     if (pp.decided_early) { out[i] = pp.early; continue; }
     int slot = pp.fail_slot;
-    if (res[i] != 0xffffffffu) slot = (int)res[i];   // a raised flag is always in front of the slot that failed while planning
+    if (res[i] != 0xffffffffu) slot = (int)res[i];   // a raised flag is always in front of the slot that failed while planning (the last one, also behind deferred slots)
     if (slot >= 0) { out[i].check = pp.slots[slot].check; out[i].message = pp.slots[slot].message; }
   }
   if (!detail) return;

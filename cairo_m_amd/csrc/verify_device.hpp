@@ -46,8 +46,9 @@ struct VerifySlotDetail {
 };
 // out[i] = the verdict on proofs[i]; throws CmError for everything that is not a verdict (no device: code 3).
 // detail (optional): every proof's slots in the host verifier's order, read from the flag words of the same launches.
+// flags: 0 or CM_VERIFY_ARITH_ON_DEVICE (the LogUp sum and the OODS check as the first two slots: verify_prelude.hpp).
 void verify_many_device(const ProofData* const* proofs, uint32_t n, const cm_pcs_config& cfg, std::vector<VerifyOutcome>& out, hipStream_t st,
-                        std::vector<std::vector<VerifySlotDetail>>* detail = nullptr);
+                        std::vector<std::vector<VerifySlotDetail>>* detail = nullptr, uint32_t flags = 0);
 // the calling thread's last verify_many_device: plan, upload, kernels, download (ms)
 void verify_many_timing(double ms[4]);
 // Host code, no GPU: the shapes of the plan verify_many_device would launch for each proof ALONE (read back from the tables the

@@ -980,14 +980,28 @@ def _proof_handles(proofs):
     return (C.c_void_p * len(proofs))(*[p.h.value if isinstance(p.h, C.c_void_p) else p.h for p in proofs])
 
 
-def verify_many(proofs, cfg=None, lib=None, stream=0, checks=False):
+VERIFY_ARITH_ON_DEVICE = 1   # CM_VERIFY_ARITH_ON_DEVICE
+
+
+def _verify_flags(arith):
+    if arith not in ("host", "device"):
+        raise ValueError("arith must be 'host' or 'device'")
+    return VERIFY_ARITH_ON_DEVICE if arith == "device" else 0
+
+
+def verify_many(proofs, cfg=None, lib=None, stream=0, checks=False, arith="host"):
     """cm_verify_many (GPU, no CPU fallback): every proof's verdict from one batch — [(status, message)], the host verifier's own
     status and words per proof (checks=True: (status, message, CM_VERIFY_* id)).  Raises CmError for everything that is not a
-    verdict (no device, no proofs)."""
+    verdict (no device, no proofs).  arith="device": cm_verify_many_ex with CM_VERIFY_ARITH_ON_DEVICE, the public LogUp sum and
+    the OODS check decided by the GPU as well."""
     L = lib or proofs[0].L
     n = len(proofs)
     res = (VerifyResultC * max(n, 1))()
-    rc = L.cm_verify_many(_proof_handles(proofs), C.c_uint32(n), _cfg(cfg), res, C.c_uint64(stream))
+    flags = _verify_flags(arith)
+    if flags:
+        rc = L.cm_verify_many_ex(_proof_handles(proofs), C.c_uint32(n), _cfg(cfg), C.c_uint32(flags), res, C.c_uint64(stream))
+    else:
+        rc = L.cm_verify_many(_proof_handles(proofs), C.c_uint32(n), _cfg(cfg), res, C.c_uint64(stream))
     if rc not in (0, 11):
         raise _lib_error(L, rc)
     out = [(r.status, r.message.decode(errors="replace")) + ((r.check,) if checks else ()) for r in res[:n]]
@@ -1020,17 +1034,23 @@ def verify_plan_stats(proofs, cfg=None, lib=None):
     return [{name: getattr(s, name) for name, _ in VerifyStatsC._fields_[1:]} for s in out[:n]]
 
 
-def verify_many_detail(proofs, cfg=None, lib=None, stream=0):
+def verify_many_detail(proofs, cfg=None, lib=None, stream=0, arith="host"):
     """cm_verify_many_detail (GPU): per proof ((status, message, check), [(check, message, on_device, raised)]) — cm_verify_many's
-    verdict and every slot of the proof in the host verifier's order, from the same launches."""
+    verdict and every slot of the proof in the host verifier's order, from the same launches.  arith="device":
+    cm_verify_many_detail_ex with CM_VERIFY_ARITH_ON_DEVICE (the LogUp sum and the OODS check are the first two slots)."""
     L = lib or proofs[0].L
     n = len(proofs)
+    flags = _verify_flags(arith)
     res = (VerifyResultC * max(n, 1))()
     first = (C.c_uint32 * (n + 1))()
     cap = 64 * max(n, 1)
     while True:
         slots = (VerifySlotC * cap)()
-        rc = L.cm_verify_many_detail(_proof_handles(proofs), C.c_uint32(n), _cfg(cfg), res, slots, C.c_uint32(cap), first, C.c_uint64(stream))
+        if flags:
+            rc = L.cm_verify_many_detail_ex(_proof_handles(proofs), C.c_uint32(n), _cfg(cfg), C.c_uint32(flags), res, slots, C.c_uint32(cap),
+                                            first, C.c_uint64(stream))
+        else:
+            rc = L.cm_verify_many_detail(_proof_handles(proofs), C.c_uint32(n), _cfg(cfg), res, slots, C.c_uint32(cap), first, C.c_uint64(stream))
         if rc == 1 and first[n] > cap:
             cap = first[n]
             continue
@@ -1050,13 +1070,20 @@ def verify_many_timing(lib=None):
     return dict(zip(("plan", "upload", "kernels", "download"), list(ms)))
 
 
-def verify_run(proofs, cfg=None, lib=None, device=False):
+def verify_run(proofs, cfg=None, lib=None, device=False, arith="host"):
     """cm_verify_run (host code; device=True: cm_verify_run_device, the proofs checked on the GPU in one batch): (status, message);
-    0 = every proof verifies and each starts where its predecessor stopped."""
+    0 = every proof verifies and each starts where its predecessor stopped.  arith="device" (with device=True):
+    cm_verify_run_device_ex with CM_VERIFY_ARITH_ON_DEVICE."""
     L = lib or proofs[0].L
     n = len(proofs)
     hs = _proof_handles(proofs)
-    rc = (L.cm_verify_run_device if device else L.cm_verify_run)(hs, C.c_uint32(n), _cfg(cfg))
+    flags = _verify_flags(arith)
+    if flags and not device:
+        raise ValueError("arith='device' needs device=True")
+    if flags:
+        rc = L.cm_verify_run_device_ex(hs, C.c_uint32(n), _cfg(cfg), C.c_uint32(flags))
+    else:
+        rc = (L.cm_verify_run_device if device else L.cm_verify_run)(hs, C.c_uint32(n), _cfg(cfg))
     buf = C.create_string_buffer(1024)
     L.cm_last_error(buf, C.c_size_t(1024))
     return rc, buf.value.decode(errors="replace") if rc else ""
@@ -1064,10 +1091,112 @@ def verify_run(proofs, cfg=None, lib=None, device=False):
 
 Backend.run_begin = lambda self, initial_memory, initial_heap, ranges: Run(self, initial_memory, initial_heap, ranges)
 Backend.prove_run = lambda self, host_segments, inflight=3, cfg=None: prove_run(self, host_segments, inflight, cfg)
-Backend.verify_run = lambda self, proofs, cfg=None, device=False: verify_run(proofs, cfg, self.L, device)
-Backend.verify_many = lambda self, proofs, cfg=None: verify_many(proofs, cfg, self.L)
-Backend.verify_many_detail = lambda self, proofs, cfg=None: verify_many_detail(proofs, cfg, self.L)
+Backend.verify_run = lambda self, proofs, cfg=None, device=False, arith="host": verify_run(proofs, cfg, self.L, device, arith)
+Backend.verify_many = lambda self, proofs, cfg=None, arith="host": verify_many(proofs, cfg, self.L, arith=arith)
+Backend.verify_many_detail = lambda self, proofs, cfg=None, arith="host": verify_many_detail(proofs, cfg, self.L, arith=arith)
 Backend.verify_plan_stats = lambda self, proofs, cfg=None: verify_plan_stats(proofs, cfg, self.L)
+
+
+# ---- the verifier prelude's arithmetic, op level (include/cairom_hip.h: cm_public_logup_sum_op, cm_point_eval_op) ------------
+VERIFY_PUBLIC_SUM_ENTRIES = 256   # CM_PUBLIC_SUM_ENTRIES: entries per workgroup of k_verify_public_sum
+RELATIONS_WORDS = 4 * 8 * (1 + 16)  # CM_RELATIONS_WORDS
+
+
+class PublicSumJobC(C.Structure):
+    """cm_public_sum_job"""
+    _fields_ = [("head", C.c_uint32 * 7), ("n_program", C.c_uint32), ("n_input", C.c_uint32), ("n_output", C.c_uint32),
+                ("entries", C.c_void_p), ("rel_words", C.c_void_p)]
+
+
+class PointEvalJobC(C.Structure):
+    """cm_point_eval_job"""
+    _fields_ = [("component", C.c_uint32), ("n_tr_words", C.c_uint32), ("n_it_words", C.c_uint32), ("n_coeff_words", C.c_uint32),
+                ("tr", C.c_void_p), ("it", C.c_void_p), ("pp", C.c_void_p), ("rel_words", C.c_void_p), ("coeff", C.c_void_p),
+                ("shift", C.c_uint32 * 4)]
+
+
+def _u32_words(a):
+    return np.ascontiguousarray(a, dtype=np.uint32).reshape(-1)
+
+
+def _addr(a):
+    return a.ctypes.data if a.size else None
+
+
+def public_sum_job(head, program, inp, output, rel_words):
+    """(cm_public_sum_job, the arrays it points into): head = 7 words; each list = rows of the 7 words present, addr, value[4], clock"""
+    lists = [_u32_words(x) for x in (program, inp, output)]
+    for x in lists:
+        assert x.size % 7 == 0
+    entries = np.concatenate(lists) if sum(x.size for x in lists) else np.zeros(0, np.uint32)
+    rel = _u32_words(rel_words)
+    assert rel.size == RELATIONS_WORDS and len(head) == 7
+    j = PublicSumJobC()
+    j.head[:] = [int(w) for w in head]
+    j.n_program, j.n_input, j.n_output = (x.size // 7 for x in lists)
+    j.entries, j.rel_words = _addr(entries), _addr(rel)
+    return j, (entries, rel)
+
+
+def point_eval_job(component, tr, it, pp, rel_words, coeff, shift):
+    """(cm_point_eval_job, the arrays it points into): every array is flat uint32 words, four per QM31"""
+    keep = tuple(_u32_words(x) for x in (tr, it, pp, rel_words, coeff))
+    j = PointEvalJobC()
+    j.component = component
+    j.n_tr_words, j.n_it_words, j.n_coeff_words = keep[0].size, keep[1].size, keep[4].size
+    j.tr, j.it, j.pp, j.rel_words, j.coeff = (_addr(x) for x in keep)
+    j.shift[:] = [int(w) for w in shift]
+    return j, keep
+
+
+def _op_jobs(ctype, jobs):
+    arr = (ctype * max(len(jobs), 1))()
+    for k, (j, _) in enumerate(jobs):
+        arr[k] = j
+    return arr
+
+
+def _op_ck(L, rc):
+    if rc:
+        raise _lib_error(L, rc)
+
+
+def public_logup_sum(jobs, lib=None, stream=0):
+    """cm_public_logup_sum_op (GPU): jobs = [public_sum_job(...)]; one 4-word tuple per job"""
+    L = lib or load_library()
+    out = (C.c_uint32 * (4 * max(len(jobs), 1)))()
+    _op_ck(L, L.cm_public_logup_sum_op(_op_jobs(PublicSumJobC, jobs), C.c_uint32(len(jobs)), C.c_uint64(stream), out))
+    return [tuple(out[4 * k:4 * k + 4]) for k in range(len(jobs))]
+
+
+def public_logup_sum_host(job, lib=None):
+    """cm_public_logup_sum_host (host code, no GPU): the host verifier's initial_logup_sum of one job"""
+    L = lib or load_library()
+    out = (C.c_uint32 * 4)()
+    _op_ck(L, L.cm_public_logup_sum_host(C.byref(job[0]), out))
+    return tuple(out)
+
+
+def point_eval(jobs, lib=None, stream=0):
+    """cm_point_eval_op (GPU): jobs = [point_eval_job(...)]; one 4-word tuple per job"""
+    L = lib or load_library()
+    out = (C.c_uint32 * (4 * max(len(jobs), 1)))()
+    _op_ck(L, L.cm_point_eval_op(_op_jobs(PointEvalJobC, jobs), C.c_uint32(len(jobs)), C.c_uint64(stream), out))
+    return [tuple(out[4 * k:4 * k + 4]) for k in range(len(jobs))]
+
+
+def point_eval_host(job, lib=None):
+    """cm_point_eval_host (host code, no GPU): the host verifier's point_eval of one job"""
+    L = lib or load_library()
+    out = (C.c_uint32 * 4)()
+    _op_ck(L, L.cm_point_eval_host(C.byref(job[0]), out))
+    return tuple(out)
+
+
+Backend.public_logup_sum = lambda self, jobs, stream=0: public_logup_sum(jobs, self.L, stream)
+Backend.public_logup_sum_host = lambda self, job: public_logup_sum_host(job, self.L)
+Backend.point_eval = lambda self, jobs, stream=0: point_eval(jobs, self.L, stream)
+Backend.point_eval_host = lambda self, job: point_eval_host(job, self.L)
 
 
 # ---- device-memory accounting, estimate and budget (include/cairom_hip.h, revision 9) --------------------------

@@ -151,6 +151,15 @@ SHA_K = [
 SHA_H0 = [0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19]
 
 
+def padded_program(program, n_cells):
+    """`program` with data cells behind its last instruction, up to n_cells cells in all.  Every cell of a program is public, so
+    this is how a proof with a large public program is made (tools/verify_bench.py, tests/test_gpu_verify_prelude.py); the VM
+    takes such images, the data cells are never executed.  A data cell is four words below P."""
+    assert n_cells >= len(program)
+    pad = [[(7 * k + 1) % 1000, (k * k) % 977, 2**30, P - 1] for k in range(n_cells - len(program))]
+    return list(program) + pad
+
+
 def sha256_pad(msg: bytes):
     """FIPS 180-4 padding -> list of 32-bit big-endian words (a multiple of 16)."""
     ml = len(msg) * 8

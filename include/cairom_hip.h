@@ -55,7 +55,10 @@
  *    Still 10 (additive: one new function, no struct): cm_compose_transitions.
  *    Still 10 (additive: four new functions and two structs, nothing moved): cm_tail_piece, cm_tail_tables_out, cm_tail_grind_op,
  *    cm_tail_tables_op, cm_tail_tab_words, cm_tail_last_op.
- *    Still 10 (additive: one new function and one struct, nothing moved): cm_eval_job, cm_eval_at_points_op. */
+ *    Still 10 (additive: one new function and one struct, nothing moved): cm_eval_job, cm_eval_at_points_op.
+ *    Still 10 (additive: seven new functions, two structs and one flag, nothing moved): CM_VERIFY_ARITH_ON_DEVICE, cm_verify_many_ex,
+ *    cm_verify_many_detail_ex, cm_verify_run_device_ex, cm_public_sum_job, cm_public_logup_sum_op, cm_public_logup_sum_host,
+ *    cm_point_eval_job, cm_point_eval_op, cm_point_eval_host. */
 #define CM_ABI_REVISION 10
 
 #ifdef __cplusplus
@@ -756,7 +759,9 @@ int32_t cm_verify_many_timing(double ms[4]);
  * code, works without a GPU; the tests read it to prove that a config reaches a kernel's second stride trip or the LDS limit).
  * Set out[i].struct_size = sizeof(cm_verify_stats) before the call.  A proof decided in front of the queries reports its
  * CM_VERIFY_* id in early_check and zeros elsewhere.  A proof wider than the device limit still gets its stats: the refusal
- * stays with cm_verify_many. */
+ * stays with cm_verify_many.  Development aid: with CM_VERIFY_PLAN_MARKS=1 in the environment the call also prints one line per
+ * proof on stderr, how its planning time splits into replay and host checks, public LogUp sum, OODS evaluation and tables
+ * (tools/verify_bench.py --plan-split); nothing else reads the switch. */
 typedef struct cm_verify_stats {
   uint32_t struct_size;
   int32_t  early_check;        /* 0, or the CM_VERIFY_* id of the check that failed in front of the queries */
@@ -784,6 +789,56 @@ typedef struct cm_verify_slot {
 } cm_verify_slot;
 int32_t cm_verify_many_detail(const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected, cm_verify_result* results,
                               cm_verify_slot* slots, uint32_t cap_slots, uint32_t* slot_first, cm_stream_t s);
+/* ---- the prelude's arithmetic on the GPU (additive to revision 10) -----------------------------------------------------------
+ * Two checks in front of the queries are pure field arithmetic whose outcome the transcript does not depend on: the public LogUp
+ * sum (InvalidLogupSum: one QM31 inverse per register / root term and five per present public entry) and the OODS composition
+ * check (OodsNotMatching: all 34 components evaluated over the sampled mask values).  With CM_VERIFY_ARITH_ON_DEVICE in `flags`
+ * the host skips both while it replays the transcript and the device decides them: they become the FIRST TWO slots of the proof,
+ * CM_VERIFY_LOGUP_SUM then CM_VERIFY_OODS, each with its own flag word, in front of the four tree slots, decided by six more
+ * launches (k_verify_public_sum, k_verify_oods once per component group, k_verify_prelude_fin; the number depends on neither the
+ * batch nor the public entries) in front of k_verify_reduce: same stream, same upload, same single download.  The verdict rule is unchanged (the lowest raised or failed slot), and so are the verdicts and words.
+ * A host check that fails in front of the LogUp sum (config, structure, ProofOfWork(interaction)) still decides the proof early
+ * and sends nothing.  A host check that fails behind a deferred one (the sampled values' shape, Fri(InvalidNumFriLayers),
+ * Fri(LastLayerDegreeInvalid), ProofOfWork) becomes a planned slot behind the deferred slots, which still run: they may be the
+ * earlier failure.  The sampled values' shape sits between the two: the LogUp slot goes out and the OODS slot does not.
+ * flags == 0: exactly cm_verify_many / cm_verify_many_detail / cm_verify_run_device.  An unknown flag bit: status 1.
+ * cm_verify_many_timing reports the same four fields after either. */
+/* (a flag bit, not a check id: set apart from the CM_VERIFY_<check> <id> list above by its alignment) */
+#define CM_VERIFY_ARITH_ON_DEVICE   1u
+int32_t cm_verify_many_ex(const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected, uint32_t flags,
+                          cm_verify_result* results, cm_stream_t s);
+int32_t cm_verify_many_detail_ex(const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected, uint32_t flags,
+                                 cm_verify_result* results, cm_verify_slot* slots, uint32_t cap_slots, uint32_t* slot_first, cm_stream_t s);
+int32_t cm_verify_run_device_ex(const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected, uint32_t flags);
+/* Op-level entries: the same kernels on inputs the caller chooses, each with a host twin that calls the host verifier's own
+ * function (initial_logup_sum, point_eval) and nothing else.  Every argument is checked on the host before any launch (status 1
+ * and a message): null pointers, n_jobs outside 1..65536, a list longer than 2^24 entries, a component id outside 0..33, counts
+ * that differ from cm_component_info's, `present` above 1 and any field word not below P.
+ * cm_public_logup_sum_op: out = 4 words per job, initial_logup_sum of the job's public data under rel_words (k_verify_public_sum,
+ * one workgroup per CM_PUBLIC_SUM_ENTRIES entries of a list, then k_verify_prelude_fin).  An entry with present == 0 is
+ * skipped; a zero denominator contributes nothing, as inv(0) = 0 does on the host. */
+#define CM_PUBLIC_SUM_ENTRIES 256u
+#define CM_RELATIONS_WORDS (4u * CM_N_RELATIONS * (1u + CM_MAX_RELATION_SIZE))
+typedef struct cm_public_sum_job {
+  uint32_t head[7];          /* initial_pc, initial_fp, final_pc, final_fp, clock, initial_root, final_root */
+  uint32_t n_program, n_input, n_output;
+  const uint32_t* entries;   /* 7 words per entry (present, addr, value[4], clock): program, then input, then output; may be
+                              * NULL when all three counts are 0 */
+  const uint32_t* rel_words; /* CM_RELATIONS_WORDS words in cm_relations' layout */
+} cm_public_sum_job;
+int32_t cm_public_logup_sum_op(const cm_public_sum_job* jobs, uint32_t n_jobs, cm_stream_t s, uint32_t* out);
+int32_t cm_public_logup_sum_host(const cm_public_sum_job* job, uint32_t out4[4]);
+/* cm_point_eval_op: out = 4 words per job, sum_k coeff[k] * C_k of component `component` at the mask values (k_verify_oods, one
+ * lane per job, in job order).  tr: one QM31 per trace column; it: one QM31 per interaction column and a second one ([-1, 0]
+ * mask, previous row first) for each of the last four; pp: CM_N_PREPROCESSED QM31; coeff: one QM31 per constraint, base
+ * constraints first.  n_*_words count uint32 words (4 per QM31). */
+typedef struct cm_point_eval_job {
+  uint32_t component, n_tr_words, n_it_words, n_coeff_words;
+  const uint32_t *tr, *it, *pp, *rel_words, *coeff;
+  uint32_t shift[4];         /* the cumulative-sum shift, claimed_sum / 2^log_size */
+} cm_point_eval_job;
+int32_t cm_point_eval_op(const cm_point_eval_job* jobs, uint32_t n_jobs, cm_stream_t s, uint32_t* out);
+int32_t cm_point_eval_host(const cm_point_eval_job* job, uint32_t out4[4]);
 /* (Checking a whole run BEFORE proving it — cm_link_diff, cm_check_chain, cm_check_run — is declared behind the relation tracker
  * below: its records embed cm_check_report.) */
 /* Copy a device-resident ProverInput back (tests: device adapter vs host adapter). */

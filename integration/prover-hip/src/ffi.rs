@@ -486,6 +486,34 @@ pub struct cm_eval_job {
     pub shift_y: u32,
     pub reserved: u32,
 }
+/// `CM_VERIFY_ARITH_ON_DEVICE`: the public LogUp sum and the OODS check of every proof decided on the GPU (`cm_verify_many_ex`).
+pub const CM_VERIFY_ARITH_ON_DEVICE: u32 = 1;
+/// One public data set for `cm_public_logup_sum_op` / `cm_public_logup_sum_host` (test surface of the verifier's prelude kernels).
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct cm_public_sum_job {
+    pub head: [u32; 7],
+    pub n_program: u32,
+    pub n_input: u32,
+    pub n_output: u32,
+    pub entries: *const u32,
+    pub rel_words: *const u32,
+}
+/// One component's mask values for `cm_point_eval_op` / `cm_point_eval_host`.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct cm_point_eval_job {
+    pub component: u32,
+    pub n_tr_words: u32,
+    pub n_it_words: u32,
+    pub n_coeff_words: u32,
+    pub tr: *const u32,
+    pub it: *const u32,
+    pub pp: *const u32,
+    pub rel_words: *const u32,
+    pub coeff: *const u32,
+    pub shift: [u32; 4],
+}
 unsafe extern "C" {
     pub fn cm_init(device: i32) -> i32;
     pub fn cm_shutdown() -> i32;
@@ -579,6 +607,13 @@ unsafe extern "C" {
     pub fn cm_tail_tab_words(nq_pad: u32) -> u64;
     pub fn cm_tail_last_op(digest: *const u32, last: *const cm_handle, log_n: u32, log_keep: u32, ar: *const u32, n_ar_words: u32, digest_out: *mut u32, degree_flag: *mut u32, last_out: *mut u32, ar_out: *mut u32, nonce_cell: *mut u64, s: cm_stream_t) -> i32;
     pub fn cm_eval_at_points_op(jobs: *const cm_eval_job, n_jobs: u32, t4: *const u32, want_landing: u32, out: *mut u32, landing: *mut u32, s: cm_stream_t) -> i32;
+    pub fn cm_verify_many_ex(proofs: *const *const cm_proof, n: u32, expected: *const cm_pcs_config, flags: u32, results: *mut cm_verify_result, s: cm_stream_t) -> i32;
+    pub fn cm_verify_many_detail_ex(proofs: *const *const cm_proof, n: u32, expected: *const cm_pcs_config, flags: u32, results: *mut cm_verify_result, slots: *mut cm_verify_slot, cap_slots: u32, slot_first: *mut u32, s: cm_stream_t) -> i32;
+    pub fn cm_verify_run_device_ex(proofs: *const *const cm_proof, n: u32, expected: *const cm_pcs_config, flags: u32) -> i32;
+    pub fn cm_public_logup_sum_op(jobs: *const cm_public_sum_job, n_jobs: u32, s: cm_stream_t, out: *mut u32) -> i32;
+    pub fn cm_public_logup_sum_host(job: *const cm_public_sum_job, out4: *mut u32) -> i32;
+    pub fn cm_point_eval_op(jobs: *const cm_point_eval_job, n_jobs: u32, s: cm_stream_t, out: *mut u32) -> i32;
+    pub fn cm_point_eval_host(job: *const cm_point_eval_job, out4: *mut u32) -> i32;
     pub fn cm_proof_from_words(words: *const u32, n_words: u64, out: *mut *mut cm_proof) -> i32;
     pub fn cm_proof_words(p: *const cm_proof, words_out: *mut *const u32, n_out: *mut u64) -> i32;
     pub fn cm_proof_json(p: *const cm_proof, json_out: *mut *const c_char, len_out: *mut usize) -> i32;

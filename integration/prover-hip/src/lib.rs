@@ -241,11 +241,19 @@ pub fn verify_words_hip(proof: &ProofHandleRef, pcs_config: Option<PcsConfig>) -
 /// device hashes every decommitment path and folds the FRI layers).  One entry per proof, in order; the error carries the words
 /// `cm_verify_proof` would have left for that proof.  Panics when the batch cannot be run at all (no GPU, null proof).
 pub fn verify_cairo_m_many(proofs: &[ProofHandleRef], pcs_config: Option<PcsConfig>) -> Vec<Result<(), VerificationError>> {
+    verify_many_with_flags(proofs, pcs_config, 0)
+}
+/// `cm_verify_many_ex` with `CM_VERIFY_ARITH_ON_DEVICE`: as `verify_cairo_m_many`, with the public LogUp sum and the OODS
+/// composition check of every proof decided on the GPU as well (worth it for proofs with large public programs).  Same verdicts.
+pub fn verify_cairo_m_many_arith_on_device(proofs: &[ProofHandleRef], pcs_config: Option<PcsConfig>) -> Vec<Result<(), VerificationError>> {
+    verify_many_with_flags(proofs, pcs_config, CM_VERIFY_ARITH_ON_DEVICE)
+}
+fn verify_many_with_flags(proofs: &[ProofHandleRef], pcs_config: Option<PcsConfig>, flags: u32) -> Vec<Result<(), VerificationError>> {
     ensure_init();
     let cfg = pcs(&pcs_config.unwrap_or(REGULAR_96_BITS));
     let raw: Vec<*const cm_proof> = proofs.iter().map(|p| p.0).collect();
     let mut results = vec![cm_verify_result { status: 0, check: 0, message: [0; 160] }; raw.len()];
-    let rc = unsafe { cm_verify_many(raw.as_ptr(), raw.len() as u32, &cfg, results.as_mut_ptr(), 0) };
+    let rc = unsafe { cm_verify_many_ex(raw.as_ptr(), raw.len() as u32, &cfg, flags, results.as_mut_ptr(), 0) };
     assert!(rc == 0 || rc == 11, "cm_verify_many: status {rc}: {}", last_error());
     results
         .iter()
