@@ -24,6 +24,7 @@
 //   k_link_missing   for the lowest listed address that a given ascending set does not hold (a minimum).
 #include "../../include/cairom_hip.h"
 #include "segment_input.hpp"
+#include "mem_tree.hpp"
 #include <hipcub/hipcub.hpp>
 #include <algorithm>
 #include <cstring>
@@ -146,8 +147,6 @@ k_link_missing(const uint32_t* __restrict__ prev, const uint32_t* __restrict__ n
   if (lo >= n_set || set[lo] != a) atomicMin(missing, a);
 }
 
-inline dim3 blocks_for(uint64_t n) { return dim3((uint32_t)((n + LINK_BLOCK - 1) / LINK_BLOCK)); }
-
 void set_message(cm_link_report& rep, const std::string& m) {
   const size_t n = std::min(m.size(), sizeof(rep.message) - 1);
   memcpy(rep.message, m.data(), n);
@@ -169,7 +168,7 @@ void link_merge_enqueue(const uint32_t* a, uint64_t n_a, const uint32_t* b, uint
   m.state.alloc(LS_WORDS * 4); m.flag.alloc(n_slots * 4); m.src.alloc(n_slots * 8);
   CM_HIP(hipMemsetAsync(m.state.p, 0, LS_WORDS * 4, st));
   CM_HIP(hipMemsetAsync(m.flag.p, 0, n_slots * 4, st));
-  const dim3 ga = blocks_for(n_a), gb = blocks_for(n_b);
+  const dim3 ga = blocks_for(n_a, LINK_BLOCK), gb = blocks_for(n_b, LINK_BLOCK);
   const int vec16 = (((uintptr_t)a | (uintptr_t)b) & 15u) == 0;
   hipLaunchKernelGGL(k_link_classify, dim3(ga.x + gb.x), dim3(LINK_BLOCK), 0, st, a, (uint32_t)n_a, b, (uint32_t)n_b, ga.x, vec16, m.flag.u32(),
                      m.src.as<uint2>(), m.state.u32());
@@ -181,12 +180,12 @@ void link_merge_enqueue(const uint32_t* a, uint64_t n_a, const uint32_t* b, uint
   CM_HIP(hipcub::DeviceScan::ExclusiveSum(m.tmp.p, tmp_bytes, m.flag.u32(), m.pos.u32(), (int)n_slots, st));
 }
 void link_addresses_enqueue(const LinkMerge& m, uint32_t* out, uint32_t cap, hipStream_t st) {
-  hipLaunchKernelGGL(k_link_addresses, blocks_for(m.n_slots), dim3(LINK_BLOCK), 0, st, m.prev, m.next, (const uint32_t*)m.flag.u32(),
+  hipLaunchKernelGGL(k_link_addresses, blocks_for(m.n_slots, LINK_BLOCK), dim3(LINK_BLOCK), 0, st, m.prev, m.next, (const uint32_t*)m.flag.u32(),
                      (const uint32_t*)m.pos.u32(), (const uint2*)m.src.as<uint2>(), m.n_slots, cap, out);
 }
 void link_missing_enqueue(const LinkMerge& m, const uint32_t* set, uint32_t n_set, uint32_t* missing, hipStream_t st) {
   CM_HIP(hipMemsetAsync(missing, 0xff, 4, st));
-  hipLaunchKernelGGL(k_link_missing, blocks_for(m.n_slots), dim3(LINK_BLOCK), 0, st, m.prev, m.next, (const uint32_t*)m.flag.u32(),
+  hipLaunchKernelGGL(k_link_missing, blocks_for(m.n_slots, LINK_BLOCK), dim3(LINK_BLOCK), 0, st, m.prev, m.next, (const uint32_t*)m.flag.u32(),
                      (const uint2*)m.src.as<uint2>(), m.n_slots, set, n_set, missing);
 }
 
@@ -206,7 +205,7 @@ void link_diff(const DeviceInput& prev, const DeviceInput& next, uint32_t seg_in
     link_merge_enqueue(a, n_prev, b, n_next, true, m, st);
     DevBuf &state = m.state, &flag = m.flag, &pos = m.pos, &src = m.src;
     if (cap_dev)
-      hipLaunchKernelGGL(k_link_compact, blocks_for(n_slots), dim3(LINK_BLOCK), 0, st, a, (uint32_t)n_prev, b, (uint32_t)n_next, flag.u32(), pos.u32(),
+      hipLaunchKernelGGL(k_link_compact, blocks_for(n_slots, LINK_BLOCK), dim3(LINK_BLOCK), 0, st, a, (uint32_t)n_prev, b, (uint32_t)n_next, flag.u32(), pos.u32(),
                          src.as<uint2>(), (uint32_t)n_slots, (uint32_t)cap_dev, recs.u32());
     CM_HIP(hipGetLastError());
     // totals and the first cells in one round trip
@@ -270,20 +269,10 @@ void check_link_into(const DeviceInput& prev, const DeviceInput& next, uint32_t 
 }  // namespace cm
 
 // ================================================================= C ABI
-extern "C" int32_t cm_set_last_error(const char* msg);
-namespace {
-template <class F>
-int32_t link_guard(F&& f) {
-  try { f(); return 0; }
-  catch (const cm::CmError& e) { cm_set_last_error(e.what()); return e.code ? e.code : 1; }
-  catch (const std::exception& e) { cm_set_last_error(e.what()); return 1; }
-}
-}  // namespace
-
 extern "C" {
 int32_t cm_link_diff(const cm_device_input* prev, const cm_device_input* next, cm_link_report* report, cm_link_cell* cells, uint64_t cap,
                      uint64_t* n_total) {
-  return link_guard([&] {
+  return cm::abi_guard([&] {
     cm::require_device("cm_link_diff");
     CM_CHECK(prev && prev->d && next && next->d && report && n_total, "cm_link_diff: null argument");
     CM_CHECK(cells || cap == 0, "cm_link_diff: null cells with a capacity");
@@ -297,7 +286,7 @@ int32_t cm_link_diff(const cm_device_input* prev, const cm_device_input* next, c
   });
 }
 int32_t cm_check_chain(const cm_device_input* const* inputs, uint32_t n, cm_run_check* out, cm_link_cell* cells, uint64_t cap_per_link) {
-  return link_guard([&] {
+  return cm::abi_guard([&] {
     cm::require_device("cm_check_chain");
     CM_CHECK(n >= 1 && inputs && out, "cm_check_chain: no inputs / null output");
     CM_CHECK(cells || cap_per_link == 0, "cm_check_chain: null cells with a capacity");

@@ -288,14 +288,6 @@ k_compose_gather(uint32_t n_cells, const unsigned long long* __restrict__ uflag,
   out[pos] = words[woff[rj.x] + q];
 }
 
-inline dim3 blocks_for(uint64_t n) { return dim3((uint32_t)((n + SET_BLOCK - 1) / SET_BLOCK)); }
-
-// nothing of a call goes back to the pool while the stream still runs, on the error paths too (declared behind the buffers)
-struct StreamWait {
-  hipStream_t st;
-  ~StreamWait() { (void)hipStreamSynchronize(st); }
-};
-
 // ---- GPU path ----------------------------------------------------------------------------------------------------------
 cm_mem_transition* compose_device(const Chain& c) {
   std::unique_ptr<cm_mem_transition> tr = result_of(c);
@@ -316,7 +308,7 @@ cm_mem_transition* compose_device(const Chain& c) {
   const uint32_t* const d_words = d_in.u32() + c.at_words();
   // 2. the merge: equal addresses come out in chain order
   d_iota.alloc((size_t)N * 4); d_saddr.alloc((size_t)N * 4); d_se.alloc((size_t)N * 4);
-  hipLaunchKernelGGL(k_compose_iota, blocks_for(N), dim3(SET_BLOCK), 0, st, d_iota.u32(), N);
+  hipLaunchKernelGGL(k_compose_iota, blocks_for(N, SET_BLOCK), dim3(SET_BLOCK), 0, st, d_iota.u32(), N);
   size_t bytes = 0;
   CM_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, d_addr, d_saddr.u32(), (const uint32_t*)d_iota.u32(), d_se.u32(), (int)N, 0, 28, st));
   tmp_sort.alloc(bytes ? bytes : 4);
@@ -327,7 +319,7 @@ cm_mem_transition* compose_device(const Chain& c) {
   uint32_t* const d_trip = d_rank.u32() + N;
   const uint32_t no_seam = NO_SLOT;
   stage_upload(d_trip + CR_SEAM, &no_seam, 4, st);
-  hipLaunchKernelGGL(k_compose_heads, blocks_for((uint64_t)N + 1), dim3(SET_BLOCK), 0, st, (const uint32_t*)d_saddr.u32(), (const uint32_t*)d_se.u32(), N, d_old,
+  hipLaunchKernelGGL(k_compose_heads, blocks_for((uint64_t)N + 1, SET_BLOCK), dim3(SET_BLOCK), 0, st, (const uint32_t*)d_saddr.u32(), (const uint32_t*)d_se.u32(), N, d_old,
                      d_new, d_head.u32(), d_trip + CR_SEAM);
   bytes = 0;
   CM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, d_head.u32(), d_rank.u32(), (int)(N + 1), st));
@@ -364,30 +356,30 @@ cm_mem_transition* compose_device(const Chain& c) {
   uint32_t* const o_words = o_addr + nu;
   const uint32_t head0[COMPOSE_HEAD_WORDS] = {0, 0, 0, 0};
   stage_upload(o_head, head0, sizeof(head0), st);
-  hipLaunchKernelGGL(k_compose_cells, blocks_for(N), dim3(SET_BLOCK), 0, st, (const uint32_t*)d_saddr.u32(), (const uint32_t*)d_se.u32(),
+  hipLaunchKernelGGL(k_compose_cells, blocks_for(N, SET_BLOCK), dim3(SET_BLOCK), 0, st, (const uint32_t*)d_saddr.u32(), (const uint32_t*)d_se.u32(),
                      (const uint32_t*)d_head.u32(), (const uint32_t*)d_rank.u32(), N, d_off, n_parts, d_old, d_new, nu, o_addr, o_old, o_new, d_src.as<uint2>());
   // 5. the flags of U by the one rule, the flags of all parts in one pass and one scan
   set_flags_and_scan(o_addr, nu, uflag, uscan, tmp_u, st);
   const uint32_t n_pairs = SET_DEPTHS * N;
   pflag.alloc((size_t)n_pairs * 8);
   pscan.alloc((size_t)n_pairs * 8);
-  hipLaunchKernelGGL(k_compose_flags, blocks_for(n_pairs), dim3(SET_BLOCK), 0, st, d_addr, d_off, n_parts, N, pflag.as<unsigned long long>());
+  hipLaunchKernelGGL(k_compose_flags, blocks_for(n_pairs, SET_BLOCK), dim3(SET_BLOCK), 0, st, d_addr, d_off, n_parts, N, pflag.as<unsigned long long>());
   bytes = 0;
   CM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, pflag.as<unsigned long long>(), pscan.as<unsigned long long>(), (int)n_pairs, st));
   tmp_parts.alloc(bytes ? bytes : 4);
   CM_HIP(hipcub::DeviceScan::ExclusiveSum(tmp_parts.p, bytes, pflag.as<unsigned long long>(), pscan.as<unsigned long long>(), (int)n_pairs, st));
   // 6. the words
-  hipLaunchKernelGGL(k_compose_gather, blocks_for((uint64_t)SET_DEPTHS * nu), dim3(SET_BLOCK), 0, st, nu, (const unsigned long long*)uflag.as<unsigned long long>(),
+  hipLaunchKernelGGL(k_compose_gather, blocks_for((uint64_t)SET_DEPTHS * nu, SET_BLOCK), dim3(SET_BLOCK), 0, st, nu, (const unsigned long long*)uflag.as<unsigned long long>(),
                      (const unsigned long long*)uscan.as<unsigned long long>(), (const uint2*)d_src.as<uint2>(), d_off, n_parts, d_woff, d_words, N,
                      (const unsigned long long*)pflag.as<unsigned long long>(), (const unsigned long long*)pscan.as<unsigned long long>(), cap_words, o_words,
                      o_head);
   CM_HIP(hipGetLastError());
-  // 7. trips of at most SET_LAND_BYTES; the first carries the header, whose count says where the block ends
+  // 7. trips of at most TREE_LAND_BYTES; the first carries the header, whose count says where the block ends
   size_t total = head_bytes + 2 * val_bytes + addr_bytes + (size_t)cap_words * 4;
   uint32_t m_words = 0;
   std::vector<uint8_t> host(total);
   for (size_t done = 0, t = 0; done < total; t++) {
-    const size_t part = std::min(total - done, SET_LAND_BYTES);
+    const size_t part = std::min(total - done, TREE_LAND_BYTES);
     const void* land = stage_download_async(d_out.as<uint8_t>() + done, part, st);
     CM_HIP(hipStreamSynchronize(st));
     memcpy(host.data() + done, land, part);
@@ -421,10 +413,8 @@ cm_mem_transition* compose_device(const Chain& c) {
 }  // namespace cm
 
 // ================================================================= C ABI
-extern "C" int32_t cm_set_last_error(const char* msg);
-
 extern "C" int32_t cm_compose_transitions(const cm_mem_transition_view* parts, uint32_t n_parts, uint32_t device, cm_mem_transition** out) {
-  try {
+  return cm::abi_guard([&] {
     if (device == 1) cm::open_require_device("cm_compose_transitions");   // before any argument is looked at
     if (out) *out = nullptr;
     CM_CHECK(device <= 1, "cm_compose_transitions: `device` is not 0 (host code) or 1 (the GPU)");
@@ -432,7 +422,5 @@ extern "C" int32_t cm_compose_transitions(const cm_mem_transition_view* parts, u
     CM_CHECK(n_parts >= 1 && n_parts <= cm::COMPOSE_MAX_PARTS, "cm_compose_transitions: no parts, or more than 2^16 parts in one call: compose in groups");
     const cm::Chain c = cm::chain_of(parts, n_parts);
     *out = device ? cm::compose_device(c) : cm::compose_host(c);
-    return 0;
-  } catch (const cm::CmError& e) { cm_set_last_error(e.what()); return e.code ? e.code : 1; }
-  catch (const std::exception& e) { cm_set_last_error(e.what()); return 1; }
+  });
 }

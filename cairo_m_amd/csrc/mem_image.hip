@@ -12,10 +12,11 @@
 //   k_img_check      one lane per cell half: the current value (range_find in the depth-30 slice, zeros when absent), compared with
 //                    old_values when given; the lowest differing cell by atomicMin (a minimum: no order decides it).
 //   k_img_cells      one lane per cell: the two depth-30 records and the depth-29 record from the new value alone, three hashes.
-//   k_img_level      one lane per PARENT of S_{k+1} while S_k is wider than SET_TAIL: set_parent's index arithmetic; a child in S_k
+// then the shared ladder of set_fold.hpp with the image's policy, ImageFold:
+//   k_fold_level     one lane per PARENT of S_{k+1} while S_k is wider than SET_TAIL: set_parent's index arithmetic; a child in S_k
 //                    takes its new hash from the level below, a child that is not takes the old tree's word (range_find of the old
 //                    record of that pair, or the depth's default hash); the dirty record of depth 28 - k and the parent's hash.
-//   k_img_tail       one workgroup: the remaining depths in LDS with a barrier between them; the depth-1 record's parent is the root.
+//   k_fold_tail      one workgroup: the remaining depths in LDS with a barrier between them; the depth-1 record's parent is the root.
 // The steps, their widths and the kernel choice are cm_mem_set_plan's for the same addresses.  The commit:
 //   k_img_rank       one lane per dirty record: its bisection rank in the old slice of its depth and whether it is an insert;
 //   ExclusiveSum     of the insert flags, in node-list order;
@@ -30,6 +31,7 @@
 // Host images run the same fold in plain C++ (host_update, host_merge): same roots, same node words, same statuses and messages.
 #include "../../include/cairom_hip.h"
 #include "mem_transition.hpp"
+#include "set_fold.hpp"
 #include "mem_open.hpp"
 #include <hipcub/hipcub.hpp>
 #include <algorithm>
@@ -127,52 +129,34 @@ struct ImgTree {
   uint4* dirty;
 };
 
-// parent r of S_{k+1}, where in[c] = the new hash of node c of S_k: the dirty record of depth 28 - k at slot `at`, the parent's hash
-__device__ __forceinline__ uint32_t img_parent(const SetView& s, const ImgTree& tr, const SetDefaults& dflt, const uint32_t* in, uint32_t k, uint32_t r,
-                                               uint32_t at) {
-  // (the parent's head lane is the head lane of its first child: set_parent's arithmetic, which also needs the address here)
-  const uint32_t i = k + 1 < SET_DEPTHS ? s.heads[(uint32_t)(s.scan[(size_t)(k + 1) * s.n] >> 32) + r] : 0u;
-  const size_t t = (size_t)k * s.n + i;
-  const uint32_t c = (uint32_t)(s.scan[t] >> 32) - (uint32_t)(s.scan[(size_t)k * s.n] >> 32);
-  const uint32_t x = s.a[i] >> k, depth = SET_DEPTHS - k, me = in[c];
-  uint32_t l, rr, lm = 1u, rm = 1u;
-  if (!((uint32_t)s.flag[t] & 1u)) { l = me; rr = in[c + 1]; }   // an even node whose successor in S_k is x + 1
-  else {
-    const uint32_t* const nd = range_find(tr.nodes, tr.off, depth, x & ~1u);
-    const bool odd = x & 1u;
-    const uint32_t w = nd ? (odd ? nd[2] : nd[3]) : dflt.h[depth], wm = nd ? (odd ? nd[5] : nd[6]) : 0u;
-    l = odd ? w : me; rr = odd ? me : w;
-    lm = odd ? wm : 1u; rm = odd ? 1u : wm;
+// The image's policy of the shared ladder (set_fold.hpp): a node is its new hash; a child that is not in S_k takes the OLD tree's
+// word, so no record of sibling words is read and nothing is checked; every parent files the dirty record of its depth.
+struct ImageFold {
+  using Node = uint32_t;
+  static constexpr bool CHECKS = false;
+  ImgTree tr;
+  TreeDefaults dflt;
+  ImgSlices sl;
+  // parent r of S_{k+1}, where in[c] = the new hash of node c of S_k: the dirty record of depth 28 - k at slot sl.o[2 + k] + r,
+  // the parent's hash
+  __device__ __forceinline__ uint32_t parent(const SetView& s, const uint32_t* in, uint32_t k, uint32_t r, bool&) const {
+    const SetParent p = set_parent(s, k, r);
+    const uint32_t depth = SET_DEPTHS - k, me = in[p.c];
+    uint32_t l, rr, lm = 1u, rm = 1u;
+    if (p.paired) { l = me; rr = in[p.c + 1]; }
+    else {
+      const uint32_t empty = dflt.h[depth];   // (read as a value in front of the lookup: merged with nd's loads it would put the policy in scratch)
+      const uint32_t* const nd = range_find(tr.nodes, tr.off, depth, p.x & ~1u);
+      const uint32_t w = nd ? (p.odd ? nd[2] : nd[3]) : empty, wm = nd ? (p.odd ? nd[5] : nd[6]) : 0u;
+      l = p.odd ? w : me; rr = p.odd ? me : w;
+      lm = p.odd ? wm : 1u; rm = p.odd ? 1u : wm;
+    }
+    const uint32_t h = host::poseidon2_hash(l, rr);
+    put_node(tr.dirty, sl.o[2 + k] + r, p.x & ~1u, depth, l, rr, h, lm, rm);
+    return h;
   }
-  const uint32_t h = host::poseidon2_hash(l, rr);
-  put_node(tr.dirty, at, x & ~1u, depth, l, rr, h, lm, rm);
-  return h;
-}
-
-// in = S_k, out = S_{k+1} (n_out nodes); base = the first dirty slot of depth 28 - k
-__global__ void __launch_bounds__(SET_BLOCK)
-k_img_level(SetView s, ImgTree tr, SetDefaults dflt, const uint32_t* __restrict__ in, uint32_t k, uint32_t n_out, uint32_t base, uint32_t* __restrict__ out) {
-  const uint32_t r = blockIdx.x * SET_BLOCK + threadIdx.x;
-  if (r >= n_out) return;
-  out[r] = img_parent(s, tr, dflt, in, k, r, base + r);
-}
-
-// S_k0 (w.w[k0] <= SET_TAIL nodes) up to the root, which goes to dev[IW_ROOT]
-__global__ void __launch_bounds__(SET_TAIL)
-k_img_tail(SetView s, ImgTree tr, SetDefaults dflt, const uint32_t* __restrict__ in, SetWidths w, ImgSlices sl, uint32_t k0, uint32_t* __restrict__ dev) {
-  __shared__ uint32_t level[2][SET_TAIL];
-  const uint32_t t = threadIdx.x;
-  if (t < w.w[k0]) level[0][t] = in[t];
-  __syncthreads();
-  uint32_t cur = 0;
-#pragma unroll 1
-  for (uint32_t k = k0; k < SET_DEPTHS; k++) {
-    if (t < w.w[k + 1]) level[cur ^ 1][t] = img_parent(s, tr, dflt, level[cur], k, t, sl.o[2 + k] + t);
-    __syncthreads();
-    cur ^= 1;
-  }
-  if (t == 0) dev[IW_ROOT] = level[cur][0];
-}
+  __device__ __forceinline__ void finish(uint32_t top, bool, uint32_t* dev) const { dev[IW_ROOT] = top; }
+};
 
 // the slice q of dirty record j: o[q] <= j < o[q + 1]
 __device__ __forceinline__ uint32_t img_slice_of(const ImgSlices& sl, uint32_t j) {
@@ -237,25 +221,6 @@ k_img_offsets(const uint32_t* __restrict__ off, ImgSlices sl, const uint32_t* __
   const uint32_t q = threadIdx.x;
   if (blockIdx.x || q > IMG_SLICES) return;
   out[q] = off[q] + scan[sl.o[q]];
-}
-
-inline dim3 blocks_for(uint64_t n) { return dim3((uint32_t)((n + SET_BLOCK - 1) / SET_BLOCK)); }
-
-// nothing of a call goes back to the pool while the stream still runs, on the error paths too (declared behind the buffers)
-struct StreamWait {
-  hipStream_t st;
-  ~StreamWait() { (void)hipStreamSynchronize(st); }
-};
-
-// `bytes` of device memory at `src` into `dst` through the pinned landing buffer, at most SET_LAND_BYTES a trip; waits for st
-void download(void* dst, const void* src, size_t bytes, hipStream_t st) {
-  for (size_t done = 0; done < bytes;) {
-    const size_t m = std::min(bytes - done, SET_LAND_BYTES);
-    const void* land = stage_download_async((const uint8_t*)src + done, m, st);
-    CM_HIP(hipStreamSynchronize(st));
-    memcpy((uint8_t*)dst + done, land, m);
-    done += m;
-  }
 }
 
 [[noreturn]] void reject(const std::string& why) { throw CmError(11, "memory image: " + why); }
@@ -363,13 +328,6 @@ std::vector<cm_merkle_node> host_merge(const std::vector<cm_merkle_node>& old_no
 }
 
 // ---- device images -------------------------------------------------------------------------------------------------------
-SetDefaults defaults() {
-  SetDefaults dflt;
-  const std::vector<uint32_t>& dh = host::poseidon2_default_hashes();
-  for (uint32_t d = 0; d <= air::TREE_HEIGHT; d++) dflt.h[d] = dh[d];
-  return dflt;
-}
-
 void device_create(cm_mem_image& img, const uint32_t* a, const uint32_t* values, uint32_t n) {
   bind_thread_to_library_device();
   const hipStream_t st = thread_main_stream();
@@ -380,7 +338,7 @@ void device_create(cm_mem_image& img, const uint32_t* a, const uint32_t* values,
     stage_upload(d_addr.p, a, (size_t)n * 4, st);
     stage_upload(d_vals.p, values, (size_t)n * 16, st);
     leaves_tree_build(n, [&](uint32_t* idx, uint32_t* val, uint32_t* mult) {
-      hipLaunchKernelGGL(k_img_leaves, blocks_for(n), dim3(SET_BLOCK), 0, st, (const uint32_t*)d_addr.u32(), (const uint4*)d_vals.as<uint4>(), n,
+      hipLaunchKernelGGL(k_img_leaves, blocks_for(n, SET_BLOCK), dim3(SET_BLOCK), 0, st, (const uint32_t*)d_addr.u32(), (const uint4*)d_vals.as<uint4>(), n,
                          reinterpret_cast<uint4*>(idx), reinterpret_cast<uint4*>(val), reinterpret_cast<uint4*>(mult));
     }, img.d_nodes, img.n_nodes, img.root, st);
   } else {
@@ -406,13 +364,11 @@ void device_update(const cm_mem_image& img, const uint32_t* a, uint32_t n, const
   const ImgSlices sl = slices_of(steps, n);
   const uint32_t n_dirty = sl.o[IMG_SLICES], n_old = (uint32_t)img.n_nodes;
   CM_CHECK((uint64_t)n_old + n_dirty < (1ull << 32), "memory image: the tree is too large");
-  SetWidths w;
-  uint64_t n_heads = 0;
-  for (uint32_t s = 0; s < SET_STEPS; s++) { w.w[s] = steps[s].n_nodes; if (s < SET_DEPTHS) n_heads += w.w[s]; }
   uint32_t words0[IMG_DEV_WORDS] = {0};
   words0[IW_MISMATCH] = NO_CELL;
-  DevBuf d_addr((size_t)n * 4), d_new((size_t)n * 16), d_old, d_cur((size_t)n * 16), d_heads(n_heads * 4), d_a((size_t)n * 4), d_b((size_t)n * 4),
-      d_dirty((size_t)n_dirty * 32), d_rank((size_t)n_dirty * 4), d_ins(((size_t)n_dirty + 1) * 4), d_scan(((size_t)n_dirty + 1) * 4), flag, scan, tmp, tmp_ins;
+  DevBuf d_addr((size_t)n * 4), d_new((size_t)n * 16), d_old, d_cur((size_t)n * 16), d_a((size_t)n * 4), d_b((size_t)n * 4),
+      d_dirty((size_t)n_dirty * 32), d_rank((size_t)n_dirty * 4), d_ins(((size_t)n_dirty + 1) * 4), d_scan(((size_t)n_dirty + 1) * 4), tmp_ins;
+  SetFold f;
   up.words.alloc(IMG_DEV_WORDS * 4);
   up.nodes.alloc(((size_t)n_old + n_dirty) * 32);
   const StreamWait wait{st};
@@ -423,32 +379,20 @@ void device_update(const cm_mem_image& img, const uint32_t* a, uint32_t n, const
   const uint32_t* const nodes = img.d_nodes.u32();
   const uint32_t* const off = img.d_off();
   // the cells: the current values against the old ones, and the three self-contained records of every cell
-  hipLaunchKernelGGL(k_img_check, blocks_for(2ull * n), dim3(SET_BLOCK), 0, st, nodes, off, (const uint32_t*)d_addr.u32(), n,
+  hipLaunchKernelGGL(k_img_check, blocks_for(2ull * n, SET_BLOCK), dim3(SET_BLOCK), 0, st, nodes, off, (const uint32_t*)d_addr.u32(), n,
                      (const uint32_t*)(ov ? d_old.u32() : nullptr), d_cur.u32(), up.words.u32());
-  uint32_t* in = d_a.u32();
-  uint32_t* out = d_b.u32();
-  hipLaunchKernelGGL(k_img_cells, blocks_for(n), dim3(SET_BLOCK), 0, st, (const uint32_t*)d_addr.u32(), (const uint4*)d_new.as<uint4>(), n, d_dirty.as<uint4>(), in);
+  hipLaunchKernelGGL(k_img_cells, blocks_for(n, SET_BLOCK), dim3(SET_BLOCK), 0, st, (const uint32_t*)d_addr.u32(), (const uint4*)d_new.as<uint4>(), n, d_dirty.as<uint4>(),
+                     d_a.u32());
   // the levels, launched from the plan's records as the set verifier's
-  set_flags_and_scan(d_addr.u32(), n, flag, scan, tmp, st);
-  set_heads_enqueue(flag, scan, n, (uint32_t)n_heads, d_heads.u32(), st);
-  const SetView view{d_addr.u32(), flag.as<unsigned long long>(), scan.as<unsigned long long>(), d_heads.u32(), nullptr, n, 0};
-  const ImgTree tree{nodes, off, d_dirty.as<uint4>()};
-  const SetDefaults dflt = defaults();
-  uint32_t s = 1;
-  for (; s < SET_STEPS && steps[s].kernel == SET_K_LEVEL; s++) {
-    hipLaunchKernelGGL(k_img_level, blocks_for(steps[s].n_nodes), dim3(SET_BLOCK), 0, st, view, tree, dflt, (const uint32_t*)in, s - 1, steps[s].n_nodes,
-                       sl.o[1 + s], out);
-    std::swap(in, out);
-  }
-  CM_CHECK(s < SET_STEPS && steps[s].kernel == SET_K_TAIL && w.w[s - 1] <= SET_TAIL, "memory image: the plan has no tail");
-  hipLaunchKernelGGL(k_img_tail, dim3(1), dim3(SET_TAIL), 0, st, view, tree, dflt, (const uint32_t*)in, w, sl, s - 1, up.words.u32());
+  set_fold_prepare(f, d_addr.u32(), n, steps, nullptr, 0, st);
+  set_fold_enqueue(f, steps, ImageFold{ImgTree{nodes, off, d_dirty.as<uint4>()}, tree_defaults(), sl}, d_a.u32(), d_b.u32(), up.words.u32(), "memory image", st);
   // the merge into a new list; the handle keeps the old one until every check has passed
-  hipLaunchKernelGGL(k_img_rank, blocks_for((uint64_t)n_dirty + 1), dim3(SET_BLOCK), 0, st, nodes, off, (const uint32_t*)d_dirty.u32(), sl, d_rank.u32(), d_ins.u32());
+  hipLaunchKernelGGL(k_img_rank, blocks_for((uint64_t)n_dirty + 1, SET_BLOCK), dim3(SET_BLOCK), 0, st, nodes, off, (const uint32_t*)d_dirty.u32(), sl, d_rank.u32(), d_ins.u32());
   size_t bytes = 0;
   CM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, d_ins.u32(), d_scan.u32(), (int)(n_dirty + 1), st));
   tmp_ins.alloc(bytes ? bytes : 4);
   CM_HIP(hipcub::DeviceScan::ExclusiveSum(tmp_ins.p, bytes, d_ins.u32(), d_scan.u32(), (int)(n_dirty + 1), st));
-  hipLaunchKernelGGL(k_img_merge, blocks_for((uint64_t)n_old + n_dirty), dim3(SET_BLOCK), 0, st, (const uint4*)img.d_nodes.as<uint4>(), n_old,
+  hipLaunchKernelGGL(k_img_merge, blocks_for((uint64_t)n_old + n_dirty, SET_BLOCK), dim3(SET_BLOCK), 0, st, (const uint4*)img.d_nodes.as<uint4>(), n_old,
                      (const uint4*)d_dirty.as<uint4>(), sl, (const uint32_t*)d_rank.u32(), (const uint32_t*)d_scan.u32(), n_old + n_dirty, up.nodes.as<uint4>());
   hipLaunchKernelGGL(k_img_offsets, dim3(1), dim3(64), 0, st, off, sl, (const uint32_t*)d_scan.u32(), up.words.u32() + IW_OFF);
   CM_HIP(hipGetLastError());
@@ -541,19 +485,9 @@ void require_device_image(const cm_mem_image& img, const char* who) {
 }  // namespace cm
 
 // ================================================================= C ABI
-extern "C" int32_t cm_set_last_error(const char* msg);
-namespace {
-template <class F>
-int32_t image_guard(F&& f) {
-  try { f(); return 0; }
-  catch (const cm::CmError& e) { cm_set_last_error(e.what()); return e.code ? e.code : 1; }
-  catch (const std::exception& e) { cm_set_last_error(e.what()); return 1; }
-}
-}  // namespace
-
 extern "C" {
 int32_t cm_mem_image_create(const uint32_t* addresses, const uint32_t* values, uint64_t n, uint32_t device, cm_mem_image** out) {
-  return image_guard([&] {
+  return cm::abi_guard([&] {
     if (device == 1) cm::open_require_device("cm_mem_image_create");   // before any argument is looked at
     if (out) *out = nullptr;
     CM_CHECK(device <= 1, "cm_mem_image_create: `device` is not 0 (host memory) or 1 (the GPU)");
@@ -581,21 +515,21 @@ int32_t cm_mem_image_create(const uint32_t* addresses, const uint32_t* values, u
   });
 }
 int32_t cm_mem_image_free(cm_mem_image* img) {
-  return image_guard([&] {
+  return cm::abi_guard([&] {
     if (!img) return;
     if (img->device) cm::bind_thread_to_library_device();
     delete img;
   });
 }
 int32_t cm_mem_image_root(cm_mem_image* img, uint32_t* root) {
-  return image_guard([&] {
+  return cm::abi_guard([&] {
     CM_CHECK(img && root, "cm_mem_image_root: null argument");
     std::lock_guard<std::mutex> lk(img->mu);
     *root = img->root;
   });
 }
 int32_t cm_mem_image_stats_get(cm_mem_image* img, cm_mem_image_stats* out) {
-  return image_guard([&] {
+  return cm::abi_guard([&] {
     CM_CHECK(img && out, "cm_mem_image_stats_get: null argument");
     CM_CHECK(out->struct_size >= sizeof(cm_mem_image_stats),
              "cm_mem_image_stats_get: struct_size does not cover cm_mem_image_stats (set it to sizeof(cm_mem_image_stats))");
@@ -610,7 +544,7 @@ int32_t cm_mem_image_stats_get(cm_mem_image* img, cm_mem_image_stats* out) {
   });
 }
 int32_t cm_mem_image_read(cm_mem_image* img, const uint32_t* addresses, uint64_t n, uint32_t* values) {
-  return image_guard([&] {
+  return cm::abi_guard([&] {
     CM_CHECK(img && (n == 0 || (addresses && values)), "cm_mem_image_read: null argument");
     CM_CHECK(n <= cm::IMG_MAX_READ, "cm_mem_image_read: more than 2^24 addresses in one call: split it");
     for (uint64_t i = 0; i < n; i++)
@@ -624,14 +558,14 @@ int32_t cm_mem_image_read(cm_mem_image* img, const uint32_t* addresses, uint64_t
     cm::DevBuf d_addr(n * 4), d_vals(n * 16);
     const cm::StreamWait wait{st};
     cm::stage_upload(d_addr.p, addresses, n * 4, st);
-    hipLaunchKernelGGL(cm::k_img_read, cm::blocks_for(2 * n), dim3(cm::SET_BLOCK), 0, st, (const uint32_t*)img->d_nodes.u32(), img->d_off(),
+    hipLaunchKernelGGL(cm::k_img_read, cm::blocks_for(2 * n, cm::SET_BLOCK), dim3(cm::SET_BLOCK), 0, st, (const uint32_t*)img->d_nodes.u32(), img->d_off(),
                        (const uint32_t*)d_addr.u32(), (uint32_t)n, d_vals.u32());
     CM_HIP(hipGetLastError());
     cm::download(values, d_vals.p, n * 16, st);
   });
 }
 int32_t cm_mem_image_nodes(cm_mem_image* img, cm_merkle_node* nodes, uint64_t cap, uint64_t* n_total) {
-  return image_guard([&] {
+  return cm::abi_guard([&] {
     CM_CHECK(img && n_total, "cm_mem_image_nodes: null argument");
     CM_CHECK(nodes || cap == 0, "cm_mem_image_nodes: null nodes with a capacity");
     std::lock_guard<std::mutex> lk(img->mu);
@@ -644,7 +578,7 @@ int32_t cm_mem_image_nodes(cm_mem_image* img, cm_merkle_node* nodes, uint64_t ca
   });
 }
 int32_t cm_mem_image_cells(cm_mem_image* img, uint32_t* addresses, uint32_t* values, uint64_t cap, uint64_t* n_total) {
-  return image_guard([&] {
+  return cm::abi_guard([&] {
     CM_CHECK(img && n_total, "cm_mem_image_cells: null argument");
     CM_CHECK((addresses && values) || cap == 0, "cm_mem_image_cells: null arrays with a capacity");
     std::lock_guard<std::mutex> lk(img->mu);
@@ -671,7 +605,7 @@ int32_t cm_mem_image_cells(cm_mem_image* img, uint32_t* addresses, uint32_t* val
 }
 int32_t cm_mem_image_apply(cm_mem_image* img, const uint32_t* addresses, const uint32_t* new_values, uint64_t n, const uint32_t* old_values,
                            const uint32_t* root_before, const uint32_t* root_after, uint32_t* root_out, cm_mem_transition** record_out) {
-  return image_guard([&] {
+  return cm::abi_guard([&] {
     if (record_out) *record_out = nullptr;
     CM_CHECK(img && addresses && new_values && root_out, "cm_mem_image_apply: null argument");
     cm::check_update_addresses("cm_mem_image_apply", addresses, n);
@@ -680,7 +614,7 @@ int32_t cm_mem_image_apply(cm_mem_image* img, const uint32_t* addresses, const u
   });
 }
 int32_t cm_mem_image_apply_transition(cm_mem_image* img, const cm_mem_transition_view* t, cm_mem_transition** record_out) {
-  return image_guard([&] {
+  return cm::abi_guard([&] {
     if (record_out) *record_out = nullptr;
     CM_CHECK(img && t, "cm_mem_image_apply_transition: null argument");
     CM_CHECK(t->struct_size >= sizeof(cm_mem_transition_view),
@@ -709,7 +643,7 @@ int32_t cm_mem_image_apply_transition(cm_mem_image* img, const cm_mem_transition
 // The openings: thin calls into the openers of mem_open.hip, mem_range.hip and mem_set.hip over the image's node list; the
 // contract of their cm_run_open_* twins.  Device images only.
 int32_t cm_mem_image_open_memory(cm_mem_image* img, const uint32_t* addresses, uint64_t n, cm_mem_opening* out, uint32_t* root) {
-  return image_guard([&] {
+  return cm::abi_guard([&] {
     CM_CHECK(img && root, "cm_mem_image_open_memory: null argument");
     cm::open_check_addresses("cm_mem_image_open_memory", addresses, n, out);
     std::lock_guard<std::mutex> lk(img->mu);
@@ -720,7 +654,7 @@ int32_t cm_mem_image_open_memory(cm_mem_image* img, const uint32_t* addresses, u
   });
 }
 int32_t cm_mem_image_open_memory_range(cm_mem_image* img, uint32_t start, uint32_t n_cells, uint32_t* values, cm_mem_range_opening* out, uint32_t* root) {
-  return image_guard([&] {
+  return cm::abi_guard([&] {
     CM_CHECK(img && root, "cm_mem_image_open_memory_range: null argument");
     cm::open_range_check("cm_mem_image_open_memory_range", start, n_cells, values, out);
     std::lock_guard<std::mutex> lk(img->mu);
@@ -732,7 +666,7 @@ int32_t cm_mem_image_open_memory_range(cm_mem_image* img, uint32_t start, uint32
 }
 int32_t cm_mem_image_open_memory_set(cm_mem_image* img, const uint32_t* addresses, uint64_t n, uint32_t* values, uint32_t* siblings, uint32_t cap_siblings,
                                      uint32_t* n_siblings, uint32_t* root) {
-  return image_guard([&] {
+  return cm::abi_guard([&] {
     CM_CHECK(img && root, "cm_mem_image_open_memory_set: null argument");
     cm::open_set_check("cm_mem_image_open_memory_set", addresses, n, values, siblings, cap_siblings, n_siblings);
     std::lock_guard<std::mutex> lk(img->mu);

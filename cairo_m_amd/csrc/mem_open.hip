@@ -24,6 +24,7 @@
 //   k_image_leaves        one lane per cell of a run's image: its four leaves, `hi` reversed into ascending address order.
 #include "../../include/cairom_hip.h"
 #include "mem_open.hpp"
+#include "mem_tree.hpp"
 #include "segment_input.hpp"
 #include "host_adapter.hpp"
 #include <cstring>
@@ -41,8 +42,6 @@ enum : uint32_t { OW_ADDRESS = 0, OW_PRESENT = 1, OW_VALUE = 2, OW_SIBLINGS = 6 
 
 static_assert(sizeof(cm_mem_opening) == 4 * OPEN_WORDS && sizeof(cm_merkle_node) == 4 * NODE_WORDS, "plain words, sizes as the header states them");
 static_assert(air::TREE_HEIGHT == 30 && ADDRESS_SPACE == (1u << 28), "a cell is four leaves of a tree of height 30");
-
-struct OpenDefaults { uint32_t h[air::TREE_HEIGHT + 1]; };   // h[d] = the hash of an empty subtree whose top is at depth d
 
 // ---- one opening, host and device ------------------------------------------------------------------------------------------
 // 0 = well formed; 1 address, 2 present, 3 + i value word i, 7 + k sibling k, 35 = absent with a non-zero value
@@ -90,7 +89,7 @@ k_open_depth_offsets(const uint32_t* __restrict__ nodes, uint32_t n_nodes, uint3
 
 __global__ void __launch_bounds__(OPEN_BLOCK)
 k_open_paths(const uint32_t* __restrict__ nodes, const uint32_t* __restrict__ off, const uint32_t* __restrict__ addresses, uint32_t n,
-             OpenDefaults dflt, uint32_t* __restrict__ out) {
+             TreeDefaults dflt, uint32_t* __restrict__ out) {
   const uint64_t t = (uint64_t)blockIdx.x * OPEN_BLOCK + threadIdx.x;
   const uint32_t q = (uint32_t)(t / OPEN_LANES), slot = (uint32_t)(t % OPEN_LANES);
   if (q >= n || slot >= OPEN_SIBLINGS + 2) return;
@@ -140,9 +139,6 @@ k_image_leaves(const uint4* __restrict__ lo, uint32_t n_lo, const uint4* __restr
   mult[t] = make_uint4(1u, 1u, 1u, 1u);
 }
 
-inline dim3 blocks_for(uint64_t n, uint32_t block) { return dim3((uint32_t)((n + block - 1) / block)); }
-inline hipStream_t stream_or_own(cm_stream_t s) { return s ? (hipStream_t)(uintptr_t)s : thread_main_stream(); }
-
 }  // namespace
 
 void open_require_device(const char* who) {
@@ -176,9 +172,7 @@ void image_leaves_enqueue(const uint32_t* lo, uint32_t n_lo, const uint32_t* hi,
 void open_paths(const cm_merkle_node* nodes, uint64_t n_nodes, const uint32_t* addresses, uint64_t n, cm_mem_opening* out, hipStream_t st) {
   if (!n) return;
   CM_CHECK(n <= OPEN_MAX_BATCH && n_nodes < (1ull << 32), "memory openings: the batch or the tree is too large");
-  OpenDefaults dflt;
-  const std::vector<uint32_t>& dh = host::poseidon2_default_hashes();
-  for (uint32_t d = 0; d <= air::TREE_HEIGHT; d++) dflt.h[d] = dh[d];
+  const TreeDefaults dflt = tree_defaults();
   DevBuf d_addr(n * 4), d_off((air::TREE_HEIGHT + 1) * 4), d_out(n * sizeof(cm_mem_opening));
   stage_upload(d_addr.p, addresses, n * 4, st);
   hipLaunchKernelGGL(k_open_depth_offsets, dim3(1), dim3(64), 0, st, reinterpret_cast<const uint32_t*>(nodes), (uint32_t)n_nodes, d_off.u32());
@@ -205,19 +199,9 @@ void verify_openings_device(uint32_t root, const cm_mem_opening* openings, uint6
 }  // namespace cm
 
 // ================================================================= C ABI
-extern "C" int32_t cm_set_last_error(const char* msg);
-namespace {
-template <class F>
-int32_t open_guard(F&& f) {
-  try { f(); return 0; }
-  catch (const cm::CmError& e) { cm_set_last_error(e.what()); return e.code ? e.code : 1; }
-  catch (const std::exception& e) { cm_set_last_error(e.what()); return 1; }
-}
-}  // namespace
-
 extern "C" {
 int32_t cm_input_open_memory(const cm_device_input* in, uint32_t which, const uint32_t* addresses, uint64_t n, cm_mem_opening* out, uint32_t* root) {
-  return open_guard([&] {
+  return cm::abi_guard([&] {
     cm::open_require_device("cm_input_open_memory");
     CM_CHECK(in && in->d && root, "cm_input_open_memory: null argument");
     CM_CHECK(which <= 1, "cm_input_open_memory: `which` is not 0 (the initial tree) or 1 (the final tree)");
@@ -230,7 +214,7 @@ int32_t cm_input_open_memory(const cm_device_input* in, uint32_t which, const ui
   });
 }
 int32_t cm_verify_memory_openings(uint32_t root, const cm_mem_opening* openings, uint64_t n, uint8_t* ok, cm_stream_t s) {
-  return open_guard([&] {
+  return cm::abi_guard([&] {
     cm::open_require_device("cm_verify_memory_openings");
     CM_CHECK(n == 0 || (openings && ok), "cm_verify_memory_openings: null openings or null ok");
     CM_CHECK(n <= cm::OPEN_MAX_BATCH, "cm_verify_memory_openings: more than 2^26 openings in one call: split it");

@@ -10,7 +10,8 @@
 //                    being default[28 - k], or stores 0 for a slot the range does not use.  The lookup rule of k_open_paths; every
 //                    word is written by exactly one lane: no atomic, the same bytes every time.
 // Verification (launched from the records of mem_range_plan, which cm_mem_range_plan hands out):
-//   k_range_cells    one lane per cell: its four words range-checked, three Poseidon2 calls -> the node of depth 28.
+//   k_fold_cells     the set verifier's (set_cells_enqueue of mem_set.hip): one lane per cell, its four words range-checked,
+//                    three Poseidon2 calls -> the node of depth 28.
 //   k_range_level    one lane per parent of the next depth: its children are two nodes of the interval, or at the ends a node and
 //                    the record's left[k] / right[k]; from one ping-pong buffer into the other.
 //   k_range_tail     one workgroup, once the interval is at most RANGE_TAIL nodes: the level in LDS, a barrier between depths, every
@@ -19,6 +20,7 @@
 // permutation.
 #include "../../include/cairom_hip.h"
 #include "mem_range.hpp"
+#include "mem_set.hpp"
 #include "mem_open.hpp"
 #include "segment_input.hpp"
 #include <cstring>
@@ -30,16 +32,14 @@ namespace {
 
 constexpr uint32_t RANGE_BLOCK = 256;
 constexpr uint32_t RANGE_LAND_CELLS = 1u << 19;   // 8 MB of values per trip through the pinned landing buffer
-// device words behind the record: the malformed flag of k_range_cells, the verdict of k_range_tail
+// device words behind the record: the malformed flag of the cells kernel, the verdict of k_range_tail
 enum : uint32_t { RW_FLAG = RANGE_WORDS, RW_VERDICT = RANGE_WORDS + 1, RANGE_DEV_WORDS = RANGE_WORDS + 2 };
 
 static_assert(RANGE_TAIL <= 1024 && RANGE_TAIL >= 2 && 2 * RANGE_SLOTS <= RANGE_TAIL, "one workgroup holds a level and checks the 56 slots");
 
-struct RangeDefaults { uint32_t h[air::TREE_HEIGHT + 1]; };   // h[d] = the hash of an empty subtree whose top is at depth d
-
 // ---- kernels -----------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(RANGE_BLOCK)
-k_range_open(const uint32_t* __restrict__ nodes, const uint32_t* __restrict__ off, uint32_t start, uint32_t n_cells, RangeDefaults dflt,
+k_range_open(const uint32_t* __restrict__ nodes, const uint32_t* __restrict__ off, uint32_t start, uint32_t n_cells, TreeDefaults dflt,
              uint32_t* __restrict__ values, uint32_t* __restrict__ slots) {
   const uint32_t t = blockIdx.x * RANGE_BLOCK + threadIdx.x;   // (2 * 2^24 + 56 lanes at the most)
   if (t < 2u * n_cells) {
@@ -59,16 +59,6 @@ k_range_open(const uint32_t* __restrict__ nodes, const uint32_t* __restrict__ of
     word = nd ? (is_left ? nd[2] : nd[3]) : dflt.h[depth];
   }
   slots[s] = word;
-}
-
-__global__ void __launch_bounds__(RANGE_BLOCK)
-k_range_cells(const uint4* __restrict__ values, uint32_t n_cells, uint32_t* __restrict__ out, uint32_t* __restrict__ flag) {
-  const uint32_t t = blockIdx.x * RANGE_BLOCK + threadIdx.x;
-  if (t >= n_cells) return;
-  const uint4 q = values[t];
-  const uint32_t v[4] = {q.x, q.y, q.z, q.w};
-  if (v[0] >= P || v[1] >= P || v[2] >= P || v[3] >= P) *flag = 1u;
-  out[t] = range_cell_node(v);
 }
 
 // in[i] = node lo + i of the interval [lo, hi]; out[j] = node (lo >> 1) + j of the depth above, j < n_out
@@ -107,9 +97,6 @@ k_range_tail(const uint32_t* __restrict__ in, uint32_t lo, uint32_t hi, uint32_t
   if (t == 0) rec[RW_VERDICT] = (!bad && level[cur][0] == root) ? 1u : 0u;
 }
 
-inline dim3 blocks_for(uint64_t n, uint32_t block) { return dim3((uint32_t)((n + block - 1) / block)); }
-inline hipStream_t stream_or_own(cm_stream_t s) { return s ? (hipStream_t)(uintptr_t)s : thread_main_stream(); }
-
 }  // namespace
 
 void open_range_check(const char* who, uint32_t start, uint32_t n_cells, const uint32_t* values, const cm_mem_range_opening* out) {
@@ -123,9 +110,7 @@ void open_range_check(const char* who, uint32_t start, uint32_t n_cells, const u
 void open_range(const cm_merkle_node* nodes, uint64_t n_nodes, uint32_t start, uint32_t n_cells, uint32_t* values, cm_mem_range_opening* out,
                 hipStream_t st) {
   CM_CHECK(!range_header_bad(start, n_cells) && n_cells <= RANGE_MAX_CELLS, "memory range: a bad range reached the device path");
-  RangeDefaults dflt;
-  const std::vector<uint32_t>& dh = host::poseidon2_default_hashes();
-  for (uint32_t d = 0; d <= air::TREE_HEIGHT; d++) dflt.h[d] = dh[d];
+  const TreeDefaults dflt = tree_defaults();
   constexpr size_t SLOT_BYTES = 2 * RANGE_SLOTS * 4;
   DevBuf d_off((air::TREE_HEIGHT + 1) * 4), d_vals((size_t)n_cells * 16), d_slots(SLOT_BYTES);
   open_depth_offsets_enqueue(nodes, n_nodes, d_off.u32(), st);
@@ -163,8 +148,7 @@ void verify_range_device(uint32_t root, const cm_mem_range_opening* opening, con
   stage_upload(d_vals.p, values, (size_t)n_cells * 16, st);
   uint32_t* in = d_a.u32();
   uint32_t* out = d_b.u32();
-  hipLaunchKernelGGL(k_range_cells, blocks_for(n_cells, RANGE_BLOCK), dim3(RANGE_BLOCK), 0, st, (const uint4*)d_vals.as<uint4>(), n_cells, in,
-                     d_rec.u32() + RW_FLAG);
+  set_cells_enqueue(d_vals.u32(), n_cells, in, d_rec.u32() + RW_FLAG, st);
   uint32_t s = 1;
   for (; s < RANGE_STEPS && steps[s].kernel == RANGE_K_LEVEL; s++) {
     const uint32_t n_out = steps[s].hi - steps[s].lo + 1;   // (<= n_cells / 2 + 1: the size of the second buffer)
@@ -184,20 +168,10 @@ void verify_range_device(uint32_t root, const cm_mem_range_opening* opening, con
 }  // namespace cm
 
 // ================================================================= C ABI
-extern "C" int32_t cm_set_last_error(const char* msg);
-namespace {
-template <class F>
-int32_t range_guard(F&& f) {
-  try { f(); return 0; }
-  catch (const cm::CmError& e) { cm_set_last_error(e.what()); return e.code ? e.code : 1; }
-  catch (const std::exception& e) { cm_set_last_error(e.what()); return 1; }
-}
-}  // namespace
-
 extern "C" {
 int32_t cm_input_open_memory_range(const cm_device_input* in, uint32_t which, uint32_t start, uint32_t n_cells, uint32_t* values,
                                    cm_mem_range_opening* out, uint32_t* root) {
-  return range_guard([&] {
+  return cm::abi_guard([&] {
     cm::open_require_device("cm_input_open_memory_range");
     CM_CHECK(in && in->d && root, "cm_input_open_memory_range: null argument");
     CM_CHECK(which <= 1, "cm_input_open_memory_range: `which` is not 0 (the initial tree) or 1 (the final tree)");
@@ -210,7 +184,7 @@ int32_t cm_input_open_memory_range(const cm_device_input* in, uint32_t which, ui
   });
 }
 int32_t cm_verify_memory_range(uint32_t root, const cm_mem_range_opening* opening, const uint32_t* values, uint8_t* ok, cm_stream_t s) {
-  return range_guard([&] {
+  return cm::abi_guard([&] {
     cm::open_require_device("cm_verify_memory_range");
     CM_CHECK(opening && values && ok, "cm_verify_memory_range: null argument");
     CM_CHECK(opening->n_cells <= cm::RANGE_MAX_CELLS, "cm_verify_memory_range: more than 2^24 cells in one call: split the range");
@@ -255,7 +229,7 @@ int32_t cm_verify_memory_range_host(uint32_t root, const cm_mem_range_opening* o
   return reject("the range hashes to root " + std::to_string(a[0]) + ", not " + std::to_string(root));
 }
 int32_t cm_mem_range_plan(uint32_t start, uint32_t n_cells, cm_mem_range_step* steps, uint32_t cap, uint32_t* n_steps) {
-  return range_guard([&] {
+  return cm::abi_guard([&] {
     CM_CHECK(steps && n_steps, "cm_mem_range_plan: null argument");
     CM_CHECK(n_cells > 0 && !cm::range_header_bad(start, n_cells), "cm_mem_range_plan: no cells, or the range ends beyond the address space of 2^28 cells");
     CM_CHECK(cap >= cm::RANGE_STEPS, "cm_mem_range_plan: output buffer too small (29 steps)");

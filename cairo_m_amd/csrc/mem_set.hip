@@ -17,18 +17,19 @@
 //                    one lane: no atomic, the same bytes every time.
 // Verification (launched from the records of mem_set_plan, which cm_mem_set_plan hands out):
 //   k_set_heads      lane t with the head flag stores i at heads[scan[t] >> 32]: the head lane of every node, depth-major.
-//   k_set_cells      one lane per cell: its four words range-checked, three Poseidon2 calls -> the node of depth 28.
-//   k_set_level      one lane per PARENT r of S_{k+1}: its head lane i (heads) is also the head of its first child in S_k, whose rank
+// and then the shared ladder of set_fold.hpp with the one-plane verifier policy, VerifyFold<1>:
+//   k_fold_cells     one lane per cell: its four words range-checked, three Poseidon2 calls -> the node of depth 28.
+//   k_fold_level     one lane per PARENT r of S_{k+1}: its head lane i (heads) is also the head of its first child in S_k, whose rank
 //                    and flags say where the two children are: the node and the next sibling word (left or right by the node's
 //                    parity), or two neighbouring nodes of S_k.  From one ping-pong buffer into the other.  No lane idles on an
 //                    address that shares its parent with another, so the upper depths keep their waves as full as the set allows.
-//   k_set_tail       one workgroup, once S_k is at most SET_TAIL nodes: the level in LDS, a barrier between depths, every remaining
+//   k_fold_tail      one workgroup, once S_k is at most SET_TAIL nodes: the level in LDS, a barrier between depths, every remaining
 //                    depth; it checks the count of sibling words, compares with the root and writes the verdict and the root.
 // A malformed word raises a flag word with a plain store (every writer stores 1).  Each kernel has one call site of the
 // permutation.  Temporaries: flags and scan 2 * 8 * 28 = 448 bytes per cell on both paths; the verifier adds the head lanes (4 bytes
 // per node of every S_k, at most 112 per cell), the values, the addresses and two node buffers of n words.
 #include "../../include/cairom_hip.h"
-#include "mem_set.hpp"
+#include "set_fold.hpp"
 #include "mem_open.hpp"
 #include "segment_input.hpp"
 #include <hipcub/hipcub.hpp>
@@ -40,10 +41,6 @@
 namespace cm {
 namespace {
 
-// device words of the verifier: the malformed flag of the hashing kernels, the verdict and the root of k_set_tail
-enum : uint32_t { SW_FLAG = 0, SW_VERDICT = 1, SW_ROOT = 2, SET_DEV_WORDS = 3 };
-
-static_assert(SET_TAIL <= 1024 && SET_TAIL >= 2, "one workgroup holds a level");
 static_assert((uint64_t)SET_DEPTHS * SET_MAX_CELLS + 2ull * SET_MAX_CELLS < (1ull << 32), "the lanes of a launch fit 32 bits");
 
 // ---- kernels -----------------------------------------------------------------------------------------------------------
@@ -57,7 +54,7 @@ k_set_flags(const uint32_t* __restrict__ a, uint32_t n, unsigned long long* __re
 
 __global__ void __launch_bounds__(SET_BLOCK)
 k_set_gather(const uint32_t* __restrict__ nodes, const uint32_t* __restrict__ off, const uint32_t* __restrict__ a, uint32_t n,
-             const unsigned long long* __restrict__ flag, const unsigned long long* __restrict__ scan, SetDefaults dflt, uint32_t cap_words,
+             const unsigned long long* __restrict__ flag, const unsigned long long* __restrict__ scan, TreeDefaults dflt, uint32_t cap_words,
              uint32_t* __restrict__ values, uint32_t* __restrict__ words, uint32_t* __restrict__ count) {
   const uint32_t t = blockIdx.x * SET_BLOCK + threadIdx.x, n_pairs = SET_DEPTHS * n;
   if (t >= n_pairs) {
@@ -81,70 +78,21 @@ k_set_heads(const unsigned long long* __restrict__ flag, const unsigned long lon
   if (rank < cap_heads) heads[rank] = t % n;
 }
 
-__global__ void __launch_bounds__(SET_BLOCK)
-k_set_cells(const uint4* __restrict__ values, uint32_t n, uint32_t* __restrict__ out, uint32_t* __restrict__ bad) {
-  const uint32_t t = blockIdx.x * SET_BLOCK + threadIdx.x;
-  if (t >= n) return;
-  const uint4 q = values[t];
-  const uint32_t v[4] = {q.x, q.y, q.z, q.w};
-  if (v[0] >= P || v[1] >= P || v[2] >= P || v[3] >= P) *bad = 1u;
-  out[t] = range_cell_node(v);
-}
-
-// the children of parent r of S_{k+1}, where in[c] = node c of S_k; false when the sibling word it needs is missing or not below P
-__device__ __forceinline__ bool set_children(const SetView& s, const uint32_t* in, uint32_t k, uint32_t r, uint32_t& l, uint32_t& rr) {
-  const SetParent p = set_parent(s, k, r);
-  const uint32_t me = in[p.c];
-  if (p.paired) { l = me; rr = in[p.c + 1]; return true; }
-  l = p.odd ? p.w : me; rr = p.odd ? me : p.w;
-  return p.w < P;
-}
-
-// in = S_k, out = S_{k+1} (n_out nodes)
-__global__ void __launch_bounds__(SET_BLOCK)
-k_set_level(SetView s, const uint32_t* __restrict__ in, uint32_t k, uint32_t n_out, uint32_t* __restrict__ out, uint32_t* __restrict__ bad) {
-  const uint32_t r = blockIdx.x * SET_BLOCK + threadIdx.x;
-  if (r >= n_out) return;
-  uint32_t l, rr;
-  if (!set_children(s, in, k, r, l, rr)) *bad = 1u;
-  out[r] = host::poseidon2_hash(l, rr);
-}
-
-// S_k0 (w.w[k0] <= SET_TAIL nodes) up to the root; dev[SW_FLAG] in, dev[SW_VERDICT] and dev[SW_ROOT] out
-__global__ void __launch_bounds__(SET_TAIL)
-k_set_tail(SetView s, const uint32_t* __restrict__ in, SetWidths w, uint32_t k0, uint32_t root, uint32_t* __restrict__ dev) {
-  __shared__ uint32_t level[2][SET_TAIL];
-  __shared__ uint32_t bad;
-  const uint32_t t = threadIdx.x;
-  if (t == 0) {
-    // the count of the addresses' own flags against the record's
-    const size_t last = (size_t)SET_DEPTHS * s.n - 1;
-    const uint32_t need = (uint32_t)s.scan[last] + ((uint32_t)s.flag[last] & 1u);
-    bad = (dev[SW_FLAG] || need != s.n_words) ? 1u : 0u;
-  }
-  if (t < w.w[k0]) level[0][t] = in[t];
-  __syncthreads();
-  uint32_t cur = 0;
-#pragma unroll 1
-  for (uint32_t k = k0; k < SET_DEPTHS; k++) {
-    if (t < w.w[k + 1]) {
-      uint32_t l, rr;
-      if (!set_children(s, level[cur], k, t, l, rr)) bad = 1u;
-      level[cur ^ 1][t] = host::poseidon2_hash(l, rr);
-    }
-    __syncthreads();
-    cur ^= 1;
-  }
-  if (t == 0) {
-    dev[SW_VERDICT] = (!bad && level[cur][0] == root) ? 1u : 0u;
-    dev[SW_ROOT] = bad ? 0u : level[cur][0];
-  }
-}
-
-inline dim3 blocks_for(uint64_t n, uint32_t block) { return dim3((uint32_t)((n + block - 1) / block)); }
-inline hipStream_t stream_or_own(cm_stream_t s) { return s ? (hipStream_t)(uintptr_t)s : thread_main_stream(); }
-
 }  // namespace
+
+void set_cells_enqueue(const uint32_t* values, uint32_t n, uint32_t* out, uint32_t* bad, hipStream_t st) {
+  hipLaunchKernelGGL(k_fold_cells<1>, blocks_for(n, SET_BLOCK), dim3(SET_BLOCK), 0, st, FoldValues<1>{{reinterpret_cast<const uint4*>(values)}}, n, out, bad);
+}
+
+void set_fold_prepare(SetFold& f, const uint32_t* d_addr, uint32_t n, const cm_mem_set_step steps[SET_STEPS], const uint32_t* words, uint32_t n_words,
+                      hipStream_t st) {
+  uint64_t n_heads = 0;
+  for (uint32_t s = 0; s < SET_STEPS; s++) { f.w.w[s] = steps[s].n_nodes; if (s < SET_DEPTHS) n_heads += f.w.w[s]; }
+  f.heads.alloc(n_heads * 4);
+  set_flags_and_scan(d_addr, n, f.flag, f.scan, f.tmp, st);
+  set_heads_enqueue(f.flag, f.scan, n, (uint32_t)n_heads, f.heads.u32(), st);
+  f.view = SetView{d_addr, f.flag.as<unsigned long long>(), f.scan.as<unsigned long long>(), f.heads.u32(), words, n, n_words};
+}
 
 // flag[t] and scan[t] of the 28 n pairs, enqueued on st (the scan's temporary lives in `tmp` until the stream has run)
 void set_flags_and_scan(const uint32_t* d_addr, uint32_t n, DevBuf& flag, DevBuf& scan, DevBuf& tmp, hipStream_t st) {
@@ -186,9 +134,7 @@ void open_set_check(const char* who, const uint32_t* addresses, uint64_t n, cons
 void open_set(const cm_merkle_node* nodes, uint64_t n_nodes, const uint32_t* addresses, uint32_t n, uint32_t* values, uint32_t* siblings,
               uint32_t n_siblings, hipStream_t st) {
   CM_CHECK(n > 0 && n <= SET_MAX_CELLS && n_siblings <= SET_DEPTHS * n, "memory set: a bad set reached the device path");
-  SetDefaults dflt;
-  const std::vector<uint32_t>& dh = host::poseidon2_default_hashes();
-  for (uint32_t d = 0; d <= air::TREE_HEIGHT; d++) dflt.h[d] = dh[d];
+  const TreeDefaults dflt = tree_defaults();
   // one block behind the other: the count, the values, the words — what the trips through the landing buffer carry
   const size_t val_bytes = (size_t)n * 16, word_bytes = (size_t)n_siblings * 4, out_bytes = 16 + val_bytes + word_bytes;
   DevBuf d_addr((size_t)n * 4), d_off((air::TREE_HEIGHT + 1) * 4), d_out(out_bytes), flag, scan, tmp;
@@ -204,7 +150,7 @@ void open_set(const cm_merkle_node* nodes, uint64_t n_nodes, const uint32_t* add
   CM_HIP(hipGetLastError());
   std::vector<uint8_t> words_first;   // nothing reaches the caller's arrays before the count has been compared
   for (size_t done = 0; done < out_bytes;) {
-    const size_t m = std::min(out_bytes - done, SET_LAND_BYTES);
+    const size_t m = std::min(out_bytes - done, TREE_LAND_BYTES);
     const uint8_t* const land = (const uint8_t*)stage_download_async(d_out.as<uint8_t>() + done, m, st);
     CM_HIP(hipStreamSynchronize(st));   // (also keeps the temporaries alive until the kernels have run)
     if (!done) {
@@ -225,55 +171,14 @@ void verify_set_device(uint32_t root, const uint32_t* addresses, uint32_t n, con
                        uint8_t* ok, uint32_t* computed_root, hipStream_t st) {
   *ok = 0;
   if (computed_root) *computed_root = 0;
-  // nothing to launch from: these verdicts need no GPU
-  if (n == 0 || set_first_bad_address(addresses, n) < n) return;
-  cm_mem_set_step steps[SET_STEPS];
-  if (mem_set_plan(addresses, n, steps) != n_siblings) return;
-  SetWidths w;
-  uint64_t n_heads = 0;
-  for (uint32_t s = 0; s < SET_STEPS; s++) { w.w[s] = steps[s].n_nodes; if (s < SET_DEPTHS) n_heads += w.w[s]; }
-  const uint32_t words0[SET_DEV_WORDS] = {0, 0, 0};
-  DevBuf d_dev(sizeof(words0)), d_addr((size_t)n * 4), d_vals((size_t)n * 16), d_words((size_t)n_siblings * 4), d_heads(n_heads * 4),
-      d_a((size_t)n * 4), d_b((size_t)n * 4), flag, scan, tmp;
-  stage_upload(d_dev.p, words0, sizeof(words0), st);
-  stage_upload(d_addr.p, addresses, (size_t)n * 4, st);
-  stage_upload(d_vals.p, values, (size_t)n * 16, st);
-  stage_upload(d_words.p, siblings, (size_t)n_siblings * 4, st);
-  set_flags_and_scan(d_addr.u32(), n, flag, scan, tmp, st);
-  set_heads_enqueue(flag, scan, n, (uint32_t)n_heads, d_heads.u32(), st);
-  uint32_t* in = d_a.u32();
-  uint32_t* out = d_b.u32();
-  hipLaunchKernelGGL(k_set_cells, blocks_for(n, SET_BLOCK), dim3(SET_BLOCK), 0, st, (const uint4*)d_vals.as<uint4>(), n, in, d_dev.u32() + SW_FLAG);
-  const SetView view{d_addr.u32(), flag.as<unsigned long long>(), scan.as<unsigned long long>(), d_heads.u32(), d_words.u32(), n, n_siblings};
-  uint32_t s = 1;
-  for (; s < SET_STEPS && steps[s].kernel == SET_K_LEVEL; s++) {
-    hipLaunchKernelGGL(k_set_level, blocks_for(steps[s].n_nodes, SET_BLOCK), dim3(SET_BLOCK), 0, st, view, (const uint32_t*)in, s - 1, steps[s].n_nodes, out,
-                       d_dev.u32() + SW_FLAG);
-    std::swap(in, out);
-  }
-  CM_CHECK(s < SET_STEPS && steps[s].kernel == SET_K_TAIL && w.w[s - 1] <= SET_TAIL, "memory set: the plan has no tail");
-  hipLaunchKernelGGL(k_set_tail, dim3(1), dim3(SET_TAIL), 0, st, view, (const uint32_t*)in, w, s - 1, root, d_dev.u32());
-  CM_HIP(hipGetLastError());
-  const uint32_t* land = (const uint32_t*)stage_download_async(d_dev.p, sizeof(words0), st);
-  CM_HIP(hipStreamSynchronize(st));   // the buffers go back to the pool behind this wait
-  *ok = land[SW_VERDICT] == 1 ? 1 : 0;
-  if (computed_root) *computed_root = land[SW_ROOT];
+  if (n == 0) return;   // nothing to launch from: the verdict needs no GPU
+  verify_fold_device<1>("memory set", {root}, addresses, n, {values}, siblings, n_siblings, ok, computed_root, st);
 }
 }  // namespace
 
 }  // namespace cm
 
 // ================================================================= C ABI
-extern "C" int32_t cm_set_last_error(const char* msg);
-namespace {
-template <class F>
-int32_t set_guard(F&& f) {
-  try { f(); return 0; }
-  catch (const cm::CmError& e) { cm_set_last_error(e.what()); return e.code ? e.code : 1; }
-  catch (const std::exception& e) { cm_set_last_error(e.what()); return 1; }
-}
-}  // namespace
-
 namespace cm {
 int32_t set_root_host(const char* who, const uint32_t* a, uint64_t n64, const uint32_t* values, const uint32_t* words, uint32_t n_words, uint32_t* root_out,
                       const char* noun, const char* value_word) {
@@ -319,7 +224,7 @@ int32_t set_root_host(const char* who, const uint32_t* a, uint64_t n64, const ui
 
 extern "C" {
 int32_t cm_mem_set_plan(const uint32_t* addresses, uint64_t n, cm_mem_set_step* steps, uint32_t cap, uint32_t* n_steps, uint32_t* n_siblings) {
-  return set_guard([&] {
+  return cm::abi_guard([&] {
     CM_CHECK(addresses && steps && n_steps && n_siblings, "cm_mem_set_plan: null argument");
     CM_CHECK(n > 0 && n <= cm::SET_MAX_CELLS, "cm_mem_set_plan: no cells, or more than 2^20 cells in one call: split the set");
     const uint64_t bad = cm::set_first_bad_address(addresses, n);
@@ -331,7 +236,7 @@ int32_t cm_mem_set_plan(const uint32_t* addresses, uint64_t n, cm_mem_set_step* 
 }
 int32_t cm_input_open_memory_set(const cm_device_input* in, uint32_t which, const uint32_t* addresses, uint64_t n, uint32_t* values,
                                  uint32_t* siblings, uint32_t cap_siblings, uint32_t* n_siblings, uint32_t* root) {
-  return set_guard([&] {
+  return cm::abi_guard([&] {
     cm::open_require_device("cm_input_open_memory_set");
     CM_CHECK(in && in->d && root, "cm_input_open_memory_set: null argument");
     CM_CHECK(which <= 1, "cm_input_open_memory_set: `which` is not 0 (the initial tree) or 1 (the final tree)");
@@ -345,7 +250,7 @@ int32_t cm_input_open_memory_set(const cm_device_input* in, uint32_t which, cons
 }
 int32_t cm_verify_memory_set(uint32_t root, const uint32_t* addresses, uint64_t n, const uint32_t* values, const uint32_t* siblings,
                              uint32_t n_siblings, uint8_t* ok, uint32_t* computed_root, cm_stream_t s) {
-  return set_guard([&] {
+  return cm::abi_guard([&] {
     cm::open_require_device("cm_verify_memory_set");
     CM_CHECK(addresses && values && siblings && ok, "cm_verify_memory_set: null argument");
     CM_CHECK(n <= cm::SET_MAX_CELLS, "cm_verify_memory_set: more than 2^20 cells in one call: split the set");

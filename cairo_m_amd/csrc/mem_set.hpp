@@ -8,6 +8,7 @@
 #include "engine.hpp"
 #include "host_adapter.hpp"
 #include "mem_range.hpp"
+#include "mem_tree.hpp"
 #include <string>
 #include <vector>
 
@@ -87,13 +88,11 @@ inline uint32_t mem_set_plan(const uint32_t* a, uint32_t n, cm_mem_set_step step
 
 // ---- what the kernels of the set openings and of the transitions (mem_transition.hip) share, device only ---------------------
 constexpr uint32_t SET_BLOCK = 256;
-constexpr size_t SET_LAND_BYTES = (size_t)8 << 20;   // per trip through the pinned landing buffer
-struct SetDefaults { uint32_t h[air::TREE_HEIGHT + 1]; };   // h[d] = the hash of an empty subtree whose top is at depth d
 struct SetWidths { uint32_t w[SET_STEPS]; };                  // w[k] = |S_k|, k = 0 .. 28 (the plan's)
 // the sibling word of lane t = k * n + i, which has the needs flag: the other half of the pair x & ~1, x = a[i] >> k (the left half
 // when x is odd), from depth 28 - k's slice of the node list, or that depth's default hash
 __device__ __forceinline__ uint32_t set_gather_word(const uint32_t* __restrict__ nodes, const uint32_t* __restrict__ off, const uint32_t* __restrict__ a,
-                                                    uint32_t n, uint32_t t, const SetDefaults& dflt) {
+                                                    uint32_t n, uint32_t t, const TreeDefaults& dflt) {
   const uint32_t k = t / n, depth = SET_DEPTHS - k, x = a[t % n] >> k;
   const uint32_t* const nd = range_find(nodes, off, depth, x & ~1u);
   return nd ? ((x & 1u) ? nd[2] : nd[3]) : dflt.h[depth];
@@ -116,8 +115,9 @@ struct SetView {
 };
 // Parent r of S_{k+1}: its first child is node c of S_k.  paired: an even node whose successor in S_k is x + 1, the children are
 // nodes c and c + 1.  Else the other child is the sibling word w, on the left when the node is odd; w = P when the record has no
-// such word.  Index arithmetic only: the same for every plane of values folded over the addresses.
-struct SetParent { uint32_t c, w; bool paired, odd; };
+// such word.  x = that first child's index at its depth, a[i] >> k, for a fold that files what it hashes (the image); one that
+// does not read it pays nothing for it.  Index arithmetic only: the same for every plane of values folded over the addresses.
+struct SetParent { uint32_t c, w, x; bool paired, odd; };
 __device__ __forceinline__ SetParent set_parent(const SetView& s, uint32_t k, uint32_t r) {
   // the parent's head lane is the head lane of its first child: a lane that starts a node at shift k + 1 starts one at shift k
   const uint32_t i = k + 1 < SET_DEPTHS ? s.heads[(uint32_t)(s.scan[(size_t)(k + 1) * s.n] >> 32) + r] : 0u;
@@ -125,12 +125,13 @@ __device__ __forceinline__ SetParent set_parent(const SetView& s, uint32_t k, ui
   SetParent p;
   p.c = (uint32_t)(s.scan[t] >> 32) - (uint32_t)(s.scan[(size_t)k * s.n] >> 32);
   p.paired = !((uint32_t)s.flag[t] & 1u);
+  p.x = s.a[i] >> k;
   p.w = 0u;
   p.odd = false;
   if (p.paired) return p;
   const uint32_t q = (uint32_t)s.scan[t];
   p.w = q < s.n_words ? s.words[q] : P;
-  p.odd = (s.a[i] >> k) & 1u;
+  p.odd = p.x & 1u;
   return p;
 }
 
@@ -139,6 +140,9 @@ __device__ __forceinline__ SetParent set_parent(const SetView& s, uint32_t k, ui
 void set_flags_and_scan(const uint32_t* d_addr, uint32_t n, DevBuf& flag, DevBuf& scan, DevBuf& tmp, hipStream_t st);
 // heads[rank] = the head lane of every node of S_0 .. S_27, depth-major (k_set_heads), n_heads of them
 void set_heads_enqueue(const DevBuf& flag, const DevBuf& scan, uint32_t n, uint32_t n_heads, uint32_t* heads, hipStream_t st);
+// out[t] = the node of depth 28 of cell t, its four value words range-checked into *bad (k_fold_cells<1> of set_fold.hpp, also the
+// first step of the range verifier)
+CM_INTERNAL void set_cells_enqueue(const uint32_t* values, uint32_t n, uint32_t* out, uint32_t* bad, hipStream_t st);
 // what is wrong with address `bad` = set_first_bad_address(a, n) < n
 std::string set_address_complaint(const uint32_t* a, uint64_t bad);
 // the host fold: 0 and *root_out, or 11 and the message "<noun> of <n> cells: ...", a bad value named "<value_word> <j> of cell <a>"

@@ -62,7 +62,7 @@ k_pid_cells(const uint32_t* __restrict__ tab, uint32_t n_items, uint32_t total, 
 // item i = blockIdx.x: a[off .. off + count) holds its nodes of depth 28; b[off + i .. off + i + count / 2 + 1) is its second buffer.
 // out[2 i] = the id, out[2 i + 1] = the flag (1 for an item without cells).
 __global__ void __launch_bounds__(PID_TAIL)
-k_pid_tree(const uint32_t* __restrict__ tab, uint32_t n_items, uint32_t* a, uint32_t* b, PidDefaults dflt, uint32_t* __restrict__ out) {
+k_pid_tree(const uint32_t* __restrict__ tab, uint32_t n_items, uint32_t* a, uint32_t* b, TreeDefaults dflt, uint32_t* __restrict__ out) {
   __shared__ uint32_t level[2][PID_TAIL];
   const uint32_t i = blockIdx.x, t = threadIdx.x;
   const uint32_t off = tab[PT_OFF * n_items + i], count = tab[PT_COUNT * n_items + i], first = tab[PT_FIRST * n_items + i];
@@ -90,9 +90,6 @@ k_pid_tree(const uint32_t* __restrict__ tab, uint32_t n_items, uint32_t* a, uint
   }
   if (t == 0) { out[2 * i] = in[0]; out[2 * i + 1] = tab[PT_FLAG * n_items + i]; }
 }
-
-inline dim3 blocks_for(uint64_t n, uint32_t block) { return dim3((uint32_t)((n + block - 1) / block)); }
-inline hipStream_t stream_or_own(cm_stream_t s) { return s ? (hipStream_t)(uintptr_t)s : thread_main_stream(); }
 
 // ---- what makes a list of entries a program -----------------------------------------------------------------------------------
 // "" or what is wrong with e[7 n]; words: also range-check the value words (the device path leaves those to k_pid_cells)
@@ -159,9 +156,7 @@ void ids_device(std::vector<Item>& items, uint32_t* ids, int32_t* status, std::s
     for (uint64_t c = 0; c < it.n; c++) memcpy(vals + 4 * ((size_t)off + c), it.e + PID_ENTRY_WORDS * c + 2, 16);
     off += (uint32_t)it.n;
   }
-  PidDefaults dflt;
-  const std::vector<uint32_t>& dh = host::poseidon2_default_hashes();
-  for (uint32_t d = 0; d <= air::TREE_HEIGHT; d++) dflt.h[d] = dh[d];
+  const TreeDefaults dflt = tree_defaults();
   DevBuf d_up(up.size() * 4), d_a((total + 1) * 4), d_b((total + n) * 4), d_out((size_t)n * 8);
   stage_upload(d_up.p, up.data(), up.size() * 4, st);
   const uint32_t* const tab = d_up.u32();
@@ -204,14 +199,7 @@ std::string hex8(uint32_t x) {
 }  // namespace cm
 
 // ================================================================= C ABI
-extern "C" int32_t cm_set_last_error(const char* msg);
 namespace {
-template <class F>
-int32_t pid_guard(F&& f) {
-  try { f(); return 0; }
-  catch (const cm::CmError& e) { cm_set_last_error(e.what()); return e.code ? e.code : 1; }
-  catch (const std::exception& e) { cm_set_last_error(e.what()); return 1; }
-}
 int32_t batch_result(const std::string& first_bad) {
   if (first_bad.empty()) return 0;
   cm_set_last_error(first_bad.c_str());
@@ -222,7 +210,7 @@ int32_t batch_result(const std::string& first_bad) {
 extern "C" {
 // host code: no device call on this path
 int32_t cm_program_id_entries(const uint32_t* entries, uint64_t n, uint32_t* id) {
-  return pid_guard([&] {
+  return cm::abi_guard([&] {
     CM_CHECK(entries && id, "cm_program_id_entries: null argument");
     const std::string bad = cm::entries_error(entries, n, true);
     CM_CHECK(bad.empty(), "cm_program_id_entries: " + bad);
@@ -230,7 +218,7 @@ int32_t cm_program_id_entries(const uint32_t* entries, uint64_t n, uint32_t* id)
   });
 }
 int32_t cm_proof_program_id(const cm_proof* p, uint32_t* id) {
-  return pid_guard([&] {
+  return cm::abi_guard([&] {
     CM_CHECK(p && id, "cm_proof_program_id: null argument");
     const std::vector<uint32_t> e = cm::proof_entries(p, 0);
     const std::string bad = cm::entries_error(e.data(), e.size() / cm::PID_ENTRY_WORDS, true);
@@ -240,7 +228,7 @@ int32_t cm_proof_program_id(const cm_proof* p, uint32_t* id) {
 }
 int32_t cm_program_ids(const uint32_t* const* entries, const uint64_t* n_entries, uint32_t n, uint32_t* ids, int32_t* status, cm_stream_t s) {
   std::string first_bad;
-  const int32_t rc = pid_guard([&] {
+  const int32_t rc = cm::abi_guard([&] {
     cm::open_require_device("cm_program_ids");
     CM_CHECK(n >= 1 && entries && n_entries && ids && status, "cm_program_ids: no items / null argument");
     CM_CHECK(n <= cm::PID_MAX_ITEMS, "cm_program_ids: more than 2^20 items in one call: split the batch");
@@ -253,7 +241,7 @@ int32_t cm_program_ids(const uint32_t* const* entries, const uint64_t* n_entries
 }
 int32_t cm_proofs_program_ids(const cm_proof* const* proofs, uint32_t n, uint32_t* ids, int32_t* status, cm_stream_t s) {
   std::string first_bad;
-  const int32_t rc = pid_guard([&] {
+  const int32_t rc = cm::abi_guard([&] {
     cm::open_require_device("cm_proofs_program_ids");
     CM_CHECK(n >= 1 && proofs && ids && status, "cm_proofs_program_ids: no proofs / null argument");
     CM_CHECK(n <= cm::PID_MAX_ITEMS, "cm_proofs_program_ids: more than 2^20 proofs in one call: split the batch");
@@ -274,7 +262,7 @@ int32_t cm_proofs_program_ids(const cm_proof* const* proofs, uint32_t n, uint32_
 int32_t cm_run_statement_of(const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected, const uint32_t* expected_program_id,
                             uint32_t device, cm_run_statement* out) {
   {
-    const int32_t rc = pid_guard([&] {
+    const int32_t rc = cm::abi_guard([&] {
       CM_CHECK(out, "cm_run_statement_of: null output");
       CM_CHECK(out->struct_size >= sizeof(cm_run_statement),
                "cm_run_statement_of: struct_size does not cover cm_run_statement (set it to sizeof(cm_run_statement))");
@@ -284,7 +272,7 @@ int32_t cm_run_statement_of(const cm_proof* const* proofs, uint32_t n, const cm_
   }
   const int32_t chain = device ? cm_verify_run_device(proofs, n, expected) : cm_verify_run(proofs, n, expected);
   if (chain) return chain;   // (status and message are the chain check's own)
-  return pid_guard([&] {
+  return cm::abi_guard([&] {
     const std::vector<uint32_t> prog = cm::proof_entries(proofs[0], 0);
     const uint64_t m = prog.size() / cm::PID_ENTRY_WORDS;
     for (uint32_t i = 1; i < n; i++) {

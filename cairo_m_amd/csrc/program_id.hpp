@@ -5,6 +5,7 @@
 #pragma once
 #include "../../include/cairom_hip.h"
 #include "mem_range.hpp"
+#include "mem_tree.hpp"
 
 namespace cm {
 
@@ -13,8 +14,6 @@ constexpr uint32_t PID_MAX_ENTRIES = 1u << 24;     // one program
 constexpr uint64_t PID_MAX_BATCH_CELLS = 1ull << 26;   // one batch call: 1 GB of values
 constexpr uint32_t PID_MAX_ITEMS = 1u << 20;
 constexpr uint32_t PID_TAIL = 1024;                // an interval of at most this many nodes lives in LDS (one lane per node)
-
-struct PidDefaults { uint32_t h[air::TREE_HEIGHT + 1]; };   // h[d] = the hash of an empty subtree whose top is at depth d
 
 // ---- the interval arithmetic: one fold for the host call and k_pid_tree ---------------------------------------------------------
 // step k = 0 .. 27 hashes the nodes [lo, hi] of depth 28 - k into [lo >> 1, hi >> 1] of depth 27 - k; once lo == hi the same step

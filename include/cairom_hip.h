@@ -1117,7 +1117,7 @@ typedef struct {
 } cm_mem_range_opening;         /* sizeof = 232 */
 typedef struct {
   uint32_t depth, lo, hi;       /* the step produces the nodes lo .. hi of this depth */
-  uint32_t kernel;              /* 0 k_range_cells, 1 k_range_level, 2 k_range_tail */
+  uint32_t kernel;              /* 0 k_fold_cells, 1 k_range_level, 2 k_range_tail */
   uint32_t uses_left, uses_right;
 } cm_mem_range_step;            /* sizeof = 24 */
 /* which: 0 = the input's initial tree, 1 = its final tree.  values: 4 * n_cells words.  *root receives that tree's root. */
@@ -1187,7 +1187,7 @@ typedef struct {
   uint32_t depth;               /* the step produces n_nodes nodes of this depth */
   uint32_t n_nodes;
   uint32_t n_siblings;          /* sibling words the step reads: count[27 - depth], 0 for the cells */
-  uint32_t kernel;              /* 0 k_set_cells, 1 k_set_level, 2 k_set_tail */
+  uint32_t kernel;              /* 0 k_fold_cells, 1 k_fold_level, 2 k_fold_tail */
 } cm_mem_set_step;              /* sizeof = 16 */
 int32_t cm_mem_set_plan(const uint32_t* addresses, uint64_t n, cm_mem_set_step* steps, uint32_t cap, uint32_t* n_steps, uint32_t* n_siblings);
 /* which: 0 = the input's initial tree, 1 = its final tree.  values: 4 * n words.  siblings: cap_siblings words.  *root receives
@@ -1242,9 +1242,9 @@ int32_t cm_verify_memory_set_host(uint32_t root, const uint32_t* addresses, uint
  * segment that changes nothing gives n == 0 and no words, and one that changes more than 2^20 cells is refused.  Without a GPU
  * the status is cm_init's (3).
  * cm_verify_memory_transition checks both roots on the GPU in ONE fold over two value planes (stream s; 0 = the calling thread's
- * own).  The set verifier's flag pass, scan and head scatter run once; k_trans_cells, one lane per cell, range-checks all eight
- * words and writes two nodes of depth 28; k_trans_level, one lane per parent while S_k is wider than 128 nodes, does the index
- * arithmetic and loads the sibling word once and compresses twice; k_trans_tail, one workgroup, finishes the remaining depths of
+ * own).  The set verifier's flag pass, scan and head scatter run once; k_fold_cells, one lane per cell, range-checks all eight
+ * words and writes two nodes of depth 28; k_fold_level, one lane per parent while S_k is wider than 128 nodes, does the index
+ * arithmetic and loads the sibling word once and compresses twice; k_fold_tail, one workgroup, finishes the remaining depths of
  * both planes in LDS, checks the count, compares both roots and writes the verdict and the roots; four words come back.  The
  * launches come from cm_mem_set_plan's records.  *ok = 1 when the statement is well formed and both folds match; computed (may be
  * NULL) receives the two roots it folds to when well formed (n == 0: root_before twice), else zeros.  Malformed input is a verdict
@@ -1365,8 +1365,8 @@ int32_t cm_compose_transitions(const cm_mem_transition_view* parts, uint32_t n_p
  * On the GPU (the calling thread's stream and pool): k_img_check, one lane per cell half, bisects the depth-30 slice for the
  * current value and reports the lowest differing cell by an atomic minimum; k_img_cells, one lane per cell, writes the two
  * depth-30 records and the depth-29 record from the new value alone; the set verifier's flag pass, scan and head scatter; then
- * the steps of cm_mem_set_plan for the same addresses — k_img_level, one lane per parent while S_k is wider than 128 nodes, and
- * k_img_tail, one workgroup, for the rest — where a child in S_k takes its new hash from the level below and any other child
+ * the steps of cm_mem_set_plan for the same addresses — k_fold_level, one lane per parent while S_k is wider than 128 nodes, and
+ * k_fold_tail, one workgroup, for the rest — where a child in S_k takes its new hash from the level below and any other child
  * the old tree's word (the openers' lookup; a missing record is the depth's default hash).  The commit: k_img_rank bisects
  * every dirty record's place in the old slice of its depth, one exclusive scan counts the inserts, k_img_merge moves old and
  * dirty records into a new buffer in one launch and k_img_offsets updates the depth offsets.  Everything is enqueued before
