@@ -33,6 +33,7 @@
 // no tail flag is stored — k_compose_cells reads the successor's address itself.
 #include "../../include/cairom_hip.h"
 #include "mem_transition.hpp"
+#include "mem_batch.hpp"
 #include "mem_open.hpp"
 #include <hipcub/hipcub.hpp>
 #include <algorithm>
@@ -56,15 +57,7 @@ static_assert((uint64_t)SET_DEPTHS * SET_MAX_CELLS < (1ull << 32), "the lanes of
 
 inline uint32_t round4(uint32_t x) { return (x + 3u) & ~3u; }
 
-// the last part p with off[p] <= e (off[0] = 0, so there is one): the part of element e, empty parts skipped
-CM_HD uint32_t compose_part_of(const uint32_t* off, uint32_t n_parts, uint32_t e) {
-  uint32_t lo = 0, hi = n_parts;
-  while (hi - lo > 1) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (off[mid] <= e) lo = mid; else hi = mid;
-  }
-  return lo;
-}
+// (compose_part_of, the part of an element, is mem_batch.hpp's: the batched verifiers bisect the same tables)
 
 // A validated chain as one block of words, every array on a 16-byte boundary:
 // off[n_parts + 1] | woff[n_parts + 1] | addresses[N] | old[4 N] | new[4 N] | words[W]
@@ -360,14 +353,7 @@ cm_mem_transition* compose_device(const Chain& c) {
                      (const uint32_t*)d_head.u32(), (const uint32_t*)d_rank.u32(), N, d_off, n_parts, d_old, d_new, nu, o_addr, o_old, o_new, d_src.as<uint2>());
   // 5. the flags of U by the one rule, the flags of all parts in one pass and one scan
   set_flags_and_scan(o_addr, nu, uflag, uscan, tmp_u, st);
-  const uint32_t n_pairs = SET_DEPTHS * N;
-  pflag.alloc((size_t)n_pairs * 8);
-  pscan.alloc((size_t)n_pairs * 8);
-  hipLaunchKernelGGL(k_compose_flags, blocks_for(n_pairs, SET_BLOCK), dim3(SET_BLOCK), 0, st, d_addr, d_off, n_parts, N, pflag.as<unsigned long long>());
-  bytes = 0;
-  CM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, pflag.as<unsigned long long>(), pscan.as<unsigned long long>(), (int)n_pairs, st));
-  tmp_parts.alloc(bytes ? bytes : 4);
-  CM_HIP(hipcub::DeviceScan::ExclusiveSum(tmp_parts.p, bytes, pflag.as<unsigned long long>(), pscan.as<unsigned long long>(), (int)n_pairs, st));
+  parts_flags_and_scan(d_addr, d_off, n_parts, N, pflag, pscan, tmp_parts, st);
   // 6. the words
   hipLaunchKernelGGL(k_compose_gather, blocks_for((uint64_t)SET_DEPTHS * nu, SET_BLOCK), dim3(SET_BLOCK), 0, st, nu, (const unsigned long long*)uflag.as<unsigned long long>(),
                      (const unsigned long long*)uscan.as<unsigned long long>(), (const uint2*)d_src.as<uint2>(), d_off, n_parts, d_woff, d_words, N,
@@ -410,6 +396,20 @@ cm_mem_transition* compose_device(const Chain& c) {
 }
 
 }  // namespace
+
+// the segmented flag pass and its scan, also the first step of the batched verifiers (mem_batch.hip)
+void parts_flags_and_scan(const uint32_t* d_addr, const uint32_t* d_off, uint32_t n_parts, uint32_t n, DevBuf& flag, DevBuf& scan, DevBuf& tmp,
+                          hipStream_t st) {
+  const uint32_t n_pairs = SET_DEPTHS * n;
+  flag.alloc((size_t)n_pairs * 8);
+  scan.alloc((size_t)n_pairs * 8);
+  hipLaunchKernelGGL(k_compose_flags, blocks_for(n_pairs, SET_BLOCK), dim3(SET_BLOCK), 0, st, d_addr, d_off, n_parts, n, flag.as<unsigned long long>());
+  size_t bytes = 0;
+  CM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, flag.as<unsigned long long>(), scan.as<unsigned long long>(), (int)n_pairs, st));
+  tmp.alloc(bytes ? bytes : 4);
+  CM_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, bytes, flag.as<unsigned long long>(), scan.as<unsigned long long>(), (int)n_pairs, st));
+}
+
 }  // namespace cm
 
 // ================================================================= C ABI

@@ -117,8 +117,10 @@ struct SetView {
 // nodes c and c + 1.  Else the other child is the sibling word w, on the left when the node is odd; w = P when the record has no
 // such word.  x = that first child's index at its depth, a[i] >> k, for a fold that files what it hashes (the image); one that
 // does not read it pays nothing for it.  Index arithmetic only: the same for every plane of values folded over the addresses.
+// A batch (mem_batch.hip) scans the pairs of many sets at once: the view is then one set's slice of the flags and of the scan with
+// `heads` the whole batch's list, and q0 = the low word of the scan at the slice's start, which the word positions are taken from.
 struct SetParent { uint32_t c, w, x; bool paired, odd; };
-__device__ __forceinline__ SetParent set_parent(const SetView& s, uint32_t k, uint32_t r) {
+__device__ __forceinline__ SetParent set_parent_from(const SetView& s, uint32_t k, uint32_t r, uint32_t q0) {
   // the parent's head lane is the head lane of its first child: a lane that starts a node at shift k + 1 starts one at shift k
   const uint32_t i = k + 1 < SET_DEPTHS ? s.heads[(uint32_t)(s.scan[(size_t)(k + 1) * s.n] >> 32) + r] : 0u;
   const size_t t = (size_t)k * s.n + i;
@@ -129,11 +131,12 @@ __device__ __forceinline__ SetParent set_parent(const SetView& s, uint32_t k, ui
   p.w = 0u;
   p.odd = false;
   if (p.paired) return p;
-  const uint32_t q = (uint32_t)s.scan[t];
+  const uint32_t q = (uint32_t)s.scan[t] - q0;
   p.w = q < s.n_words ? s.words[q] : P;
   p.odd = p.x & 1u;
   return p;
 }
+__device__ __forceinline__ SetParent set_parent(const SetView& s, uint32_t k, uint32_t r) { return set_parent_from(s, k, r, 0u); }
 
 // ---- the host pieces both verifiers and both openers run (mem_set.hip) ---------------------------------------------------------
 // flag[t] and scan[t] of the 28 n pairs, enqueued on st (the scan's temporary lives in `tmp` until the stream has run)

@@ -2250,13 +2250,40 @@ def verify_transition_host(t, lib=None):
     return rc, buf.value.decode(errors="replace")
 
 
-def follow_run(proofs, transitions, lib=None, device=True):
+def _roots_fit(who, i, proof, t):
+    d = proof.public_data()
+    for side, want in (("before", d["initial_root"]), ("after", d["final_root"])):
+        got = getattr(t, "root_" + side)
+        if got != want:
+            raise CmError(f"{who}segment {i}: the transition's root {side} is {got}, the proof's is {want}")
+
+
+def follow_run(proofs, transitions, lib=None, device=True, batched=False):
     """What a client that holds only the proofs' roots does with a run's transitions: transition i must go from proof i's public
     initial_root to its final_root and must verify (device=True: on the GPU, else in host code).  Returns the updates
-    [(address, new value)] in run order; raises CmError naming the first segment whose transition does not fit."""
+    [(address, new value)] in run order; raises CmError naming the first segment whose transition does not fit.
+    batched=True (GPU only): the same root checks, in order, up to the first segment whose roots do not fit; ONE
+    verify_transitions over the segments in front of it; the same CmError for the first segment that fails either way."""
     L = lib or proofs[0].L
     if len(proofs) != len(transitions):
         raise CmError(f"follow_run: {len(transitions)} transitions for {len(proofs)} proofs")
+    if batched:
+        if not device:
+            raise CmError("follow_run: batched=True verifies on the GPU (device=True)")
+        misfit, fit = None, 0
+        for i, (p, t) in enumerate(zip(proofs, transitions)):
+            try:
+                _roots_fit("follow_run: ", i, p, t)
+            except CmError as e:
+                misfit = e
+                break
+            fit += 1
+        oks = verify_transitions(transitions[:fit], L) if fit else []
+        if not all(oks):
+            raise CmError(f"follow_run: segment {oks.index(False)}: the transition does not verify on the GPU")
+        if misfit:
+            raise misfit
+        return [u for t in transitions for u in t.updates()]
     out = []
     for i, (p, t) in enumerate(zip(proofs, transitions)):
         d = p.public_data()
@@ -2335,8 +2362,100 @@ def run_transition(proofs, transitions, lib=None, device=True):
     return t
 
 
+# ---- batched verification of transitions and sets (include/cairom_hip.h: cm_verify_memory_transitions .. cm_mem_batch_plan) -----
+class MemSetViewC(C.Structure):
+    """cm_mem_set_view"""
+    _fields_ = [(n, C.c_uint32) for n in ("struct_size", "root", "n", "n_siblings")] + [(n, _u32p) for n in ("addresses", "values", "siblings")]
+
+
+class MemBatchStep(C.Structure):
+    """cm_mem_batch_step: one hashing step of a batch (cm_mem_batch_plan)."""
+    _fields_ = [("depth", C.c_uint32), ("n_nodes", C.c_uint32), ("widest_part", C.c_uint32), ("kernel", C.c_uint32)]
+
+
+def _set_view(root, opening):
+    """(a filled cm_mem_set_view over the opening's arrays, the arrays to keep alive)"""
+    a, s, v = opening.addresses, opening.siblings, opening.values.reshape(-1)
+    if v.size != 4 * a.size:
+        raise ValueError(f"{v.size} value words for a set of {a.size} cells")
+    view = MemSetViewC()
+    view.struct_size = C.sizeof(MemSetViewC)
+    view.root, view.n, view.n_siblings = int(root), a.size, s.size
+    for name, x in (("addresses", a), ("values", v), ("siblings", s)):
+        if x.size:
+            setattr(view, name, _p(x))
+    return view, (a, v, s)
+
+
+def _verify_batch(L, fn, views, n, planes, stream):
+    ok, got = (C.c_uint8 * max(n, 1))(), (C.c_uint32 * max(planes * n, 1))()
+    rc = fn(views, C.c_uint32(n), ok, got, C.c_uint64(stream))
+    if rc:
+        _raise_status(L, rc)
+    return [bool(x) for x in ok[:n]], list(got[:planes * n])
+
+
+def verify_transitions(ts, lib=None, stream=0, with_roots=False):
+    """cm_verify_memory_transitions (GPU) -> [bool]: verify_transition of every MemTransition of `ts`, in one batch whose number of
+    launches does not depend on len(ts); with_roots: [(bool, (the two roots it folds to, zeros when malformed))].  A malformed
+    part is a verdict and does not disturb the others; CmError (.status, .message) only for what the call itself refuses."""
+    L = lib or load_library()
+    ts = list(ts)
+    views = (MemTransitionViewC * max(len(ts), 1))()
+    keep = []
+    for i, t in enumerate(ts):
+        views[i], k = _transition_view(t)
+        keep.append(k)
+    ok, got = _verify_batch(L, L.cm_verify_memory_transitions, views, len(ts), 2, stream)
+    return [(o, (got[2 * i], got[2 * i + 1])) for i, o in enumerate(ok)] if with_roots else ok
+
+
+def verify_sets(roots, openings, lib=None, stream=0, with_roots=False):
+    """cm_verify_memory_sets (GPU) -> [bool]: verify_set(roots[i], openings[i]) for every i in one batch; with_roots: [(bool, the
+    root it folds to, 0 when malformed)].  `roots` may be one root for all."""
+    L = lib or load_library()
+    openings = list(openings)
+    roots = [int(roots)] * len(openings) if np.isscalar(roots) else [int(r) for r in roots]
+    if len(roots) != len(openings):
+        raise ValueError(f"{len(roots)} roots for {len(openings)} sets")
+    views = (MemSetViewC * max(len(openings), 1))()
+    keep = []
+    for i, (r, o) in enumerate(zip(roots, openings)):
+        views[i], k = _set_view(r, o)
+        keep.append(k)
+    ok, got = _verify_batch(L, L.cm_verify_memory_sets, views, len(openings), 1, stream)
+    return list(zip(ok, got)) if with_roots else ok
+
+
+def mem_batch_plan(address_lists, lib=None):
+    """cm_mem_batch_plan of the parts' strictly ascending address lists: [one dict per hashing step of the batch: depth, n_nodes (of
+    all parts together), widest_part, kernel (a SET_KERNELS name)]; [] when no part reaches the device.  Consecutive tail steps
+    are one launch.  Host code: needs no GPU."""
+    L = lib or load_library()
+    lists = [_set_addresses(a) for a in address_lists]
+    ptrs = (_u32p * max(len(lists), 1))()
+    for i, a in enumerate(lists):
+        if a.size:
+            ptrs[i] = _p(a)
+    n = np.array([a.size for a in lists] or [0], dtype=np.uint32)
+    steps, k = (MemBatchStep * 29)(), C.c_uint32(0)
+    rc = L.cm_mem_batch_plan(ptrs, _p(n), C.c_uint32(len(lists)), steps, C.c_uint32(29), C.byref(k))
+    if rc:
+        _raise_status(L, rc)
+    return [{"depth": s.depth, "n_nodes": s.n_nodes, "widest_part": s.widest_part, "kernel": SET_KERNELS[s.kernel]} for s in steps[:k.value]]
+
+
+def mem_batch_launches(plan):
+    """the hashing launches of a mem_batch_plan: the cells, one per level step, one tail"""
+    kinds = [s["kernel"] for s in plan]
+    return kinds.count("cells") + kinds.count("level") + (1 if "tail" in kinds else 0)
+
+
 Backend.write_set = _backend_write_set
 Backend.open_transition = _backend_open_transition
+Backend.verify_transitions = lambda self, ts, stream=0, with_roots=False: verify_transitions(ts, self.L, stream, with_roots)
+Backend.verify_sets = lambda self, roots, openings, stream=0, with_roots=False: verify_sets(roots, openings, self.L, stream, with_roots)
+Backend.mem_batch_plan = lambda self, address_lists: mem_batch_plan(address_lists, self.L)
 Backend.verify_transition = lambda self, t, stream=0, with_roots=False: verify_transition(t, self.L, stream, with_roots)
 Backend.compose_transitions = lambda self, transitions, device=True: compose_transitions(transitions, self.L, device)
 
@@ -2487,15 +2606,36 @@ class MemImage:
             self.h = None
 
 
-def follow_run_image(proofs, updates, image):
+def follow_run_image(proofs, updates, image, batched=False):
     """What a follower that keeps its own copy of the memory does with a run: update i — a MemTransition, bare or full, or an
     (addresses, new_values) pair — is applied to `image` from proof i's public initial_root to its final_root.  Raises CmError
-    naming the first segment that does not fit; the image then stays at the last good segment.  Returns the image's root."""
+    naming the first segment that does not fit; the image then stays at the last good segment.  Returns the image's root.
+    batched=True: every update is a full MemTransition.  The records of the segments in front of the first whose roots do not fit
+    are screened by ONE verify_transitions before the image is touched, and the segments in front of the first failure are
+    applied as usual.  That segment then goes to the image like any other, so what it refuses is refused in its own words; a
+    record the image takes (it never reads the sibling words, and checks the values against both roots itself) is still an
+    error here: "the transition does not verify on the GPU"."""
     if len(proofs) != len(updates):
         raise CmError(f"follow_run_image: {len(updates)} updates for {len(proofs)} proofs")
+    screened = None
+    if batched:
+        if not all(isinstance(u, MemTransition) for u in updates):
+            raise CmError("follow_run_image: batched=True takes full MemTransitions only")
+        fit = 0
+        for i, (p, u) in enumerate(zip(proofs, updates)):
+            try:
+                _roots_fit("", i, p, u)
+            except CmError:
+                break
+            fit += 1
+        oks = verify_transitions(updates[:fit], image.L) if fit else []
+        screened = oks.index(False) if not all(oks) else None
     for i, (p, u) in enumerate(zip(proofs, updates)):
         d = p.public_data()
         try:
+            if i == screened:
+                image.apply_transition(u)
+                raise CmError("the transition does not verify on the GPU")
             if isinstance(u, MemTransition):
                 for side, want in (("before", d["initial_root"]), ("after", d["final_root"])):
                     if getattr(u, "root_" + side) != want:

@@ -53,6 +53,8 @@
  *    Still 10 (additive: one host-only query, one entry point, two structs): cm_verify_stats, cm_verify_plan_stats, cm_verify_slot,
  *    cm_verify_many_detail.
  *    Still 10 (additive: one new function, no struct): cm_compose_transitions.
+ *    Still 10 (additive: three new functions and two structs, nothing moved; listed with the family they batch): cm_mem_set_view,
+ *    cm_mem_batch_step, cm_verify_memory_transitions, cm_verify_memory_sets, cm_mem_batch_plan.
  *    Still 10 (additive: four new functions and two structs, nothing moved): cm_tail_piece, cm_tail_tables_out, cm_tail_grind_op,
  *    cm_tail_tables_op, cm_tail_tab_words, cm_tail_last_op.
  *    Still 10 (additive: one new function and one struct, nothing moved): cm_eval_job, cm_eval_at_points_op.
@@ -1322,6 +1324,56 @@ int32_t cm_prove_run_transitions(cm_run* r, const cm_run_segment* const* segs, u
  * seam check: where a cell occurs in part j and next in part i > j, old_i must equal new_j, else "cell <a>: part <i> reads a value
  * part <j> did not leave" for the lowest such address and, for it, the lowest i. */
 int32_t cm_compose_transitions(const cm_mem_transition_view* parts, uint32_t n_parts, uint32_t device, cm_mem_transition** out);
+/* Batched verification of transitions and sets (additive to revision 10: three new functions and two structs, nothing moved).
+ * cm_verify_memory_transitions / cm_verify_memory_sets check n_parts records in ONE fold: ok[i] and computed[2 i], computed[2 i + 1]
+ * (sets: computed[i]) are exactly what cm_verify_memory_transition / cm_verify_memory_set gives for part i alone.  parts[i] is a
+ * filled view (struct_size set); a set view is a transition view without the second plane.  Malformed input is a verdict —
+ * ok[i] = 0 with zeros in `computed` — never a failed call, and a bad part does not disturb its neighbours' verdicts or roots (the
+ * rule cm_program_ids states).  A transition part with n == 0 is accepted exactly when it has no words and its two roots are equal
+ * (computed: root_before twice); it puts nothing into any launch, and a batch of only such parts launches nothing.  A set part with
+ * n == 0 is rejected, as by the single call.
+ * Host side: every part goes through the checks the single call makes before its first launch (addresses strictly ascending and
+ * below 2^28, n_siblings = cm_mem_set_plan's); a part that fails them gets ok = 0 and is left out of the device batch, so only
+ * well-shaped parts reach a kernel.  Device side (stream s; 0 = the calling thread's own): the parts' addresses, values and words go
+ * up concatenated with their prefix tables in one copy; the segmented flag pass of cm_compose_transitions and ONE scan over the
+ * 28 N pairs of all parts; a head scatter with ranks relative to each part's slice; one lane per cell of the concatenation; one
+ * launch per depth with one lane per parent of ALL parts (a lane bisects that depth's prefix table for its part and works inside
+ * the part's slice) while any part is wider than 128 nodes — a part that is already narrow rides along; then one tail launch with
+ * one workgroup per part: the level in LDS, the remaining depths, the count, the root or roots compared, four words per part
+ * written.  One upload, one download of 16 bytes per part, one wait.  The number of launches and round trips does not depend on
+ * n_parts: it is that of the part with the most per-level steps plus a constant (cm_mem_batch_plan lists them).  Temporaries per
+ * cell of the batch: the single call's (flags and scan 448 bytes, head lanes up to 112, values 16 per plane, address 4, two node
+ * buffers 4 per plane each) plus 116 + 4 * planes + 16 bytes of tables per part.  The call keeps nothing: every device buffer is
+ * back in the pool when it returns.
+ * Status 1, cm_last_error() naming the part, all decided before any address is read: a NULL `parts` or `ok`; n_parts == 0 or
+ * n_parts > 2^16; a part with a short struct_size; a NULL array in a part whose count is non-zero; a part with n > 2^20; the
+ * parts' n summing to more than 2^20 ("verify in groups").  Without a GPU a call that passes these returns cm_init's status (3).
+ * cm_mem_batch_plan lists, host code only and from the addresses alone, the launches the batch would make: none when no part
+ * reaches the device (a part without cells or with bad addresses does not), else always 29 steps — steps[0] the cells (depth 28),
+ * steps[k + 1] the step that hashes every part's S_k into S_{k+1}; n_nodes = the parents of all parts together, widest_part = the
+ * most any one part has, `kernel` = 0 the per-cell kernel, 1 the per-level kernel (while any part's S_k is wider than 128 nodes), 2
+ * the tail (consecutive tail steps are one launch).  The launch path runs the same host code.  Status 1: a NULL argument,
+ * n_parts == 0 or > 2^16, a NULL address list with a count, a part or a sum over 2^20 cells, cap < *n_steps (which is still
+ * written). */
+typedef struct {
+  uint32_t struct_size;
+  uint32_t root;
+  uint32_t n;
+  uint32_t n_siblings;
+  const uint32_t* addresses;    /* n */
+  const uint32_t* values;       /* 4 n */
+  const uint32_t* siblings;     /* n_siblings */
+} cm_mem_set_view;              /* sizeof = 40 */
+typedef struct {
+  uint32_t depth;               /* the step produces nodes of this depth */
+  uint32_t n_nodes;             /* in all parts together */
+  uint32_t widest_part;         /* the most nodes any one part has at that depth */
+  uint32_t kernel;              /* 0 cells, 1 level, 2 tail */
+} cm_mem_batch_step;            /* sizeof = 16 */
+int32_t cm_verify_memory_transitions(const cm_mem_transition_view* parts, uint32_t n_parts, uint8_t* ok, uint32_t* computed, cm_stream_t s);
+int32_t cm_verify_memory_sets(const cm_mem_set_view* parts, uint32_t n_parts, uint8_t* ok, uint32_t* computed, cm_stream_t s);
+int32_t cm_mem_batch_plan(const uint32_t* const* addresses, const uint32_t* n, uint32_t n_parts, cm_mem_batch_step* steps, uint32_t cap,
+                          uint32_t* n_steps);
 /* ---- followed memory (additive to revision 10: new symbols and one struct, nothing moved) --------------------------------------
  * The party between the prover and the light client: a follower (a bridge, an RPC node, a checkpoint service) that keeps its own
  * copy of a run's memory and answers openings under the run's latest root.  cm_mem_image is that copy: a memory image with its

@@ -325,6 +325,28 @@ pub struct cm_mem_transition_view {
     pub new_values: *const u32,
     pub siblings: *const u32,
 }
+/// One set of a batch (`cm_verify_memory_sets`): a transition view without the second plane; set `struct_size`
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct cm_mem_set_view {
+    pub struct_size: u32,
+    pub root: u32,
+    pub n: u32,
+    pub n_siblings: u32,
+    pub addresses: *const u32,
+    pub values: *const u32,
+    pub siblings: *const u32,
+}
+/// One hashing step of a batch of sets or transitions (`cm_mem_batch_plan`): the `n_nodes` nodes of `depth` all parts produce
+/// together, the most any one part has and the kernel that runs it (0 per cell, 1 per level, 2 the tail, one workgroup per part)
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct cm_mem_batch_step {
+    pub depth: u32,
+    pub n_nodes: u32,
+    pub widest_part: u32,
+    pub kernel: u32,
+}
 /// A followed memory image (`cm_mem_image_create`): opaque, freed with `cm_mem_image_free`
 #[repr(C)]
 pub struct cm_mem_image {
@@ -667,6 +689,9 @@ unsafe extern "C" {
     pub fn cm_verify_memory_transition_host(root_before: u32, root_after: u32, addresses: *const u32, n: u64, old_values: *const u32, new_values: *const u32, siblings: *const u32, n_siblings: u32) -> i32;
     pub fn cm_prove_run_transitions(r: *mut cm_run, segs: *const *const cm_run_segment, n: u32, config: *const cm_pcs_config, inflight: u32, outs: *mut *mut cm_proof, transitions: *mut *mut cm_mem_transition) -> i32;
     pub fn cm_compose_transitions(parts: *const cm_mem_transition_view, n_parts: u32, device: u32, out: *mut *mut cm_mem_transition) -> i32;
+    pub fn cm_verify_memory_transitions(parts: *const cm_mem_transition_view, n_parts: u32, ok: *mut u8, computed: *mut u32, s: cm_stream_t) -> i32;
+    pub fn cm_verify_memory_sets(parts: *const cm_mem_set_view, n_parts: u32, ok: *mut u8, computed: *mut u32, s: cm_stream_t) -> i32;
+    pub fn cm_mem_batch_plan(addresses: *const *const u32, n: *const u32, n_parts: u32, steps: *mut cm_mem_batch_step, cap: u32, n_steps: *mut u32) -> i32;
     pub fn cm_mem_image_create(addresses: *const u32, values: *const u32, n: u64, device: u32, out: *mut *mut cm_mem_image) -> i32;
     pub fn cm_mem_image_free(img: *mut cm_mem_image) -> i32;
     pub fn cm_mem_image_root(img: *mut cm_mem_image, root: *mut u32) -> i32;

@@ -690,6 +690,32 @@ pub fn compose_transitions(parts: &[MemTransition], device: bool) -> Result<MemT
     if device {
         ensure_init();
     }
+    let views = transition_views(parts)?;
+    let mut h: *mut cm_mem_transition = std::ptr::null_mut();
+    let rc = unsafe { cm_compose_transitions(views.as_ptr(), views.len() as u32, if device { 1 } else { 0 }, &mut h) };
+    if rc != 0 {
+        return Err(last_error());
+    }
+    take_transition(h)
+}
+
+/// Transitions checked against their roots on the GPU in ONE batch (`cm_verify_memory_transitions`) -> per part what
+/// `verify_memory_transition` gives for it alone: (accepted, the two roots it folds to; zeros when malformed).  The number of
+/// launches does not depend on `parts.len()`; a malformed part is a `false` and does not disturb its neighbours.
+pub fn verify_memory_transitions(parts: &[MemTransition]) -> Result<Vec<(bool, [u32; 2])>, String> {
+    ensure_init();
+    let views = transition_views(parts)?;
+    let mut ok: Vec<u8> = vec![0; parts.len()];
+    let mut got: Vec<u32> = vec![0; 2 * parts.len()];
+    let rc = unsafe { cm_verify_memory_transitions(views.as_ptr(), views.len() as u32, ok.as_mut_ptr(), got.as_mut_ptr(), 0) };
+    if rc != 0 {
+        return Err(last_error());
+    }
+    Ok((0..parts.len()).map(|i| (ok[i] != 0, [got[2 * i], got[2 * i + 1]])).collect())
+}
+
+/// One filled `cm_mem_transition_view` per part, over the parts' own arrays
+fn transition_views(parts: &[MemTransition]) -> Result<Vec<cm_mem_transition_view>, String> {
     let mut views: Vec<cm_mem_transition_view> = Vec::with_capacity(parts.len());
     for t in parts {
         if t.old_values.len() != 4 * t.addresses.len() || t.new_values.len() != 4 * t.addresses.len() {
@@ -708,12 +734,7 @@ pub fn compose_transitions(parts: &[MemTransition], device: bool) -> Result<MemT
         v.siblings = t.siblings.as_ptr();
         views.push(v);
     }
-    let mut h: *mut cm_mem_transition = std::ptr::null_mut();
-    let rc = unsafe { cm_compose_transitions(views.as_ptr(), views.len() as u32, if device { 1 } else { 0 }, &mut h) };
-    if rc != 0 {
-        return Err(last_error());
-    }
-    take_transition(h)
+    Ok(views)
 }
 
 /// A followed memory image (`cm_mem_image_*`): a copy of a run's memory with its partial Merkle tree, on the GPU (`device` = true)
