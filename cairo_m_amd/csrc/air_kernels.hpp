@@ -1,6 +1,7 @@
 // Host-visible declarations of the per-component AIR kernels (kernels_air.hip).
 #pragma once
 #include "engine.hpp"
+#include "air/components.hpp"
 
 namespace cm {
 
@@ -29,6 +30,27 @@ struct ConstraintArgs {
   const uint32_t* const* it_prev = nullptr;
 };
 
+// coset_vanishing of CanonicCoset(log).coset at p (QM31 or M31 point)
+template <class F>
+static F coset_vanishing_canonic(uint32_t log, CPoint<F> p) {
+  // shift = -initial + step/2 = 0 for a canonic (odds) coset: initial = G_{2^(log+1)} = step/2
+  F x = p.x;
+  for (uint32_t i = 1; i < log; i++) x = double_x(x);
+  return x;
+}
+// the launch arguments both provers (and the per-component C-ABI entry point) compute alike; column tables, row range and `acc`
+// stay with the caller
+inline void fill_constraint_args(ConstraintArgs& a, int c, uint32_t log_size, const QM31& claimed_sum, const DevRelations* rels, const uint32_t* coeff) {
+  a.rels = rels;
+  a.coeff = coeff;
+  a.log_size = log_size;
+  a.n_base = air::component_info(c).n_base_constraints;
+  (claimed_sum * inv(M31::from_u32(1u << log_size))).to_u32(a.cumsum_shift);
+  for (uint32_t k = 0; k < 2; k++) {
+    CPoint<M31> p = point_at_index(domain_index_at(log_size + 1, k));
+    a.denom_inv[k] = inv(coset_vanishing_canonic<M31>(log_size, p)).v;
+  }
+}
 void launch_opcode_trace(int cid, const void* bundles, uint32_t n, const void* acc, uint32_t log_size, uint32_t* const* d_cols,
                          hipStream_t st);
 void launch_memory_trace(const void* init, uint32_t ni, const void* fin, uint32_t nf, uint32_t root_i, uint32_t root_f,

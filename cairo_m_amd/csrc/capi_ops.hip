@@ -5,22 +5,14 @@
 #include "engine.hpp"
 #include "fri_kernels.hpp"
 #include "air_kernels.hpp"
+#include "abi.hpp"
 #include <vector>
 #include <string>
 #include <algorithm>
 
 using namespace cm;
-extern "C" int32_t cm_set_last_error(const char* msg);
 
 namespace {
-inline hipStream_t S(cm_stream_t s) { return (hipStream_t)(uintptr_t)s; }
-inline uint32_t* P32(cm_handle h) { return (uint32_t*)(uintptr_t)h; }
-template <class F>
-int32_t guard(F&& f) {
-  try { f(); return 0; }
-  catch (const CmError& e) { cm_set_last_error(e.what()); return e.code ? e.code : 1; }
-  catch (const std::exception& e) { cm_set_last_error(e.what()); return 1; }
-}
 __global__ void k_inverse_m31(const uint32_t* in, uint32_t* out, uint64_t n) {
   uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out[i] = inv(M31(in[i])).v;
@@ -70,27 +62,27 @@ extern "C" {
 
 // AccumulationOps (Stwo core::air::accumulation): column += other, and the powers of the random coefficient
 int32_t cm_accumulate(const cm_handle dst[4], const cm_handle src[4], uint64_t n, cm_stream_t s) {
-  return guard([&] {
+  return abi_guard([&] {
     CM_CHECK(n < (1ull << 32), "cm_accumulate: column too long");
     std::vector<uint32_t*> d(4);
     std::vector<const uint32_t*> c(4);
-    for (int k = 0; k < 4; k++) { d[k] = P32(dst[k]); c[k] = P32(src[k]); CM_CHECK(d[k] && c[k], "cm_accumulate: null column"); }
-    DevBuf dd = upload(d, S(s)), dc = upload(c, S(s));
-    add_columns(dd.as<uint32_t*>(), dc.as<const uint32_t*>(), 4, (uint32_t)n, S(s));
-    CM_HIP(hipStreamSynchronize(S(s)));
+    for (int k = 0; k < 4; k++) { d[k] = as_words(dst[k]); c[k] = as_words(src[k]); CM_CHECK(d[k] && c[k], "cm_accumulate: null column"); }
+    DevBuf dd = upload(d, as_stream(s)), dc = upload(c, as_stream(s));
+    add_columns(dd.as<uint32_t*>(), dc.as<const uint32_t*>(), 4, (uint32_t)n, as_stream(s));
+    CM_HIP(hipStreamSynchronize(as_stream(s)));
   });
 }
 int32_t cm_generate_secure_powers(const uint32_t felt[4], uint64_t n, uint32_t* out) {
-  return guard([&] {
+  return abi_guard([&] {
     QM31 f = QM31::from_u32(felt), cur(M31(1));
     for (uint64_t i = 0; i < n; i++) { cur.to_u32(out + 4 * i); cur = cur * f; }
   });
 }
 int32_t cm_col_zero(cm_handle h, uint64_t n_u32, cm_stream_t s) {
-  return guard([&] {
+  return abi_guard([&] {
     CM_CHECK(h, "cm_col_zero: null column");
-    CM_HIP(hipMemsetAsync(P32(h), 0, n_u32 * 4, S(s)));
-    CM_HIP(hipStreamSynchronize(S(s)));
+    CM_HIP(hipMemsetAsync(as_words(h), 0, n_u32 * 4, as_stream(s)));
+    CM_HIP(hipStreamSynchronize(as_stream(s)));
   });
 }
 
@@ -98,65 +90,65 @@ int32_t cm_col_zero(cm_handle h, uint64_t n_u32, cm_stream_t s) {
 // evaluation, g = f -/+ lambda).  Not on the prove_cairo_m path (every committed column is inside the FFT space), kept
 // for the Backend trait surface.
 int32_t cm_fri_decompose(const cm_handle f[4], uint32_t log_n, uint32_t lambda_out[4], cm_stream_t s) {
-  return guard([&] {
+  return abi_guard([&] {
     CM_CHECK(log_n >= 1 && log_n <= 30, "cm_fri_decompose: bad log size");
     CP4 c; P4 m;
-    for (int k = 0; k < 4; k++) { m.p[k] = P32(f[k]); c.p[k] = m.p[k]; CM_CHECK(m.p[k], "cm_fri_decompose: null column"); }
+    for (int k = 0; k < 4; k++) { m.p[k] = as_words(f[k]); c.p[k] = m.p[k]; CM_CHECK(m.p[k], "cm_fri_decompose: null column"); }
     const uint64_t n = 1ull << log_n;
     const uint32_t blocks = (uint32_t)std::min<uint64_t>((n + 255) / 256, 64);
     DevBuf partial((size_t)blocks * 16), lam(16);
-    hipLaunchKernelGGL(k_decompose_sum, dim3(blocks), dim3(256), 0, S(s), c, log_n, partial.u32());
-    hipLaunchKernelGGL(k_decompose_apply, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(s), m, log_n, partial.u32(), blocks,
+    hipLaunchKernelGGL(k_decompose_sum, dim3(blocks), dim3(256), 0, as_stream(s), c, log_n, partial.u32());
+    hipLaunchKernelGGL(k_decompose_apply, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(s), m, log_n, partial.u32(), blocks,
                        lam.u32());
     CM_HIP(hipGetLastError());
-    CM_HIP(hipMemcpyAsync(lambda_out, lam.p, 16, hipMemcpyDeviceToHost, S(s)));
-    CM_HIP(hipStreamSynchronize(S(s)));
+    CM_HIP(hipMemcpyAsync(lambda_out, lam.p, 16, hipMemcpyDeviceToHost, as_stream(s)));
+    CM_HIP(hipStreamSynchronize(as_stream(s)));
   });
 }
 
 // FieldOps::batch_inverse: element-wise inverses (the Montgomery trick of the CPU backend is a
 // latency optimisation; one Fermat chain per lane is the GPU-native form and gives the same values).
 int32_t cm_batch_inverse_m31(cm_handle in, cm_handle out, uint64_t n, cm_stream_t s) {
-  return guard([&] {
+  return abi_guard([&] {
     if (!n) return;
-    hipLaunchKernelGGL(k_inverse_m31, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(s), P32(in), P32(out), n);
+    hipLaunchKernelGGL(k_inverse_m31, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(s), as_words(in), as_words(out), n);
     CM_HIP(hipGetLastError());
-    CM_HIP(hipStreamSynchronize(S(s)));
+    CM_HIP(hipStreamSynchronize(as_stream(s)));
   });
 }
 int32_t cm_batch_inverse_qm31(const cm_handle in[4], const cm_handle out[4], uint64_t n, cm_stream_t s) {
-  return guard([&] {
+  return abi_guard([&] {
     if (!n) return;
     CP4 i4; P4 o4;
-    for (int k = 0; k < 4; k++) { i4.p[k] = P32(in[k]); o4.p[k] = P32(out[k]); }
-    hipLaunchKernelGGL(k_inverse_qm31, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(s), i4, o4, n);
+    for (int k = 0; k < 4; k++) { i4.p[k] = as_words(in[k]); o4.p[k] = as_words(out[k]); }
+    hipLaunchKernelGGL(k_inverse_qm31, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(s), i4, o4, n);
     CM_HIP(hipGetLastError());
-    CM_HIP(hipStreamSynchronize(S(s)));
+    CM_HIP(hipStreamSynchronize(as_stream(s)));
   });
 }
 int32_t cm_fri_fold_circle_into_line(const cm_handle dst[4], const cm_handle src[4], const uint32_t alpha[4], uint32_t log_n,
                                      cm_handle tw, cm_stream_t s) {
-  return guard([&] {
+  return abi_guard([&] {
     CM_CHECK(tw, "cm_fri_fold_circle_into_line: null twiddles");
     uint32_t* d[4]; const uint32_t* c[4];
-    for (int k = 0; k < 4; k++) { d[k] = P32(dst[k]); c[k] = P32(src[k]); }
-    fold_circle_into_line(d, c, log_n, *(Twiddles*)(uintptr_t)tw, QM31::from_u32(alpha), true, S(s));
-    CM_HIP(hipStreamSynchronize(S(s)));
+    for (int k = 0; k < 4; k++) { d[k] = as_words(dst[k]); c[k] = as_words(src[k]); }
+    fold_circle_into_line(d, c, log_n, *(Twiddles*)(uintptr_t)tw, QM31::from_u32(alpha), true, as_stream(s));
+    CM_HIP(hipStreamSynchronize(as_stream(s)));
   });
 }
 int32_t cm_fri_fold_line(const cm_handle in[4], const uint32_t alpha[4], uint32_t log_n, cm_handle tw, const cm_handle out[4],
                          cm_stream_t s) {
-  return guard([&] {
+  return abi_guard([&] {
     CM_CHECK(tw, "cm_fri_fold_line: null twiddles");
     uint32_t* d[4]; const uint32_t* c[4];
-    for (int k = 0; k < 4; k++) { d[k] = P32(out[k]); c[k] = P32(in[k]); }
-    fold_line(d, c, log_n, *(Twiddles*)(uintptr_t)tw, QM31::from_u32(alpha), S(s));
-    CM_HIP(hipStreamSynchronize(S(s)));
+    for (int k = 0; k < 4; k++) { d[k] = as_words(out[k]); c[k] = as_words(in[k]); }
+    fold_line(d, c, log_n, *(Twiddles*)(uintptr_t)tw, QM31::from_u32(alpha), as_stream(s));
+    CM_HIP(hipStreamSynchronize(as_stream(s)));
   });
 }
 int32_t cm_fri_fold_line_leaves(const cm_handle* in, const cm_handle* circle, const uint32_t* alpha, const uint32_t* alpha_circle,
                                 uint32_t log_n, cm_handle tw, const cm_handle out[4], cm_handle leaf_hashes, cm_stream_t s) {
-  return guard([&] {
+  return abi_guard([&] {
     CM_CHECK(tw, "cm_fri_fold_line_leaves: null twiddles");
     CM_CHECK(log_n >= 2, "cm_fri_fold_line_leaves: log_n < 2");
     CM_CHECK(in || circle, "cm_fri_fold_line_leaves: neither a line nor a circle source");
@@ -164,32 +156,32 @@ int32_t cm_fri_fold_line_leaves(const cm_handle* in, const cm_handle* circle, co
              "cm_fri_fold_line_leaves: every source comes with its challenge");
     const Twiddles& T = *(Twiddles*)(uintptr_t)tw;
     uint32_t* d[4]; const uint32_t* c[4] = {nullptr, nullptr, nullptr, nullptr}; const uint32_t* q[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int k = 0; k < 4; k++) { d[k] = P32(out[k]); if (in) c[k] = P32(in[k]); if (circle) q[k] = P32(circle[k]); }
+    for (int k = 0; k < 4; k++) { d[k] = as_words(out[k]); if (in) c[k] = as_words(in[k]); if (circle) q[k] = as_words(circle[k]); }
     std::vector<uint32_t> a8(8, 0);
     if (alpha) memcpy(a8.data(), alpha, 16);
     if (alpha_circle) memcpy(a8.data() + 4, alpha_circle, 16);
-    DevBuf d_a = upload(a8, S(s));
-    const bool fused = in ? fold_line_leaf(d, c, circle ? q : nullptr, log_n, T, S(s), d_a.u32(), circle ? d_a.u32() + 4 : nullptr, P32(leaf_hashes))
-                          : fold_circle_leaf(d, q, log_n, T, S(s), d_a.u32() + 4, P32(leaf_hashes));
+    DevBuf d_a = upload(a8, as_stream(s));
+    const bool fused = in ? fold_line_leaf(d, c, circle ? q : nullptr, log_n, T, as_stream(s), d_a.u32(), circle ? d_a.u32() + 4 : nullptr, as_words(leaf_hashes))
+                          : fold_circle_leaf(d, q, log_n, T, as_stream(s), d_a.u32() + 4, as_words(leaf_hashes));
     if (!fused) {
       // small layers: the two launches the fused kernel replaces
-      if (!in) fold_circle_into_line(d, q, log_n, T, QM31::from_u32(alpha_circle), false, S(s));
-      else if (circle) fold_line_and_circle(d, c, q, log_n, T, S(s), d_a.u32(), d_a.u32() + 4);
-      else fold_line(d, c, log_n, T, QM31::from_u32(alpha), S(s));
+      if (!in) fold_circle_into_line(d, q, log_n, T, QM31::from_u32(alpha_circle), false, as_stream(s));
+      else if (circle) fold_line_and_circle(d, c, q, log_n, T, as_stream(s), d_a.u32(), d_a.u32() + 4);
+      else fold_line(d, c, log_n, T, QM31::from_u32(alpha), as_stream(s));
       std::vector<const uint32_t*> cols(d, d + 4);
-      DevBuf d_cols = upload(cols, S(s));
-      merkle_layer(log_n - 1, nullptr, d_cols.as<const uint32_t*>(), 4, P32(leaf_hashes), S(s));
+      DevBuf d_cols = upload(cols, as_stream(s));
+      merkle_layer(log_n - 1, nullptr, d_cols.as<const uint32_t*>(), 4, as_words(leaf_hashes), as_stream(s));
     }
-    CM_HIP(hipStreamSynchronize(S(s)));
+    CM_HIP(hipStreamSynchronize(as_stream(s)));
   });
 }
 int32_t cm_accumulate_quotients(uint32_t log_size, const cm_handle* cols, uint32_t n_cols, const cm_sample_batches* b,
                                 const uint32_t random_coeff[4], const cm_handle out[4], cm_handle tw, cm_stream_t s) {
-  return guard([&] {
+  return abi_guard([&] {
     CM_CHECK(tw, "cm_accumulate_quotients: null twiddles");
     QM31 rc = QM31::from_u32(random_coeff);
     std::vector<const uint32_t*> c(n_cols);
-    for (uint32_t i = 0; i < n_cols; i++) c[i] = P32(cols[i]);
+    for (uint32_t i = 0; i < n_cols; i++) c[i] = as_words(cols[i]);
     std::vector<QuotientBatch> qb(b->n_batches);
     std::vector<uint32_t> col_index, coef_c;
     for (uint32_t k = 0; k < b->n_batches; k++) {
@@ -217,7 +209,7 @@ int32_t cm_accumulate_quotients(uint32_t log_size, const cm_handle* cols, uint32
       qpow(rc, b->batch_off[k + 1] - b->batch_off[k]).to_u32(qb[k].batch_coeff);
     }
     std::vector<uint32_t*> o(4);
-    for (int k = 0; k < 4; k++) o[k] = P32(out[k]);
+    for (int k = 0; k < 4; k++) o[k] = as_words(out[k]);
     // per entry: the column pointer itself, as quotient_plan.hpp resolves it for the prover — the op then runs the kernel the
     // "quot_rows" tuning key selects (k_quotients_rows<2> by default) and not only the one-row kernel's 8-wide loop
     std::vector<const uint32_t*> ep(col_index.size());
@@ -225,15 +217,15 @@ int32_t cm_accumulate_quotients(uint32_t log_size, const cm_handle* cols, uint32
       CM_CHECK(col_index[e] < n_cols, "cm_accumulate_quotients: column index out of range");
       ep[e] = c[col_index[e]];
     }
-    DevBuf dcols = upload(c, S(s)), dci = upload(col_index, S(s)), dcc = upload(coef_c, S(s)), dqb = upload(qb, S(s)),
-           dout = upload(o, S(s)), dep = upload(ep, S(s));
+    DevBuf dcols = upload(c, as_stream(s)), dci = upload(col_index, as_stream(s)), dcc = upload(coef_c, as_stream(s)), dqb = upload(qb, as_stream(s)),
+           dout = upload(o, as_stream(s)), dep = upload(ep, as_stream(s));
     QuotientArgs a;
     a.tw = view(*(Twiddles*)(uintptr_t)tw); a.log_size = log_size; a.cols = dcols.as<const uint32_t*>();
     a.col_index = dci.u32(); a.coef_c = dcc.u32(); a.batches = dqb.as<QuotientBatch>(); a.n_batches = b->n_batches;
     a.out = dout.as<uint32_t*>();
     a.entry_cols = dep.as<const uint32_t*>();
-    launch_quotients(a, (double)n_cols, S(s));
-    CM_HIP(hipStreamSynchronize(S(s)));
+    launch_quotients(a, (double)n_cols, as_stream(s));
+    CM_HIP(hipStreamSynchronize(as_stream(s)));
   });
 }
 
@@ -242,7 +234,7 @@ int32_t cm_accumulate_quotients(uint32_t log_size, const cm_handle* cols, uint32
 // In a whole proof the transcript picks the felt and the components pick the sizes; here the tests pick them.
 int32_t cm_eval_at_points_op(const cm_eval_job* jobs, uint32_t n_jobs, const uint32_t* t4, uint32_t want_landing, uint32_t* out,
                              uint32_t* landing, cm_stream_t s) {
-  return guard([&] {
+  return abi_guard([&] {
     CM_CHECK(jobs && out && (landing || !want_landing), "cm_eval_at_points_op: null argument");
     CM_CHECK(n_jobs >= 1, "cm_eval_at_points_op: n_jobs is 0");
     CM_CHECK(n_jobs <= CM_EVAL_MAX_JOBS, "cm_eval_at_points_op: more than 64 jobs");
@@ -262,12 +254,12 @@ int32_t cm_eval_at_points_op(const cm_eval_job* jobs, uint32_t n_jobs, const uin
       n_ptrs += j.n_cols;
     }
 
-    hipStream_t st = S(s);
+    hipStream_t st = as_stream(s);
     // every job's column pointers in one device table (the prover's d_oods_table)
     std::vector<const uint32_t*> col_ptrs;
     col_ptrs.reserve(n_ptrs);
     for (uint32_t k = 0; k < n_jobs; k++)
-      for (uint32_t c = 0; c < jobs[k].n_cols; c++) col_ptrs.push_back(P32(jobs[k].coeffs[c]));
+      for (uint32_t c = 0; c < jobs[k].n_cols; c++) col_ptrs.push_back(as_words(jobs[k].coeffs[c]));
     DevBuf d_cols = upload(col_ptrs, st);
     // {4 words per column | guard} per job, on the device and, if asked for, in the pinned landing buffer (a guard of four
     // words keeps every slice 16-byte aligned, which the kernel's uint4 store into the landing buffer needs)

@@ -7,6 +7,8 @@
 // value was out of range).  Threading as cm_prove_device: the calling thread's main stream and device pool.
 #include "../../include/cairom_hip.h"
 #include "segment_input.hpp"
+#include "handles.hpp"
+#include "abi.hpp"
 #include "air_kernels.hpp"
 #include "check_kernels.hpp"
 #include <algorithm>
@@ -41,7 +43,6 @@ void set_message(cm_check_report& rep, const std::string& m) {
 }  // namespace
 
 void check_segment(const DeviceInput& din, const cm_relations* relations, cm_check_report& rep, CheckColumns* keep) {
-  static_assert(sizeof(cm_relations) == sizeof(DevRelations), "cm_relations must mirror DevRelations");
   static_assert(CM_N_COMPONENTS == air::N_COMPONENTS && CM_N_RELATIONS == air::N_RELATIONS, "report dimensions");
   static_assert(sizeof(cm_check_report) % 8 == 0 && offsetof(cm_check_report, row) == 16, "cm_check_report: plain words");
   bind_thread_to_library_device();
@@ -241,25 +242,16 @@ void check_segment(const DeviceInput& din, const cm_relations* relations, cm_che
 }  // namespace cm
 
 // ================================================================= C ABI
-extern "C" int32_t cm_set_last_error(const char* msg);
 namespace {
-template <class F>
-int32_t check_guard(F&& f) {
-  try { f(); return 0; }
-  catch (const cm::CmError& e) { cm_set_last_error(e.what()); return e.code ? e.code : 1; }
-  catch (const std::exception& e) { cm_set_last_error(e.what()); return 1; }
-}
 std::vector<uint32_t*> column_handles(const cm_handle* h, int n) {
   CM_CHECK(h || n == 0, "null column array");
-  std::vector<uint32_t*> v(n);
-  for (int i = 0; i < n; i++) { v[i] = (uint32_t*)(uintptr_t)h[i]; CM_CHECK(v[i], "null column handle"); }
-  return v;
+  return cm::handles(h, n);
 }
 }  // namespace
 
 extern "C" {
 int32_t cm_check_constraints(const cm_device_input* input, const cm_relations* relations, cm_check_report* out) {
-  return check_guard([&] {
+  return cm::abi_guard([&] {
     CM_CHECK(input && input->d && out, "cm_check_constraints: null input / report");
     memset(out, 0, sizeof(*out));
     cm::check_segment(*input->d, relations, *out);
@@ -268,13 +260,13 @@ int32_t cm_check_constraints(const cm_device_input* input, const cm_relations* r
 int32_t cm_constraints_check(int32_t c, const cm_handle* trace_cols, const cm_handle* interaction_cols, const cm_handle* preprocessed,
                              uint32_t log_size, const cm_relations* relations, const uint32_t claimed_sum[4], cm_handle row_status,
                              uint64_t* failing_rows, int32_t* first_constraint, uint64_t* first_row, cm_stream_t s) {
-  return check_guard([&] {
+  return cm::abi_guard([&] {
     using namespace cm;
     CM_CHECK(c >= 0 && c < air::N_COMPONENTS, "bad component id");
     CM_CHECK(log_size >= 4 && log_size <= 26, "cm_constraints_check: log_size must be in 4..26");
     CM_CHECK(relations && claimed_sum, "cm_constraints_check: null relations / claimed sum");
     bind_thread_to_library_device();
-    const hipStream_t st = (hipStream_t)(uintptr_t)s;
+    const hipStream_t st = cm::as_stream(s);
     const air::ComponentInfo& info = air::component_info(c);
     UploadBatch ub;
     uint32_t** d_tr = nullptr; uint32_t** d_it = nullptr; uint32_t** d_pp = nullptr; uint32_t* d_cs = nullptr;
@@ -288,7 +280,7 @@ int32_t cm_constraints_check(int32_t c, const cm_handle* trace_cols, const cm_ha
     CM_HIP(hipMemsetAsync(out.as<uint8_t>() + 8, 0xFF, 8, st));
     CheckArgs a;
     a.tr = (const uint32_t* const*)d_tr; a.it = (const uint32_t* const*)d_it; a.pp = (const uint32_t* const*)d_pp;
-    a.rels = drel.as<DevRelations>(); a.claimed_sum = d_cs; a.row_status = (uint32_t*)(uintptr_t)row_status;
+    a.rels = drel.as<DevRelations>(); a.claimed_sum = d_cs; a.row_status = cm::as_words(row_status);
     a.failing_rows = out.as<unsigned long long>(); a.first = out.as<unsigned long long>() + 1;
     a.log_size = log_size; a.n_base = info.n_base_constraints;
     launch_check(c, a, st);
@@ -302,13 +294,13 @@ int32_t cm_constraints_check(int32_t c, const cm_handle* trace_cols, const cm_ha
 }
 int32_t cm_relation_sums(int32_t c, const cm_handle* trace_cols, const cm_handle* preprocessed, uint32_t log_size,
                          const cm_relations* relations, uint32_t sums[CM_N_RELATIONS][4], cm_stream_t s) {
-  return check_guard([&] {
+  return cm::abi_guard([&] {
     using namespace cm;
     CM_CHECK(c >= 0 && c < air::N_COMPONENTS, "bad component id");
     CM_CHECK(log_size >= 4 && log_size <= 26, "cm_relation_sums: log_size must be in 4..26");
     CM_CHECK(relations && sums, "cm_relation_sums: null relations / output");
     bind_thread_to_library_device();
-    const hipStream_t st = (hipStream_t)(uintptr_t)s;
+    const hipStream_t st = cm::as_stream(s);
     UploadBatch ub;
     uint32_t** d_tr = nullptr; uint32_t** d_pp = nullptr;
     ub.add(column_handles(trace_cols, air::component_info(c).n_trace), &d_tr);

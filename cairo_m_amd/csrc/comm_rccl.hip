@@ -20,8 +20,8 @@
 #include <string>
 #include "../../include/cairom_hip.h"
 #include "engine.hpp"
+#include "abi.hpp"
 
-extern "C" int32_t cm_set_last_error(const char* msg);
 
 namespace cm {
 namespace {
@@ -113,7 +113,7 @@ int32_t cguard(cm_rccl_comm* c, F&& f) {
   }
 }
 int32_t rccl_set_stream(void* ctx, cm_stream_t s) {
-  ((cm_rccl_comm*)ctx)->stream = (hipStream_t)(uintptr_t)s;
+  ((cm_rccl_comm*)ctx)->stream = cm::as_stream(s);
   return 0;
 }
 int32_t rccl_all_gather(void* ctx, uint64_t words_per_rank) {

@@ -11,14 +11,7 @@
 #include <set>
 
 namespace cm {
-// coset_vanishing of CanonicCoset(log).coset at p (QM31 or M31 point)
-template <class F>
-static F coset_vanishing_canonic(uint32_t log, CPoint<F> p) {
-  // shift = -initial + step/2 = 0 for a canonic (odds) coset: initial = G_{2^(log+1)} = step/2
-  F x = p.x;
-  for (uint32_t i = 1; i < log; i++) x = double_x(x);
-  return x;
-}
+// (coset_vanishing_canonic, fill_constraint_args: air_kernels.hpp)
 // up to three device ranges zeroed by ONE launch (the constraints phase clears two accumulator sets and the slot buffer right in
 // front of its kernels: three dependent hipMemsetAsync = three packets on the critical path behind the interaction tree)
 struct ZeroRanges { uint4* p[3]; uint64_t n16[3]; };
@@ -94,19 +87,6 @@ struct ConstraintAccumulators {
   }
 };
 
-// the launch arguments both provers (and the per-component C-ABI entry point) compute alike; column tables, row range and `acc`
-// stay with the caller
-inline void fill_constraint_args(ConstraintArgs& a, int c, uint32_t log_size, const QM31& claimed_sum, const DevRelations* rels, const uint32_t* coeff) {
-  a.rels = rels;
-  a.coeff = coeff;
-  a.log_size = log_size;
-  a.n_base = air::component_info(c).n_base_constraints;
-  (claimed_sum * inv(M31::from_u32(1u << log_size))).to_u32(a.cumsum_shift);
-  for (uint32_t k = 0; k < 2; k++) {
-    CPoint<M31> p = point_at_index(domain_index_at(log_size + 1, k));
-    a.denom_inv[k] = inv(coset_vanishing_canonic<M31>(log_size, p)).v;
-  }
-}
 // A WIDE component of few rows (poseidon2: 443 columns, 426 constraints on 2^10 evaluation rows) is one long program per row on four
 // blocks: ~0.33 ms of pure latency.  In size order it was enqueued last and ran ALONE behind the large kernels; launched first it
 // hides under them.  "cons_wide_first" = 0: the plain size order (A/B).

@@ -24,6 +24,7 @@
 //   k_link_missing   for the lowest listed address that a given ascending set does not hold (a minimum).
 #include "../../include/cairom_hip.h"
 #include "segment_input.hpp"
+#include "handles.hpp"
 #include "mem_tree.hpp"
 #include <hipcub/hipcub.hpp>
 #include <algorithm>

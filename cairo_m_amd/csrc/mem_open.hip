@@ -26,6 +26,7 @@
 #include "mem_open.hpp"
 #include "mem_tree.hpp"
 #include "segment_input.hpp"
+#include "handles.hpp"
 #include "host_adapter.hpp"
 #include <cstring>
 #include <string>
@@ -224,22 +225,24 @@ int32_t cm_verify_memory_openings(uint32_t root, const cm_mem_opening* openings,
 }
 // host code: no device call on this path
 int32_t cm_verify_memory_opening(uint32_t root, const cm_mem_opening* opening) {
-  if (!opening) return cm_set_last_error("cm_verify_memory_opening: null opening");
-  const uint32_t* const w = reinterpret_cast<const uint32_t*>(opening);
-  const std::string who = "memory opening of address " + std::to_string(w[cm::OW_ADDRESS]) + ": ";
-  std::string why;
-  const uint32_t bad = cm::opening_malformed(w);
-  if (bad == 1) why = "the address is beyond the address space of 2^28 cells";
-  else if (bad == 2) why = "present is " + std::to_string(w[cm::OW_PRESENT]) + ", not 0 or 1";
-  else if (bad >= 3 && bad < 7) why = "value word " + std::to_string(bad - 3) + " is not below P (depth 30)";
-  else if (bad >= 7 && bad < 35) why = "the sibling at depth " + std::to_string(cm::OPEN_SIBLINGS - (bad - 7)) + " is not below P";
-  else if (bad == 35) why = "an absent cell with a non-zero value (depth 30)";
-  else {
-    const uint32_t got = cm::opening_root(w);
-    if (got == root) return 0;
-    why = "the path hashes to root " + std::to_string(got) + ", not " + std::to_string(root);
-  }
-  cm_set_last_error((who + why).c_str());
-  return 11;
+  return cm::abi_guard([&]() -> int32_t {
+    if (!opening) return cm_set_last_error("cm_verify_memory_opening: null opening");
+    const uint32_t* const w = reinterpret_cast<const uint32_t*>(opening);
+    const std::string who = "memory opening of address " + std::to_string(w[cm::OW_ADDRESS]) + ": ";
+    std::string why;
+    const uint32_t bad = cm::opening_malformed(w);
+    if (bad == 1) why = "the address is beyond the address space of 2^28 cells";
+    else if (bad == 2) why = "present is " + std::to_string(w[cm::OW_PRESENT]) + ", not 0 or 1";
+    else if (bad >= 3 && bad < 7) why = "value word " + std::to_string(bad - 3) + " is not below P (depth 30)";
+    else if (bad >= 7 && bad < 35) why = "the sibling at depth " + std::to_string(cm::OPEN_SIBLINGS - (bad - 7)) + " is not below P";
+    else if (bad == 35) why = "an absent cell with a non-zero value (depth 30)";
+    else {
+      const uint32_t got = cm::opening_root(w);
+      if (got == root) return 0;
+      why = "the path hashes to root " + std::to_string(got) + ", not " + std::to_string(root);
+    }
+    cm_set_last_error((who + why).c_str());
+    return 11;
+  });
 }
 }  // extern "C"

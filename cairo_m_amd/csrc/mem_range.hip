@@ -23,6 +23,7 @@
 #include "mem_set.hpp"
 #include "mem_open.hpp"
 #include "segment_input.hpp"
+#include "handles.hpp"
 #include <cstring>
 #include <string>
 #include <vector>
@@ -194,39 +195,41 @@ int32_t cm_verify_memory_range(uint32_t root, const cm_mem_range_opening* openin
 }
 // host code: no device call on this path
 int32_t cm_verify_memory_range_host(uint32_t root, const cm_mem_range_opening* opening, const uint32_t* values) {
-  if (!opening || !values) return cm_set_last_error("cm_verify_memory_range_host: null argument");
-  const uint32_t* const w = reinterpret_cast<const uint32_t*>(opening);
-  const uint32_t start = w[cm::RW_START], n = w[cm::RW_NCELLS];
-  if (n > cm::RANGE_MAX_CELLS) return cm_set_last_error("cm_verify_memory_range_host: more than 2^24 cells in one call: split the range");
-  const std::string who = "memory range [" + std::to_string(start) + ", " + std::to_string((uint64_t)start + n) + "): ";
-  auto reject = [&](const std::string& why) { cm_set_last_error((who + why).c_str()); return 11; };
-  if (n == 0) return reject("n_cells is 0");
-  if (cm::range_header_bad(start, n)) return reject("the range ends beyond the address space of 2^28 cells");
-  for (uint64_t i = 0; i < 4ull * n; i++)
-    if (values[i] >= cm::P) return reject("value word " + std::to_string(i % 4) + " of cell " + std::to_string(start + i / 4) + " is not below P");
-  for (uint32_t s = 0; s < 2 * cm::RANGE_SLOTS; s++) {
-    const uint32_t bad = cm::range_slot_malformed(w, s);
-    if (!bad) continue;
-    const std::string side = s < cm::RANGE_SLOTS ? "left" : "right", depth = std::to_string(cm::RANGE_SLOTS - s % cm::RANGE_SLOTS);
-    return reject(bad == 1 ? "the " + side + " sibling at depth " + depth + " is not below P" : "unused " + side + " slot at depth " + depth + " is not zero");
-  }
-  // the fold of the device path, step by step of the same plan
-  cm_mem_range_step steps[cm::RANGE_STEPS];
-  cm::mem_range_plan(start, n, steps);
-  std::vector<uint32_t> a(n), b(n / 2 + 1);
-  for (uint32_t i = 0; i < n; i++) a[i] = cm::range_cell_node(values + 4 * (size_t)i);
-  for (uint32_t s = 1; s < cm::RANGE_STEPS; s++) {
-    const uint32_t n_out = steps[s].hi - steps[s].lo + 1;
-#pragma unroll 1
-    for (uint32_t j = 0; j < n_out; j++) {
-      uint32_t l, r;
-      cm::range_children(a.data(), steps[s - 1].lo, steps[s - 1].hi, w[cm::RW_LEFT + s - 1], w[cm::RW_RIGHT + s - 1], steps[s].lo + j, l, r);
-      b[j] = cm::host::poseidon2_hash(l, r);
+  return cm::abi_guard([&]() -> int32_t {
+    if (!opening || !values) return cm_set_last_error("cm_verify_memory_range_host: null argument");
+    const uint32_t* const w = reinterpret_cast<const uint32_t*>(opening);
+    const uint32_t start = w[cm::RW_START], n = w[cm::RW_NCELLS];
+    if (n > cm::RANGE_MAX_CELLS) return cm_set_last_error("cm_verify_memory_range_host: more than 2^24 cells in one call: split the range");
+    const std::string who = "memory range [" + std::to_string(start) + ", " + std::to_string((uint64_t)start + n) + "): ";
+    auto reject = [&](const std::string& why) { cm_set_last_error((who + why).c_str()); return 11; };
+    if (n == 0) return reject("n_cells is 0");
+    if (cm::range_header_bad(start, n)) return reject("the range ends beyond the address space of 2^28 cells");
+    for (uint64_t i = 0; i < 4ull * n; i++)
+      if (values[i] >= cm::P) return reject("value word " + std::to_string(i % 4) + " of cell " + std::to_string(start + i / 4) + " is not below P");
+    for (uint32_t s = 0; s < 2 * cm::RANGE_SLOTS; s++) {
+      const uint32_t bad = cm::range_slot_malformed(w, s);
+      if (!bad) continue;
+      const std::string side = s < cm::RANGE_SLOTS ? "left" : "right", depth = std::to_string(cm::RANGE_SLOTS - s % cm::RANGE_SLOTS);
+      return reject(bad == 1 ? "the " + side + " sibling at depth " + depth + " is not below P" : "unused " + side + " slot at depth " + depth + " is not zero");
     }
-    a.swap(b);
-  }
-  if (a[0] == root) return 0;
-  return reject("the range hashes to root " + std::to_string(a[0]) + ", not " + std::to_string(root));
+    // the fold of the device path, step by step of the same plan
+    cm_mem_range_step steps[cm::RANGE_STEPS];
+    cm::mem_range_plan(start, n, steps);
+    std::vector<uint32_t> a(n), b(n / 2 + 1);
+    for (uint32_t i = 0; i < n; i++) a[i] = cm::range_cell_node(values + 4 * (size_t)i);
+    for (uint32_t s = 1; s < cm::RANGE_STEPS; s++) {
+      const uint32_t n_out = steps[s].hi - steps[s].lo + 1;
+  #pragma unroll 1
+      for (uint32_t j = 0; j < n_out; j++) {
+        uint32_t l, r;
+        cm::range_children(a.data(), steps[s - 1].lo, steps[s - 1].hi, w[cm::RW_LEFT + s - 1], w[cm::RW_RIGHT + s - 1], steps[s].lo + j, l, r);
+        b[j] = cm::host::poseidon2_hash(l, r);
+      }
+      a.swap(b);
+    }
+    if (a[0] == root) return 0;
+    return reject("the range hashes to root " + std::to_string(a[0]) + ", not " + std::to_string(root));
+  });
 }
 int32_t cm_mem_range_plan(uint32_t start, uint32_t n_cells, cm_mem_range_step* steps, uint32_t cap, uint32_t* n_steps) {
   return cm::abi_guard([&] {

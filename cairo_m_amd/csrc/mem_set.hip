@@ -32,6 +32,7 @@
 #include "set_fold.hpp"
 #include "mem_open.hpp"
 #include "segment_input.hpp"
+#include "handles.hpp"
 #include <hipcub/hipcub.hpp>
 #include <algorithm>
 #include <cstring>
@@ -261,14 +262,16 @@ int32_t cm_verify_memory_set(uint32_t root, const uint32_t* addresses, uint64_t 
 // host code: no device call on these paths
 int32_t cm_memory_set_root_host(const uint32_t* addresses, uint64_t n, const uint32_t* values, const uint32_t* siblings, uint32_t n_siblings,
                                 uint32_t* root_out) {
-  return cm::set_root_host("cm_memory_set_root_host", addresses, n, values, siblings, n_siblings, root_out);
+  return cm::abi_guard([&] { return cm::set_root_host("cm_memory_set_root_host", addresses, n, values, siblings, n_siblings, root_out); });
 }
 int32_t cm_verify_memory_set_host(uint32_t root, const uint32_t* addresses, uint64_t n, const uint32_t* values, const uint32_t* siblings,
                                   uint32_t n_siblings) {
-  uint32_t got = 0;
-  const int32_t rc = cm::set_root_host("cm_verify_memory_set_host", addresses, n, values, siblings, n_siblings, &got);
-  if (rc || got == root) return rc;
-  cm_set_last_error(("memory set of " + std::to_string(n) + " cells: the set hashes to root " + std::to_string(got) + ", not " + std::to_string(root)).c_str());
-  return 11;
+  return cm::abi_guard([&]() -> int32_t {
+    uint32_t got = 0;
+    const int32_t rc = cm::set_root_host("cm_verify_memory_set_host", addresses, n, values, siblings, n_siblings, &got);
+    if (rc || got == root) return rc;
+    cm_set_last_error(("memory set of " + std::to_string(n) + " cells: the set hashes to root " + std::to_string(got) + ", not " + std::to_string(root)).c_str());
+    return 11;
+  });
 }
 }  // extern "C"

@@ -262,24 +262,26 @@ int32_t cm_verify_memory_transition(uint32_t root_before, uint32_t root_after, c
 // host code: no device call on this path.  Both folds are set_root_host's; the old side is judged, and named, first.
 int32_t cm_verify_memory_transition_host(uint32_t root_before, uint32_t root_after, const uint32_t* addresses, uint64_t n, const uint32_t* old_values,
                                          const uint32_t* new_values, const uint32_t* siblings, uint32_t n_siblings) {
-  const char* const who = "cm_verify_memory_transition_host";
-  if (!new_values) return cm_set_last_error((std::string(who) + ": null argument").c_str());
-  const std::string head = "memory transition of " + std::to_string(n) + " cells: ";
-  if (n == 0 && addresses && old_values && siblings) {
-    if (n_siblings) return cm_set_last_error((head + std::to_string(n_siblings) + " sibling words where the addresses need 0").c_str()), 11;
-    if (root_before == root_after) return 0;
-    cm_set_last_error((head + "no cell changes, and root " + std::to_string(root_before) + " is not root " + std::to_string(root_after)).c_str());
-    return 11;
-  }
-  uint32_t got0 = 0, got1 = 0;
-  int32_t rc = cm::set_root_host(who, addresses, n, old_values, siblings, n_siblings, &got0, "memory transition", "old value word");
-  if (rc) return rc;
-  rc = cm::set_root_host(who, addresses, n, new_values, siblings, n_siblings, &got1, "memory transition", "new value word");
-  if (rc) return rc;
-  if (got0 != root_before)
-    return cm_set_last_error((head + "the old values hash to root " + std::to_string(got0) + ", not " + std::to_string(root_before)).c_str()), 11;
-  if (got1 != root_after)
-    return cm_set_last_error((head + "the new values hash to root " + std::to_string(got1) + ", not " + std::to_string(root_after)).c_str()), 11;
-  return 0;
+  return cm::abi_guard([&]() -> int32_t {
+    const char* const who = "cm_verify_memory_transition_host";
+    if (!new_values) return cm_set_last_error((std::string(who) + ": null argument").c_str());
+    const std::string head = "memory transition of " + std::to_string(n) + " cells: ";
+    if (n == 0 && addresses && old_values && siblings) {
+      if (n_siblings) return cm_set_last_error((head + std::to_string(n_siblings) + " sibling words where the addresses need 0").c_str()), 11;
+      if (root_before == root_after) return 0;
+      cm_set_last_error((head + "no cell changes, and root " + std::to_string(root_before) + " is not root " + std::to_string(root_after)).c_str());
+      return 11;
+    }
+    uint32_t got0 = 0, got1 = 0;
+    int32_t rc = cm::set_root_host(who, addresses, n, old_values, siblings, n_siblings, &got0, "memory transition", "old value word");
+    if (rc) return rc;
+    rc = cm::set_root_host(who, addresses, n, new_values, siblings, n_siblings, &got1, "memory transition", "new value word");
+    if (rc) return rc;
+    if (got0 != root_before)
+      return cm_set_last_error((head + "the old values hash to root " + std::to_string(got0) + ", not " + std::to_string(root_before)).c_str()), 11;
+    if (got1 != root_after)
+      return cm_set_last_error((head + "the new values hash to root " + std::to_string(got1) + ", not " + std::to_string(root_after)).c_str()), 11;
+    return 0;
+  });
 }
 }  // extern "C"

@@ -5,13 +5,7 @@
 #include "../../include/cairom_hip.h"
 #include "mem_set.hpp"
 #include "segment_input.hpp"
-#include <vector>
-
-// what cm_input_open_transition hands out; cm_mem_transition_get points into the vectors
-struct cm_mem_transition {
-  std::vector<uint32_t> addresses, old_values, new_values, siblings;
-  uint32_t root_before = 0, root_after = 0, n_zero_only = 0;
-};
+#include "handles.hpp"   // cm_mem_transition: what cm_input_open_transition hands out
 
 namespace cm {
 

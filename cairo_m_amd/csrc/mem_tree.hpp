@@ -1,18 +1,14 @@
 // What the memory-tree family shares (mem_open, mem_range, mem_set, mem_transition, mem_compose, mem_image, program_id, link): the
-// default hashes as a kernel argument, the launch and stream helpers, the chunked download and the guard of their C ABI.  None of
-// it is part of the library's exported symbols.
+// default hashes as a kernel argument, the launch and stream helpers and the chunked download (the guard of their C ABI: abi.hpp).
+// None of it is part of the library's exported symbols.
 #pragma once
 #include "../../include/cairom_hip.h"
 #include "engine.hpp"
 #include "host_adapter.hpp"
+#include "abi.hpp"
 #include <algorithm>
 #include <cstring>
-#include <exception>
 #include <vector>
-
-extern "C" int32_t cm_set_last_error(const char* msg);
-
-#define CM_INTERNAL __attribute__((visibility("hidden")))
 
 namespace cm {
 
@@ -27,7 +23,6 @@ CM_INTERNAL inline TreeDefaults tree_defaults() {
 }
 
 CM_INTERNAL inline dim3 blocks_for(uint64_t n, uint32_t block) { return dim3((uint32_t)((n + block - 1) / block)); }
-CM_INTERNAL inline hipStream_t stream_or_own(cm_stream_t s) { return s ? (hipStream_t)(uintptr_t)s : thread_main_stream(); }
 
 // nothing of a call goes back to the pool while the stream still runs, on the error paths too (declared behind the buffers)
 struct CM_INTERNAL StreamWait {
@@ -44,14 +39,6 @@ CM_INTERNAL inline void download(void* dst, const void* src, size_t bytes, hipSt
     memcpy((uint8_t*)dst + done, land, m);
     done += m;
   }
-}
-
-// the body of a C-ABI call: 0, or the error's status (1 when it has none) with its message left for cm_last_error()
-template <class F>
-CM_INTERNAL int32_t abi_guard(F&& f) {
-  try { f(); return 0; }
-  catch (const CmError& e) { cm_set_last_error(e.what()); return e.code ? e.code : 1; }
-  catch (const std::exception& e) { cm_set_last_error(e.what()); return 1; }
 }
 
 }  // namespace cm

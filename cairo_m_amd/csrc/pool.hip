@@ -4,6 +4,7 @@
 // sizes, 1 for the third identical proof at the metric config — DESIGN 3.5); cm_shutdown()/pool_trim() hands everything back.
 #include <algorithm>
 #include "engine.hpp"
+#include "abi.hpp"
 #include "tail_device.hpp"
 #include "../../include/cairom_hip.h"
 #include <atomic>
@@ -705,38 +706,41 @@ Fork::~Fork() {
 
 }  // namespace cm
 
-extern "C" int32_t cm_set_last_error(const char* msg);
 extern "C" {
 int32_t cm_mem_stats_get(cm_mem_stats* out) {
-  if (!out) return cm_set_last_error("cm_mem_stats_get: null argument");
-  if (out->struct_size < sizeof(cm_mem_stats)) return cm_set_last_error("cm_mem_stats_get: struct_size does not cover cm_mem_stats (set it to sizeof(cm_mem_stats))");
-  cm::MemGlobal& g = cm::mg();
-  cm_mem_stats s;
-  memset(&s, 0, sizeof(s));
-  s.struct_size = sizeof(s);
-  s.budget_bytes = cm::mem_budget();
-  s.proofs_in_flight = g.in_flight.load(std::memory_order_relaxed);
-  s.peak_proofs_in_flight = g.peak_in_flight.load(std::memory_order_relaxed);
-  s.live_bytes = g.live.load(std::memory_order_relaxed);
-  s.reserved_bytes = g.reserved.load(std::memory_order_relaxed);
-  s.peak_live_bytes = g.peak_live.load(std::memory_order_relaxed);
-  s.peak_reserved_bytes = g.peak_reserved.load(std::memory_order_relaxed);
-  s.pinned_host_bytes = g.pinned.load(std::memory_order_relaxed);
-  s.driver_allocs = g.driver_allocs.load(std::memory_order_relaxed);
-  memcpy(out, &s, sizeof(s));
-  return 0;
+  return cm::abi_guard([&]() -> int32_t {
+    if (!out) return cm_set_last_error("cm_mem_stats_get: null argument");
+    if (out->struct_size < sizeof(cm_mem_stats)) return cm_set_last_error("cm_mem_stats_get: struct_size does not cover cm_mem_stats (set it to sizeof(cm_mem_stats))");
+    cm::MemGlobal& g = cm::mg();
+    cm_mem_stats s;
+    memset(&s, 0, sizeof(s));
+    s.struct_size = sizeof(s);
+    s.budget_bytes = cm::mem_budget();
+    s.proofs_in_flight = g.in_flight.load(std::memory_order_relaxed);
+    s.peak_proofs_in_flight = g.peak_in_flight.load(std::memory_order_relaxed);
+    s.live_bytes = g.live.load(std::memory_order_relaxed);
+    s.reserved_bytes = g.reserved.load(std::memory_order_relaxed);
+    s.peak_live_bytes = g.peak_live.load(std::memory_order_relaxed);
+    s.peak_reserved_bytes = g.peak_reserved.load(std::memory_order_relaxed);
+    s.pinned_host_bytes = g.pinned.load(std::memory_order_relaxed);
+    s.driver_allocs = g.driver_allocs.load(std::memory_order_relaxed);
+    memcpy(out, &s, sizeof(s));
+    return 0;
+  });
 }
 int32_t cm_mem_reset_peak(void) {
-  cm::MemGlobal& g = cm::mg();
-  g.peak_live.store(g.live.load(std::memory_order_relaxed), std::memory_order_relaxed);
-  g.peak_reserved.store(g.reserved.load(std::memory_order_relaxed), std::memory_order_relaxed);
-  g.peak_in_flight.store(g.in_flight.load(std::memory_order_relaxed), std::memory_order_relaxed);
-  g.driver_allocs.store(0, std::memory_order_relaxed);
-  return 0;
+  return cm::abi_guard([&] {
+    cm::MemGlobal& g = cm::mg();
+    g.peak_live.store(g.live.load(std::memory_order_relaxed), std::memory_order_relaxed);
+    g.peak_reserved.store(g.reserved.load(std::memory_order_relaxed), std::memory_order_relaxed);
+    g.peak_in_flight.store(g.in_flight.load(std::memory_order_relaxed), std::memory_order_relaxed);
+    g.driver_allocs.store(0, std::memory_order_relaxed);
+  });
 }
 int32_t cm_set_memory_budget(uint64_t bytes) {
-  (void)cm::mem_budget();   // (the environment's initial value must not overwrite this one later)
-  cm::mg().budget.store(bytes, std::memory_order_relaxed);
-  return 0;
+  return cm::abi_guard([&] {
+    (void)cm::mem_budget();   // (the environment's initial value must not overwrite this one later)
+    cm::mg().budget.store(bytes, std::memory_order_relaxed);
+  });
 }
 }

@@ -23,6 +23,7 @@
 #include "../../include/cairom_hip.h"
 #include "program_id.hpp"
 #include "mem_open.hpp"
+#include "handles.hpp"
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -179,14 +180,14 @@ void ids_device(std::vector<Item>& items, uint32_t* ids, int32_t* status, std::s
   }
 }
 
-// a proof's entries of one kind through the public calls (proofs are opaque here)
+// a proof's entries of one kind, as cm_proof_public_entries lays them out
 std::vector<uint32_t> proof_entries(const cm_proof* p, uint32_t which) {
-  uint64_t n = 0;
-  if (cm_proof_public_entries(p, which, nullptr, 0, &n)) throw CmError(1, "program id: the proof's public entries cannot be read");
-  std::vector<uint32_t> e(PID_ENTRY_WORDS * n + 1);
-  if (n && cm_proof_public_entries(p, which, e.data(), n, &n)) throw CmError(1, "program id: the proof's public entries cannot be read");
-  e.resize(PID_ENTRY_WORDS * n);
-  return e;
+  if (!p || !p->d || which > 2) throw CmError(1, "program id: the proof's public entries cannot be read");
+  const PublicData& d = p->d->public_data;
+  const std::vector<PublicEntry>& v = which == 0 ? d.program : which == 1 ? d.input : d.output;
+  static_assert(sizeof(PublicEntry) == 4 * PID_ENTRY_WORDS, "PID_ENTRY_WORDS words per public entry");
+  const uint32_t* w = (const uint32_t*)v.data();
+  return std::vector<uint32_t>(w, w + PID_ENTRY_WORDS * v.size());
 }
 
 std::string hex8(uint32_t x) {

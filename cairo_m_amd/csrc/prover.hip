@@ -15,6 +15,7 @@
 #include "shard_kernels.hpp"
 #include "segment_input.hpp"
 #include "tail_plan.hpp"
+#include "prover_api.hpp"
 #include <atomic>
 #include <chrono>
 #include <deque>
@@ -90,7 +91,7 @@ static PublicData make_public_data(const cm_prover_input& in) {
 // enqueued on `st` and only `st` is waited for — the streaming ingest (cm_prove_many_host) uploads segment k + 1 on the calling
 // thread's stream while the workers' proofs of segments <= k keep the GPU busy; a device-wide wait would stall the uploader
 // behind every proof in flight.
-DeviceInput* upload_input(const cm_prover_input& in, hipStream_t st = nullptr) {
+DeviceInput* upload_input(const cm_prover_input& in, hipStream_t st) {
   bind_thread_to_library_device();
   std::unique_ptr<DeviceInput> dh(new DeviceInput());
   DeviceInput* d = dh.get();
@@ -155,25 +156,7 @@ DeviceInput* make_device_input_resident(const cm_prover_input& meta, DevBuf (&bu
   d->init_tree = std::move(init_tree); d->fin_tree = std::move(fin_tree);
   return d.release();
 }
-DeviceInput* adapt_segment_device(const cm_runner_segment& seg);  // adapter_device.hip
-// the run object (adapter_run.inc)
-struct Run;
-Run* run_begin(const uint32_t* initial_memory, uint64_t n_initial_memory, const uint32_t* initial_heap, uint64_t n_initial_heap, const uint32_t ranges[6]);
-DeviceInput* run_adapt_next(Run& run, const cm_run_segment& seg);
-void run_memory(Run& r, uint32_t* locals, uint64_t cap_l, uint64_t* n_l, uint32_t* heap, uint64_t cap_h, uint64_t* n_h);
-uint64_t run_image_bytes(const Run& r);
-uint64_t run_rows_bound(const Run& r, uint64_t n_memory_trace);
-std::mutex& run_mutex(Run& r);
-void run_open_memory(Run& r, const uint32_t* addresses, uint64_t n, cm_mem_opening* out, uint32_t* root);
-void open_require_device(const char* who);   // mem_open.hip
-void open_check_addresses(const char* who, const uint32_t* addresses, uint64_t n, const cm_mem_opening* out);
-void run_open_memory_range(Run& r, uint32_t start, uint32_t n_cells, uint32_t* values, cm_mem_range_opening* out, uint32_t* root);
-void open_range_check(const char* who, uint32_t start, uint32_t n_cells, const uint32_t* values, const cm_mem_range_opening* out);   // mem_range.hip
-void run_open_memory_set(Run& r, const uint32_t* addresses, uint32_t n, uint32_t* values, uint32_t* siblings, uint32_t n_siblings, uint32_t* root);
-void open_set_check(const char* who, const uint32_t* addresses, uint64_t n, const uint32_t* values, const uint32_t* siblings, uint32_t cap_siblings,
-                    uint32_t* n_siblings);   // mem_set.hip
-cm_mem_transition* open_transition(const DeviceInput& d, const uint32_t* addresses, uint64_t n);   // mem_transition.hip
-void run_free(Run* r);
+// (adapt_segment_device, the run object and the openers: prover_api.hpp)
 // copy a device-resident input back to the host (tests)
 void download_input(const DeviceInput& d, host::ProverInputOwned& o) {
   CM_HIP(hipDeviceSynchronize());
@@ -199,7 +182,7 @@ void download_input(const DeviceInput& d, host::ProverInputOwned& o) {
 // coefficients, LDE and Merkle tree are the same for every proof of one PCS config.  OFF by default — a proof then
 // recomputes them like the reference does (prover.rs:70-73) and bench.py times that; cm_set_preprocessed_cache(1) or
 // CM_PREPROCESSED_CACHE=1 keeps the committed tree per host thread (it lives in that thread's device pool).
-static std::atomic<int> g_pp_cache{-1};
+std::atomic<int> g_pp_cache{-1};
 static bool pp_cache_enabled() {
   int v = g_pp_cache.load(std::memory_order_relaxed);
   if (v < 0) {
@@ -225,7 +208,7 @@ static bool no_small_batch() { static const bool v = getenv("CM_NO_SMALL_BATCH")
 // so by default every proof builds its own tables (in pool memory, on a side stream next to trace generation); they
 // depend only on the domain size, and cm_set_twiddle_cache(1) / CM_TWIDDLE_CACHE=1 keeps one table per size for the
 // process instead (OFF in every quoted number, like the preprocessed-tree cache).
-static std::atomic<int> g_tw_cache{-1};
+std::atomic<int> g_tw_cache{-1};
 static bool tw_cache_enabled() {
   int v = g_tw_cache.load(std::memory_order_relaxed);
   if (v < 0) {
@@ -246,10 +229,8 @@ static Twiddles* cached_twiddles(uint32_t R, hipStream_t st) {
   cache[R] = t;
   return t;
 }
-}  // namespace cm
-#include "mem_estimate.hpp"
-namespace cm {
-static MemSwitches mem_switches() { return MemSwitches{pp_cache_enabled(), tw_cache_enabled(), tune(T_DEFER_TEARDOWN) != 0}; }
+// (MemSwitches, estimate_memory: mem_estimate.hpp)
+MemSwitches mem_switches() { return MemSwitches{pp_cache_enabled(), tw_cache_enabled(), tune(T_DEFER_TEARDOWN) != 0}; }
 // ---- memory budget (cm_set_memory_budget) ----------------------------------------------------------------------------------
 // What one item needs: its resident input and the estimate's bound on what its proof adds to the proving thread's pool.
 struct ItemBytes { uint64_t input = 0, working = 0; };
@@ -303,7 +284,6 @@ struct Admission {
 static Admission& admission() { static Admission* a = new Admission(); return *a; }
 // One proof of a pipeline worker under the admission rules.  With a budget the worker gives back what its previous proof parked
 // before it waits (parked blocks are live bytes nobody admitted), and trims its pool when the process holds more than the budget.
-ProofData* prove(const DeviceInput& din, const cm_pcs_config& cfg);
 static ProofData* prove_admitted(const DeviceInput& din, const cm_pcs_config& cfg, const char* who) {
   const uint64_t budget = mem_budget();
   if (!budget) return prove(din, cfg);
@@ -1446,140 +1426,27 @@ struct ProveWorkers {
 };
 ProveWorkers& prove_workers() { static ProveWorkers* w = new ProveWorkers(); return *w; }
 }  // namespace
-}  // namespace cm
 
-#include "verify_device.hpp"
-namespace cm {
-std::string verify_proof(const ProofData& pf, const cm_pcs_config& expected);                 // verifier.hip
-bool proof_from_words(const uint32_t* w, uint64_t n, ProofData& p, std::string& err);
-}  // namespace cm
-
-// ================================================================= C ABI
-struct cm_proof {   // owns its ProofData: every failure path (parse error, exception mid-proof) releases it with the wrapper
-  cm::ProofData* d = nullptr; std::string json, transcript_json; std::vector<uint32_t> words;
-  ~cm_proof() { delete d; }
-};
-extern "C" int32_t cm_set_last_error(const char* msg);
-
-template <class F>
-static int32_t pguard(F&& f) {
-  try { f(); return 0; }
-  catch (const cm::CmError& e) { cm_set_last_error(e.what()); return e.code ? e.code : 1; }
-  catch (const std::exception& e) { cm_set_last_error(e.what()); return 1; }
-}
-static cm_pcs_config default_cfg() { return cm_pcs_config{16, 1, 0, 80}; }
-
-extern "C" {
-int32_t cm_input_upload(const cm_prover_input* input, cm_device_input** out) {
-  return pguard([&] { std::unique_ptr<cm_device_input> h(new cm_device_input()); h->d = cm::upload_input(*input); *out = h.release(); });
-}
-struct cm_host_input { cm::host::ProverInputOwned owned; cm_prover_input view; };  // = host_api.hip
-int32_t cm_adapt_segment_device(const cm_runner_segment* seg, cm_device_input** out) {
-  return pguard([&] { std::unique_ptr<cm_device_input> h(new cm_device_input()); h->d = cm::adapt_segment_device(*seg); *out = h.release(); });
-}
-int32_t cm_device_input_download(const cm_device_input* in, cm_host_input** out) {
-  return pguard([&] {
-    cm_host_input* h = new cm_host_input();
-    cm::download_input(*in->d, h->owned);
-    h->view = h->owned.view();
-    *out = h;
-  });
-}
-int32_t cm_input_free(cm_device_input* h) { delete h; return 0; }
-int32_t cm_prove_device(const cm_device_input* input, const cm_pcs_config* config, cm_proof** out) {
-  return pguard([&] {
-    cm_pcs_config cfg = config ? *config : default_cfg();
-    std::unique_ptr<cm_proof> p(new cm_proof());
-    p->d = cm::prove(*input->d, cfg);
-    *out = p.release();
-  });
-}
-int32_t cm_prove_segment(const cm_prover_input* input, const cm_pcs_config* config, cm_proof** out) {
-  cm_device_input* di = nullptr;
-  int32_t rc = cm_input_upload(input, &di);
-  if (rc) return rc;
-  rc = cm_prove_device(di, config, out);
-  cm_input_free(di);
-  return rc;
-}
-int32_t cm_shard_plan(const cm_prover_input* input, const cm_pcs_config* config, uint32_t world, int32_t owner_out[CM_N_COMPONENTS],
-                      uint64_t* staging_words) {
-  return pguard([&] {
-    CM_CHECK(world >= 1 && world <= 8 && (world & (world - 1)) == 0, "cm_shard_plan: world must be 1, 2, 4 or 8");
-    const cm_pcs_config cfg = config ? *config : default_cfg();
-    CM_CHECK(cfg.log_blowup_factor >= 1 && cfg.log_blowup_factor <= 4, "cm_shard_plan: log_blowup_factor");
-    uint32_t clog[air::N_COMPONENTS];
-    cm::component_logs(*input, clog);
-    // the SAME plan cm_prove_sharded will run under this config (components are split only at log_blowup_factor 1)
-    const cm::ShardPlan p = cm::make_shard_plan(clog, world, cfg.log_blowup_factor == 1);
-    for (int c = 0; c < air::N_COMPONENTS; c++) if (owner_out) owner_out[c] = p.owner[c];
-    // (the bound is computed for a blowup of 2; the LDE, and with it every exchange, grows by 2^(B - 1))
-    if (staging_words) *staging_words = cm::shard_staging_words(clog, p, world) << (cfg.log_blowup_factor - 1);
-  });
-}
-int32_t cm_shard_plan_columns(const cm_prover_input* input, const cm_pcs_config* config, uint32_t world, int32_t* trace_col_owner,
-                              uint32_t* n_trace_cols, int32_t* interaction_col_owner, uint32_t* n_interaction_cols, uint64_t load_cells[8]) {
-  return pguard([&] {
-    CM_CHECK(world >= 1 && world <= 8 && (world & (world - 1)) == 0, "cm_shard_plan_columns: world must be 1, 2, 4 or 8");
-    const cm_pcs_config cfg = config ? *config : default_cfg();
-    uint32_t clog[air::N_COMPONENTS];
-    cm::component_logs(*input, clog);
-    const cm::ShardPlan p = cm::make_shard_plan(clog, world, cfg.log_blowup_factor == 1);
-    // n_*_cols: capacity of the array on entry, the number of columns on return; an array that is too small is an error, never
-    // an overrun
-    if (trace_col_owner) {
-      CM_CHECK(n_trace_cols && *n_trace_cols >= p.tr_owner.size(), "cm_shard_plan_columns: trace_col_owner is too small (set *n_trace_cols to its capacity)");
-      for (size_t j = 0; j < p.tr_owner.size(); j++) trace_col_owner[j] = p.tr_owner[j];
-    }
-    if (interaction_col_owner) {
-      CM_CHECK(n_interaction_cols && *n_interaction_cols >= p.it_owner.size(),
-               "cm_shard_plan_columns: interaction_col_owner is too small (set *n_interaction_cols to its capacity)");
-      for (size_t j = 0; j < p.it_owner.size(); j++) interaction_col_owner[j] = p.it_owner[j];
-    }
-    if (n_trace_cols) *n_trace_cols = (uint32_t)p.tr_owner.size();
-    if (n_interaction_cols) *n_interaction_cols = (uint32_t)p.it_owner.size();
-    if (load_cells) for (int k = 0; k < 8; k++) load_cells[k] = p.load[k];
-  });
-}
-int32_t cm_prove_sharded(const cm_device_input* input, const cm_pcs_config* config, const cm_comm* comm, cm_proof** out) {
-  return pguard([&] {
-    // the caller's struct may be older / shorter than this library's: copy what its struct_size covers, the rest stays zero
-    CM_CHECK(comm && comm->struct_size >= offsetof(cm_comm, flags) && comm->struct_size <= 4096,
-             "cm_prove_sharded: cm_comm.struct_size does not cover the required fields (set it to sizeof(cm_comm))");
-    cm_comm cc;
-    memset(&cc, 0, sizeof(cc));
-    memcpy(&cc, comm, std::min<size_t>(comm->struct_size, sizeof(cm_comm)));
-    CM_CHECK(cc.all_gather && cc.all_to_all_v && cc.send_buf && cc.recv_buf, "cm_prove_sharded: incomplete cm_comm");
-    cm_pcs_config cfg = config ? *config : default_cfg();
-    std::unique_ptr<cm_proof> p(new cm_proof());
-    try {
-      p->d = cm::prove_sharded(*input->d, cfg, cc);
-    } catch (...) {
-      if (cc.abort) cc.abort(cc.ctx);   // the peers are heading for a collective this rank will never join
-      throw;
-    }
-    *out = p.release();
-  });
-}
-int32_t cm_prove_many(const cm_device_input* const* inputs, uint32_t n, const cm_pcs_config* config, uint32_t inflight,
-                      cm_proof** outs) {
-  if (!n) return 0;
+// ---- the drivers behind cm_prove_many* and cm_prove_run* (api_prove.hip, api_run.hip): they return when every item has been
+// proved or given up, and throw the first error of a worker or producer ----
+void prove_many(const cm_device_input* const* inputs, uint32_t n, const cm_pcs_config* config, uint32_t inflight, cm_proof** outs) {
+  if (!n) return;
   if (inflight < 1) inflight = 1;
   if (inflight > 8) inflight = 8;
   cm_pcs_config cfg = config ? *config : default_cfg();
-  cm::ProveWorkers& w = cm::prove_workers();
+  ProveWorkers& w = prove_workers();
   w.ensure(inflight);
   struct Shared { std::mutex mu; std::condition_variable cv; uint32_t done = 0, next = 0; int32_t rc = 0; std::string err; } sh;
   for (uint32_t i = 0; i < n; i++) outs[i] = nullptr;
   const uint32_t runners = inflight < n ? inflight : n;
-  // under a memory budget the caller's inputs count as resident for the whole call (cm::Admission)
+  // under a memory budget the caller's inputs count as resident for the whole call (Admission)
   uint64_t resident = 0;
-  if (cm::mem_budget()) for (uint32_t i = 0; i < n; i++) if (inputs[i] && inputs[i]->d) resident += cm::device_input_bytes(*inputs[i]->d);
-  struct Resident { uint64_t b; Resident(uint64_t b_) : b(b_) { if (b) cm::admission().add_inputs(b); } ~Resident() { if (b) cm::admission().sub_inputs(b); } } resident_scope(resident);
+  if (mem_budget()) for (uint32_t i = 0; i < n; i++) if (inputs[i] && inputs[i]->d) resident += device_input_bytes(*inputs[i]->d);
+  struct Resident { uint64_t b; Resident(uint64_t b_) : b(b_) { if (b) admission().add_inputs(b); } ~Resident() { if (b) admission().sub_inputs(b); } } resident_scope(resident);
   // `runners` jobs, each pulling segment indices until none is left: exactly that many proofs are in flight
   for (uint32_t r = 0; r < runners; r++) {
     w.submit([&] {
-      struct InFlight { InFlight() { cm::g_proofs_in_flight.fetch_add(1); } ~InFlight() { cm::g_proofs_in_flight.fetch_sub(1); } } in_flight;
+      struct InFlight { InFlight() { g_proofs_in_flight.fetch_add(1); } ~InFlight() { g_proofs_in_flight.fetch_sub(1); } } in_flight;
       for (;;) {
         uint32_t i;
         { std::lock_guard<std::mutex> lk(sh.mu); i = sh.next++; }
@@ -1588,9 +1455,9 @@ int32_t cm_prove_many(const cm_device_input* const* inputs, uint32_t n, const cm
         std::string err;
         try {
           std::unique_ptr<cm_proof> p(new cm_proof());
-          p->d = cm::prove_admitted(*inputs[i]->d, cfg, "cm_prove_many");
+          p->d = prove_admitted(*inputs[i]->d, cfg, "cm_prove_many");
           outs[i] = p.release();
-        } catch (const cm::CmError& e) { rc = e.code ? e.code : 1; err = e.what(); }
+        } catch (const CmError& e) { rc = e.code ? e.code : 1; err = e.what(); }
         catch (const std::exception& e) { rc = 1; err = e.what(); }
         if (rc) { std::lock_guard<std::mutex> lk(sh.mu); if (!sh.rc) { sh.rc = rc; sh.err = err; } }
       }
@@ -1602,8 +1469,7 @@ int32_t cm_prove_many(const cm_device_input* const* inputs, uint32_t n, const cm
   std::unique_lock<std::mutex> lk(sh.mu);
   sh.cv.wait(lk, [&] { return sh.done == runners; });
   lk.unlock();
-  if (sh.rc) { cm_set_last_error(sh.err.c_str()); return sh.rc; }
-  return 0;
+  if (sh.rc) throw CmError(sh.rc, sh.err);
 }
 // ---- streaming ingest (prover.rs:23-29 takes a HOST `&mut ProverInput`, the reference's bench clones one per
 // iteration, benches/prover_speed_benchmark.rs:65) ---------------------------------------------------------------------------
@@ -1611,18 +1477,16 @@ int32_t cm_prove_many(const cm_device_input* const* inputs, uint32_t n, const cm
 // adapter on a runner segment) on its own stream and device pool while up to `inflight` worker threads prove the items before
 // it.  At most inflight + 1 device inputs are alive (the ones being proved and the one being produced); a spent input goes back
 // to the producer, which releases it into ITS pool — the next upload reuses the same blocks, so a steady stream of equal-sized
-// segments performs no hipMalloc / hipFree.  The PCIe copies run on the SDMA engines next to the proofs' kernels.
-extern "C++" {
 // n_producers: threads that turn items into device inputs (the calling thread + n_producers - 1 library threads).  One is enough
 // for plain uploads (6 ms of PCIe per 10 ms proof); the device adapter is ~13 ms of uploads, kernels and five host round trips per
 // segment while the GPU is busy proving, so runner segments get two.  An input is released by the producer that made it (its
 // device pool owns the blocks).
-// need(i, cfg, known): the bytes item i takes (cm::ItemBytes), for the memory budget; known = false when only an upper guess of the
+// need(i, cfg, known): the bytes item i takes (ItemBytes), for the memory budget; known = false when only an upper guess of the
 // input can be made before the item exists (runner segments: the refusal then happens in front of the proof, not the adapter)
 template <class Produce, class Need>
-static int32_t prove_streamed(uint32_t n, Produce&& produce, Need&& need, const cm_pcs_config* config, uint32_t inflight, cm_proof** outs,
-                              uint32_t n_producers = 1) {
-  if (!n) return 0;
+static void prove_streamed(uint32_t n, Produce&& produce, Need&& need, const cm_pcs_config* config, uint32_t inflight, cm_proof** outs,
+                           uint32_t n_producers = 1) {
+  if (!n) return;
   if (inflight < 1) inflight = 1;
   if (inflight > 8) inflight = 8;
   if (n_producers < 1) n_producers = 1;
@@ -1630,14 +1494,14 @@ static int32_t prove_streamed(uint32_t n, Produce&& produce, Need&& need, const 
   if (n_producers > n) n_producers = n;
   const cm_pcs_config cfg = config ? *config : default_cfg();
   for (uint32_t i = 0; i < n; i++) outs[i] = nullptr;
-  cm::ProveWorkers& w = cm::prove_workers();
+  ProveWorkers& w = prove_workers();
   w.ensure(inflight + n_producers - 1);
-  struct Job { uint32_t i; cm::DeviceInput* d; uint32_t pid; uint64_t bytes; };   // bytes: what cm::Admission counts as resident for it
+  struct Job { uint32_t i; DeviceInput* d; uint32_t pid; uint64_t bytes; };   // bytes: what Admission counts as resident for it
   struct Shared {
     std::mutex mu;
     std::condition_variable cv;
     std::deque<Job> ready;                         // produced, not yet picked up
-    std::deque<std::pair<cm::DeviceInput*, uint64_t>> spent[3];   // proved: back to the producer that made them (with Job::bytes)
+    std::deque<std::pair<DeviceInput*, uint64_t>> spent[3];   // proved: back to the producer that made them (with Job::bytes)
     uint32_t outstanding[3] = {0, 0, 0};           // inputs of producer p that exist (being produced, ready, being proved, spent)
     uint32_t alive = 0, next_i = 0, workers_done = 0, producers_done = 0, n_producers = 1;
     uint32_t extra_done = 0;                       // library-thread producers that have left `sh` for good (counted under `mu`)
@@ -1650,7 +1514,7 @@ static int32_t prove_streamed(uint32_t n, Produce&& produce, Need&& need, const 
   const uint32_t runners = inflight < n ? inflight : n;
   for (uint32_t r = 0; r < runners; r++) {
     w.submit([&sh, &cfg, outs] {
-      struct InFlight { InFlight() { cm::g_proofs_in_flight.fetch_add(1); } ~InFlight() { cm::g_proofs_in_flight.fetch_sub(1); } } in_flight;
+      struct InFlight { InFlight() { g_proofs_in_flight.fetch_add(1); } ~InFlight() { g_proofs_in_flight.fetch_sub(1); } } in_flight;
       for (;;) {
         Job job;
         {
@@ -1664,9 +1528,9 @@ static int32_t prove_streamed(uint32_t n, Produce&& produce, Need&& need, const 
         std::string err;
         try {
           std::unique_ptr<cm_proof> p(new cm_proof());
-          p->d = cm::prove_admitted(*job.d, cfg, "cm_prove_many (streamed)");
+          p->d = prove_admitted(*job.d, cfg, "cm_prove_many (streamed)");
           outs[job.i] = p.release();
-        } catch (const cm::CmError& e) { rc = e.code ? e.code : 1; err = e.what(); }
+        } catch (const CmError& e) { rc = e.code ? e.code : 1; err = e.what(); }
         catch (const std::exception& e) { rc = 1; err = e.what(); }
         catch (...) { rc = 1; err = "unknown error"; }
         std::lock_guard<std::mutex> lk(sh.mu);
@@ -1681,14 +1545,14 @@ static int32_t prove_streamed(uint32_t n, Produce&& produce, Need&& need, const 
   }
   // one producer: takes the next index while a slot is free, makes the device input, hands it to the workers; frees what comes back
   auto producer = [&sh, &produce, &need, &cfg, n, cap](uint32_t pid) {
-    cm::bind_thread_to_library_device();
+    bind_thread_to_library_device();
     auto release_spent = [&](std::unique_lock<std::mutex>& lk) {   // lock held on entry and exit; the frees run outside of it
-      std::deque<std::pair<cm::DeviceInput*, uint64_t>> v;
+      std::deque<std::pair<DeviceInput*, uint64_t>> v;
       v.swap(sh.spent[pid]);
       sh.alive -= (uint32_t)v.size();
       sh.outstanding[pid] -= (uint32_t)v.size();
       lk.unlock();
-      for (auto& d : v) { delete d.first; if (d.second) cm::admission().sub_inputs(d.second); }
+      for (auto& d : v) { delete d.first; if (d.second) admission().sub_inputs(d.second); }
       lk.lock();
       sh.cv.notify_all();
     };
@@ -1704,19 +1568,19 @@ static int32_t prove_streamed(uint32_t n, Produce&& produce, Need&& need, const 
         sh.alive++;
         sh.outstanding[pid]++;
       }
-      cm::DeviceInput* d = nullptr;
+      DeviceInput* d = nullptr;
       int32_t rc = 0;
       std::string err;
-      uint64_t counted = 0;     // bytes cm::Admission holds as resident for this item
+      uint64_t counted = 0;     // bytes Admission holds as resident for this item
       bool refused = false;     // over the memory budget on its own: this item fails, the others go on
       try {
-        if (const uint64_t budget = cm::mem_budget()) {
+        if (const uint64_t budget = mem_budget()) {
           bool known = true;
-          const cm::ItemBytes b = need(i, cfg, known);
-          if (known) { refused = true; cm::check_item_fits(b, budget, "cm_prove_many (streamed)"); refused = false; }
+          const ItemBytes b = need(i, cfg, known);
+          if (known) { refused = true; check_item_fits(b, budget, "cm_prove_many (streamed)"); refused = false; }
           // while this producer waits for room, the inputs it is asked to release must still go back (a worker's proof ends,
           // its input comes back here, and only its release makes the room)
-          while (!cm::admission().try_admit_input(b.input)) {
+          while (!admission().try_admit_input(b.input)) {
             std::unique_lock<std::mutex> lk(sh.mu);
             if (!sh.spent[pid].empty()) release_spent(lk);
             else sh.cv.wait_for(lk, std::chrono::milliseconds(1));   // (a finished proof notifies; the limit covers other pipelines' proofs)
@@ -1725,15 +1589,15 @@ static int32_t prove_streamed(uint32_t n, Produce&& produce, Need&& need, const 
         }
         d = produce(i);
         if (counted) {   // the real size, once the input exists
-          const uint64_t real = cm::device_input_bytes(*d);
-          if (real > counted) cm::admission().add_inputs(real - counted); else cm::admission().sub_inputs(counted - real);
+          const uint64_t real = device_input_bytes(*d);
+          if (real > counted) admission().add_inputs(real - counted); else admission().sub_inputs(counted - real);
           counted = real;
         }
       }
-      catch (const cm::CmError& e) { rc = e.code ? e.code : 1; err = e.what(); }
+      catch (const CmError& e) { rc = e.code ? e.code : 1; err = e.what(); }
       catch (const std::exception& e) { rc = 1; err = e.what(); }
       catch (...) { rc = 1; err = "unknown error"; }
-      if (!d && counted) cm::admission().sub_inputs(counted);
+      if (!d && counted) admission().sub_inputs(counted);
       std::lock_guard<std::mutex> lk(sh.mu);
       if (!d) {   // this item cannot be made: report it, stop producing (the items already handed over are still proved)
         if (!sh.rc) { sh.rc = rc ? rc : 1; sh.err = err; }
@@ -1757,32 +1621,30 @@ static int32_t prove_streamed(uint32_t n, Produce&& produce, Need&& need, const 
   for (uint32_t pid = 1; pid < n_producers; pid++)
     w.submit([&producer, &sh, pid] { producer(pid); std::lock_guard<std::mutex> lk(sh.mu); sh.extra_done++; sh.cv.notify_all(); });
   {
-    cm::AffinityScope cpu_scope;
+    AffinityScope cpu_scope;
     producer(0);
   }
   {
     std::unique_lock<std::mutex> lk(sh.mu);
     sh.cv.wait(lk, [&] { return sh.workers_done == runners && sh.extra_done == n_producers - 1; });
   }
-  if (sh.rc) { cm_set_last_error(sh.err.c_str()); return sh.rc; }
-  return 0;
+  if (sh.rc) throw CmError(sh.rc, sh.err);
 }
-}  // extern "C++"
-int32_t cm_prove_many_host(const cm_prover_input* const* inputs, uint32_t n, const cm_pcs_config* config, uint32_t inflight, cm_proof** outs) {
-  return prove_streamed(n, [&](uint32_t i) {
+void prove_many_host(const cm_prover_input* const* inputs, uint32_t n, const cm_pcs_config* config, uint32_t inflight, cm_proof** outs) {
+  prove_streamed(n, [&](uint32_t i) {
     CM_CHECK(inputs && inputs[i], "cm_prove_many_host: null input");
-    return cm::upload_input(*inputs[i], cm::thread_main_stream());
+    return upload_input(*inputs[i], thread_main_stream());
   }, [&](uint32_t i, const cm_pcs_config& cfg, bool& known) {
     CM_CHECK(inputs && inputs[i], "cm_prove_many_host: null input");
     known = true;
-    return cm::item_bytes(*inputs[i], cm::estimate_input_bytes(*inputs[i]), cfg, 1);
+    return item_bytes(*inputs[i], estimate_input_bytes(*inputs[i]), cfg, 1);
   }, config, inflight, outs);
 }
-int32_t cm_prove_many_segments(const cm_runner_segment* const* segments, uint32_t n, const cm_pcs_config* config, uint32_t inflight,
-                               cm_proof** outs) {
-  return prove_streamed(n, [&](uint32_t i) {
+void prove_many_segments(const cm_runner_segment* const* segments, uint32_t n, const cm_pcs_config* config, uint32_t inflight,
+                         cm_proof** outs) {
+  prove_streamed(n, [&](uint32_t i) {
     CM_CHECK(segments && segments[i], "cm_prove_many_segments: null segment");
-    return cm::adapt_segment_device(*segments[i]);
+    return adapt_segment_device(*segments[i]);
   }, [&](uint32_t i, const cm_pcs_config&, bool& known) {
     CM_CHECK(segments && segments[i], "cm_prove_many_segments: null segment");
     // before the adapter has run only the step and access counts are known: one bundle per step, one data access and at most one
@@ -1790,598 +1652,33 @@ int32_t cm_prove_many_segments(const cm_runner_segment* const* segments, uint32_
     known = false;
     const cm_runner_segment& g = *segments[i];
     const uint64_t cells = g.n_initial_memory + g.n_initial_heap + g.n_memory_trace;
-    return cm::ItemBytes{g.n_trace * sizeof(cm_bundle) + g.n_memory_trace * (sizeof(cm_data_access) + sizeof(cm_clock_update)) +
+    return ItemBytes{g.n_trace * sizeof(cm_bundle) + g.n_memory_trace * (sizeof(cm_data_access) + sizeof(cm_clock_update)) +
                              2 * cells * sizeof(cm_memory_cell), 0};
   }, config, inflight, outs, /*n_producers=*/2);
 }
-// ---- a whole run (header revision 10): memory carried on the device, chained segment proofs --------------------------------
-struct cm_run { cm::Run* r = nullptr; ~cm_run() { cm::run_free(r); } };
-int32_t cm_run_begin(const uint32_t* initial_memory, uint64_t n_initial_memory, const uint32_t* initial_heap, uint64_t n_initial_heap,
-                     const uint32_t ranges[6], cm_run** out) {
-  return pguard([&] {
-    CM_CHECK(out, "cm_run_begin: null output");
-    std::unique_ptr<cm_run> h(new cm_run());
-    h->r = cm::run_begin(initial_memory, n_initial_memory, initial_heap, n_initial_heap, ranges);
-    *out = h.release();
-  });
-}
-static void check_run_segment(const cm_run_segment* seg, const char* who) {
+void check_run_segment(const cm_run_segment* seg, const char* who) {
   CM_CHECK(seg, (std::string(who) + ": null segment").c_str());
   CM_CHECK(seg->trace && seg->memory_trace, (std::string(who) + ": null trace or memory trace").c_str());
 }
-int32_t cm_run_adapt_next(cm_run* r, const cm_run_segment* seg, cm_device_input** out) {
-  return pguard([&] {
-    CM_CHECK(r && r->r && out, "cm_run_adapt_next: null argument");
-    check_run_segment(seg, "cm_run_adapt_next");
-    std::lock_guard<std::mutex> lk(cm::run_mutex(*r->r));
-    std::unique_ptr<cm_device_input> h(new cm_device_input());
-    h->d = cm::run_adapt_next(*r->r, *seg);
-    *out = h.release();
-  });
-}
-int32_t cm_run_memory(const cm_run* r, uint32_t* locals, uint64_t cap_l, uint64_t* n_l, uint32_t* heap, uint64_t cap_h, uint64_t* n_h) {
-  return pguard([&] {
-    CM_CHECK(r && r->r, "cm_run_memory: null run");
-    std::lock_guard<std::mutex> lk(cm::run_mutex(*r->r));
-    cm::run_memory(*r->r, locals, cap_l, n_l, heap, cap_h, n_h);
-  });
-}
-// openings under the root of the image as it is now (mem_open.hip, adapter_run.inc); every refusal comes before the first write
-int32_t cm_run_open_memory(cm_run* r, const uint32_t* addresses, uint64_t n, cm_mem_opening* out, uint32_t* root) {
-  return pguard([&] {
-    cm::open_require_device("cm_run_open_memory");
-    CM_CHECK(r && r->r && root, "cm_run_open_memory: null argument");
-    cm::open_check_addresses("cm_run_open_memory", addresses, n, out);
-    std::lock_guard<std::mutex> lk(cm::run_mutex(*r->r));
-    cm::run_open_memory(*r->r, addresses, n, out, root);
-  });
-}
-// a range under the same root (mem_range.hip); every refusal comes before the first write
-int32_t cm_run_open_memory_range(cm_run* r, uint32_t start, uint32_t n_cells, uint32_t* values, cm_mem_range_opening* out, uint32_t* root) {
-  return pguard([&] {
-    cm::open_require_device("cm_run_open_memory_range");
-    CM_CHECK(r && r->r && root, "cm_run_open_memory_range: null argument");
-    cm::open_range_check("cm_run_open_memory_range", start, n_cells, values, out);
-    std::lock_guard<std::mutex> lk(cm::run_mutex(*r->r));
-    cm::run_open_memory_range(*r->r, start, n_cells, values, out, root);
-  });
-}
-// a set of cells under the same root (mem_set.hip); every refusal comes before the first write to values or siblings
-int32_t cm_run_open_memory_set(cm_run* r, const uint32_t* addresses, uint64_t n, uint32_t* values, uint32_t* siblings, uint32_t cap_siblings,
-                               uint32_t* n_siblings, uint32_t* root) {
-  return pguard([&] {
-    cm::open_require_device("cm_run_open_memory_set");
-    CM_CHECK(r && r->r && root, "cm_run_open_memory_set: null argument");
-    cm::open_set_check("cm_run_open_memory_set", addresses, n, values, siblings, cap_siblings, n_siblings);
-    std::lock_guard<std::mutex> lk(cm::run_mutex(*r->r));
-    cm::run_open_memory_set(*r->r, addresses, (uint32_t)n, values, siblings, *n_siblings, root);
-  });
-}
-int32_t cm_run_free(cm_run* r) { delete r; return 0; }
-// The ingest loop of cm_prove_run and cm_prove_run_transitions.  adapted (optional; null for cm_prove_run): called on the adapting
-// thread with segment i's input right after the adapter, before the input is handed to a worker; when it throws the segment counts
-// as one that could not be made.
-extern "C++" {
-template <class Adapted>
-static int32_t prove_run_ingest(const char* who, cm_run* r, const cm_run_segment* const* segs, uint32_t n, const cm_pcs_config* config, uint32_t inflight,
-                                cm_proof** outs, Adapted adapted) {
+// The ingest loop of cm_prove_run and cm_prove_run_transitions.  transitions (null for cm_prove_run): segment i's write-set transition
+// (mem_transition.hip) is opened on the adapting thread right after the adapter, before the input is handed to a worker; when that
+// throws the segment counts as one that could not be made.
+void prove_run(const char* who, Run& run, const cm_run_segment* const* segs, uint32_t n, const cm_pcs_config* config, uint32_t inflight, cm_proof** outs,
+               cm_mem_transition** transitions) {
   // the image is serial: ONE producer (the calling thread) adapts the segments in order, the workers prove behind it
-  std::lock_guard<std::mutex> lk(cm::run_mutex(*r->r));
-  return prove_streamed(n, [&](uint32_t i) {
+  std::lock_guard<std::mutex> lk(run_mutex(run));
+  prove_streamed(n, [&](uint32_t i) {
     check_run_segment(segs[i], who);
-    std::unique_ptr<cm::DeviceInput> d(cm::run_adapt_next(*r->r, *segs[i]));
-    if constexpr (!std::is_same<Adapted, std::nullptr_t>::value) adapted(i, *d);
+    std::unique_ptr<DeviceInput> d(run_adapt_next(run, *segs[i]));
+    if (transitions) transitions[i] = open_transition(*d, nullptr, 0);
     return d.release();
   }, [&](uint32_t i, const cm_pcs_config&, bool& known) {
     check_run_segment(segs[i], who);
     known = false;   // as for cm_prove_many_segments: the component sizes exist once the adapter has run
     const cm_run_segment& g = *segs[i];
-    const uint64_t cells = cm::run_rows_bound(*r->r, g.n_memory_trace);   // (the image as it is now: this thread is its only writer)
-    return cm::ItemBytes{g.n_trace * sizeof(cm_bundle) + g.n_memory_trace * (sizeof(cm_data_access) + sizeof(cm_clock_update)) +
+    const uint64_t cells = run_rows_bound(run, g.n_memory_trace);   // (the image as it is now: this thread is its only writer)
+    return ItemBytes{g.n_trace * sizeof(cm_bundle) + g.n_memory_trace * (sizeof(cm_data_access) + sizeof(cm_clock_update)) +
                              2 * cells * sizeof(cm_memory_cell), 0};
   }, config, inflight, outs, /*n_producers=*/1);
 }
-}  // extern "C++"
-int32_t cm_prove_run(cm_run* r, const cm_run_segment* const* segs, uint32_t n, const cm_pcs_config* config, uint32_t inflight, cm_proof** outs) {
-  if (!r || !r->r || (n && (!segs || !outs))) return cm_set_last_error("cm_prove_run: null argument");
-  return prove_run_ingest("cm_prove_run", r, segs, n, config, inflight, outs, nullptr);
-}
-// the same with every adapted segment's write-set transition (mem_transition.hip) opened on this thread before a worker takes the input
-int32_t cm_prove_run_transitions(cm_run* r, const cm_run_segment* const* segs, uint32_t n, const cm_pcs_config* config, uint32_t inflight,
-                                 cm_proof** outs, cm_mem_transition** transitions) {
-  if (!r || !r->r || (n && (!segs || !outs || !transitions))) return cm_set_last_error("cm_prove_run_transitions: null argument");
-  for (uint32_t i = 0; i < n; i++) transitions[i] = nullptr;
-  return prove_run_ingest("cm_prove_run_transitions", r, segs, n, config, inflight, outs,
-                          [&](uint32_t i, const cm::DeviceInput& d) { transitions[i] = cm::open_transition(d, nullptr, 0); });
-}
-// The same walk with the PCS-free check (check.hip) and the link diff (link.hip) in the place of the proof: every verdict is
-// collected, only a segment that cannot be adapted ends the call.  Segment i - 1's input lives until link i has been looked at.
-int32_t cm_check_run(cm_run* r, const cm_run_segment* const* segs, uint32_t n, const cm_relations* relations, cm_run_check* out,
-                     cm_link_cell* cells, uint64_t cap_per_link) {
-  return pguard([&] {
-    CM_CHECK(r && r->r && (!n || (segs && out)), "cm_check_run: null argument");
-    CM_CHECK(cells || cap_per_link == 0, "cm_check_run: null cells with a capacity");
-    std::lock_guard<std::mutex> lk(cm::run_mutex(*r->r));
-    if (n) memset(out, 0, (size_t)n * sizeof(cm_run_check));
-    std::unique_ptr<cm::DeviceInput> prev;
-    for (uint32_t i = 0; i < n; i++) {
-      check_run_segment(segs[i], "cm_check_run");
-      std::unique_ptr<cm::DeviceInput> cur(cm::run_adapt_next(*r->r, *segs[i]));
-      cm::check_segment(*cur, relations, out[i].check);
-      if (prev) cm::check_link_into(*prev, *cur, i, out[i], cells, cap_per_link);
-      prev = std::move(cur);
-    }
-    cm_set_last_error(cm::run_check_summary(out, n, true).c_str());
-  });
-}
-int32_t cm_proof_public_data(const cm_proof* p, cm_public_data* out) {
-  return pguard([&] {
-    CM_CHECK(p && p->d && out, "cm_proof_public_data: null argument");
-    CM_CHECK(out->struct_size >= sizeof(cm_public_data), "cm_proof_public_data: struct_size does not cover cm_public_data (set it to sizeof(cm_public_data))");
-    const cm::PublicData& d = p->d->public_data;
-    cm_public_data o;
-    memset(&o, 0, sizeof(o));
-    o.struct_size = sizeof(o);
-    o.initial_pc = d.initial_pc; o.initial_fp = d.initial_fp; o.final_pc = d.final_pc; o.final_fp = d.final_fp; o.clock = d.clock;
-    o.initial_root = d.initial_root; o.final_root = d.final_root;
-    o.n_program = (uint32_t)d.program.size(); o.n_input = (uint32_t)d.input.size(); o.n_output = (uint32_t)d.output.size();
-    memcpy(out, &o, sizeof(o));
-  });
-}
-static void public_entries_out(const cm::PublicData& d, uint32_t which, uint32_t* out, uint64_t cap_entries, uint64_t* n_entries, const char* too_small) {
-  const std::vector<cm::PublicEntry>& v = which == 0 ? d.program : which == 1 ? d.input : d.output;
-  *n_entries = v.size();
-  if (!out) return;
-  CM_CHECK(cap_entries >= v.size(), too_small);
-  static_assert(sizeof(cm::PublicEntry) == 28, "seven words per public entry");
-  if (!v.empty()) memcpy(out, v.data(), v.size() * sizeof(cm::PublicEntry));
-}
-int32_t cm_proof_public_entries(const cm_proof* p, uint32_t which, uint32_t* out, uint64_t cap_entries, uint64_t* n_entries) {
-  return pguard([&] {
-    CM_CHECK(p && p->d && n_entries && which <= 2, "cm_proof_public_entries: null argument, or `which` is not 0 (program), 1 (input) or 2 (output)");
-    public_entries_out(p->d->public_data, which, out, cap_entries, n_entries, "cm_proof_public_entries: the output array is too small (the count is reported)");
-  });
-}
-// the public data a device input already holds (host memory: no GPU work)
-int32_t cm_device_input_public_entries(const cm_device_input* in, uint32_t which, uint32_t* out, uint64_t cap_entries, uint64_t* n_entries) {
-  return pguard([&] {
-    CM_CHECK(in && in->d && n_entries && which <= 2, "cm_device_input_public_entries: null argument, or `which` is not 0 (program), 1 (input) or 2 (output)");
-    public_entries_out(in->d->public_data, which, out, cap_entries, n_entries, "cm_device_input_public_entries: the output array is too small (the count is reported)");
-  });
-}
-// host code: every proof verifies, and each segment starts where its predecessor stopped (crates/prover/tests/prover.rs:198-243;
-// the registers are the execution boundary of public_data.rs:192-227)
-int32_t cm_verify_run(const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected) {
-  return pguard([&] {
-    CM_CHECK(n >= 1 && proofs, "cm_verify_run: no proofs");
-    for (uint32_t i = 0; i < n; i++) {
-      CM_CHECK(proofs[i] && proofs[i]->d, "cm_verify_run: null proof");
-      const std::string e = cm::verify_proof(*proofs[i]->d, expected ? *expected : default_cfg());
-      if (!e.empty()) throw cm::CmError(11, "run: segment " + std::to_string(i) + ": verification failed: " + e);
-    }
-    for (uint32_t i = 1; i < n; i++) {
-      const cm::PublicData &a = proofs[i - 1]->d->public_data, &b = proofs[i]->d->public_data;
-      const char* field = b.initial_pc != a.final_pc ? "pc" : b.initial_fp != a.final_fp ? "fp" : b.initial_root != a.final_root ? "root" : nullptr;
-      if (field)
-        throw cm::CmError(11, "run: segment " + std::to_string(i) + " initial_" + field + " != segment " + std::to_string(i - 1) + " final_" + field);
-    }
-  });
-}
-// The same verdicts from the GPU, for a whole batch (verify_device.hip): results[i] = what cm_verify_proof says about proofs[i]
-static int32_t verify_many_impl(const char* who, const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected,
-                                std::vector<cm::VerifyOutcome>& out, cm_stream_t s,
-                                std::vector<std::vector<cm::VerifySlotDetail>>* detail = nullptr, uint32_t flags = 0) {
-  return pguard([&] {
-    CM_CHECK((flags & ~CM_VERIFY_ARITH_ON_DEVICE) == 0, std::string(who) + ": unknown flag bit");
-    CM_CHECK(n >= 1 && proofs, std::string(who) + ": no proofs");
-    std::vector<const cm::ProofData*> pd(n);
-    for (uint32_t i = 0; i < n; i++) {
-      CM_CHECK(proofs[i] && proofs[i]->d, std::string(who) + ": null proof");
-      pd[i] = proofs[i]->d;
-    }
-    cm::verify_many_device(pd.data(), n, expected ? *expected : default_cfg(), out, (hipStream_t)(uintptr_t)s, detail, flags);
-  });
-}
-// the verdicts of a batch as cm_verify_many reports them: results, the call's status and cm_last_error()
-static int32_t verify_many_report(const std::vector<cm::VerifyOutcome>& out, uint32_t n, cm_verify_result* results) {
-  int64_t first = -1;
-  for (uint32_t i = 0; i < n; i++) {
-    const bool ok = out[i].message.empty();
-    if (!ok && first < 0) first = i;
-    if (!results) continue;
-    memset(&results[i], 0, sizeof(cm_verify_result));
-    if (ok) continue;
-    results[i].status = 11;
-    results[i].check = out[i].check;
-    snprintf(results[i].message, sizeof(results[i].message), "verification failed: %s", out[i].message.c_str());
-  }
-  if (first < 0) return 0;
-  cm_set_last_error(("proof " + std::to_string(first) + ": verification failed: " + out[first].message).c_str());
-  return 11;
-}
-int32_t cm_verify_many_ex(const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected, uint32_t flags, cm_verify_result* results,
-                          cm_stream_t s) {
-  std::vector<cm::VerifyOutcome> out;
-  const int32_t rc = verify_many_impl("cm_verify_many", proofs, n, expected, out, s, nullptr, flags);
-  return rc ? rc : verify_many_report(out, n, results);
-}
-int32_t cm_verify_many(const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected, cm_verify_result* results, cm_stream_t s) {
-  return cm_verify_many_ex(proofs, n, expected, 0, results, s);
-}
-int32_t cm_verify_many_detail(const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected, cm_verify_result* results,
-                              cm_verify_slot* slots, uint32_t cap_slots, uint32_t* slot_first, cm_stream_t s) {
-  return cm_verify_many_detail_ex(proofs, n, expected, 0, results, slots, cap_slots, slot_first, s);
-}
-int32_t cm_verify_many_detail_ex(const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected, uint32_t flags, cm_verify_result* results,
-                                 cm_verify_slot* slots, uint32_t cap_slots, uint32_t* slot_first, cm_stream_t s) {
-  if (!slot_first || (!slots && cap_slots)) return cm_set_last_error("cm_verify_many_detail: null output");
-  std::vector<cm::VerifyOutcome> out;
-  std::vector<std::vector<cm::VerifySlotDetail>> detail;
-  const int32_t rc = verify_many_impl("cm_verify_many_detail", proofs, n, expected, out, s, &detail, flags);
-  if (rc) return rc;
-  slot_first[0] = 0;
-  for (uint32_t i = 0; i < n; i++) slot_first[i + 1] = slot_first[i] + (uint32_t)detail[i].size();
-  if (slot_first[n] > cap_slots) return cm_set_last_error("cm_verify_many_detail: the slot array is too small (the count is in slot_first[n])");
-  for (uint32_t i = 0; i < n; i++)
-    for (size_t k = 0; k < detail[i].size(); k++) {
-      cm_verify_slot& o = slots[slot_first[i] + k];
-      memset(&o, 0, sizeof(o));
-      o.check = detail[i][k].check;
-      o.on_device = detail[i][k].on_device ? 1u : 0u;
-      o.raised = detail[i][k].raised ? 1u : 0u;
-      snprintf(o.message, sizeof(o.message), "%s", detail[i][k].message.c_str());
-    }
-  return verify_many_report(out, n, results);
-}
-int32_t cm_verify_plan_stats(const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected, cm_verify_stats* out) {
-  return pguard([&] {
-    CM_CHECK(n >= 1 && proofs && out, "cm_verify_plan_stats: no proofs, or null output");
-    std::vector<const cm::ProofData*> pd(n);
-    for (uint32_t i = 0; i < n; i++) {
-      CM_CHECK(proofs[i] && proofs[i]->d, "cm_verify_plan_stats: null proof");
-      CM_CHECK(out[i].struct_size >= sizeof(cm_verify_stats), "cm_verify_plan_stats: struct_size does not cover cm_verify_stats (set it to sizeof(cm_verify_stats))");
-      pd[i] = proofs[i]->d;
-    }
-    std::vector<cm_verify_stats> st(n);
-    cm::verify_plan_stats(pd.data(), n, expected ? *expected : default_cfg(), st.data());
-    for (uint32_t i = 0; i < n; i++) { const uint32_t keep = out[i].struct_size; out[i] = st[i]; out[i].struct_size = keep; }
-  });
-}
-int32_t cm_verify_run_device(const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected) {
-  return cm_verify_run_device_ex(proofs, n, expected, 0);
-}
-int32_t cm_verify_run_device_ex(const cm_proof* const* proofs, uint32_t n, const cm_pcs_config* expected, uint32_t flags) {
-  std::vector<cm::VerifyOutcome> out;
-  const int32_t rc = verify_many_impl("cm_verify_run_device", proofs, n, expected, out, 0, nullptr, flags);
-  if (rc) return rc;
-  return pguard([&] {
-    for (uint32_t i = 0; i < n; i++)
-      if (!out[i].message.empty()) throw cm::CmError(11, "run: segment " + std::to_string(i) + ": verification failed: " + out[i].message);
-    for (uint32_t i = 1; i < n; i++) {
-      const cm::PublicData &a = proofs[i - 1]->d->public_data, &b = proofs[i]->d->public_data;
-      const char* field = b.initial_pc != a.final_pc ? "pc" : b.initial_fp != a.final_fp ? "fp" : b.initial_root != a.final_root ? "root" : nullptr;
-      if (field)
-        throw cm::CmError(11, "run: segment " + std::to_string(i) + " initial_" + field + " != segment " + std::to_string(i - 1) + " final_" + field);
-    }
-  });
-}
-int32_t cm_verify_many_timing(double ms[4]) {
-  return pguard([&] { CM_CHECK(ms, "cm_verify_many_timing: null output"); cm::verify_many_timing(ms); });
-}
-// ---- per-component AIR ops (include/cairom_hip.h): the kernels of the whole-segment prover, one component
-// at a time on caller-owned columns --------------------------------------------------------------------------------
-extern "C++" {
-namespace {
-inline hipStream_t S_(cm_stream_t s) { return (hipStream_t)(uintptr_t)s; }
-inline uint32_t* H_(cm_handle h) { return (uint32_t*)(uintptr_t)h; }
-uint32_t component_log_size(const cm_prover_input& in, int c) {
-  using namespace cm;
-  if (c < air::N_OPCODE_COMPONENTS) return log_size_for(in.n_bundles[c]);
-  switch (c) {
-    case air::C_MEMORY: return log_size_for(in.n_initial_memory + in.n_final_memory);
-    case air::C_MERKLE: case air::C_POSEIDON2: return log_size_for(in.n_initial_tree + in.n_final_tree);
-    case air::C_CLOCK_UPDATE: return log_size_for(in.n_clock_updates);
-    case air::C_RC8: return 8; case air::C_RC16: return 16; case air::C_RC20: return 20; case air::C_BITWISE: return 18;
-  }
-  throw CmError(1, "bad component id");
-}
-std::vector<uint32_t*> handles(const cm_handle* h, int n) {
-  std::vector<uint32_t*> v(n);
-  for (int i = 0; i < n; i++) { v[i] = H_(h[i]); if (!v[i]) throw cm::CmError(1, "null column handle"); }
-  return v;
-}
-void check_component(int32_t c) { if (c < 0 || c >= air::N_COMPONENTS) throw cm::CmError(1, "bad component id"); }
-}  // namespace
-}  // extern "C++"
-
-int32_t cm_component_info(int32_t component, uint32_t* n_trace_cols, uint32_t* n_interaction_cols, uint32_t* n_constraints) {
-  return pguard([&] {
-    check_component(component);
-    const air::ComponentInfo& i = air::component_info(component);
-    if (n_trace_cols) *n_trace_cols = (uint32_t)i.n_trace;
-    if (n_interaction_cols) *n_interaction_cols = (uint32_t)i.n_interaction;
-    if (n_constraints) *n_constraints = (uint32_t)i.n_constraints;
-  });
-}
-int32_t cm_component_log_size(const cm_device_input* input, int32_t component, uint32_t* log_size) {
-  return pguard([&] { check_component(component); *log_size = component_log_size(input->d->meta, component); });
-}
-int32_t cm_trace_write(const cm_device_input* input, int32_t c, const cm_handle* cols, cm_stream_t s) {
-  return pguard([&] {
-    using namespace cm;
-    check_component(c);
-    CM_CHECK(c <= air::C_POSEIDON2, "cm_trace_write: the lookup-table components' trace is their multiplicity column (cm_histogram)");
-    bind_thread_to_library_device();
-    const DeviceInput& d = *input->d;
-    const cm_prover_input& in = d.meta;
-    const uint32_t lg = component_log_size(in, c);
-    hipStream_t st = S_(s);
-    DevBuf tab = upload(handles(cols, air::component_info(c).n_trace), st);
-    uint32_t* const* dc = tab.as<uint32_t*>();
-    if (c < air::N_OPCODE_COMPONENTS) launch_opcode_trace(c, d.bundles[c].p, (uint32_t)in.n_bundles[c], d.data_accesses.p, lg, dc, st);
-    else if (c == air::C_MEMORY)
-      launch_memory_trace(d.init_mem.p, (uint32_t)in.n_initial_memory, d.fin_mem.p, (uint32_t)in.n_final_memory, in.initial_root,
-                          in.final_root, lg, dc, st);
-    else if (c == air::C_MERKLE)
-      launch_merkle_trace(d.init_tree.p, (uint32_t)in.n_initial_tree, d.fin_tree.p, (uint32_t)in.n_final_tree, in.initial_root,
-                          in.final_root, lg, dc, st);
-    else if (c == air::C_CLOCK_UPDATE) launch_clock_update_trace(d.clock_updates.p, (uint32_t)in.n_clock_updates, lg, dc, st);
-    else launch_poseidon2_trace(d.init_tree.p, (uint32_t)in.n_initial_tree, d.fin_tree.p, (uint32_t)in.n_final_tree, lg, dc, st);
-    CM_HIP(hipStreamSynchronize(st));
-  });
-}
-int32_t cm_histogram(int32_t c, const cm_handle* trace_cols, uint32_t log_size, cm_handle rc8, cm_handle rc16, cm_handle rc20,
-                     cm_handle bitwise, cm_stream_t s) {
-  return pguard([&] {
-    using namespace cm;
-    CM_CHECK(c >= 0 && c < air::N_OPCODE_COMPONENTS, "cm_histogram: opcode components only");
-    bind_thread_to_library_device();
-    hipStream_t st = S_(s);
-    DevBuf tab = upload(handles(trace_cols, air::component_info(c).n_trace), st), flag(4);
-    CM_HIP(hipMemsetAsync(flag.p, 0, 4, st));
-    HistPtrs h;
-    h.rc8 = H_(rc8); h.rc16 = H_(rc16); h.rc20 = H_(rc20); h.bitwise = H_(bitwise); h.error_flag = flag.u32();
-    CM_CHECK(h.rc8 && h.rc16 && h.rc20 && h.bitwise, "cm_histogram: null multiplicity column");
-    launch_hist(c, (const uint32_t* const*)tab.as<uint32_t*>(), log_size, h, st);
-    uint32_t f = 0;
-    CM_HIP(hipMemcpyAsync(&f, flag.p, 4, hipMemcpyDeviceToHost, st));
-    CM_HIP(hipStreamSynchronize(st));
-    CM_CHECK(f == 0, "cm_histogram: a range-check / bitwise lookup value is out of range");
-  });
-}
-int32_t cm_preprocessed_column(int32_t id, cm_handle col, cm_stream_t s) {
-  return pguard([&] {
-    using namespace cm;
-    CM_CHECK(id >= 0 && id < air::N_PREPROC && col, "cm_preprocessed_column: bad id / null column");
-    bind_thread_to_library_device();
-    launch_preproc(id, air::PREPROC_LOG[id], H_(col), S_(s));
-    CM_HIP(hipStreamSynchronize(S_(s)));
-  });
-}
-int32_t cm_interaction_write(int32_t c, const cm_handle* trace_cols, const cm_handle* preprocessed, uint32_t log_size,
-                             const cm_relations* relations, const cm_handle* out, uint32_t claimed_sum[4], cm_stream_t s) {
-  return pguard([&] {
-    using namespace cm;
-    check_component(c);
-    static_assert(sizeof(cm_relations) == sizeof(DevRelations), "cm_relations must mirror DevRelations");
-    bind_thread_to_library_device();
-    hipStream_t st = S_(s);
-    const air::ComponentInfo& info = air::component_info(c);
-    std::vector<uint32_t*> oc = handles(out, info.n_interaction);
-    UploadBatch ub;
-    uint32_t** d_tr = nullptr; uint32_t** d_pp = nullptr; uint32_t** d_out = nullptr;
-    ub.add(handles(trace_cols, info.n_trace), &d_tr);
-    ub.add(handles(preprocessed, air::N_PREPROC), &d_pp);
-    ub.add(oc, &d_out);
-    DevBuf tabs = ub.flush(st), drel(sizeof(DevRelations)), d_sums(16);
-    stage_upload(drel.p, relations, sizeof(DevRelations), st);
-    launch_logup(c, (const uint32_t* const*)d_tr, (const uint32_t* const*)d_pp, log_size, drel.as<DevRelations>(), d_out, st);
-    std::vector<LogupTailJob> jobs(1);
-    for (int k = 0; k < 4; k++) jobs[0].col[k] = oc[info.n_interaction - 4 + k];
-    jobs[0].log_size = log_size;
-    logup_finalize_all(jobs, d_sums.u32(), st);
-    CM_HIP(hipMemcpyAsync(claimed_sum, d_sums.p, 16, hipMemcpyDeviceToHost, st));
-    CM_HIP(hipStreamSynchronize(st));
-  });
-}
-int32_t cm_constraints_accumulate(int32_t c, const cm_handle* trace_lde, const cm_handle* interaction_lde,
-                                  const cm_handle* preprocessed_lde, uint32_t log_size, const cm_relations* relations,
-                                  const uint32_t* coeff_powers, const uint32_t claimed_sum[4], const cm_handle acc[4],
-                                  cm_stream_t s) {
-  return pguard([&] {
-    using namespace cm;
-    check_component(c);
-    bind_thread_to_library_device();
-    hipStream_t st = S_(s);
-    const air::ComponentInfo& info = air::component_info(c);
-    UploadBatch ub;
-    uint32_t** d_tr = nullptr; uint32_t** d_it = nullptr; uint32_t** d_pp = nullptr; uint32_t** d_acc = nullptr;
-    uint32_t* d_coeff = nullptr;
-    ub.add(handles(trace_lde, info.n_trace), &d_tr);
-    ub.add(handles(interaction_lde, info.n_interaction), &d_it);
-    ub.add(handles(preprocessed_lde, air::N_PREPROC), &d_pp);
-    ub.add(handles(acc, 4), &d_acc);
-    ub.add(std::vector<uint32_t>(coeff_powers, coeff_powers + 4 * (size_t)info.n_constraints), &d_coeff);
-    DevBuf tabs = ub.flush(st), drel(sizeof(DevRelations));
-    stage_upload(drel.p, relations, sizeof(DevRelations), st);
-    ConstraintArgs a;
-    a.tr = (const uint32_t* const*)d_tr; a.it = (const uint32_t* const*)d_it; a.pp = (const uint32_t* const*)d_pp;
-    a.acc = d_acc;
-    fill_constraint_args(a, c, log_size, QM31::from_u32(claimed_sum), drel.as<DevRelations>(), d_coeff);
-    launch_constraints(c, a, st);
-    CM_HIP(hipStreamSynchronize(st));
-  });
-}
-// verify_cairo_m (crates/prover/src/verifier.rs:17-95): 0 = accepted; status 11 + cm_last_error() = name of the failed check
-int32_t cm_verify_proof(const cm_proof* p, const cm_pcs_config* expected) {
-  return pguard([&] {
-    std::string e = cm::verify_proof(*p->d, expected ? *expected : default_cfg());
-    if (!e.empty()) throw cm::CmError(11, "verification failed: " + e);
-  });
-}
-int32_t cm_verify_proof_words(const uint32_t* words, uint64_t n_words, const cm_pcs_config* expected) {
-  return pguard([&] {
-    cm::ProofData pd;
-    std::string e;
-    if (!cm::proof_from_words(words, n_words, pd, e)) throw cm::CmError(11, "verification failed: " + e);
-    e = cm::verify_proof(pd, expected ? *expected : default_cfg());
-    if (!e.empty()) throw cm::CmError(11, "verification failed: " + e);
-  });
-}
-// proof object from its flat word stream (cm_proof_words format): host code, no GPU needed — lets a verifier-side process
-// re-serialise a received proof (cm_proof_json) or hand it to cm_verify_proof
-int32_t cm_proof_from_words(const uint32_t* words, uint64_t n_words, cm_proof** out) {
-  return pguard([&] {
-    std::unique_ptr<cm_proof> p(new cm_proof());
-    p->d = new cm::ProofData();
-    std::string e;
-    if (!cm::proof_from_words(words, n_words, *p->d, e)) throw cm::CmError(11, "cm_proof_from_words: " + e);
-    *out = p.release();
-  });
-}
-int32_t cm_proof_free(cm_proof* p) { delete p; return 0; }
-int32_t cm_proof_json(const cm_proof* p, const char** json_out, size_t* len_out) {
-  return pguard([&] {
-    cm_proof* q = const_cast<cm_proof*>(p);
-    if (q->json.empty()) q->json = cm::proof_to_json(*p->d);
-    *json_out = q->json.c_str();
-    *len_out = q->json.size();
-  });
-}
-int32_t cm_set_transcript_log(int32_t on) { cm::g_transcript_log.store(on ? 1 : 0); return 0; }
-int32_t cm_proof_transcript(const cm_proof* p, const char** json_out, size_t* len_out) {
-  return pguard([&] {
-    cm_proof* q = const_cast<cm_proof*>(p);
-    if (q->transcript_json.empty()) q->transcript_json = cm::transcript_to_json(p->d->transcript);
-    *json_out = q->transcript_json.c_str();
-    *len_out = q->transcript_json.size();
-  });
-}
-int32_t cm_proof_words(const cm_proof* p, const uint32_t** words_out, uint64_t* n_out) {
-  return pguard([&] {
-    cm_proof* q = const_cast<cm_proof*>(p);
-    if (q->words.empty()) q->words = cm::proof_to_words(*p->d);
-    *words_out = q->words.data();
-    *n_out = q->words.size();
-  });
-}
-int32_t cm_proof_commitments(const cm_proof* p, uint8_t roots[4][32]) {
-  for (int t = 0; t < 4; t++) memcpy(roots[t], p->d->commitments[t].data(), 32);
-  return 0;
-}
-int32_t cm_kprof_enable(int32_t on) {
-  cm::KProf::get().reset();
-  cm::KProf::get().on = on != 0;
-  cm::KProf::get().only.clear();
-  return 0;
-}
-// time only one kernel class (name as reported by cm_kprof_report); NULL / "" = all classes
-int32_t cm_set_preprocessed_cache(int32_t on) {
-  cm::g_pp_cache.store(on ? 1 : 0, std::memory_order_relaxed);
-  return 0;
-}
-int32_t cm_set_tuning(const char* key, int32_t value) {
-  if (!key) return cm_set_last_error("cm_set_tuning: null key");
-  for (int k = 0; k < cm::T_COUNT; k++)
-    if (strcmp(cm::TUNE_TABLE[k].key, key) == 0) {
-      if (value < cm::TUNE_TABLE[k].lo || value > cm::TUNE_TABLE[k].hi) return cm_set_last_error("cm_set_tuning: value out of the key's range");
-      cm::tune_values()[k].store(value);
-      return 0;
-    }
-  return cm_set_last_error("cm_set_tuning: unknown key");
-}
-int32_t cm_set_device_tail(int32_t on) {
-  cm::g_device_tail.store(on ? 1 : 0);
-  return 0;
-}
-int32_t cm_tail_list(const uint32_t* positions, uint32_t n_positions, uint32_t log_domain, uint32_t qmask, uint32_t list, uint32_t k,
-                     uint32_t* out, uint32_t cap, uint32_t* n_out) {
-  return pguard([&] {
-    CM_CHECK(log_domain < cm::TAIL_MAX_SHIFTS && k <= log_domain && list <= 2, "cm_tail_list: bad arguments");
-    CM_CHECK((positions || n_positions == 0) && n_out && (out || cap == 0), "cm_tail_list: null argument");
-    for (uint32_t i = 0; i < n_positions; i++)   // TailTables::build assumes sorted, de-duplicated positions inside the domain
-      CM_CHECK((positions[i] >> log_domain) == 0 && (i == 0 || positions[i - 1] < positions[i]), "cm_tail_list: positions must be strictly increasing and below 2^log_domain");
-    cm::TailTables tt;
-    tt.build(std::vector<uint32_t>(positions, positions + n_positions), log_domain, qmask);
-    const uint32_t* v = tt.list(list, k);
-    const uint32_t nv = tt.cnt[list][k];
-    for (uint32_t i = 0; i < nv && i < cap; i++) out[i] = v[i];
-    *n_out = nv;
-  });
-}
-int32_t cm_set_twiddle_cache(int32_t on) {
-  cm::g_tw_cache.store(on ? 1 : 0, std::memory_order_relaxed);
-  return 0;
-}
-int32_t cm_kprof_filter(const char* name) {
-  cm::KProf::get().only = name ? name : "";
-  return 0;
-}
-// JSON: {"kernel": {"calls": n, "ms": total, "bytes": algorithmic bytes}, ...}
-int32_t cm_kprof_report(char* buf, size_t buf_len) {
-  (void)hipDeviceSynchronize();
-  cm::KProf& k = cm::KProf::get();
-  k.flush();
-  std::string s = "{";
-  bool first = true;
-  for (auto& kv : k.agg) {
-    if (!first) s += ",";
-    first = false;
-    s += "\"" + kv.first + "\":{\"calls\":" + std::to_string(kv.second.calls) + ",\"ms\":" + std::to_string(kv.second.ms) +
-         ",\"bytes\":" + std::to_string(kv.second.bytes) + ",\"work\":" + std::to_string(kv.second.work) + "}";
-  }
-  s += "}";
-  if (buf && buf_len) { size_t n = s.size() < buf_len - 1 ? s.size() : buf_len - 1; memcpy(buf, s.data(), n); buf[n] = 0; }
-  return (int32_t)s.size();
-}
-int32_t cm_proof_memory(const cm_proof* p, cm_proof_mem* out) {
-  return pguard([&] {
-    CM_CHECK(p && p->d && out, "cm_proof_memory: null argument");
-    CM_CHECK(out->struct_size >= sizeof(cm_proof_mem), "cm_proof_memory: struct_size does not cover cm_proof_mem (set it to sizeof(cm_proof_mem))");
-    cm_proof_mem m;
-    memset(&m, 0, sizeof(m));
-    m.struct_size = sizeof(m);
-    const cm::ProofData& d = *p->d;
-    m.n_phases = (uint32_t)std::min<size_t>(d.phase_peak_live.size(), 32);
-    m.start_live_bytes = d.mem_start_live; m.peak_live_bytes = d.mem_peak_live; m.peak_reserved_bytes = d.mem_peak_reserved;
-    m.input_bytes = d.mem_input_bytes; m.driver_allocs = d.mem_driver_allocs;
-    for (uint32_t k = 0; k < m.n_phases; k++) m.phase_peak_live_bytes[k] = d.phase_peak_live[k];
-    memcpy(out, &m, sizeof(m));
-  });
-}
-extern "C++" {
-static void estimate_checked(const uint32_t* clog, const cm_pcs_config* config, uint32_t world, uint64_t input_bytes, cm_mem_estimate* out, const char* who) {
-  const std::string w(who);
-  CM_CHECK(clog && out, (w + ": null argument").c_str());
-  CM_CHECK(out->struct_size >= sizeof(cm_mem_estimate), (w + ": struct_size does not cover cm_mem_estimate (set it to sizeof(cm_mem_estimate))").c_str());
-  const cm_pcs_config cfg = config ? *config : default_cfg();
-  CM_CHECK(cfg.log_blowup_factor >= 1 && cfg.log_blowup_factor <= 4, (w + ": log_blowup_factor must be in 1..4").c_str());
-  CM_CHECK(world == 1 || world == 2 || world == 4 || world == 8, (w + ": world must be 1, 2, 4 or 8").c_str());
-  CM_CHECK(cfg.n_queries <= 4096, (w + ": n_queries must be at most 4096").c_str());
-  for (int c = 0; c < air::N_COMPONENTS; c++) CM_CHECK(clog[c] <= 26, (w + ": a component's log size exceeds 26").c_str());
-  cm_mem_estimate e;
-  memset(&e, 0, sizeof(e));
-  e.struct_size = sizeof(e);
-  cm::estimate_memory(clog, cfg, world, cm::mem_switches(), e);
-  e.input_bytes = input_bytes;
-  memcpy(out, &e, sizeof(e));
-}
-}
-int32_t cm_estimate_memory_logs(const uint32_t log_size[CM_N_COMPONENTS], const cm_pcs_config* config, uint32_t world, cm_mem_estimate* out) {
-  return pguard([&] { estimate_checked(log_size, config, world, 0, out, "cm_estimate_memory_logs"); });
-}
-int32_t cm_estimate_memory(const cm_prover_input* input, const cm_pcs_config* config, uint32_t world, cm_mem_estimate* out) {
-  return pguard([&] {
-    CM_CHECK(input && out, "cm_estimate_memory: null argument");
-    uint32_t clog[air::N_COMPONENTS];
-    cm::component_logs(*input, clog);
-    estimate_checked(clog, config, world, cm::estimate_input_bytes(*input), out, "cm_estimate_memory");
-  });
-}
-int32_t cm_proof_stats(const cm_proof* p, uint64_t* cells, uint64_t* steps, double* phase_ms, uint32_t n_phases) {
-  if (cells) *cells = p->d->cells;
-  if (steps) *steps = p->d->steps;
-  for (uint32_t i = 0; i < n_phases; i++) phase_ms[i] = i < p->d->phase_ms.size() ? p->d->phase_ms[i] : 0.0;
-  return (int32_t)p->d->phase_ms.size();
-}
-}
+}  // namespace cm

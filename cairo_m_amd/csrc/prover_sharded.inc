@@ -76,19 +76,12 @@ struct ShardComm {
 // Packing: longest processing time first over the items (whole components, or single columns of split components), weight =
 // cells (columns x rows, trace + interaction); ties go to the lowest rank.  A component is split when it is an opcode component
 // of at least 2^split_min_log rows and heavier than an eighth of a fair share: LPT then keeps every rank within ~1.1 x the mean.
-struct ShardPlan {
-  int owner[air::N_COMPONENTS];          // rank that owns the whole component; -1 = split over all ranks
-  std::vector<int> tr_owner, it_owner;   // owner of every column of trees 1 / 2 (global column order)
-  std::vector<size_t> tr0, it0;          // first column of every component in trees 1 / 2
-  uint64_t load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  bool split(int c) const { return owner[c] < 0; }
-  int cum_owner(int c) const { return it_owner[it0[c] + air::component_info(c).n_interaction - 4]; }   // the cumulative-sum columns
-};
+// (struct ShardPlan: prover_api.hpp)
 static uint32_t shard_split_min_log() {   // tests lower it so that small proofs exercise the split (CM_SHARD_SPLIT_MIN_LOG; 99 = never split)
   static const uint32_t v = getenv("CM_SHARD_SPLIT_MIN_LOG") ? (uint32_t)atoi(getenv("CM_SHARD_SPLIT_MIN_LOG")) : 12u;
   return v;
 }
-static ShardPlan make_shard_plan(const uint32_t* clog, uint32_t world, bool allow_split = true) {
+ShardPlan make_shard_plan(const uint32_t* clog, uint32_t world, bool allow_split) {
   ShardPlan p;
   uint32_t logN = 0;
   while ((1u << logN) < world) logN++;
@@ -136,7 +129,7 @@ static ShardPlan make_shard_plan(const uint32_t* clog, uint32_t world, bool allo
   return p;
 }
 // staging words a sharded proof needs (upper bound over the exchanges of cm_prove_sharded)
-static uint64_t shard_staging_words(const uint32_t* clog, const ShardPlan& p, uint32_t world) {
+uint64_t shard_staging_words(const uint32_t* clog, const ShardPlan& p, uint32_t world) {
   uint64_t best = 0, max_log = 0;
   for (int c = 0; c < air::N_COMPONENTS; c++) max_log = std::max<uint64_t>(max_log, clog[c]);
   std::vector<uint64_t> tr(world, 0), it(world, 0);

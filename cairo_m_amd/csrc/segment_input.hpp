@@ -41,6 +41,7 @@ inline void component_logs(const cm_prover_input& in, uint32_t* clog) {
   for (int c = 0; c <= air::C_POSEIDON2; c++) clog[c] = log_size_for(nrows[c]);
   clog[air::C_RC8] = 8; clog[air::C_RC16] = 16; clog[air::C_RC20] = 20; clog[air::C_BITWISE] = 18;
 }
+static_assert(sizeof(cm_relations) == sizeof(DevRelations), "cm_relations must mirror DevRelations");
 // Relations::draw (prover.rs:94): (z, alpha) per relation, alpha powers for the device
 inline void draw_relations(hostch::Channel& ch, HostRelations& hrel, DevRelations& drel_h) {
   for (int r = 0; r < air::N_RELATIONS; r++) {
@@ -96,5 +97,3 @@ void check_link_into(const DeviceInput& prev, const DeviceInput& next, uint32_t 
 std::string run_check_summary(const cm_run_check* out, uint32_t n, bool with_air);
 
 }  // namespace cm
-
-struct cm_device_input { cm::DeviceInput* d = nullptr; ~cm_device_input() { delete d; } };

@@ -5,23 +5,15 @@
 #include "../../include/cairom_hip.h"
 #include "engine.hpp"
 #include "tail_device.hpp"
+#include "abi.hpp"
 #include <string.h>
 #include <algorithm>
 #include <string>
 #include <vector>
 
 using namespace cm;
-extern "C" int32_t cm_set_last_error(const char* msg);
 
 namespace {
-inline hipStream_t S(cm_stream_t s) { return (hipStream_t)(uintptr_t)s; }
-inline uint32_t* P32(cm_handle h) { return (uint32_t*)(uintptr_t)h; }
-template <class F>
-int32_t guard(F&& f) {
-  try { f(); return 0; }
-  catch (const CmError& e) { cm_set_last_error(e.what()); return e.code ? e.code : 1; }
-  catch (const std::exception& e) { cm_set_last_error(e.what()); return 1; }
-}
 static_assert(CM_TAIL_HDR_WORDS == TAIL_HDR_WORDS && CM_TAIL_SHIFTS == TAIL_MAX_SHIFTS && CM_TAIL_NO_NONCE == TAIL_NO_NONCE,
               "cairom_hip.h restates the tail's constants");
 // device channel {digest[8], n_sent}
@@ -42,15 +34,15 @@ extern "C" {
 uint64_t cm_tail_tab_words(uint32_t nq_pad) { return tail_tab_words(nq_pad); }
 
 int32_t cm_tail_grind_op(const uint32_t digest[8], uint32_t bits, uint64_t* nonce_out, cm_stream_t s) {
-  return guard([&] {
+  return abi_guard([&] {
     CM_CHECK(digest && nonce_out, "cm_tail_grind_op: null argument");
     CM_CHECK(bits <= TAIL_MAX_POW_BITS, "cm_tail_grind_op: bits above TAIL_MAX_POW_BITS (26)");
-    DevBuf d_chan = upload_channel(digest, S(s));
-    DevBuf d_nonce = upload(std::vector<unsigned long long>{~0ull}, S(s));
-    tail_grind(d_chan.u32(), bits, (unsigned long long*)d_nonce.p, S(s));
+    DevBuf d_chan = upload_channel(digest, as_stream(s));
+    DevBuf d_nonce = upload(std::vector<unsigned long long>{~0ull}, as_stream(s));
+    tail_grind(d_chan.u32(), bits, (unsigned long long*)d_nonce.p, as_stream(s));
     unsigned long long got = 0;
-    CM_HIP(hipMemcpyAsync(&got, d_nonce.p, 8, hipMemcpyDeviceToHost, S(s)));
-    CM_HIP(hipStreamSynchronize(S(s)));
+    CM_HIP(hipMemcpyAsync(&got, d_nonce.p, 8, hipMemcpyDeviceToHost, as_stream(s)));
+    CM_HIP(hipStreamSynchronize(as_stream(s)));
     *nonce_out = got;
   });
 }
@@ -58,7 +50,7 @@ int32_t cm_tail_grind_op(const uint32_t digest[8], uint32_t bits, uint64_t* nonc
 int32_t cm_tail_tables_op(const uint32_t digest[8], uint64_t nonce, uint32_t n_queries, uint32_t nq_pad, uint32_t log_domain,
                           uint32_t qmask, const cm_tail_piece* pieces, uint32_t n_pieces, uint32_t n_small, cm_tail_tables_out* out,
                           cm_stream_t s) {
-  return guard([&] {
+  return abi_guard([&] {
     CM_CHECK(digest && out && (pieces || !n_pieces), "cm_tail_tables_op: null argument");
     CM_CHECK(out->struct_size == sizeof(cm_tail_tables_out), "cm_tail_tables_op: cm_tail_tables_out.struct_size does not match this library");
     CM_CHECK(out->hdr && out->positions && out->tab && (out->offsets || !n_pieces) && (out->words || !out->words_cap),
@@ -87,12 +79,12 @@ int32_t cm_tail_tables_op(const uint32_t digest[8], uint64_t nonce, uint32_t n_q
     CM_CHECK(out->words_cap >= bound, "cm_tail_tables_op: words_cap below the bound of the pieces");
     CM_CHECK(bound < ((size_t)1 << 28), "cm_tail_tables_op: pieces too large");
 
-    hipStream_t st = S(s);
+    hipStream_t st = as_stream(s);
     // the device tables of column pointers of the row pieces (MerkleTree::dcols() in the prover), one upload
     std::vector<const uint32_t*> col_ptrs;
     col_ptrs.reserve(n_col_ptrs);
     for (uint32_t d = n_small; d < n_pieces; d++)
-      for (uint32_t c = 0; c < pieces[d].width; c++) col_ptrs.push_back(P32(pieces[d].cols[c]));
+      for (uint32_t c = 0; c < pieces[d].width; c++) col_ptrs.push_back(as_words(pieces[d].cols[c]));
     DevBuf d_cols = upload(col_ptrs, st);
     // the descriptors, as DeviceTail::enqueue builds them
     std::vector<TailDesc> desc;
@@ -104,9 +96,9 @@ int32_t cm_tail_tables_op(const uint32_t digest[8], uint64_t nonce, uint32_t n_q
         desc.push_back(TailDesc{{d_cols.as<const uint32_t*>() + col0, nullptr, nullptr, nullptr}, p.kind, p.k, p.width, 0});
         col0 += p.width;
       } else if (p.kind == TD_COORDS_W) {
-        desc.push_back(TailDesc{{P32(p.cols[0]), P32(p.cols[1]), P32(p.cols[2]), P32(p.cols[3])}, p.kind, p.k, 4, 0});
+        desc.push_back(TailDesc{{as_words(p.cols[0]), as_words(p.cols[1]), as_words(p.cols[2]), as_words(p.cols[3])}, p.kind, p.k, 4, 0});
       } else {
-        desc.push_back(TailDesc{{P32(p.cols[0]), nullptr, nullptr, nullptr}, p.kind, p.k, 8, 0});
+        desc.push_back(TailDesc{{as_words(p.cols[0]), nullptr, nullptr, nullptr}, p.kind, p.k, 8, 0});
       }
     }
     // pinned: descriptors in; {header | positions | witnesses} out
@@ -142,7 +134,7 @@ int32_t cm_tail_tables_op(const uint32_t digest[8], uint64_t nonce, uint32_t n_q
 int32_t cm_tail_last_op(const uint32_t digest[8], const cm_handle last[4], uint32_t log_n, uint32_t log_keep, const uint32_t* ar,
                         uint32_t n_ar_words, uint32_t digest_out[8], uint32_t* degree_flag, uint32_t* last_out, uint32_t* ar_out,
                         uint64_t* nonce_cell, cm_stream_t s) {
-  return guard([&] {
+  return abi_guard([&] {
     CM_CHECK(digest && last && digest_out && degree_flag && last_out && nonce_cell && ((ar && ar_out) || !n_ar_words),
              "cm_tail_last_op: null argument");
     for (int c = 0; c < 4; c++) CM_CHECK(last[c], "cm_tail_last_op: null column handle");
@@ -150,7 +142,7 @@ int32_t cm_tail_last_op(const uint32_t digest[8], const cm_handle last[4], uint3
     CM_CHECK(log_keep <= log_n, "cm_tail_last_op: log_keep above log_n");
     CM_CHECK(n_ar_words <= PIN_LAST_LAYER - PIN_ALPHAS, "cm_tail_last_op: more than 384 challenge / root words");
     static_assert((4u << 6) <= PIN_LAST_LAYER_END - PIN_LAST_LAYER, "the last layer's pinned slot");
-    hipStream_t st = S(s);
+    hipStream_t st = as_stream(s);
     const uint32_t n = 1u << log_n;
     DevBuf d_chan = upload_channel(digest, st);
     DevBuf d_ar = upload(std::vector<uint32_t>(ar, ar + n_ar_words), st);
@@ -161,7 +153,7 @@ int32_t cm_tail_last_op(const uint32_t digest[8], const cm_handle last[4], uint3
     memset(&a, 0, sizeof(a));
     a.d_ar = d_ar.u32();
     a.n_ar_words = n_ar_words;
-    for (int c = 0; c < 4; c++) a.last[c] = P32(last[c]);
+    for (int c = 0; c < 4; c++) a.last[c] = as_words(last[c]);
     a.log_n = log_n;
     a.log_keep = log_keep;
     tail_last_twiddles(log_n, &a.ninv, a.xinv);

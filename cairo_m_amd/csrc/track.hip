@@ -14,6 +14,8 @@
 // exactly as they do in the sum check.
 #include "../../include/cairom_hip.h"
 #include "segment_input.hpp"
+#include "handles.hpp"
+#include "abi.hpp"
 #include "track_kernels.hpp"
 #include "air_kernels.hpp"
 #include "kprof.hpp"
@@ -290,20 +292,10 @@ void track_relations(const std::vector<int>& cids, const std::vector<const uint3
 }  // namespace cm
 
 // ================================================================= C ABI
-extern "C" int32_t cm_set_last_error(const char* msg);
-namespace {
-template <class F>
-int32_t track_guard(F&& f) {
-  try { f(); return 0; }
-  catch (const cm::CmError& e) { cm_set_last_error(e.what()); return e.code ? e.code : 1; }
-  catch (const std::exception& e) { cm_set_last_error(e.what()); return 1; }
-}
-}  // namespace
-
 extern "C" {
 int32_t cm_track_relations(const cm_device_input* input, const cm_relations* relations, uint32_t relation_mask, cm_check_report* report,
                            cm_relation_entry* entries, uint64_t cap, uint64_t* n_total) {
-  return track_guard([&] {
+  return cm::abi_guard([&] {
     using namespace cm;
     CM_CHECK(input && input->d && n_total, "cm_track_relations: null input / n_total");
     CM_CHECK(entries || cap == 0, "cm_track_relations: null entries with a non-zero cap");
@@ -332,7 +324,7 @@ int32_t cm_track_relations(const cm_device_input* input, const cm_relations* rel
 int32_t cm_relation_entries(int32_t c, const cm_handle* trace_cols, const cm_handle* preprocessed, uint32_t log_size,
                             const cm_relations* relations, uint32_t relation_mask, cm_relation_entry* entries, uint64_t cap,
                             uint64_t* n_total, cm_stream_t s) {
-  return track_guard([&] {
+  return cm::abi_guard([&] {
     using namespace cm;
     CM_CHECK(c >= 0 && c < air::N_COMPONENTS, "bad component id");
     CM_CHECK(log_size >= 4 && log_size <= 26, "cm_relation_entries: log_size must be in 4..26");
@@ -342,12 +334,7 @@ int32_t cm_relation_entries(int32_t c, const cm_handle* trace_cols, const cm_han
     CM_CHECK(relation_mask < (1u << air::N_RELATIONS), "cm_relation_entries: relation_mask has bits beyond the 8 relations");
     *n_total = 0;
     bind_thread_to_library_device();
-    const hipStream_t st = (hipStream_t)(uintptr_t)s;
-    const auto handles = [](const cm_handle* h, int n) {
-      std::vector<uint32_t*> v(n);
-      for (int i = 0; i < n; i++) { v[i] = (uint32_t*)(uintptr_t)h[i]; CM_CHECK(v[i], "null column handle"); }
-      return v;
-    };
+    const hipStream_t st = cm::as_stream(s);
     UploadBatch ub;
     uint32_t** d_tr = nullptr; uint32_t** d_pp = nullptr;
     ub.add(handles(trace_cols, air::component_info(c).n_trace), &d_tr);

@@ -6,6 +6,7 @@
 #include "engine.hpp"
 #include "verifier_common.hpp"
 #include "verify_prelude.hpp"
+#include "abi.hpp"
 #include <string.h>
 #include <string>
 #include <vector>
@@ -168,16 +169,9 @@ void launch_verify_prelude_fin(const uint32_t* blob, uint32_t* scr, uint32_t* fl
 
 // ================================================================= op-level entries
 using namespace cm;
-extern "C" int32_t cm_set_last_error(const char* msg);
 
 namespace {
 constexpr uint32_t OP_MAX_JOBS = 1u << 16, OP_MAX_LIST = 1u << 24;
-template <class F>
-int32_t guard(F&& f) {
-  try { f(); return 0; }
-  catch (const CmError& e) { cm_set_last_error(e.what()); return e.code ? e.code : 1; }
-  catch (const std::exception& e) { cm_set_last_error(e.what()); return 1; }
-}
 void need_device(const char* who) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw CmError(3, std::string(who) + ": no HIP device available (libcairom_hip has no CPU fallback)");
@@ -263,7 +257,7 @@ void run_and_fetch(OpSink& sk, const std::vector<uint32_t>& offs, uint32_t* out,
 extern "C" {
 
 int32_t cm_public_logup_sum_host(const cm_public_sum_job* job, uint32_t out4[4]) {
-  return guard([&] {
+  return abi_guard([&] {
     CM_CHECK(job && out4, "cm_public_logup_sum_host: null argument");
     check_sum_job("cm_public_logup_sum_host", *job);
     verif::initial_logup_sum(sum_job_data(*job), relations_from_words(job->rel_words)).to_u32(out4);
@@ -271,7 +265,7 @@ int32_t cm_public_logup_sum_host(const cm_public_sum_job* job, uint32_t out4[4])
 }
 
 int32_t cm_public_logup_sum_op(const cm_public_sum_job* jobs, uint32_t n_jobs, cm_stream_t s, uint32_t* out) {
-  return guard([&] {
+  return abi_guard([&] {
     CM_CHECK(jobs && out, "cm_public_logup_sum_op: null argument");
     CM_CHECK(n_jobs >= 1 && n_jobs <= OP_MAX_JOBS, "cm_public_logup_sum_op: n_jobs outside 1..65536");
     for (uint32_t j = 0; j < n_jobs; j++) check_sum_job("cm_public_logup_sum_op", jobs[j]);
@@ -288,7 +282,7 @@ int32_t cm_public_logup_sum_op(const cm_public_sum_job* jobs, uint32_t n_jobs, c
     }
     const uint32_t n_sum = (uint32_t)(sum_jobs.size() / VP_SUM_JOB_WORDS);
     const uint32_t sum_off = sk.put(sum_jobs.data(), sum_jobs.size()), fin_off = sk.put(fin_jobs.data(), fin_jobs.size());
-    const hipStream_t st = (hipStream_t)(uintptr_t)s;
+    const hipStream_t st = as_stream(s);
     run_and_fetch(sk, offs, out, st, [&](const uint32_t* blob, uint32_t* scr) {
       launch_verify_public_sum(blob, scr, blob + sum_off, n_sum, st);
       launch_verify_prelude_fin(blob, scr, nullptr, blob + fin_off, n_jobs, st);
@@ -297,7 +291,7 @@ int32_t cm_public_logup_sum_op(const cm_public_sum_job* jobs, uint32_t n_jobs, c
 }
 
 int32_t cm_point_eval_host(const cm_point_eval_job* job, uint32_t out4[4]) {
-  return guard([&] {
+  return abi_guard([&] {
     CM_CHECK(job && out4, "cm_point_eval_host: null argument");
     check_eval_job("cm_point_eval_host", *job);
     const air::ComponentInfo& info = air::component_info((int)job->component);
@@ -314,7 +308,7 @@ int32_t cm_point_eval_host(const cm_point_eval_job* job, uint32_t out4[4]) {
 }
 
 int32_t cm_point_eval_op(const cm_point_eval_job* jobs, uint32_t n_jobs, cm_stream_t s, uint32_t* out) {
-  return guard([&] {
+  return abi_guard([&] {
     CM_CHECK(jobs && out, "cm_point_eval_op: null argument");
     CM_CHECK(n_jobs >= 1 && n_jobs <= OP_MAX_JOBS, "cm_point_eval_op: n_jobs outside 1..65536");
     for (uint32_t j = 0; j < n_jobs; j++) check_eval_job("cm_point_eval_op", jobs[j]);
@@ -331,7 +325,7 @@ int32_t cm_point_eval_op(const cm_point_eval_job* jobs, uint32_t n_jobs, cm_stre
       offs.push_back(job[10]);
     }
     const uint32_t jobs_off = sk.put(oods_jobs.data(), oods_jobs.size());
-    const hipStream_t st = (hipStream_t)(uintptr_t)s;
+    const hipStream_t st = as_stream(s);
     run_and_fetch(sk, offs, out, st, [&](const uint32_t* blob, uint32_t* scr) { launch_verify_oods(blob, scr, blob + jobs_off, n_jobs, st); });
   });
 }
