@@ -44,7 +44,9 @@ struct QuotientArgs {
   // — the row's value is hashed in the registers it was computed in, next to a kernel that otherwise waits on HBM.  null = no.
   uint32_t* leaf_hashes = nullptr;
 };
-void launch_quotients(const QuotientArgs& a, double n_cols, hipStream_t st);
+// the kernel family the launch chose (the values of CM_QUOT_PATH_* in include/cairom_hip.h)
+enum QuotientPath : uint32_t { QUOT_ROWS2 = 1, QUOT_ROWS4 = 2, QUOT_ROWS2_LEAF = 3, QUOT_ONE_ROW = 4, QUOT_SLICES8 = 5, QUOT_SLICES64 = 6 };
+QuotientPath launch_quotients(const QuotientArgs& a, double n_cols, hipStream_t st);
 bool quotient_leaf_serves(const QuotientArgs& a);   // may `leaf_hashes` be set for this launch?
 void fold_circle_into_line(uint32_t* const dst[4], const uint32_t* const src[4], uint32_t log_n, const Twiddles& tw,
                            const QM31& alpha, bool accumulate, hipStream_t st, const uint32_t* d_alpha = nullptr);

@@ -529,23 +529,35 @@ bool quotient_leaf_serves(const QuotientArgs& a) {
   return (n & (n - 1)) == 0 && n >= (1u << tune(T_MERKLE_MULTI_TOP)) && a.row0 % n == 0 && tune(T_QUOT_ROWS) == 2 && a.entry_cols && a.n_batches >= 1 &&
          a.n_batches <= 2;
 }
-void launch_quotients(const QuotientArgs& a, double n_cols, hipStream_t st) {
+QuotientPath launch_quotients(const QuotientArgs& a, double n_cols, hipStream_t st) {
   uint32_t n = a.n_rows ? a.n_rows : (1u << a.log_size);
   KProfScope kp("k_quotients", (4.0 * n_cols + 16.0 + (a.leaf_hashes ? 32.0 : 0.0)) * (double)n, st);
   // two rows per thread with one shared denominator inversion (A/B: CM_QUOT_ROWS=1 restores the one-row kernel)
   const int rows = tune(T_QUOT_ROWS);
+  QuotientPath path;
   if (a.leaf_hashes) {   // (the caller has checked quotient_leaf_serves)
     CM_CHECK(quotient_leaf_serves(a), "launch_quotients: leaf hashes asked for a launch the row kernel does not serve");
+    path = QUOT_ROWS2_LEAF;
     if (framing().hash_node_rfc) hipLaunchKernelGGL((k_quotients_rows<2, true, true>), dim3(n / 512), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((k_quotients_rows<2, true, false>), dim3(n / 512), dim3(256), 0, st, a);
-  } else if (a.log_size >= 14 && rows == 2 && a.entry_cols && a.n_batches >= 1 && a.n_batches <= 2 && n % 512 == 0)
+  } else if (a.log_size >= 14 && rows == 2 && a.entry_cols && a.n_batches >= 1 && a.n_batches <= 2 && n % 512 == 0) {
+    path = QUOT_ROWS2;
     hipLaunchKernelGGL(k_quotients_rows<2>, dim3(n / 512), dim3(256), 0, st, a);
-  else if (a.log_size >= 14 && rows == 4 && a.entry_cols && a.n_batches >= 1 && a.n_batches <= 2 && n % 1024 == 0)
+  } else if (a.log_size >= 14 && rows == 4 && a.entry_cols && a.n_batches >= 1 && a.n_batches <= 2 && n % 1024 == 0) {
+    path = QUOT_ROWS4;
     hipLaunchKernelGGL(k_quotients_rows<4>, dim3(n / 1024), dim3(256), 0, st, a);
-  else if (a.log_size >= 14) hipLaunchKernelGGL(k_quotients<1>, dim3((n + 255) / 256), dim3(256), 0, st, a);
-  else if (a.log_size >= 10) hipLaunchKernelGGL(k_quotients<8>, dim3((n + 31) / 32), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(k_quotients<64>, dim3((n + 3) / 4), dim3(256), 0, st, a);
+  } else if (a.log_size >= 14) {
+    path = QUOT_ONE_ROW;
+    hipLaunchKernelGGL(k_quotients<1>, dim3((n + 255) / 256), dim3(256), 0, st, a);
+  } else if (a.log_size >= 10) {
+    path = QUOT_SLICES8;
+    hipLaunchKernelGGL(k_quotients<8>, dim3((n + 31) / 32), dim3(256), 0, st, a);
+  } else {
+    path = QUOT_SLICES64;
+    hipLaunchKernelGGL(k_quotients<64>, dim3((n + 3) / 4), dim3(256), 0, st, a);
+  }
   CM_HIP(hipGetLastError());
+  return path;
 }
 void fold_circle_into_line(uint32_t* const dst[4], const uint32_t* const src[4], uint32_t log_n, const Twiddles& tw,
                            const QM31& alpha, bool accumulate, hipStream_t st, const uint32_t* d_alpha) {

@@ -108,6 +108,17 @@ class TailTablesOut(C.Structure):
 EVAL_MAX_JOBS, EVAL_GUARD_WORDS, EVAL_GUARD = 64, 4, 0xA5A5A5A5     # cm_eval_at_points_op
 
 
+FOLD_CIRCLE, FOLD_ACCUMULATE, FOLD_ALPHA_ON_DEVICE = 1, 2, 4     # cm_fri_fold_rows_op flags
+# cm_accumulate_quotients_rows_op: the kernel family launch_quotients chose
+QUOT_PATHS = {1: "rows2", 2: "rows4", 3: "rows2-leaf", 4: "one-row", 5: "slices8", 6: "slices64"}
+
+
+class SampleBatches(C.Structure):
+    """cm_sample_batches"""
+    _fields_ = [("n_batches", C.c_uint32), ("points", C.c_void_p), ("batch_off", C.c_void_p), ("col_index", C.c_void_p),
+                ("values", C.c_void_p)]
+
+
 class EvalJob(C.Structure):
     """cm_eval_job"""
     _fields_ = [("log_n", C.c_uint32), ("n_cols", C.c_uint32), ("coeffs", C.POINTER(C.c_uint64)), ("point", C.c_uint32 * 8),
@@ -359,6 +370,72 @@ class Backend:
         b = Batches(len(off) - 1, pts.ctypes.data, off.ctypes.data, ci.ctypes.data, vals.ctypes.data)
         self._ck(self.L.cm_accumulate_quotients(C.c_uint32(log_size), self._harr(cols), C.c_uint32(len(cols)), C.byref(b),
                                                 _p(co), self._harr(out4), C.c_uint64(tw), C.c_uint64(0)))
+
+    # -- row-range and prover-only forms, the sharded prover's data movement (cm_*_rows_op, shard_ops.hip) --------------
+    def fri_fold_rows(self, out4, src4, alpha, log_n, tw, i0, n_out, circle=False, accumulate=False, alpha_on_device=False):
+        """cm_fri_fold_rows_op: outputs [i0, i0 + n_out) of fold_line (circle: fold_circle_into_line) of 2^log_n values; src4 holds
+        source rows [2 i0, 2 (i0 + n_out)), out4 the outputs."""
+        a = np.ascontiguousarray(alpha, dtype=np.uint32)
+        flags = (FOLD_CIRCLE if circle else 0) | (FOLD_ACCUMULATE if accumulate else 0) | (FOLD_ALPHA_ON_DEVICE if alpha_on_device else 0)
+        self._ck(self.L.cm_fri_fold_rows_op(self._harr(out4), self._harr(src4), _p(a), C.c_uint32(log_n), C.c_uint64(tw), C.c_uint32(i0),
+                                            C.c_uint32(n_out), C.c_uint32(flags), C.c_uint64(0)))
+
+    def fri_fold_leaves_rows(self, src4, alpha, log_n, tw, row0, n_rows, out4, leaf_hashes, circle4=None, alpha_circle=None):
+        """cm_fri_fold_leaves_rows_op: fri_fold_line_leaves on outputs [row0, row0 + n_rows).  Returns `fused` (1: k_fold_leaf ran)."""
+        a = None if alpha is None else np.ascontiguousarray(alpha, dtype=np.uint32)
+        ac = None if alpha_circle is None else np.ascontiguousarray(alpha_circle, dtype=np.uint32)
+        fused = C.c_uint32(0xFFFFFFFF)
+        self._ck(self.L.cm_fri_fold_leaves_rows_op(None if src4 is None else self._harr(src4), None if circle4 is None else self._harr(circle4),
+                                                   None if a is None else _p(a), None if ac is None else _p(ac), C.c_uint32(log_n),
+                                                   C.c_uint64(tw), C.c_uint32(row0), C.c_uint32(n_rows), self._harr(out4),
+                                                   C.c_uint64(leaf_hashes), C.byref(fused), C.c_uint64(0)))
+        return fused.value
+
+    def accumulate_quotients_rows(self, log_size, cols, points, batch_off, col_index, values, coeff, out4, tw, row0=0, n_rows=0,
+                                  leaf_hashes=0, sample_idx=None):
+        """cm_accumulate_quotients_rows_op on rows [row0, row0 + n_rows) (n_rows 0: the whole domain); cols / out4 hold that range.
+        sample_idx None: `values` is (entries, 4) and the coefficients are computed on the host; returns the path name.
+        sample_idx given: `values` is (n_samples, 4), k_quotient_coeffs computes the coefficients on the device; returns
+        (path name, coef_c (entries, 4), sum_a, sum_b, batch_coeff (n_batches, 4 each))."""
+        pts = np.ascontiguousarray(points, dtype=np.uint32)
+        off = np.ascontiguousarray(batch_off, dtype=np.uint32)
+        ci = np.ascontiguousarray(col_index, dtype=np.uint32)
+        vals = np.ascontiguousarray(values, dtype=np.uint32)
+        co = np.ascontiguousarray(coeff, dtype=np.uint32)
+        b = SampleBatches(len(off) - 1, pts.ctypes.data, off.ctypes.data, ci.ctypes.data, vals.ctypes.data)
+        path = C.c_uint32(0)
+        dev = sample_idx is not None
+        si = np.ascontiguousarray(sample_idx, dtype=np.uint32) if dev else None
+        cc = np.zeros((ci.size, 4), dtype=np.uint32)
+        sums = np.zeros((len(off) - 1, 12), dtype=np.uint32)
+        self._ck(self.L.cm_accumulate_quotients_rows_op(
+            C.c_uint32(log_size), self._harr(cols), C.c_uint32(len(cols)), C.byref(b), _p(co), self._harr(out4), C.c_uint64(tw),
+            C.c_uint32(row0), C.c_uint32(n_rows), C.c_uint64(leaf_hashes), C.c_uint32(1 if dev else 0), _p(si) if dev else None,
+            C.c_uint32(vals.size // 4 if dev else 0), C.byref(path), _p(cc) if dev else None, _p(sums) if dev else None, C.c_uint64(0)))
+        name = QUOT_PATHS[path.value]
+        return (name, cc, sums[:, 0:4].copy(), sums[:, 4:8].copy(), sums[:, 8:12].copy()) if dev else name
+
+    def pack_parity(self, src, dst, half_len, parity):
+        self._ck(self.L.cm_pack_parity_op(C.c_uint64(src), C.c_uint64(dst), C.c_uint32(half_len), C.c_uint32(parity), C.c_uint64(0)))
+
+    def halo_build(self, even_half, odd_half, even_src, odd_src, row0, length, n, trace_log, log_ranks, out):
+        """cm_halo_build_op; returns the kernel's error word."""
+        err = C.c_uint32(0xFFFFFFFF)
+        self._ck(self.L.cm_halo_build_op(C.c_uint64(even_half), C.c_uint64(odd_half), C.c_uint32(even_src), C.c_uint32(odd_src),
+                                         C.c_uint32(row0), C.c_uint32(length), C.c_uint32(n), C.c_uint32(trace_log), C.c_uint32(log_ranks),
+                                         C.c_uint64(out), C.byref(err), C.c_uint64(0)))
+        return err.value
+
+    def sum_copies(self, src, n_copies, stride, words, out, modular):
+        self._ck(self.L.cm_sum_copies_op(C.c_uint64(src), C.c_uint32(n_copies), C.c_uint64(stride), C.c_uint64(words), C.c_uint64(out),
+                                         C.c_uint32(1 if modular else 0), C.c_uint64(0)))
+
+    def copy_segments(self, segs):
+        """cm_copy_segments_op: segs = [(src handle, dst handle, words)]."""
+        n = len(segs)
+        src, dst = self._harr([s[0] for s in segs] or [0]), self._harr([s[1] for s in segs] or [0])
+        words = (C.c_uint64 * max(n, 1))(*([s[2] for s in segs] or [0]))
+        self._ck(self.L.cm_copy_segments_op(src, dst, words, C.c_uint32(n), C.c_uint64(0)))
 
 
 class HostInput:

@@ -58,6 +58,9 @@
  *    Still 10 (additive: four new functions and two structs, nothing moved): cm_tail_piece, cm_tail_tables_out, cm_tail_grind_op,
  *    cm_tail_tables_op, cm_tail_tab_words, cm_tail_last_op.
  *    Still 10 (additive: one new function and one struct, nothing moved): cm_eval_job, cm_eval_at_points_op.
+ *    Still 10 (additive: seven new functions and two sets of constants, nothing moved): CM_FOLD_*, CM_QUOT_PATH_*,
+ *    cm_fri_fold_rows_op, cm_fri_fold_leaves_rows_op, cm_accumulate_quotients_rows_op, cm_pack_parity_op, cm_halo_build_op,
+ *    cm_sum_copies_op, cm_copy_segments_op.
  *    Still 10 (additive: seven new functions, two structs and one flag, nothing moved): CM_VERIFY_ARITH_ON_DEVICE, cm_verify_many_ex,
  *    cm_verify_many_detail_ex, cm_verify_run_device_ex, cm_public_sum_job, cm_public_logup_sum_op, cm_public_logup_sum_host,
  *    cm_point_eval_job, cm_point_eval_op, cm_point_eval_host. */
@@ -565,6 +568,68 @@ enum { CM_EVAL_MAX_JOBS = 64, CM_EVAL_GUARD_WORDS = 4 };
  * heights of the caller's columns cannot be checked.  The stream is synchronised before the call returns. */
 int32_t cm_eval_at_points_op(const cm_eval_job* jobs, uint32_t n_jobs, const uint32_t* t4, uint32_t want_landing, uint32_t* out,
                              uint32_t* landing, cm_stream_t s);
+/* ---- the row-range and prover-only forms of the FRI and quotient kernels, and the sharded prover's data movement, on inputs the
+ * caller chooses (test surface; cairo_m_amd/csrc/shard_ops.hip) ------------------------------------------------------------------
+ * Each entry calls the host wrapper the provers call and synchronises the stream.  Every argument is checked before the first
+ * device call (status 1 and a message that starts with the entry's name): NULL pointers and handles, a count of 0, log_n / log_size
+ * against what the twiddle handle covers, a row range that leaves the domain, an index out of range, a field word >= P.  The
+ * lengths of the caller's columns cannot be checked.  Handles of "slices" are plain column handles whose word 0 is the first row
+ * of the range.
+ *
+ * Outputs [i0, i0 + n_out) of a fold of 2^log_n values (fold_line_rows; with CM_FOLD_CIRCLE fold_circle_into_line_rows, which with
+ * CM_FOLD_ACCUMULATE computes out * alpha^2 + fold): src holds source rows [2 i0, 2 (i0 + n_out)), out holds the n_out outputs.
+ * CM_FOLD_ALPHA_ON_DEVICE: the challenge is uploaded and passed as the wrappers' d_alpha, the way both provers pass it (the kernel
+ * argument is then another value); otherwise it is the kernel argument.  n_out >= 1, i0 + n_out <= 2^(log_n - 1). */
+#define CM_FOLD_CIRCLE 1u
+#define CM_FOLD_ACCUMULATE 2u
+#define CM_FOLD_ALPHA_ON_DEVICE 4u
+int32_t cm_fri_fold_rows_op(const cm_handle out[4], const cm_handle src[4], const uint32_t alpha[4], uint32_t log_n, cm_handle tw,
+                            uint32_t i0, uint32_t n_out, uint32_t flags, cm_stream_t s);
+/* cm_fri_fold_line_leaves on outputs [row0, row0 + n_rows) of the layer (n_rows a power of two, row0 + n_rows <= 2^(log_n - 1)):
+ * in / circle hold source rows [2 row0, 2 (row0 + n_rows)), out the n_rows outputs, leaf_hashes 8 words per output row.
+ * *fused = 1 when k_fold_leaf made the launch (fold_line_leaf / fold_circle_leaf with row0, n_rows), 0 when the wrapper declined
+ * and the entry did what the sharded prover then does: fold_line_rows / fold_circle_into_line_rows with device challenges, then
+ * the leaf layer of the slice (merkle_layer). */
+int32_t cm_fri_fold_leaves_rows_op(const cm_handle* in, const cm_handle* circle, const uint32_t* alpha, const uint32_t* alpha_circle,
+                                   uint32_t log_n, cm_handle tw, uint32_t row0, uint32_t n_rows, const cm_handle out[4],
+                                   cm_handle leaf_hashes, uint32_t* fused, cm_stream_t s);
+/* cm_accumulate_quotients on rows [row0, row0 + n_rows) of the 2^log_size domain: cols and out hold that row range only
+ * (n_rows == 0 with row0 == 0: the whole domain, as the single-GPU prover launches it).  *path = the kernel family
+ * launch_quotients chose, one of CM_QUOT_PATH_*.
+ * leaf_hashes != 0: 8 words per row of the range, written by k_quotients_rows<2, LEAF> = MerkleOps::commit_on_layer(no children,
+ * out); the launch must be one quotient_leaf_serves admits (one or two batches, "quot_rows" 2, a power-of-two range of at least
+ * 2^"merkle_multi_top" rows with row0 a multiple of it), any other is refused.
+ * device_coeffs != 0: the provers' route from sampled values to quotients.  batches->values then holds n_samples sampled values
+ * (4 words each) and sample_idx[e] < n_samples names entry e's; the entry builds one QuotientCoefJob per batch, k_quotient_coeffs
+ * fills coef_c, sum_a, sum_b and batch_coeff on the device, the quotient launch reads them there, and they come back: coef_c_out
+ * (4 words per entry), sums_out (per batch 12 words: sum_a, sum_b, batch_coeff).  device_coeffs == 0: batches->values holds one
+ * value per entry, the coefficients are computed on the host as in cm_accumulate_quotients, and sample_idx, n_samples, coef_c_out
+ * and sums_out are not read. */
+#define CM_QUOT_PATH_ROWS2 1u
+#define CM_QUOT_PATH_ROWS4 2u
+#define CM_QUOT_PATH_ROWS2_LEAF 3u
+#define CM_QUOT_PATH_ONE_ROW 4u
+#define CM_QUOT_PATH_SLICES8 5u
+#define CM_QUOT_PATH_SLICES64 6u
+int32_t cm_accumulate_quotients_rows_op(uint32_t log_size, const cm_handle* cols, uint32_t n_cols, const cm_sample_batches* batches,
+                                        const uint32_t random_coeff[4], const cm_handle out[4], cm_handle tw, uint32_t row0,
+                                        uint32_t n_rows, cm_handle leaf_hashes, uint32_t device_coeffs, const uint32_t* sample_idx,
+                                        uint32_t n_samples, uint32_t* path, uint32_t* coef_c_out, uint32_t* sums_out, cm_stream_t s);
+/* The sharded prover's data movement (kernels_shard.hip).  pack_parity: dst[i] = src[2 i + parity], i < half_len.
+ * halo_build: out[q] = the column at the previous trace row of global position row0 + q, q < len, looked up in the halves
+ * (2^(n - log_ranks - 1) words each) received from ranks even_src / odd_src; n = log of the domain, trace_log <= n the trace
+ * domain's (the prover passes n - 1), 1 <= log_ranks < n; *err = the kernel's error word: 1 when a lookup fell outside the two
+ * neighbours, whose output words are then left unwritten.
+ * sum_copies: out[i] = sum over k < n_copies of in[k * stride + i], i < words, stride >= words; modular != 0: M31 sums of
+ * canonical words, else u32 sums that wrap.
+ * copy_segments: dst[i][j] = src[i][j], j < words[i], every segment in one launch; a segment of 0 words is skipped and a call
+ * whose segments are all empty, or that has none, launches nothing. */
+int32_t cm_pack_parity_op(cm_handle src, cm_handle dst, uint32_t half_len, uint32_t parity, cm_stream_t s);
+int32_t cm_halo_build_op(cm_handle even_half, cm_handle odd_half, uint32_t even_src, uint32_t odd_src, uint32_t row0, uint32_t len,
+                         uint32_t n, uint32_t trace_log, uint32_t log_ranks, cm_handle out, uint32_t* err, cm_stream_t s);
+int32_t cm_sum_copies_op(cm_handle in, uint32_t n_copies, uint64_t stride, uint64_t words, cm_handle out, uint32_t modular,
+                         cm_stream_t s);
+int32_t cm_copy_segments_op(const cm_handle* src, const cm_handle* dst, const uint64_t* words, uint32_t n_segs, cm_stream_t s);
 /* Proof object from its flat word stream (host code, no GPU): re-serialise with cm_proof_json / verify with cm_verify_proof. */
 int32_t cm_proof_from_words(const uint32_t* words, uint64_t n_words, cm_proof** out);
 /* Flat u32 serialisation of the proof (format: cairo_m_amd/csrc/proof.hpp), used by the parity tests. */

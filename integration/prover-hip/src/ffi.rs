@@ -510,6 +510,17 @@ pub struct cm_eval_job {
 }
 /// `CM_VERIFY_ARITH_ON_DEVICE`: the public LogUp sum and the OODS check of every proof decided on the GPU (`cm_verify_many_ex`).
 pub const CM_VERIFY_ARITH_ON_DEVICE: u32 = 1;
+/// `cm_fri_fold_rows_op` flags.
+pub const CM_FOLD_CIRCLE: u32 = 1;
+pub const CM_FOLD_ACCUMULATE: u32 = 2;
+pub const CM_FOLD_ALPHA_ON_DEVICE: u32 = 4;
+/// The kernel family `cm_accumulate_quotients_rows_op` reports in `*path`.
+pub const CM_QUOT_PATH_ROWS2: u32 = 1;
+pub const CM_QUOT_PATH_ROWS4: u32 = 2;
+pub const CM_QUOT_PATH_ROWS2_LEAF: u32 = 3;
+pub const CM_QUOT_PATH_ONE_ROW: u32 = 4;
+pub const CM_QUOT_PATH_SLICES8: u32 = 5;
+pub const CM_QUOT_PATH_SLICES64: u32 = 6;
 /// One public data set for `cm_public_logup_sum_op` / `cm_public_logup_sum_host` (test surface of the verifier's prelude kernels).
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -629,6 +640,13 @@ unsafe extern "C" {
     pub fn cm_tail_tab_words(nq_pad: u32) -> u64;
     pub fn cm_tail_last_op(digest: *const u32, last: *const cm_handle, log_n: u32, log_keep: u32, ar: *const u32, n_ar_words: u32, digest_out: *mut u32, degree_flag: *mut u32, last_out: *mut u32, ar_out: *mut u32, nonce_cell: *mut u64, s: cm_stream_t) -> i32;
     pub fn cm_eval_at_points_op(jobs: *const cm_eval_job, n_jobs: u32, t4: *const u32, want_landing: u32, out: *mut u32, landing: *mut u32, s: cm_stream_t) -> i32;
+    pub fn cm_fri_fold_rows_op(out: *const cm_handle, src: *const cm_handle, alpha: *const u32, log_n: u32, tw: cm_handle, i0: u32, n_out: u32, flags: u32, s: cm_stream_t) -> i32;
+    pub fn cm_fri_fold_leaves_rows_op(src: *const cm_handle, circle: *const cm_handle, alpha: *const u32, alpha_circle: *const u32, log_n: u32, tw: cm_handle, row0: u32, n_rows: u32, out: *const cm_handle, leaf_hashes: cm_handle, fused: *mut u32, s: cm_stream_t) -> i32;
+    pub fn cm_accumulate_quotients_rows_op(log_size: u32, cols: *const cm_handle, n_cols: u32, batches: *const cm_sample_batches, random_coeff: *const u32, out: *const cm_handle, tw: cm_handle, row0: u32, n_rows: u32, leaf_hashes: cm_handle, device_coeffs: u32, sample_idx: *const u32, n_samples: u32, path: *mut u32, coef_c_out: *mut u32, sums_out: *mut u32, s: cm_stream_t) -> i32;
+    pub fn cm_pack_parity_op(src: cm_handle, dst: cm_handle, half_len: u32, parity: u32, s: cm_stream_t) -> i32;
+    pub fn cm_halo_build_op(even_half: cm_handle, odd_half: cm_handle, even_src: u32, odd_src: u32, row0: u32, len: u32, n: u32, trace_log: u32, log_ranks: u32, out: cm_handle, err: *mut u32, s: cm_stream_t) -> i32;
+    pub fn cm_sum_copies_op(src: cm_handle, n_copies: u32, stride: u64, words: u64, out: cm_handle, modular: u32, s: cm_stream_t) -> i32;
+    pub fn cm_copy_segments_op(src: *const cm_handle, dst: *const cm_handle, words: *const u64, n_segs: u32, s: cm_stream_t) -> i32;
     pub fn cm_verify_many_ex(proofs: *const *const cm_proof, n: u32, expected: *const cm_pcs_config, flags: u32, results: *mut cm_verify_result, s: cm_stream_t) -> i32;
     pub fn cm_verify_many_detail_ex(proofs: *const *const cm_proof, n: u32, expected: *const cm_pcs_config, flags: u32, results: *mut cm_verify_result, slots: *mut cm_verify_slot, cap_slots: u32, slot_first: *mut u32, s: cm_stream_t) -> i32;
     pub fn cm_verify_run_device_ex(proofs: *const *const cm_proof, n: u32, expected: *const cm_pcs_config, flags: u32) -> i32;

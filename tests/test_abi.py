@@ -20,7 +20,9 @@ def test_all_declared_symbols_exported():
     L = load_library()
     syms = declared_symbols()
     assert len(syms) >= 40
-    assert {"cm_tail_grind_op", "cm_tail_tables_op", "cm_tail_tab_words", "cm_tail_last_op", "cm_bit_reverse", "cm_eval_at_points_op"} <= set(syms)
+    assert {"cm_tail_grind_op", "cm_tail_tables_op", "cm_tail_tab_words", "cm_tail_last_op", "cm_bit_reverse", "cm_eval_at_points_op",
+            "cm_fri_fold_rows_op", "cm_fri_fold_leaves_rows_op", "cm_accumulate_quotients_rows_op", "cm_pack_parity_op", "cm_halo_build_op",
+            "cm_sum_copies_op", "cm_copy_segments_op"} <= set(syms)
     missing = [s for s in syms if not hasattr(L, s)]
     assert not missing, missing
 

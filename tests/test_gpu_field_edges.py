@@ -259,8 +259,9 @@ def test_accumulate_quotients_edges(backend, oracle, quotient_refs, quot_rows, l
     one-column tail, one shared inversion of the 2R denominators; quot_rows = 1 reaches k_quotients<1> with its 16-group, 8-group
     and tail loops; 2^10 and 2^3 reach the column-sliced k_quotients<8> / <64>; three batches fall back to k_quotients<1> under
     every setting.  The first-batch sizes cross every loop boundary of the three kernels (multiples of 4, 8 and 16, one less, one
-    more), the second batch is every third column.  The LEAF variant of k_quotients_rows stays reachable only from the prover:
-    it shares the accumulation code tested here and adds the leaf hashes that test_gpu_prove.py pins.
+    more), the second batch is every third column.  The LEAF variant of k_quotients_rows shares the accumulation code tested here;
+    its leaf hashes, and every kernel here on a row range, are held to the oracle by test_quotient_leaf and test_quotient_rows
+    of tests/test_gpu_fri_rows.py.
 
     The coefficient a kernel multiplies a column by is coeff^(k+1) * (conj_u(y) - y); its words 0 and 1 are zero whenever coeff
     lies in CM31, so all four words of EVERY entry cannot be P-1 at once.  What is asserted below, from the Python reference, about

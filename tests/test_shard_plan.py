@@ -79,21 +79,8 @@ def test_previous_row_halo_neighbours():
     n - 1) the previous trace row of every EVEN local position of rank R's row range lies in the range of rank bitrev(bitrev(R) - 1),
     of every ODD position in the range of rank bitrev(bitrev(R) + 1), at a local position of the same parity — so the even half of a
     rank's slice goes to one neighbour, the odd half to the other, and nothing else is needed.  Model of cm::shifted_row
-    (device_common.hpp), exhaustive for 2 / 4 / 8 ranks at three sizes."""
-    def brev(i, log):
-        r = 0
-        for b in range(log):
-            r |= ((i >> b) & 1) << (log - 1 - b)
-        return r
-
-    def shifted_row(r, n, trace_log, offset):
-        i = brev(r, n)
-        half = 1 << (n - 1)
-        mask = (1 << (n + 1)) - 1
-        e = (1 + 4 * i) if i < half else (-(1 + 4 * (i - half))) & 0xffffffff
-        e = (e + offset * (1 << (n + 1 - trace_log))) & mask
-        j = (e - 1) // 4 if (e & 3) == 1 else half + (((mask + 1) - e - 1) & mask) // 4
-        return brev(j, n)
+    (device_common.hpp; tests/shard_ref.py, which test_gpu_shard_ops.py holds k_halo_build itself against), exhaustive for 2 / 4 / 8 ranks at three sizes."""
+    from tests.shard_ref import brev, shifted_row
 
     for n in (6, 9, 11):
         for log_ranks in (1, 2, 3):
