@@ -36,30 +36,6 @@ namespace {
 static_assert(sizeof(cm_mem_set_view) == 16 + 3 * sizeof(void*), "four words and three pointers, as the header states");
 static_assert(BATCH_ROOT + 2 == BATCH_WORDS && BATCH_FLAG == FOLD_FLAG, "a part's words hold both planes' roots");
 
-// what the lanes of a batch read
-struct BatchView {
-  const uint32_t* lvl;    // SET_STEPS rows of B + 1
-  const uint32_t* woff;   // B + 1
-  const uint32_t* roots;  // PLANES per part
-  const uint32_t* a;
-  const unsigned long long* flag;
-  const unsigned long long* scan;
-  const uint32_t* heads;
-  const uint32_t* words;
-  uint32_t B, n_heads;
-  __device__ __forceinline__ const uint32_t* level(uint32_t k) const { return lvl + (size_t)k * (B + 1); }
-};
-// part p's own view for set_parent_from: its slice of the addresses, of the pairs and of the words; the head lanes stay the
-// batch's (the scan's high word counts the heads of the parts in front).  at = off[p], q0 = the word position at the slice's start
-struct BatchPart { SetView s; uint32_t at, q0; };
-__device__ __forceinline__ BatchPart batch_part(const BatchView& v, uint32_t p) {
-  BatchPart bp;
-  bp.at = v.lvl[p];
-  const size_t slice = (size_t)SET_DEPTHS * bp.at;
-  bp.q0 = (uint32_t)v.scan[slice];
-  bp.s = SetView{v.a + bp.at, v.flag + slice, v.scan + slice, v.heads, v.words + v.woff[p], v.lvl[p + 1] - bp.at, v.woff[p + 1] - v.woff[p]};
-  return bp;
-}
 // VerifyFold's parent with the word position taken from the part's slice
 template <class Node>
 __device__ __forceinline__ Node batch_parent(const BatchPart& bp, const Node* in, uint32_t k, uint32_t r, bool& bad) {
@@ -77,15 +53,6 @@ __device__ __forceinline__ Node batch_parent(const BatchPart& bp, const Node* in
 }
 
 // ---- kernels -----------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(SET_BLOCK)
-k_batch_heads(BatchView v, uint32_t n, uint32_t* __restrict__ heads) {
-  const uint32_t t = blockIdx.x * SET_BLOCK + threadIdx.x;
-  if (t >= SET_DEPTHS * n || !(v.flag[t] >> 32)) return;
-  const uint32_t p = compose_part_of(v.lvl, v.B, t / SET_DEPTHS), at = v.lvl[p], np = v.lvl[p + 1] - at;
-  const uint32_t rank = (uint32_t)(v.scan[t] >> 32);
-  if (rank < v.n_heads) heads[rank] = (t - SET_DEPTHS * at) % np;
-}
-
 template <uint32_t PLANES>
 __global__ void __launch_bounds__(SET_BLOCK)
 k_batch_cells(FoldValues<PLANES> values, BatchView bv, uint32_t n, typename FoldPlanes<PLANES>::Node* __restrict__ out, uint32_t* __restrict__ dev) {

@@ -81,4 +81,44 @@ inline void batch_plan(const uint32_t* const* addresses, const uint32_t* n, cons
     bp.steps.push_back(cm_mem_batch_step{27 - k, bp.level(k + 1)[B], widest[k + 1], k < bp.k_tail ? SET_K_LEVEL : SET_K_TAIL});
 }
 
+// ---- what the lanes of every batched fold read (mem_batch.hip, the batched image update of mem_image.hip), device only -------------
+// Internal linkage, as set_fold.hpp's: every translation unit instantiates its own.
+namespace {
+
+// what the lanes of a batch read
+struct BatchView {
+  const uint32_t* lvl;    // SET_STEPS rows of B + 1
+  const uint32_t* woff;   // B + 1
+  const uint32_t* roots;  // PLANES per part
+  const uint32_t* a;
+  const unsigned long long* flag;
+  const unsigned long long* scan;
+  const uint32_t* heads;
+  const uint32_t* words;
+  uint32_t B, n_heads;
+  __device__ __forceinline__ const uint32_t* level(uint32_t k) const { return lvl + (size_t)k * (B + 1); }
+};
+// part p's own view for set_parent_from: its slice of the addresses, of the pairs and of the words; the head lanes stay the
+// batch's (the scan's high word counts the heads of the parts in front).  at = off[p], q0 = the word position at the slice's start
+struct BatchPart { SetView s; uint32_t at, q0; };
+__device__ __forceinline__ BatchPart batch_part(const BatchView& v, uint32_t p) {
+  BatchPart bp;
+  bp.at = v.lvl[p];
+  const size_t slice = (size_t)SET_DEPTHS * bp.at;
+  bp.q0 = (uint32_t)v.scan[slice];
+  bp.s = SetView{v.a + bp.at, v.flag + slice, v.scan + slice, v.heads, v.words + v.woff[p], v.lvl[p + 1] - bp.at, v.woff[p + 1] - v.woff[p]};
+  return bp;
+}
+// lane t with the head flag stores its lane index INSIDE its part at heads[scan[t] >> 32]
+__global__ void __launch_bounds__(SET_BLOCK)
+k_batch_heads(BatchView v, uint32_t n, uint32_t* __restrict__ heads) {
+  const uint32_t t = blockIdx.x * SET_BLOCK + threadIdx.x;
+  if (t >= SET_DEPTHS * n || !(v.flag[t] >> 32)) return;
+  const uint32_t p = compose_part_of(v.lvl, v.B, t / SET_DEPTHS), at = v.lvl[p], np = v.lvl[p + 1] - at;
+  const uint32_t rank = (uint32_t)(v.scan[t] >> 32);
+  if (rank < v.n_heads) heads[rank] = (t - SET_DEPTHS * at) % np;
+}
+
+}  // namespace
+
 }  // namespace cm

@@ -31,11 +31,15 @@
 // Host images run the same fold in plain C++ (host_update, host_merge): same roots, same node words, same statuses and messages.
 #include "../../include/cairom_hip.h"
 #include "mem_transition.hpp"
+#include "mem_batch.hpp"
+#include "kprof.hpp"
 #include "set_fold.hpp"
 #include "mem_open.hpp"
 #include <hipcub/hipcub.hpp>
 #include <algorithm>
+#include <cstdio>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -102,13 +106,9 @@ k_img_leaves(const uint32_t* __restrict__ a, const uint4* __restrict__ values, u
   mult[t] = make_uint4(1u, 1u, 1u, 1u);
 }
 
-// one call site of the permutation: the loop is not unrolled (range_cell_node's shape, with the three records stored on the way)
-__global__ void __launch_bounds__(SET_BLOCK)
-k_img_cells(const uint32_t* __restrict__ a, const uint4* __restrict__ new_values, uint32_t n, uint4* __restrict__ dirty, uint32_t* __restrict__ out) {
-  const uint32_t t = blockIdx.x * SET_BLOCK + threadIdx.x;
-  if (t >= n) return;
-  const uint4 q = new_values[t];
-  const uint32_t x = a[t];
+// Cell t of an update of n cells, address x and new value q: its three records into the update's dirty slice, its node of depth 28
+// returned.  One call site of the permutation: the loop is not unrolled (range_cell_node's shape, with the records stored on the way)
+__device__ __forceinline__ uint32_t img_cell_records(uint32_t x, uint4 q, uint32_t t, uint32_t n, uint4* __restrict__ dirty) {
   uint32_t h = 0, h29_0 = 0;
 #pragma unroll 1
   for (uint32_t i = 0; i < 3; i++) {
@@ -119,7 +119,13 @@ k_img_cells(const uint32_t* __restrict__ a, const uint4* __restrict__ new_values
     if (i < 2) put_node(dirty, 2 * t + i, 4u * x + 2u * i, air::TREE_HEIGHT, l, r, h, 1u, 1u);
     else put_node(dirty, 2 * n + t, 2u * x, air::TREE_HEIGHT - 1, l, r, h, 1u, 1u);
   }
-  out[t] = h;
+  return h;
+}
+__global__ void __launch_bounds__(SET_BLOCK)
+k_img_cells(const uint32_t* __restrict__ a, const uint4* __restrict__ new_values, uint32_t n, uint4* __restrict__ dirty, uint32_t* __restrict__ out) {
+  const uint32_t t = blockIdx.x * SET_BLOCK + threadIdx.x;
+  if (t >= n) return;
+  out[t] = img_cell_records(a[t], new_values[t], t, n, dirty);
 }
 
 // what a hashing lane reads beside the set's view: the old tree and where the dirty records go
@@ -128,6 +134,25 @@ struct ImgTree {
   const uint32_t* off;
   uint4* dirty;
 };
+
+// Parent p of S_{k+1} (set_parent's answer), where in[c] = the new hash of node c of S_k: a child that is not in S_k takes the OLD
+// tree's word (range_find of the old record of that pair, or the depth's default hash); the dirty record of depth 28 - k goes to
+// `slot` of tr.dirty; the parent's hash.  The single update and the batch (one tree per part) hash through this.
+__device__ __forceinline__ uint32_t img_parent(const SetParent& p, const uint32_t* in, uint32_t k, const ImgTree& tr, const TreeDefaults& dflt, uint32_t slot) {
+  const uint32_t depth = SET_DEPTHS - k, me = in[p.c];
+  uint32_t l, rr, lm = 1u, rm = 1u;
+  if (p.paired) { l = me; rr = in[p.c + 1]; }
+  else {
+    const uint32_t empty = dflt.h[depth];   // (read as a value in front of the lookup: merged with nd's loads it would put the policy in scratch)
+    const uint32_t* const nd = range_find(tr.nodes, tr.off, depth, p.x & ~1u);
+    const uint32_t w = nd ? (p.odd ? nd[2] : nd[3]) : empty, wm = nd ? (p.odd ? nd[5] : nd[6]) : 0u;
+    l = p.odd ? w : me; rr = p.odd ? me : w;
+    lm = p.odd ? wm : 1u; rm = p.odd ? 1u : wm;
+  }
+  const uint32_t h = host::poseidon2_hash(l, rr);
+  put_node(tr.dirty, slot, p.x & ~1u, depth, l, rr, h, lm, rm);
+  return h;
+}
 
 // The image's policy of the shared ladder (set_fold.hpp): a node is its new hash; a child that is not in S_k takes the OLD tree's
 // word, so no record of sibling words is read and nothing is checked; every parent files the dirty record of its depth.
@@ -140,20 +165,7 @@ struct ImageFold {
   // parent r of S_{k+1}, where in[c] = the new hash of node c of S_k: the dirty record of depth 28 - k at slot sl.o[2 + k] + r,
   // the parent's hash
   __device__ __forceinline__ uint32_t parent(const SetView& s, const uint32_t* in, uint32_t k, uint32_t r, bool&) const {
-    const SetParent p = set_parent(s, k, r);
-    const uint32_t depth = SET_DEPTHS - k, me = in[p.c];
-    uint32_t l, rr, lm = 1u, rm = 1u;
-    if (p.paired) { l = me; rr = in[p.c + 1]; }
-    else {
-      const uint32_t empty = dflt.h[depth];   // (read as a value in front of the lookup: merged with nd's loads it would put the policy in scratch)
-      const uint32_t* const nd = range_find(tr.nodes, tr.off, depth, p.x & ~1u);
-      const uint32_t w = nd ? (p.odd ? nd[2] : nd[3]) : empty, wm = nd ? (p.odd ? nd[5] : nd[6]) : 0u;
-      l = p.odd ? w : me; rr = p.odd ? me : w;
-      lm = p.odd ? wm : 1u; rm = p.odd ? 1u : wm;
-    }
-    const uint32_t h = host::poseidon2_hash(l, rr);
-    put_node(tr.dirty, sl.o[2 + k] + r, p.x & ~1u, depth, l, rr, h, lm, rm);
-    return h;
+    return img_parent(set_parent(s, k, r), in, k, tr, dflt, sl.o[2 + k] + r);
   }
   __device__ __forceinline__ void finish(uint32_t top, bool, uint32_t* dev) const { dev[IW_ROOT] = top; }
 };
@@ -176,25 +188,27 @@ __device__ __forceinline__ uint32_t img_lower_bound(const uint32_t* __restrict__
 
 // rank[j] = the old records in front of dirty record j (those of deeper slices and those of its own with a lower index);
 // ins[j] = 1 when the old list has no record of that depth and index; ins[n_dirty] = 0 so that the scan ends in the total
-__global__ void __launch_bounds__(SET_BLOCK)
-k_img_rank(const uint32_t* __restrict__ nodes, const uint32_t* __restrict__ off, const uint32_t* __restrict__ dirty, ImgSlices sl, uint32_t* __restrict__ rank,
-           uint32_t* __restrict__ ins) {
-  const uint32_t j = blockIdx.x * SET_BLOCK + threadIdx.x, n_dirty = sl.o[IMG_SLICES];
-  if (j > n_dirty) return;
-  if (j == n_dirty) { ins[j] = 0u; return; }
+__device__ __forceinline__ void img_rank_lane(const uint32_t* __restrict__ nodes, const uint32_t* __restrict__ off, const uint32_t* __restrict__ dirty,
+                                              const ImgSlices& sl, uint32_t j, uint32_t* __restrict__ rank, uint32_t* __restrict__ ins) {
+  if (j == sl.o[IMG_SLICES]) { ins[j] = 0u; return; }
   const uint32_t q = img_slice_of(sl, j), index = dirty[RANGE_NODE_WORDS * (size_t)j], end = off[q + 1];
   const uint32_t lb = img_lower_bound(nodes, off[q], end, index);
   rank[j] = lb;
   ins[j] = (lb < end && nodes[RANGE_NODE_WORDS * (size_t)lb] == index) ? 0u : 1u;
 }
+__global__ void __launch_bounds__(SET_BLOCK)
+k_img_rank(const uint32_t* __restrict__ nodes, const uint32_t* __restrict__ off, const uint32_t* __restrict__ dirty, ImgSlices sl, uint32_t* __restrict__ rank,
+           uint32_t* __restrict__ ins) {
+  const uint32_t j = blockIdx.x * SET_BLOCK + threadIdx.x;
+  if (j <= sl.o[IMG_SLICES]) img_rank_lane(nodes, off, dirty, sl, j, rank, ins);
+}
 
 // lane t < n_old: old record t, unless a dirty record replaces it; lane n_old + j: dirty record j.  scan[j] = the inserts in front
-// of dirty record j.  cap = the records `out` has room for.
-__global__ void __launch_bounds__(SET_BLOCK)
-k_img_merge(const uint4* __restrict__ nodes, uint32_t n_old, const uint4* __restrict__ dirty, ImgSlices sl, const uint32_t* __restrict__ rank,
-            const uint32_t* __restrict__ scan, uint32_t cap, uint4* __restrict__ out) {
-  const uint32_t t = blockIdx.x * SET_BLOCK + threadIdx.x, n_dirty = sl.o[IMG_SLICES];
-  if (t >= n_old + n_dirty) return;
+// of dirty record j, counted from scan0 (a batch scans the records of many updates at once: scan0 = the scan at this update's
+// first record).  cap = the records `out` has room for.
+__device__ __forceinline__ void img_merge_lane(const uint4* __restrict__ nodes, uint32_t n_old, const uint4* __restrict__ dirty, const ImgSlices& sl,
+                                               const uint32_t* __restrict__ rank, const uint32_t* __restrict__ scan, uint32_t scan0, uint32_t cap,
+                                               uint4* __restrict__ out, uint32_t t) {
   const uint4* src;
   uint32_t pos;
   if (t < n_old) {
@@ -204,15 +218,21 @@ k_img_merge(const uint4* __restrict__ nodes, uint32_t n_old, const uint4* __rest
     const uint32_t q = air::TREE_HEIGHT - head.y, end = sl.o[q + 1];
     const uint32_t lb = img_lower_bound(reinterpret_cast<const uint32_t*>(dirty), sl.o[q], end, head.x);
     if (lb < end && dirty[2 * (size_t)lb].x == head.x) return;
-    pos = t + scan[lb];
+    pos = t + (scan[lb] - scan0);
   } else {
     const uint32_t j = t - n_old;
     src = dirty + 2 * (size_t)j;
-    pos = rank[j] + scan[j];
+    pos = rank[j] + (scan[j] - scan0);
   }
   if (pos >= cap) return;
   out[2 * (size_t)pos] = src[0];
   out[2 * (size_t)pos + 1] = src[1];
+}
+__global__ void __launch_bounds__(SET_BLOCK)
+k_img_merge(const uint4* __restrict__ nodes, uint32_t n_old, const uint4* __restrict__ dirty, ImgSlices sl, const uint32_t* __restrict__ rank,
+            const uint32_t* __restrict__ scan, uint32_t cap, uint4* __restrict__ out) {
+  const uint32_t t = blockIdx.x * SET_BLOCK + threadIdx.x;
+  if (t < n_old + sl.o[IMG_SLICES]) img_merge_lane(nodes, n_old, dirty, sl, rank, scan, 0u, cap, out, t);
 }
 
 // the depth offsets of the merged list: every old offset moves up by the inserts of the deeper slices
@@ -417,13 +437,28 @@ void check_update_addresses(const char* who, const uint32_t* addresses, uint64_t
                          "): the addresses must be strictly ascending and below 2^28");
 }
 
+// The refusals of an update in the header's words, one function per check: the single call and the batch (mem_image_batch.inc) say
+// the same.  Checks 2 and 3 read only what the host holds.
+void check_new_words(const uint32_t* a, uint32_t n, const uint32_t* nv) {
+  for (uint64_t i = 0; i < 4ull * n; i++)
+    if (nv[i] >= P) reject("new value word " + std::to_string(i % 4) + " of cell " + std::to_string(a[i / 4]) + " is not below P");
+}
+void check_root_before(const cm_mem_image& img, const uint32_t* root_before) {
+  if (root_before && *root_before != img.root)
+    reject("the image is at root " + std::to_string(img.root) + ", the update starts from " + std::to_string(*root_before));
+}
+[[noreturn]] void old_differs(const uint32_t* a, const uint32_t* ov, uint32_t cell, const uint32_t* cur) {
+  reject("cell " + std::to_string(a[cell]) + " holds " + cell_words(cur) + ", the update's old value is " + cell_words(ov + 4 * (size_t)cell));
+}
+void check_root_after(const uint32_t* root_after, uint32_t root) {
+  if (root_after && *root_after != root) reject("the image would hash to root " + std::to_string(root) + ", not " + std::to_string(*root_after));
+}
+
 // the checks of cm_mem_image_apply from the second on, in the header's order; the image changes only behind the last of them
 void apply_locked(cm_mem_image& img, const uint32_t* a, uint32_t n, const uint32_t* nv, const uint32_t* ov, const uint32_t* root_before,
                   const uint32_t* root_after, uint32_t* root_out, cm_mem_transition** record_out) {
-  for (uint64_t i = 0; i < 4ull * n; i++)
-    if (nv[i] >= P) reject("new value word " + std::to_string(i % 4) + " of cell " + std::to_string(a[i / 4]) + " is not below P");
-  if (root_before && *root_before != img.root)
-    reject("the image is at root " + std::to_string(img.root) + ", the update starts from " + std::to_string(*root_before));
+  check_new_words(a, n, nv);
+  check_root_before(img, root_before);
   cm_mem_set_step steps[SET_STEPS];
   const uint32_t n_words = mem_set_plan(a, n, steps);
   std::unique_ptr<cm_mem_transition> rec;
@@ -435,20 +470,14 @@ void apply_locked(cm_mem_image& img, const uint32_t* a, uint32_t n, const uint32
     rec->siblings.resize(n_words);
     rec->root_before = img.root;
   }
-  auto old_differs = [&](uint32_t cell, const uint32_t* cur) {
-    reject("cell " + std::to_string(a[cell]) + " holds " + cell_words(cur) + ", the update's old value is " + cell_words(ov + 4 * (size_t)cell));
-  };
-  auto root_differs = [&](uint32_t root) {
-    if (root_after && *root_after != root) reject("the image would hash to root " + std::to_string(root) + ", not " + std::to_string(*root_after));
-  };
   if (!img.device) {
     std::vector<uint32_t> cur(4 * (size_t)n);
     host_read(img, a, n, cur.data());
     if (ov)
       for (uint32_t i = 0; i < n; i++)
-        if (memcmp(cur.data() + 4 * (size_t)i, ov + 4 * (size_t)i, 16)) old_differs(i, cur.data() + 4 * (size_t)i);
+        if (memcmp(cur.data() + 4 * (size_t)i, ov + 4 * (size_t)i, 16)) old_differs(a, ov, i, cur.data() + 4 * (size_t)i);
     HostUpdate u = host_update(img, a, n, nv);
-    root_differs(u.root);
+    check_root_after(root_after, u.root);
     CM_CHECK(u.siblings.size() == n_words, "memory image: the fold read " + std::to_string(u.siblings.size()) + " sibling words where the plan has " +
                                                std::to_string(n_words));
     if (rec) { rec->old_values = cur; rec->siblings = u.siblings; }
@@ -462,8 +491,8 @@ void apply_locked(cm_mem_image& img, const uint32_t* a, uint32_t n, const uint32
     DeviceUpdate up;
     uint32_t mismatch = NO_CELL, cur4[4] = {0, 0, 0, 0}, root = 0;
     device_update(img, a, n, nv, ov, steps, up, mismatch, cur4, root, st);
-    if (mismatch != NO_CELL) old_differs(mismatch, cur4);
-    root_differs(root);
+    if (mismatch != NO_CELL) old_differs(a, ov, mismatch, cur4);
+    check_root_after(root_after, root);
     // the record is read from the tree before the update, through the set opener
     if (rec) open_set(img.d_nodes.as<cm_merkle_node>(), img.n_nodes, a, n, rec->old_values.data(), rec->siblings.data(), n_words, st);
     img.d_nodes = std::move(up.nodes);
@@ -677,3 +706,6 @@ int32_t cm_mem_image_open_memory_set(cm_mem_image* img, const uint32_t* addresse
   });
 }
 }  // extern "C"
+
+// cm_mem_images_apply: many images, one update each, through ONE ladder
+#include "mem_image_batch.inc"

@@ -2727,6 +2727,108 @@ def follow_run_image(proofs, updates, image, batched=False):
     return image.root
 
 
+# ---- batched image updates (include/cairom_hip.h: cm_mem_images_apply) ----------------------------------------------------------
+class MemImageUpdateC(C.Structure):
+    """cm_mem_image_update"""
+    _fields_ = [("struct_size", C.c_uint32), ("n", C.c_uint32), ("img", C.c_void_p)] + \
+               [(n, _u32p) for n in ("addresses", "new_values", "old_values", "root_before", "root_after")]
+
+
+class MemImageResultC(C.Structure):
+    """cm_mem_image_result"""
+    _fields_ = [("status", C.c_int32), ("root", C.c_uint32), ("message", C.c_char * 248)]
+
+
+def _image_update(u):
+    """(image, addresses, new_values, old_values | None, root_before | None, root_after | None) of one entry of apply_images"""
+    if len(u) == 2 and isinstance(u[1], MemTransition):
+        t = u[1]
+        return u[0], t.addresses, t.new_values, t.old_values, t.root_before, t.root_after
+    image, a, nv, ov, rb, ra = tuple(u) + (None,) * (6 - len(u))
+    return image, a, nv, ov, rb, ra
+
+
+def apply_images(updates, lib=None, with_rc=False):
+    """cm_mem_images_apply: one update each to DIFFERENT device images in one call, through one ladder of launches.  updates:
+    [(image, MemTransition)] or [(image, addresses, new_values[, old_values, root_before, root_after])].  Returns one
+    (status, root, message) per part: what MemImage.apply would have done with that part alone — 0 and the new root, or the
+    refusal's status and words with the image as it was; a refused part does not disturb the others.  Raises CmError (.status,
+    .message) only when the call as a whole is refused.  with_rc: (the call's return value — 0, or the status of the lowest part
+    that has another, which cm_last_error() then names — and the list).  The batch makes no record: MemImage.apply(record=True)
+    does."""
+    ups = [_image_update(u) for u in updates]
+    L = lib or (ups[0][0].L if ups else load_library())
+    n = len(ups)
+    parts, res, keep = (MemImageUpdateC * max(n, 1))(), (MemImageResultC * max(n, 1))(), []
+    word = lambda x: None if x is None else C.pointer(C.c_uint32(int(x)))
+    for p, (image, a, nv, ov, rb, ra) in zip(parts, ups):
+        a = _set_addresses(a)
+        nv = _cell_values(nv, a.size)
+        ov = None if ov is None else _cell_values(ov, a.size)
+        pad = a if a.size else np.zeros(1, dtype=np.uint32)
+        words = (word(rb), word(ra))
+        keep.append((pad, nv, ov, words))
+        p.struct_size, p.n, p.img = C.sizeof(MemImageUpdateC), a.size, image.h
+        p.addresses, p.new_values = _p(pad), _p(nv)
+        if ov is not None:
+            p.old_values = _p(ov)
+        if words[0]:
+            p.root_before = words[0]
+        if words[1]:
+            p.root_after = words[1]
+    for r in res:
+        r.status = -1                                                             # (a call refused as a whole writes no result)
+    rc = L.cm_mem_images_apply(parts, C.c_uint32(n), res)
+    judged = n > 0 and all(r.status != -1 for r in res[:n])
+    out = [(r.status, r.root, r.message.decode(errors="replace")) for r in res[:n]] if judged else None
+    if rc and (not judged or all(r.status != rc for r in res[:n]) or rc in (2, 3)):
+        try:
+            _raise_status(L, rc)
+        except CmError as e:
+            e.results = out                                                       # (without a GPU: the host's own verdicts)
+            raise
+    return (rc, out) if with_rc else out
+
+
+def follow_runs_images(runs):
+    """follow_run_image for many runs at once.  runs: [(proofs, updates, image)], the images different device images.  Round j
+    applies segment j of every run that is still alive in ONE apply_images, from proof j's public initial_root to its final_root
+    (a MemTransition's own roots are first held against the proof's, as follow_run_image does; an update without cells changes
+    nothing and goes through the single call, which still checks the roots).  A run stops at its first refusal, its image at the
+    last good segment, and the others go on.  Returns per run (root, None) or (root, "segment <j>: <message>")."""
+    runs = [(list(p), list(u), im) for p, u, im in runs]
+    for p, u, _ in runs:
+        if len(p) != len(u):
+            raise CmError(f"follow_runs_images: {len(u)} updates for {len(p)} proofs")
+    said = [None] * len(runs)
+    for j in range(max((len(p) for p, _, _ in runs), default=0)):
+        batch, who = [], []
+        for r, (proofs, updates, image) in enumerate(runs):
+            if said[r] is not None or j >= len(proofs):
+                continue
+            d, u = proofs[j].public_data(), updates[j]
+            try:
+                if isinstance(u, MemTransition):
+                    for side, want in (("before", d["initial_root"]), ("after", d["final_root"])):
+                        if getattr(u, "root_" + side) != want:
+                            raise CmError(f"the transition's root {side} is {getattr(u, 'root_' + side)}, the proof's is {want}")
+                    a, nv, ov = u.addresses, u.new_values, u.old_values
+                else:
+                    a, nv, ov = u[0], u[1], None
+                if len(a):
+                    batch.append((image, a, nv, ov, d["initial_root"], d["final_root"]))
+                    who.append(r)
+                else:
+                    image.apply_transition(MemTransition([], [], [], [], d["initial_root"], d["final_root"]))
+            except CmError as e:
+                said[r] = f"segment {j}: {getattr(e, 'message', e)}"
+        if batch:
+            for r, (status, _, message) in zip(who, apply_images(batch, runs[who[0]][2].L)):
+                if status:
+                    said[r] = f"segment {j}: {message}"
+    return [(image.root, said[r]) for r, (_, _, image) in enumerate(runs)]
+
+
 # ---- program identity and the statement of a run (include/cairom_hip.h: cm_program_id_entries .. cm_run_statement_of) ----------
 class RunStatementC(C.Structure):
     """cm_run_statement"""

@@ -55,6 +55,8 @@
  *    Still 10 (additive: one new function, no struct): cm_compose_transitions.
  *    Still 10 (additive: three new functions and two structs, nothing moved; listed with the family they batch): cm_mem_set_view,
  *    cm_mem_batch_step, cm_verify_memory_transitions, cm_verify_memory_sets, cm_mem_batch_plan.
+ *    Still 10 (additive: one new function and two structs, nothing moved; listed with the batches): cm_mem_image_update,
+ *    cm_mem_image_result, cm_mem_images_apply.
  *    Still 10 (additive: four new functions and two structs, nothing moved): cm_tail_piece, cm_tail_tables_out, cm_tail_grind_op,
  *    cm_tail_tables_op, cm_tail_tab_words, cm_tail_last_op.
  *    Still 10 (additive: one new function and one struct, nothing moved): cm_eval_job, cm_eval_at_points_op.
@@ -1520,6 +1522,60 @@ int32_t cm_mem_image_open_memory_range(cm_mem_image* img, uint32_t start, uint32
                                        uint32_t* root);
 int32_t cm_mem_image_open_memory_set(cm_mem_image* img, const uint32_t* addresses, uint64_t n, uint32_t* values, uint32_t* siblings,
                                      uint32_t cap_siblings, uint32_t* n_siblings, uint32_t* root);
+/* ---- batched image updates (additive to revision 10: one new function and two structs, nothing moved) ------------------------
+ * cm_mem_images_apply updates n_parts DIFFERENT device images in one call, one update each, through ONE ladder of launches: a
+ * small update is bound by its chain of dependent launches, not by hashing, and independent images share that chain as the
+ * records of cm_verify_memory_transitions do.  It is what a follower of many runs (a bridge, an RPC node, a checkpoint service)
+ * calls once per round of segments.
+ * Per part: parts[i] gets exactly the status, message, root and resulting image that
+ * cm_mem_image_apply(img, addresses, new_values, n, old_values, root_before, root_after, &root, NULL) would give alone — nodes
+ * and cells byte for byte.  results[i].status = 0 (applied), 1 (a bad part) or 11 (refused), .message the single call's words
+ * ("" when applied), .root the image's root when the call returns.  A refused or bad part leaves its image byte-identical and
+ * does not disturb its neighbours, which are applied (the rule cm_program_ids and the batch verifiers state).  The checks run in
+ * the single call's order: 1 bad arguments; 2 a new value word not below P; 3 root_before; 4 old_values, naming the lowest
+ * address; 5 - 6 root_after.  A part's own status 1, never a failed call: a host image ("device images only": it takes its
+ * updates through cm_mem_image_apply), n == 0, n > 2^20, a NULL addresses or new_values, addresses not strictly ascending or not
+ * below 2^28 (the single call's message).  Such a part, and one refused by check 2 or 3 — which read only what the host holds —
+ * never reaches a kernel; the others run.
+ * Returns 0 when every part has status 0, else the status of the lowest part that has another, with cm_last_error() =
+ * "part <i>: <message>".
+ * The call as a whole is refused with status 1, before any address is read and before the device is asked for: a NULL `parts` or
+ * `results`; n_parts == 0 or n_parts > 2^16; a part with a short struct_size; a part with a NULL img; the parts' n summing to more
+ * than 2^20 ("apply in groups"); one image named by two parts — updates of one image depend on each other and do not belong in
+ * one fold; the message names both parts.  Nothing is written to `results` then.  A call that passes these asks for the device
+ * whatever its parts hold: without a GPU it returns cm_init's status (3), with the host's own verdicts (status 1) in `results`
+ * and cm_init's status and message in every other part.
+ * The batch makes no record (cm_mem_image_apply's record_out): a follower that must re-emit the full transition of an update
+ * uses the single call.
+ * Device side (the calling thread's stream and pool, as the single call): one upload of one block — per part its result words
+ * and a table entry (the image's node list and depth offsets, where its new list goes, its slice of the dirty records), the
+ * prefix tables, then the addresses, new values and old values concatenated; k_imgs_check and k_imgs_cells on the concatenation
+ * (a lane bisects the cells' prefix for its part and reads THAT part's image); the flag pass, ONE scan and the head scatter of
+ * the batched verifier; k_imgs_level, one launch per depth with one lane per parent of ALL parts while any part is wider than 128
+ * nodes — a narrow part rides along; k_imgs_tail, one workgroup per part, which writes the part's root; k_imgs_rank over the dirty
+ * records of all parts, ONE exclusive scan of the insert flags with one sentinel per part, k_imgs_merge with one lane per old and
+ * per dirty record of all parts into per-part new lists taken from the pool before the first launch, k_imgs_offsets with one
+ * block per part; one download of 144 bytes per part, one wait (one more trip of 16 bytes per part whose old values differ, for
+ * the value its message names).  The host then decides part by part: refuse and drop the new list, or swap.  The number of
+ * launches and round trips does not depend on n_parts: it is that of the part with the most per-level steps, as
+ * cm_mem_batch_plan lists for the parts' addresses, plus a constant.
+ * Threading: the handles' mutexes are taken in one global order, by handle address, and are all held until the last swap. */
+typedef struct {
+  uint32_t struct_size;          /* sizeof(cm_mem_image_update) */
+  uint32_t n;                    /* cells */
+  cm_mem_image* img;
+  const uint32_t* addresses;     /* n, strictly ascending, below 2^28 */
+  const uint32_t* new_values;    /* 4 n */
+  const uint32_t* old_values;    /* 4 n, or NULL: not compared */
+  const uint32_t* root_before;   /* NULL: not compared */
+  const uint32_t* root_after;    /* NULL: not compared */
+} cm_mem_image_update;           /* sizeof = 56 */
+typedef struct {
+  int32_t status;                /* 0 applied, 1 bad part, 11 refused */
+  uint32_t root;                 /* the image's root when the call returns */
+  char message[248];             /* "" when applied */
+} cm_mem_image_result;           /* sizeof = 256 */
+int32_t cm_mem_images_apply(const cm_mem_image_update* parts, uint32_t n_parts, cm_mem_image_result* results);
 /* ---- program identity and the statement of a run (additive to revision 10) ---------------------------------------------------
  * Which program a proof is about, as one 31-bit word: Proof::program_id() of the reference (crates/prover/src/lib.rs:75-97), the
  * Poseidon2 root of the partial memory tree that holds only the proof's public program cells.  An "entry" is the seven-word record

@@ -362,6 +362,29 @@ pub struct cm_mem_image_stats {
     pub n_nodes: u64,
     pub bytes: u64,
 }
+/// One part of `cm_mem_images_apply`: an update of `n` cells to the device image `img`; a null `old_values`, `root_before` or
+/// `root_after` is not compared; set `struct_size` before the call
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct cm_mem_image_update {
+    pub struct_size: u32,
+    pub n: u32,
+    pub img: *mut cm_mem_image,
+    pub addresses: *const u32,
+    pub new_values: *const u32,
+    pub old_values: *const u32,
+    pub root_before: *const u32,
+    pub root_after: *const u32,
+}
+/// What `cm_mem_images_apply` says of one part: 0 applied, 1 a bad part, 11 refused; the image's root when the call returns;
+/// the single call's message, NUL-terminated ("" when applied)
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct cm_mem_image_result {
+    pub status: i32,
+    pub root: u32,
+    pub message: [u8; 248],
+}
 /// What a chain of proofs states (`cm_run_statement_of`): the program's id and range, the registers and memory roots the run
 /// starts from and ends at, the counts of its input and output entries; set `struct_size` before the call
 #[repr(C)]
@@ -719,6 +742,7 @@ unsafe extern "C" {
     pub fn cm_mem_image_nodes(img: *mut cm_mem_image, nodes: *mut cm_merkle_node, cap: u64, n_total: *mut u64) -> i32;
     pub fn cm_mem_image_apply(img: *mut cm_mem_image, addresses: *const u32, new_values: *const u32, n: u64, old_values: *const u32, root_before: *const u32, root_after: *const u32, root_out: *mut u32, record_out: *mut *mut cm_mem_transition) -> i32;
     pub fn cm_mem_image_apply_transition(img: *mut cm_mem_image, t: *const cm_mem_transition_view, record_out: *mut *mut cm_mem_transition) -> i32;
+    pub fn cm_mem_images_apply(parts: *const cm_mem_image_update, n_parts: u32, results: *mut cm_mem_image_result) -> i32;
     pub fn cm_mem_image_open_memory(img: *mut cm_mem_image, addresses: *const u32, n: u64, out: *mut cm_mem_opening, root: *mut u32) -> i32;
     pub fn cm_mem_image_open_memory_range(img: *mut cm_mem_image, start: u32, n_cells: u32, values: *mut u32, out: *mut cm_mem_range_opening, root: *mut u32) -> i32;
     pub fn cm_mem_image_open_memory_set(img: *mut cm_mem_image, addresses: *const u32, n: u64, values: *mut u32, siblings: *mut u32, cap_siblings: u32, n_siblings: *mut u32, root: *mut u32) -> i32;

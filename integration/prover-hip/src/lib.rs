@@ -795,6 +795,47 @@ impl MemImage {
         self.root()
     }
 
+    /// One transition each to DIFFERENT device images in one call, through one ladder of launches (`cm_mem_images_apply`): per
+    /// part `Ok(the new root)`, or `Err((status, message))` in the words `apply_transition` would use, the image as it was; a
+    /// refused part does not disturb the others.  The outer `Err` is a call refused as a whole (one image twice, no parts, more
+    /// than 2^20 cells in all) or a missing device.
+    pub fn apply_many(updates: &mut [(&mut MemImage, &MemTransition)]) -> Result<Vec<Result<u32, (i32, String)>>, String> {
+        ensure_init();
+        let mut parts: Vec<cm_mem_image_update> = Vec::with_capacity(updates.len());
+        for (image, t) in updates.iter() {
+            if t.old_values.len() != 4 * t.addresses.len() || t.new_values.len() != 4 * t.addresses.len() {
+                return Err(format!("{} old and {} new value words for a transition of {} cells", t.old_values.len(), t.new_values.len(), t.addresses.len()));
+            }
+            let mut p: cm_mem_image_update = unsafe { std::mem::zeroed() };
+            p.struct_size = std::mem::size_of::<cm_mem_image_update>() as u32;
+            p.n = t.addresses.len() as u32;
+            p.img = image.handle;
+            p.addresses = t.addresses.as_ptr();
+            p.new_values = t.new_values.as_ptr();
+            p.old_values = t.old_values.as_ptr();
+            p.root_before = &t.root_before;
+            p.root_after = &t.root_after;
+            parts.push(p);
+        }
+        let blank = cm_mem_image_result { status: -1, root: 0, message: [0u8; 248] };
+        let mut results: Vec<cm_mem_image_result> = vec![blank; parts.len()];
+        let rc = unsafe { cm_mem_images_apply(parts.as_ptr(), parts.len() as u32, results.as_mut_ptr()) };
+        // a call refused as a whole writes no result; a call that judged every part returns the lowest bad part's status
+        if rc != 0 && (results.is_empty() || results.iter().any(|r| r.status == -1) || results.iter().all(|r| r.status != rc)) {
+            return Err(last_error());
+        }
+        Ok(results
+            .iter()
+            .map(|r| {
+                if r.status == 0 {
+                    return Ok(r.root);
+                }
+                let end = r.message.iter().position(|&b| b == 0).unwrap_or(r.message.len());
+                Err((r.status, String::from_utf8_lossy(&r.message[..end]).into_owned()))
+            })
+            .collect())
+    }
+
     /// The cells `addresses` (any order, repeats allowed: sorted and made unique here) under the image's current root, built on
     /// the GPU (`cm_mem_image_open_memory_set`; device images only): the record and that root.
     pub fn open_set(&self, addresses: &[u32]) -> Result<(MemSetOpening, u32), String> {
