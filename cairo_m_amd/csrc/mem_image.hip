@@ -709,3 +709,6 @@ int32_t cm_mem_image_open_memory_set(cm_mem_image* img, const uint32_t* addresse
 
 // cm_mem_images_apply: many images, one update each, through ONE ladder
 #include "mem_image_batch.inc"
+
+// cm_mem_images_open_memory_sets: many sets under many images, one chain of launches and one round trip
+#include "mem_image_open_batch.inc"

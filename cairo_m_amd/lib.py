@@ -2829,6 +2829,75 @@ def follow_runs_images(runs):
     return [(image.root, said[r]) for r, (_, _, image) in enumerate(runs)]
 
 
+# ---- batched set openings (include/cairom_hip.h: cm_mem_images_open_memory_sets) -------------------------------------------------
+class MemSetRequestC(C.Structure):
+    """cm_mem_set_request"""
+    _fields_ = [("struct_size", C.c_uint32), ("n", C.c_uint32), ("img", C.c_void_p), ("addresses", _u32p), ("values", _u32p), ("siblings", _u32p),
+                ("cap_siblings", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class MemSetResultC(C.Structure):
+    """cm_mem_set_result"""
+    _fields_ = [("status", C.c_int32), ("root", C.c_uint32), ("n_siblings", C.c_uint32), ("reserved", C.c_uint32), ("message", C.c_char * 240)]
+
+
+def open_sets(requests, lib=None, with_rc=False):
+    """cm_mem_images_open_memory_sets: many sets under device images in one call, through one chain of launches and one round trip.
+    requests: [(image, addresses)]; several may name one image; the addresses in any order, repeats allowed (sorted and made
+    unique here, per part, as MemImage.open_set does).  Returns one (status, message, MemSetOpening or None, root) per part: what
+    MemImage.open_set would have done with that part alone — 0, "", the record and the root it opens under, or the refusal's status
+    and words and no record; a bad part does not disturb the others.  Raises CmError (.status, .message) only when the call as a
+    whole is refused or has no device (.results then holds the host's own verdicts).  with_rc: (the call's return value — 0, or
+    the status of the lowest part that has another, which cm_last_error() then names — and the list)."""
+    reqs = [(image, np.unique(_set_addresses(a))) for image, a in requests]
+    L = lib or (reqs[0][0].L if reqs else load_library())
+    n = len(reqs)
+    parts, res, keep = (MemSetRequestC * max(n, 1))(), (MemSetResultC * max(n, 1))(), []
+    for p, (image, a) in zip(parts, reqs):
+        try:
+            plan, m = mem_set_plan(a, L)
+        except CmError:
+            plan, m = [], 0                                                       # (no cells, an address beyond 2^28: the part's own refusal)
+        values, siblings = np.zeros((max(a.size, 1), 4), dtype=np.uint32), np.zeros(max(m, 1), dtype=np.uint32)
+        pad = a if a.size else np.zeros(1, dtype=np.uint32)
+        keep.append((pad, values, siblings, [s["n_siblings"] for s in plan[1:]]))
+        p.struct_size, p.n, p.img, p.cap_siblings = C.sizeof(MemSetRequestC), a.size, image.h, m
+        p.addresses, p.values, p.siblings = _p(pad), _p(values), _p(siblings)
+    for r in res:
+        r.status = -1                                                             # (a call refused as a whole writes no result)
+    rc = L.cm_mem_images_open_memory_sets(parts, C.c_uint32(n), res)
+    judged = n > 0 and all(r.status != -1 for r in res[:n])
+    out = None
+    if judged:
+        out = []
+        for r, (image, a), (_, values, siblings, counts) in zip(res[:n], reqs, keep):
+            rec = MemSetOpening(a, values[:a.size], siblings[:r.n_siblings], counts) if r.status == 0 else None
+            out.append((r.status, r.message.decode(errors="replace"), rec, r.root))
+    if rc and (not judged or all(r.status != rc for r in res[:n]) or rc in (2, 3)):
+        try:
+            _raise_status(L, rc)
+        except CmError as e:
+            e.results = out
+            raise
+    return (rc, out) if with_rc else out
+
+
+def _image_open_sets(self, address_lists):
+    """open_sets with every part under this image -> [(MemSetOpening, root)]; raises CmError (.status, .message, .results) when
+    any part fails"""
+    rc, out = open_sets([(self, a) for a in address_lists], self.L, with_rc=True)
+    if rc:
+        try:
+            _raise_status(self.L, rc)
+        except CmError as e:
+            e.results = out
+            raise
+    return [(rec, root) for _, _, rec, root in out]
+
+
+MemImage.open_sets = _image_open_sets
+
+
 # ---- program identity and the statement of a run (include/cairom_hip.h: cm_program_id_entries .. cm_run_statement_of) ----------
 class RunStatementC(C.Structure):
     """cm_run_statement"""

@@ -57,6 +57,8 @@
  *    cm_mem_batch_step, cm_verify_memory_transitions, cm_verify_memory_sets, cm_mem_batch_plan.
  *    Still 10 (additive: one new function and two structs, nothing moved; listed with the batches): cm_mem_image_update,
  *    cm_mem_image_result, cm_mem_images_apply.
+ *    Still 10 (additive: one new function and two structs, nothing moved; listed with the batches): cm_mem_set_request,
+ *    cm_mem_set_result, cm_mem_images_open_memory_sets.
  *    Still 10 (additive: four new functions and two structs, nothing moved): cm_tail_piece, cm_tail_tables_out, cm_tail_grind_op,
  *    cm_tail_tables_op, cm_tail_tab_words, cm_tail_last_op.
  *    Still 10 (additive: one new function and one struct, nothing moved): cm_eval_job, cm_eval_at_points_op.
@@ -1576,6 +1578,60 @@ typedef struct {
   char message[248];             /* "" when applied */
 } cm_mem_image_result;           /* sizeof = 256 */
 int32_t cm_mem_images_apply(const cm_mem_image_update* parts, uint32_t n_parts, cm_mem_image_result* results);
+/* ---- batched set openings (additive to revision 10: one new function and two structs, nothing moved) --------------------------
+ * cm_mem_images_open_memory_sets opens n_parts sets in one call, each under the device image its part names, through ONE chain of
+ * launches and one round trip: a small set opening is bound by its launches and its two copies, not by hashing or gathering, and
+ * independent openings share that chain as the parts of cm_mem_images_apply do.  It is what a follower that serves clients (a
+ * bridge, an RPC node, a checkpoint service) calls once per round of pending requests, and what produces in one call the records
+ * cm_verify_memory_sets checks in one call.
+ * Per part: parts[i] gets exactly what
+ * cm_mem_image_open_memory_set(img, addresses, n, values, siblings, cap_siblings, &n_siblings, &root) would give alone —
+ * results[i].status = 0 (opened) or 1 (a bad part), .message the single call's words ("" when opened), .n_siblings, .root, and
+ * values[0 .. 4n) and siblings[0 .. n_siblings) byte for byte.  A bad part does not disturb its neighbours, which are opened, and
+ * its `values` and `siblings` are not written.  A part's own status 1, never a failed call, in the single call's order: a NULL
+ * addresses, values or siblings; n == 0; n > 2^20; addresses not strictly ascending or not below 2^28 (the single call's message);
+ * a cap_siblings below the need (.n_siblings is cm_mem_set_plan's all the same); a host image; an empty image.  Such a part never
+ * reaches a kernel; the others run.
+ * Returns 0 when every part has status 0, else the status of the lowest part that has another, with cm_last_error() =
+ * "part <i>: <message>".
+ * The call as a whole is refused with status 1, before any address is read and before the device is asked for: a NULL `parts` or
+ * `results`; n_parts == 0 or n_parts > 2^16; a part with a short struct_size; a part with a NULL img; the parts' n summing to more
+ * than 2^20 ("open in groups").  Nothing is written to `results` then.  A call that passes these asks for the device whatever its
+ * parts hold: without a GPU it returns cm_init's status (3), with the host's own verdicts (status 1) in `results` and cm_init's
+ * status and message in every other part.
+ * The one difference from cm_mem_images_apply: openings only read, so several parts MAY name one image — many clients under one
+ * root is the common case.  Every part of one call that names an image is opened under the same root of it.
+ * Nothing reaches any caller's array before EVERY part's device word count has been compared with the host plan (the single
+ * call's rule, for the whole batch); a count that differs fails the call.
+ * Device side (the calling thread's stream and pool, as the single call): one upload of one block — per part a table entry (the
+ * image's node list, the depth offsets its handle already keeps, where its values and its words go in the output block), the
+ * prefixes of the cells and of the words, the default hashes, then the addresses concatenated; the flag pass over the 28 N pairs of all parts and
+ * ONE scan, as the batched verifier's; k_sets_gather, one launch over 28 N + 2 N lanes — a lane bisects the cells' prefix for its
+ * part and reads THAT part's image; a sibling word lands in its part's slice at the scan's low word minus the scan at the part's
+ * first pair, the last pair lane of a part stores the part's count, a lane behind the pairs stores one half of a cell's value;
+ * every word is written by exactly one lane, no atomic; one download of one block (the counts, the values, the words) through
+ * the pinned landing buffer, one trip per 8 MB, scattered to the callers' arrays.  The number of launches and round trips does
+ * not depend on n_parts.
+ * Threading: each DISTINCT handle's mutex is taken once, in one global order, by handle address (the order cm_mem_images_apply
+ * takes them in), and all are held until the download has landed. */
+typedef struct {
+  uint32_t struct_size;        /* sizeof(cm_mem_set_request) */
+  uint32_t n;                  /* cells */
+  cm_mem_image* img;           /* a device image; several parts MAY name the same image */
+  const uint32_t* addresses;   /* n, strictly ascending, below 2^28 */
+  uint32_t* values;            /* out, 4 n */
+  uint32_t* siblings;          /* out, room for cap_siblings words */
+  uint32_t cap_siblings;
+  uint32_t reserved;           /* 0 */
+} cm_mem_set_request;          /* sizeof = 48 */
+typedef struct {
+  int32_t status;              /* 0 opened, 1 bad part */
+  uint32_t root;               /* the image's root (written whenever img is usable) */
+  uint32_t n_siblings;         /* the words the set needs = cm_mem_set_plan's, also when cap_siblings is short */
+  uint32_t reserved;
+  char message[240];           /* "" when opened */
+} cm_mem_set_result;           /* sizeof = 256 */
+int32_t cm_mem_images_open_memory_sets(const cm_mem_set_request* parts, uint32_t n_parts, cm_mem_set_result* results);
 /* ---- program identity and the statement of a run (additive to revision 10) ---------------------------------------------------
  * Which program a proof is about, as one 31-bit word: Proof::program_id() of the reference (crates/prover/src/lib.rs:75-97), the
  * Poseidon2 root of the partial memory tree that holds only the proof's public program cells.  An "entry" is the seven-word record

@@ -385,6 +385,31 @@ pub struct cm_mem_image_result {
     pub root: u32,
     pub message: [u8; 248],
 }
+/// One part of `cm_mem_images_open_memory_sets`: the set of `n` cells `addresses` under the device image `img` (several parts may
+/// name one image); `values` takes 4 n words, `siblings` up to `cap_siblings`; set `struct_size` before the call
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct cm_mem_set_request {
+    pub struct_size: u32,
+    pub n: u32,
+    pub img: *mut cm_mem_image,
+    pub addresses: *const u32,
+    pub values: *mut u32,
+    pub siblings: *mut u32,
+    pub cap_siblings: u32,
+    pub reserved: u32,
+}
+/// What `cm_mem_images_open_memory_sets` says of one part: 0 opened, 1 a bad part; the image's root; the words the set needs;
+/// the single call's message, NUL-terminated ("" when opened)
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct cm_mem_set_result {
+    pub status: i32,
+    pub root: u32,
+    pub n_siblings: u32,
+    pub reserved: u32,
+    pub message: [u8; 240],
+}
 /// What a chain of proofs states (`cm_run_statement_of`): the program's id and range, the registers and memory roots the run
 /// starts from and ends at, the counts of its input and output entries; set `struct_size` before the call
 #[repr(C)]
@@ -743,6 +768,7 @@ unsafe extern "C" {
     pub fn cm_mem_image_apply(img: *mut cm_mem_image, addresses: *const u32, new_values: *const u32, n: u64, old_values: *const u32, root_before: *const u32, root_after: *const u32, root_out: *mut u32, record_out: *mut *mut cm_mem_transition) -> i32;
     pub fn cm_mem_image_apply_transition(img: *mut cm_mem_image, t: *const cm_mem_transition_view, record_out: *mut *mut cm_mem_transition) -> i32;
     pub fn cm_mem_images_apply(parts: *const cm_mem_image_update, n_parts: u32, results: *mut cm_mem_image_result) -> i32;
+    pub fn cm_mem_images_open_memory_sets(parts: *const cm_mem_set_request, n_parts: u32, results: *mut cm_mem_set_result) -> i32;
     pub fn cm_mem_image_open_memory(img: *mut cm_mem_image, addresses: *const u32, n: u64, out: *mut cm_mem_opening, root: *mut u32) -> i32;
     pub fn cm_mem_image_open_memory_range(img: *mut cm_mem_image, start: u32, n_cells: u32, values: *mut u32, out: *mut cm_mem_range_opening, root: *mut u32) -> i32;
     pub fn cm_mem_image_open_memory_set(img: *mut cm_mem_image, addresses: *const u32, n: u64, values: *mut u32, siblings: *mut u32, cap_siblings: u32, n_siblings: *mut u32, root: *mut u32) -> i32;

@@ -836,6 +836,61 @@ impl MemImage {
             .collect())
     }
 
+    /// One set each under device images in one call, through one chain of launches and one round trip
+    /// (`cm_mem_images_open_memory_sets`); several parts may name one image.  Addresses in any order, repeats allowed: sorted and
+    /// made unique here, per part.  Per part `Ok((the record, the root it opens under))`, or `Err((status, message))` in the words
+    /// `open_set` would use; a bad part does not disturb the others.  The outer `Err` is a call refused as a whole (no parts, more
+    /// than 2^20 cells in all) or a missing device.
+    pub fn open_sets_many(requests: &[(&MemImage, &[u32])]) -> Result<Vec<Result<(MemSetOpening, u32), (i32, String)>>, String> {
+        ensure_init();
+        let mut sets: Vec<(Vec<u32>, Vec<u32>, Vec<u32>)> = Vec::with_capacity(requests.len());
+        for (_, addresses) in requests.iter() {
+            let mut a: Vec<u32> = addresses.to_vec();
+            a.sort_unstable();
+            a.dedup();
+            let mut steps: [cm_mem_set_step; 29] = unsafe { std::mem::zeroed() };
+            let (mut n_steps, mut need): (u32, u32) = (0, 0);
+            let rc = unsafe { cm_mem_set_plan(a.as_ptr(), a.len() as u64, steps.as_mut_ptr(), 29, &mut n_steps, &mut need) };
+            if rc != 0 {
+                return Err(last_error());
+            }
+            let values: Vec<u32> = vec![0; 4 * a.len()];
+            let siblings: Vec<u32> = vec![0; need as usize];
+            sets.push((a, values, siblings));
+        }
+        let mut parts: Vec<cm_mem_set_request> = Vec::with_capacity(requests.len());
+        for ((image, _), (a, values, siblings)) in requests.iter().zip(sets.iter_mut()) {
+            let mut p: cm_mem_set_request = unsafe { std::mem::zeroed() };
+            p.struct_size = std::mem::size_of::<cm_mem_set_request>() as u32;
+            p.n = a.len() as u32;
+            p.img = image.handle;
+            p.addresses = a.as_ptr();
+            p.values = values.as_mut_ptr();
+            p.siblings = siblings.as_mut_ptr();
+            p.cap_siblings = siblings.len() as u32;
+            parts.push(p);
+        }
+        let blank = cm_mem_set_result { status: -1, root: 0, n_siblings: 0, reserved: 0, message: [0u8; 240] };
+        let mut results: Vec<cm_mem_set_result> = vec![blank; parts.len()];
+        let rc = unsafe { cm_mem_images_open_memory_sets(parts.as_ptr(), parts.len() as u32, results.as_mut_ptr()) };
+        // a call refused as a whole writes no result; a call that judged every part returns the lowest bad part's status
+        if rc != 0 && (results.is_empty() || results.iter().any(|r| r.status == -1) || results.iter().all(|r| r.status != rc)) {
+            return Err(last_error());
+        }
+        Ok(results
+            .iter()
+            .zip(sets.into_iter())
+            .map(|(r, (a, values, mut siblings))| {
+                if r.status == 0 {
+                    siblings.truncate(r.n_siblings as usize);
+                    return Ok((MemSetOpening { addresses: a, values, siblings }, r.root));
+                }
+                let end = r.message.iter().position(|&b| b == 0).unwrap_or(r.message.len());
+                Err((r.status, String::from_utf8_lossy(&r.message[..end]).into_owned()))
+            })
+            .collect())
+    }
+
     /// The cells `addresses` (any order, repeats allowed: sorted and made unique here) under the image's current root, built on
     /// the GPU (`cm_mem_image_open_memory_set`; device images only): the record and that root.
     pub fn open_set(&self, addresses: &[u32]) -> Result<(MemSetOpening, u32), String> {
